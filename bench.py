@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""bench.py -- env-steps/sec of the fused T1D step on MI355X, with the accuracy half of BASELINE.json's metric.
+"""bench.py -- env-steps/sec of the fused T1D step on MI355X; --full adds the accuracy half of BASELINE.json's metric.
 
 One "step" = one pass of the hot path over the batch = ONE kernel launch advancing every env by one simulated
 minute (1-min dt: Navigator-class sensor, sample_time = 1).  Workload: BASELINE.json configs[3] -- 1 048 576
@@ -14,7 +14,13 @@ env_offset = first global env of the shard, so every env's Philox stream and mea
 no data-path collective); `--scaling weak` gives every rank its own --envs instead.  value = all ranks' env-steps /
 max-over-ranks wall time of the K timed launches.
 
+A plain run sets up, warms up, times the K launches and prints the JSON line (with --dump-outputs DIR it first writes
+what the last timed launch returned as DIR/<name>.npy).  --full adds what the headline figure does not need: the CPU
+baseline, the accuracy replay on the oracle with its north_star_rk4 leg and, with N > 1, the weak-scaling probe and the
+observation gather.  Both time the same episode on the same inputs.
+
     python bench.py --gpus 1 --steps 1000 --warmup 400
+    python bench.py --gpus 1 --steps 1000 --warmup 400 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -259,6 +265,46 @@ def weak_probe(a, dev, dt, tab, rank, world, steps=300, warmup=300):
             "note": "the same workload with %d envs on every rank, timed after the headline region (barrier + MAX over ranks as there)" % n}
 
 
+def accuracy_resets(a, integ, rank):
+    """full resets of the batch that --full's accuracy legs (rank 0) make ahead of the timed episode: the replay with the
+    benchmarked integrator and, unless that is RK4 already, the RK4 replay and its timing"""
+    if rank != 0 or a.no_accuracy:
+        return 0
+    return 1 if integ == "rk4" else 3
+
+
+DUMP_BYTES = 60 * 10 ** 6       # --dump-outputs: bytes of array data written by the whole job (all ranks)
+DUMP_STATE_ENVS = 65536         # envs of the patient_state sample
+
+
+def dump_outputs(env, out_dir, rank, world, seed=0):
+    """--dump-outputs: what the last timed step handed its caller -- obs (cgm), reward, done and info's bg, t and
+    patient_state -- as <out_dir>/<name>.npy (the env dtype; done as float32 0/1, t as float64).  The [n] arrays are
+    written whole while they fit in DUMP_BYTES, else on a seeded sample of envs (their global ids in env_index.npy);
+    patient_state [13, n] always on a seeded sample of at most DUMP_STATE_ENVS / N of those (global ids in
+    patient_state_envs.npy).  The ranks of an N > 1 job write <name>.rank<r>.npy for their own shard."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n, isz = env.n, env.cgm.element_size()
+    s = min(n, DUMP_STATE_ENVS // world)
+    rest = DUMP_BYTES // world - s * (13 * isz + 8)              # patient_state and its env ids come first
+    per_env = 3 * isz + 4 + 8                                    # cgm, reward, bg; done; t
+    m = n if n * per_env <= rest else rest // (per_env + 8)      # (+ env_index)
+    s = min(s, m)
+    rs = np.random.RandomState(seed)
+    idx = np.arange(n) if m == n else np.sort(rs.choice(n, m, replace=False))
+    sidx = idx if s == m else np.sort(rs.choice(idx, s, replace=False))
+    it, st = torch.as_tensor(idx, device=env.device), torch.as_tensor(sidx, device=env.device)
+    arrays = {"cgm": env.cgm[it], "reward": env.reward[it], "done": env.done[it].float(), "bg": env.bg[it],
+              "t": env.t[it].double(), "patient_state": env.x[:, st],
+              "patient_state_envs": torch.as_tensor(env.env_offset + sidx, dtype=torch.float64)}
+    if m < n:
+        arrays["env_index"] = torch.as_tensor(env.env_offset + idx, dtype=torch.float64)
+    suffix = "" if world == 1 else ".rank%d" % rank
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), np.ascontiguousarray(v.cpu().numpy()))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -284,11 +330,16 @@ def main(argv=None):
                     help="every lane takes its step-size level in place (adaptive_gut = 2) instead of levels 1 and 2 being set aside")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="t1d_ctx_set_option switches applied after the ones above (tuning runs), e.g. --opt minute_launches=0")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-accuracy", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the CPU baseline, the accuracy replay "
+                         "on the oracle with its north_star_rk4 leg and, with N > 1, the weak-scaling probe and the observation gather")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (cgm, reward, done, bg, t, a sample of patient_state) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-accuracy", action="store_true", help="--full without the accuracy replay")
     ap.add_argument("--accuracy-envs", type=int, default=1024)
     ap.add_argument("--accuracy-minutes", type=int, default=1440, help="north_star: a 24 h scenario")
-    ap.add_argument("--no-weak-probe", action="store_true", help="N > 1, strong scaling: skip the full-batch-per-rank measurement after the timed region")
+    ap.add_argument("--no-weak-probe", action="store_true", help="--full, N > 1, strong scaling: skip the full-batch-per-rank measurement after the timed region")
     ap.add_argument("--rk4-steps", type=int, default=200, help="timed launches of the north_star_rk4 leg (classical RK4, same workload)")
     ap.add_argument("--traffic-bytes", type=float, default=None,
                     help="HBM bytes per launch from a separate rocprofv3 --pmc run (FETCH_SIZE/WRITE_SIZE), copied into roofline.traffic")
@@ -313,7 +364,7 @@ def main(argv=None):
     # should not do
     integ_name = "rk4" if a.integrator == "rk4" or a.n_sub % 2 or a.n_sub > 8 else ("split" if a.fixed_step else "split_adaptive")
     cpu = None
-    if rank == 0 and not a.no_cpu_baseline:
+    if rank == 0 and a.full and not a.no_cpu_baseline:
         cpu = cpu_baseline(a.cpu_envs, a.cpu_steps, a.n_sub, a.sensor, integ_name)
         # the reference's own Python path, timed in the build container by tools/time_reference_cpu.py (it cannot travel)
         try:
@@ -372,7 +423,7 @@ def main(argv=None):
     pool = [(basal0 * 2.0 * torch.rand(n_global, generator=g, dtype=torch.float64)[env_offset:env_offset + n].to(dev, dt)).contiguous() for _ in range(8)]
 
     accuracy = rk4 = None
-    if rank == 0 and not a.no_accuracy:
+    if rank == 0 and a.full and not a.no_accuracy:
         accuracy, rk4 = accuracy_block(env, pool, mt, ma, integ, a.n_sub, a.sensor, a.accuracy_minutes, a.accuracy_envs)
         if rk4 is not None:              # north_star's literal integrator on the same workload: time it too (integrator 0 is still set)
             env.set_meals(mt, ma); env.reset()
@@ -392,6 +443,10 @@ def main(argv=None):
         # rank 0 spent seconds in the accuracy replay: nobody starts warming up until it is back, so that every rank
         # enters the timed region straight from its warm-up launches
         dist.barrier()
+    # the Philox stream of the timed episode follows the episode counter, which every full reset advances: a plain run
+    # starts it where --full's accuracy legs leave it, so that both (and earlier versions of this file, where those legs
+    # ran by default) time and dump the same episode
+    env.episode.fill_(accuracy_resets(a, integ, rank))
     env.reset()
     for k in range(a.prewarm + a.warmup):
         env.step(pool[k % 8])
@@ -414,16 +469,18 @@ def main(argv=None):
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     status = env.sync(raise_on_status=False)
+    if a.dump_outputs:
+        dump_outputs(env, a.dump_outputs, rank, world)
     if use_dist:
         tw = torch.tensor([wall], dtype=torch.float64, device=dev)
         dist.all_reduce(tw, op=dist.ReduceOp.MAX)
         wall = float(tw.item())
     kern_ms = ev0.elapsed_time(ev1) / a.steps
     total_env_steps = n_global * a.steps * st
-    # the optional exchange of the N > 1 job (north_star: "an optional RCCL gather of observations over xGMI"), outside the
-    # timed region: every rank's CGM slice gathered into one [N] tensor on every rank, as a central policy would ask for
+    # the optional exchange of the N > 1 job (north_star: "an optional RCCL gather of observations over xGMI"), --full, outside
+    # the timed region: every rank's CGM slice gathered into one [N] tensor on every rank, as a central policy would ask for
     gather = None
-    if use_dist:
+    if use_dist and a.full:
         from simglucose_amd.distributed import gather_observations
         try:
             full = gather_observations(env.cgm, n_global, force_collective=True)
@@ -442,7 +499,7 @@ def main(argv=None):
     # N > 1 under strong scaling: each rank's shard is small and its launch latency-bound; the same job
     # with a full-size batch on every rank (what --scaling weak times) is measured beside it, outside the timed region
     weak = None
-    if use_dist and (world > 1 or os.environ.get("T1D_BENCH_FORCE_DIST") == "2") and a.scaling == "strong" and not a.no_weak_probe:
+    if use_dist and a.full and (world > 1 or os.environ.get("T1D_BENCH_FORCE_DIST") == "2") and a.scaling == "strong" and not a.no_weak_probe:
         try:
             weak = weak_probe(a, dev, dt, tab, rank, world)
         except Exception as e:                      # (collective inside: every rank fails or none; the headline line survives)

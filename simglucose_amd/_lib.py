@@ -113,6 +113,10 @@ def lib():
     global _lib
     if _lib is not None:
         return _lib
+    # torch first: the library launches on torch's streams, so its libamdhip64.so.7 must resolve to the HIP runtime torch
+    # has loaded.  Loaded the other way round, torch (which asks for libamdhip64.so) maps a second HIP and HSA runtime
+    # into the process, and whichever of the two starts second finds no device.
+    import torch  # noqa: F401
     try:
         if _stale():
             build()

@@ -27,6 +27,28 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert L.t1d_abi_version() == _lib.ABI_VERSION == 4
 
 
+LOAD_ORDER = r'''
+import sys
+sys.path.insert(0, sys.argv[1])
+from simglucose_amd import _lib
+_lib.lib()                                  # before anything has imported torch
+import torch
+maps = {l.split()[-1] for l in open("/proc/self/maps") if "libamdhip64" in l or "libhsa-runtime64" in l}
+print(len([m for m in maps if "libamdhip64" in m]), len([m for m in maps if "libhsa-runtime64" in m]), sorted(maps))
+'''
+
+
+def test_library_loaded_before_torch_shares_torchs_hip_runtime():
+    """The library launches on torch's streams: loaded first in a fresh process, it must still bind to the HIP runtime
+    torch brings, not map a second HIP / HSA runtime next to it (the GPU then stays invisible to one of the two)."""
+    import subprocess
+    import sys
+    p = subprocess.run([sys.executable, "-c", LOAD_ORDER, ROOT], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
+    out = p.stdout.decode()
+    assert p.returncode == 0, out
+    assert out.split()[:2] == ["1", "1"], out
+
+
 def test_ctx_create_rejects_bad_arguments_without_touching_a_gpu():
     from simglucose_amd import _lib, params
     L = _lib.lib()
