@@ -1,5 +1,6 @@
 // t1d_abi.hip -- host side of the C ABI of libt1d_hip.so (gfx950 only; see include/t1d.h): context and tables,
-// argument checks, kernel selection and launches.  The kernels are in t1d_kernels.hpp, the per-lane arithmetic in
+// argument checks, kernel selection and launches.  A step or a roll-out is planned by plan_call (which kernel instance,
+// grid, block, dynamic LDS) and launched by launch_plan.  The kernels are in t1d_kernels.hpp, the per-lane arithmetic in
 // t1d_device.hpp.  This is the one translation unit of the library.
 #include "../../include/t1d.h"
 #include "t1d_kernels.hpp"
@@ -227,13 +228,6 @@ static int ensure_split(t1d_ctx* c, int ng)
     T1D_HIP(hipMemcpy(c->d_par32, dpf.data(), dpf.size() * 4, hipMemcpyHostToDevice));
     c->split_nsub = ng;
     return T1D_OK;
-}
-
-// which integrator a call with n_sub sub-steps uses: the split scheme needs fast math and an even n_sub <= 8
-static bool use_split(const t1d_ctx* c, int n_sub)
-{
-    const bool can = c->math != 0 && n_sub >= 2 && n_sub <= 8 && !(n_sub & 1);
-    return can && c->integrator != 0;
 }
 
 #if T1D_S1_TRACE
@@ -464,22 +458,27 @@ static hipError_t allow_lds(t1d_ctx* c, const void* fn, size_t bytes)
     return e;
 }
 
-// Which generic kernel variant a call takes (t1d_kernels.hpp): reference arithmetic, fast classical RK4, split at
-// level 1, split with per-minute step sizes in place.
-static int pick_variant(const t1d_ctx* c, bool split, int dtype)
-{
-    if (c->math == 0) return 0;
-    if (!split) return 3;
-    if (!c->adaptive_gut) return 4;
-    return dtype == T1D_F32 ? 6 : 7;           // with per-lane step sizes the parameters fit in VGPRs in fp32 only
-}
+// ---- kernel selection ------------------------------------------------------------------------------------------------
+// Which kernel a step or a roll-out launches, with which template arguments, on what grid and with how much dynamic LDS:
+// plan_call, a pure function of the context, the batch and the call (no HIP call, no change to the context; tested on
+// the CPU by tests/dispatch_plan_driver.cpp).  launch_plan maps the plan to the template instance and launches it.
+enum class Kern { step, rollout, step1, step1d, stepn };   // step_kernel, rollout_pid_kernel, step1_kernel, step1d_kernel, stepn_kernel
 
-// What the persistent kernels of a call need: the split integrator on the packed layout, the noise refill kept out of
-// the step kernel, tables that fit in LDS.
-struct PersistPlan {
-    bool ok = false;
-    int stride = 32, nchunks = 0, blocks = 0, per_block = 0;
-    size_t dyn_tables = 0;
+struct Plan {
+    Kern kernel = Kern::step;
+    bool f64 = true;
+    int variant = 0;             // step_kernel, rollout_pid_kernel: VARIANT -- reference arithmetic (0), fast classical RK4 (3),
+                                 // split at level 1 (4), split with per-minute step sizes in place (7 in fp64, 6 in fp32)
+    bool refill = false;         // step_kernel: REFILL, the noise-block refill inside the step kernel
+    int stride = 32;             // step1_kernel: STRIDE, the row stride of the tables in LDS
+    bool extra = false;          // step1_kernel, step1d_kernel, stepn_kernel: EXTRA, the optional outputs
+    bool tiered = false;         // step1_kernel: TIERED, per-minute step sizes
+    bool ctrl = false;           // stepn_kernel: CTRL, one closed-loop roll-out step per launch, the controller in its prologue
+    bool refill_ahead = false;   // refill_kernel runs ahead of the kernel (ahead of each launch of a roll-out)
+    bool tables = false;         // the split integrator is asked for: its tables are (re)built for n_sub first (ensure_split)
+    unsigned grid = 0, block = 0;
+    size_t lds = 0;              // dynamic LDS bytes
+    int nchunks = 0, cap = 0, mode = 0;   // persistent kernels: chunks of 64 envs; stepn_kernel: record capacity, mode
 };
 
 static bool is_packed(const t1d_batch* b, size_t esz)
@@ -495,165 +494,191 @@ static bool is_packed(const t1d_batch* b, size_t esz)
            (size_t)kPackedRows * rowb < ((size_t)1 << 32);
 }
 
-static PersistPlan plan_persistent(const t1d_ctx* c, const t1d_batch* b, int n_sub, bool split, bool split_refill)
+// The plan of a step (rollout = false) or of a closed-loop roll-out.  On an error *out still says whether the split tables
+// are asked for (the caller builds them either way).
+static int plan_call(const char* who, const t1d_ctx* c, const t1d_batch* b, int minutes, int n_sub, bool rollout, Plan* out)
 {
-    PersistPlan p;
-    const size_t esz = b->dtype == T1D_F64 ? 8 : 4;
-    if (!(split_refill && split && c->single_minute_kernel && is_packed(b, esz)) || (T1D_AB_FLAGS && (b->flags & 0x600))) return p;
-    p.stride = c->np <= 32 ? 32 : 64;
-    p.dyn_tables = (size_t)(DP_COUNT + kPropRows(n_sub)) * p.stride * esz;
-    if (p.dyn_tables + 512 > (size_t)c->lds_per_block) return p;
-    p.nchunks = (int)((b->n + 63) / 64);
-    p.blocks = c->s1_blocks > 0 ? c->s1_blocks : c->n_cu;           // one workgroup of 4 x T1D_S1_WAVES waves per CU
-    if (p.blocks > p.nchunks) p.blocks = p.nchunks;
-    p.per_block = (p.nchunks + p.blocks - 1) / p.blocks;
-    p.ok = true;
-    return p;
-}
+    Plan& p = *out;
+    p = Plan();
+    if (minutes < 1 || minutes > 100000) return fail(T1D_E_INVALID, std::string(who) + ": minutes out of range");
+    if (n_sub < 1 || n_sub > 4096) return fail(T1D_E_INVALID, std::string(who) + ": n_sub out of range");
+    bool split = c->math != 0 && n_sub >= 2 && n_sub <= 8 && !(n_sub & 1);     // what the split integrator needs
+    if (c->integrator == 1 && !split)
+        return fail(T1D_E_INVALID, std::string(who) + ": the split integrator needs math = 1 and n_sub in {2, 4, 6, 8}");
+    split = split && c->integrator != 0;
+    p.tables = split;
+    p.f64 = b->dtype == T1D_F64;
+    const size_t esz = p.f64 ? 8 : 4;
+    p.extra = b->lbgi || b->hbgi || b->risk || b->meal || b->insulin;
+    // At most one CGM sample per launch (minutes <= sample_time): the noise-block refill can run as its own kernel ahead of
+    // a step kernel compiled without it
+    const bool split_refill = c->math != 0 && c->split_refill && minutes <= (int)c->sensor[5];
 
-// LDS of stepn_kernel beside the tables: the redo map (one bit per env of a workgroup's share) and the records -- as many as
-// fit, never more than the workgroup's env-minutes.  -> records (a multiple of 64), or -1 where the tables leave no room.
-static int stepn_park_cap(const t1d_ctx* c, const PersistPlan& p, size_t esz, int minutes, size_t* dyn)
-{
-    const size_t rec = (size_t)kSnParkT * esz + (size_t)kSnParkI * sizeof(int);
-    const size_t fixed = p.dyn_tables;
-    if (p.stride != 32 || fixed + 1024 > (size_t)c->lds_per_block) return -1;
-    const size_t map = (size_t)p.per_block * 8 + 8;         // the redo map: one bit per env of the workgroup's share
-    if (fixed + map + 1024 > (size_t)c->lds_per_block) return -1;
-    long long cap = (long long)(((size_t)c->lds_per_block - 1024 - fixed - map) / rec) / 64 * 64;
-    const long long share = ((long long)p.per_block * 64 * minutes + 63) / 64 * 64;
-    if (cap > share) cap = share;
-    if (c->park_cap > 0 && cap > (c->park_cap + 63) / 64 * 64) cap = (c->park_cap + 63) / 64 * 64;
-    *dyn = fixed + (size_t)cap * rec + map;
-    return (int)cap;
-}
+    // The persistent kernels: the split integrator on the packed layout, the noise refill kept out of the step kernel,
+    // tables that fit in LDS; one workgroup of 4 x T1D_S1_WAVES waves per CU
+    const int stride = c->np <= 32 ? 32 : 64;
+    const size_t tables = (size_t)(DP_COUNT + kPropRows(n_sub)) * stride * esz;
+    const bool persist = split_refill && split && c->single_minute_kernel && is_packed(b, esz) &&
+                         !(T1D_AB_FLAGS && (b->flags & 0x600)) && tables + 512 <= (size_t)c->lds_per_block;
+    const int nchunks = (int)((b->n + 63) / 64);
+    const int blocks = std::min(c->s1_blocks > 0 ? c->s1_blocks : c->n_cu, nchunks);
+    const int per_block = (nchunks + blocks - 1) / blocks;
 
-template <typename T>
-static PidArgs<T> no_ctrl()
-{
-    PidArgs<T> c;
-    std::memset(&c, 0, sizeof(c));
-    return c;
-}
+    // The multi-minute kernel.  Steps of several minutes: the state in registers across the minutes, lanes of level 2
+    // parked and finished at the end (measured, Dexcom steps: fp64 147 against 184 us at 512 Ki envs, 257 against 339 at
+    // 1 Mi, 883 against 1254 at 4 Mi, level at 256 Ki, the generic kernel ahead below; fp32 within 6 % of the generic
+    // kernel at every size).  Roll-outs of large batches: one launch per step, the controller in its prologue -- the
+    // step-size rule's lanes of level 2 are set aside, where the all-steps-in-one-launch kernel runs each wave at the level
+    // of its most refined lane (a step of one minute too: the kernel takes any minutes >= 1).
+    const bool want_n = rollout
+        ? c->multi_minute_kernel != 0 && (c->rollout_launches == 2 || (c->rollout_launches == 1 &&
+              b->n >= (p.f64 ? c->rollout_launches_min_envs : c->rollout_launches_min_envs_f32)))
+        : minutes > 1 && (c->multi_minute_kernel == 2 || (c->multi_minute_kernel == 1 &&
+              b->n >= (p.f64 ? c->multi_minute_min_envs : c->multi_minute_min_envs_f32)));
+    // its LDS beside the tables: the redo map (one bit per env of the workgroup's share) and the records -- as many as fit,
+    // never more than the workgroup's env-minutes
+    const size_t map = (size_t)per_block * 8 + 8, rec = (size_t)kSnParkT * esz + (size_t)kSnParkI * sizeof(int);
+    if (persist && want_n && stride == 32 && tables + map + 1024 <= (size_t)c->lds_per_block) {
+        long long cap = (long long)(((size_t)c->lds_per_block - 1024 - tables - map) / rec) / 64 * 64;
+        const long long share = ((long long)per_block * 64 * minutes + 63) / 64 * 64;
+        if (cap > share) cap = share;
+        if (c->park_cap > 0 && cap > (c->park_cap + 63) / 64 * 64) cap = (c->park_cap + 63) / 64 * 64;
+        p.kernel = Kern::stepn;
+        p.ctrl = rollout;
+        p.extra = p.extra || rollout;            // a roll-out has the one instance stepn_kernel<T, true, true>
+        // a roll-out refills ahead of every step, whatever T1D_BATCH_NO_REFILL_DUE says (the clocks are the envs')
+        p.refill_ahead = rollout || !(b->flags & T1D_BATCH_NO_REFILL_DUE);
+        p.grid = blocks; p.block = p.f64 ? sn_threads<double>() : sn_threads<float>();
+        p.lds = tables + (size_t)cap * rec + map;
+        p.nchunks = nchunks; p.cap = (int)cap;
+        p.mode = (c->adaptive_gut != 0 ? 1 : 0) | (c->adaptive_gut == 2 ? 2 : 0) | (c->record_group_min << 8);
+        return T1D_OK;
+    }
+    if (persist && !rollout && minutes == 1) {
+        // One simulated minute per launch: the persistent early-store kernels.  With per-minute step sizes, lanes of level 2
+        // are set aside and integrated together at the end of the launch (step1d_kernel) where the list of the CU's envs
+        // fits next to the tables; adaptive_gut = 2 asks for the in-place form, 3 for the set-aside form at any batch size.
+        const size_t lds1d = tables + (size_t)kS1DPark * (18 * esz + 3 * sizeof(int)) + (size_t)per_block * 64 * sizeof(uint16_t);
+        p.tiered = c->adaptive_gut != 0;
+        const bool defer = p.tiered && (c->adaptive_gut == 3 || (c->adaptive_gut == 1 && per_block >= c->defer_min_chunks)) &&
+                           stride == 32 && per_block * 64 <= 65536 && lds1d + 512 <= (size_t)c->lds_per_block;
+        p.kernel = defer ? Kern::step1d : Kern::step1;
+        p.stride = stride;
+        p.refill_ahead = !(b->flags & T1D_BATCH_NO_REFILL_DUE);
+        p.grid = blocks;
+        p.block = defer ? (p.f64 ? s1d_threads<double>() : s1d_threads<float>()) : (p.f64 ? s1_threads<double>() : s1_threads<float>());
+        p.lds = defer ? lds1d : tables;
+        p.nchunks = nchunks;
+        return T1D_OK;
+    }
 
-// one launch of stepn_kernel: a step of `minutes` minutes, or (CTRL) one closed-loop step
-template <typename T, bool EXTRA, bool CTRL>
-static int launch_stepn(t1d_ctx* c, const t1d_batch* b, const PersistPlan& p, int cap, size_t dyn, int minutes, int n_sub, const PidArgs<T>& pa, hipStream_t s)
-{
-    T1D_HIP(allow_lds(c, (const void*)stepn_kernel<T, EXTRA, CTRL>, dyn));
-    const int mode = (c->adaptive_gut != 0 ? 1 : 0) | (c->adaptive_gut == 2 ? 2 : 0) | (c->record_group_min << 8);
-    ++c->launches;
-    hipLaunchKernelGGL((stepn_kernel<T, EXTRA, CTRL>), dim3(p.blocks), dim3(sn_threads<T>()), dyn, s, make_args<T>(c, b, minutes, n_sub), pa,
-                       p.nchunks, cap, mode);
+    // The generic kernels keep the propagator table [rows][np_pad] in dynamic LDS, next to a static parameter table in the
+    // LDS-parameter variants.  Where it does not fit (many patients x many sub-steps): classical RK4 when the caller left the
+    // choice of integrator to the library.
+    if (split) {
+        p.lds = (size_t)kPropRows(n_sub) * c->np_pad * esz;
+        if (p.lds + (size_t)DP_COUNT * kMaxPatients * esz + 1024 > (size_t)c->lds_per_block) {
+            if (c->integrator == 1)
+                return fail(T1D_E_INVALID, std::string(who) + ": split tables exceed the LDS of a workgroup" +
+                                           (rollout ? "" : " (n_patients x n_sub too large)") + "; use integrator 0 or -1");
+            split = false; p.lds = 0;          // the RK4 fallback
+        }
+    }
+    p.kernel = rollout ? Kern::rollout : Kern::step;
+    // with per-lane step sizes the parameters fit in VGPRs in fp32 only
+    p.variant = c->math == 0 ? 0 : !split ? 3 : !c->adaptive_gut ? 4 : p.f64 ? 7 : 6;
+    p.refill = !split_refill;
+    p.refill_ahead = !rollout && split_refill && !(b->flags & T1D_BATCH_NO_REFILL_DUE);
+    p.grid = (unsigned)((b->n + kBlock - 1) / kBlock); p.block = kBlock;
     return T1D_OK;
 }
 
-template <typename T>
-static void launch_refill(const t1d_ctx* c, const t1d_batch* b, int minutes, int n_sub, hipStream_t s)
+// plan_call, then the split tables wherever the split integrator is asked for: also where the plan then fails for want
+// of LDS or falls back to RK4
+static int plan_and_tables(const char* who, t1d_ctx* c, const t1d_batch* b, int minutes, int n_sub, bool rollout, Plan* p)
 {
-    hipLaunchKernelGGL(refill_kernel<T>, grid_for(b->n), dim3(kBlock), 0, s, make_args<T>(c, b, minutes, n_sub));
+    const int rc = plan_call(who, c, b, minutes, n_sub, rollout, p);
+    const int e = p->tables ? ensure_split(c, n_sub) : T1D_OK;
+    return e ? e : rc;
 }
 
-// the generic kernels keep the propagator table [rows][np_pad] in dynamic LDS (next to a static parameter table in the
-// LDS-parameter variants): does it fit?
-static bool generic_split_fits(const t1d_ctx* c, int n_sub, size_t esz, size_t* dyn)
+template <typename T, typename... X> using KernelFn = void (*)(KArgs<T>, X...);
+
+// one launch of a planned kernel, its dynamic-LDS ceiling raised first.  A persistent kernel counts the launch before its
+// arguments are built: KArgs.flags carries the new pingpong parity.
+template <typename T, typename... X, typename... A>
+static int launch(t1d_ctx* c, const t1d_batch* b, const Plan& p, int minutes, int n_sub, hipStream_t s, KernelFn<T, X...> kernel, A... rest)
 {
-    *dyn = (size_t)kPropRows(n_sub) * c->np_pad * esz;
-    return *dyn + (size_t)DP_COUNT * kMaxPatients * esz + 1024 <= (size_t)c->lds_per_block;
+    T1D_HIP(allow_lds(c, (const void*)kernel, p.lds));
+    if (p.kernel != Kern::step && p.kernel != Kern::rollout) ++c->launches;
+    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(p.block), p.lds, s, make_args<T>(c, b, minutes, n_sub), rest...);
+    return T1D_OK;
+}
+
+// the generic kernels by variant; the split variant with per-minute step sizes is 7 in fp64, 6 in fp32
+template <typename T, bool REFILL>
+static KernelFn<T> step_fn(int variant)
+{
+    switch (variant) {
+    case 0: return step_kernel<0, T, REFILL>;
+    case 3: return step_kernel<3, T, REFILL>;
+    case 4: return step_kernel<4, T, REFILL>;
+    default: return step_kernel<sizeof(T) == 8 ? 7 : 6, T, REFILL>;
+    }
+}
+
+template <typename T>
+static KernelFn<T, PidArgs<T>> rollout_fn(int variant)
+{
+    switch (variant) {
+    case 0: return rollout_pid_kernel<0, T>;
+    case 3: return rollout_pid_kernel<3, T>;
+    case 4: return rollout_pid_kernel<4, T>;
+    default: return rollout_pid_kernel<sizeof(T) == 8 ? 7 : 6, T>;
+    }
+}
+
+template <typename T, int STRIDE>
+static KernelFn<T, int> step1_fn(bool extra, bool tiered)
+{
+    if (extra) return tiered ? step1_kernel<T, STRIDE, true, true> : step1_kernel<T, STRIDE, true, false>;
+    return tiered ? step1_kernel<T, STRIDE, false, true> : step1_kernel<T, STRIDE, false, false>;
+}
+
+// the refill (if planned), then the planned kernel; pa: the controller of a roll-out (stepn_kernel: of one step)
+template <typename T>
+static int launch_plan(t1d_ctx* c, const t1d_batch* b, const Plan& p, int minutes, int n_sub, const PidArgs<T>& pa, hipStream_t s)
+{
+    if (p.refill_ahead)
+        hipLaunchKernelGGL(refill_kernel<T>, grid_for(b->n), dim3(kBlock), 0, s, make_args<T>(c, b, minutes, n_sub));
+    switch (p.kernel) {
+    case Kern::step:
+        return launch(c, b, p, minutes, n_sub, s, p.refill ? step_fn<T, true>(p.variant) : step_fn<T, false>(p.variant));
+    case Kern::rollout:
+        return launch(c, b, p, minutes, n_sub, s, rollout_fn<T>(p.variant), pa);
+    case Kern::step1:
+        return launch(c, b, p, minutes, n_sub, s, p.stride == 32 ? step1_fn<T, 32>(p.extra, p.tiered) : step1_fn<T, 64>(p.extra, p.tiered),
+                      p.nchunks);
+    case Kern::step1d:
+        return launch(c, b, p, minutes, n_sub, s, p.extra ? step1d_kernel<T, true> : step1d_kernel<T, false>, p.nchunks);
+    case Kern::stepn:
+        return launch(c, b, p, minutes, n_sub, s,
+                      p.ctrl ? stepn_kernel<T, true, true> : p.extra ? stepn_kernel<T, true, false> : stepn_kernel<T, false, false>,
+                      pa, p.nchunks, p.cap, p.mode);
+    }
+    return T1D_OK;
 }
 
 extern "C" int t1d_step(t1d_ctx* c, const t1d_batch* b, int minutes, int n_sub, void* stream)
 {
     int rc = check_batch("t1d_step", c, b, true);
     if (rc) return rc;
-    if (minutes < 1 || minutes > 100000) return fail(T1D_E_INVALID, "t1d_step: minutes out of range");
-    if (n_sub < 1 || n_sub > 4096) return fail(T1D_E_INVALID, "t1d_step: n_sub out of range");
+    Plan p;
+    rc = plan_and_tables("t1d_step", c, b, minutes, n_sub, false, &p);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (c->integrator == 1 && !use_split(c, n_sub))
-        return fail(T1D_E_INVALID, "t1d_step: the split integrator needs math = 1 and n_sub in {2, 4, 6, 8}");
-    bool split = use_split(c, n_sub);
-    const size_t esz = b->dtype == T1D_F64 ? 8 : 4;
-    if (split) {
-        rc = ensure_split(c, n_sub);
-        if (rc) return rc;
-    }
-    int variant = pick_variant(c, split, b->dtype);
-    // At most one CGM sample per launch (minutes <= sample_time): the noise-block refill runs as its own
-    // kernel ahead of a step kernel compiled without it, unless the caller vouches that none is due.
-    const bool split_refill = variant != 0 && c->split_refill && minutes <= (int)c->sensor[5];
-    const PersistPlan p = plan_persistent(c, b, n_sub, split, split_refill);
-    size_t dyn_n = 0;
-    // (measured, Dexcom steps: fp64 147 against 184 us at 512 Ki envs, 257 against 339 at 1 Mi, 883 against 1254 at 4 Mi, level
-    // at 256 Ki, the generic kernel ahead below; fp32 within 6 % of the generic kernel at every size)
-    const bool want_n = c->multi_minute_kernel == 2 || (c->multi_minute_kernel == 1 && b->n >= (b->dtype == T1D_F64 ? c->multi_minute_min_envs : c->multi_minute_min_envs_f32));
-    const int cap = p.ok && minutes > 1 && want_n ? stepn_park_cap(c, p, esz, minutes, &dyn_n) : -1;
-    const bool persistent = p.ok && (minutes == 1 || cap >= 0);
-    size_t dyn = 0;
-    if (!persistent && split && !generic_split_fits(c, n_sub, esz, &dyn)) {
-        // the generic kernel cannot hold this table (many patients x many sub-steps): classical RK4 when the caller left
-        // the choice of integrator to the library
-        if (c->integrator == 1) return fail(T1D_E_INVALID, "t1d_step: split tables exceed the LDS of a workgroup (n_patients x n_sub too large); use integrator 0 or -1");
-        split = false; dyn = 0;
-        variant = pick_variant(c, split, b->dtype);
-    }
-    if (split_refill && !(b->flags & T1D_BATCH_NO_REFILL_DUE)) {
-        if (b->dtype == T1D_F64) launch_refill<double>(c, b, minutes, n_sub, s); else launch_refill<float>(c, b, minutes, n_sub, s);
-    }
-    const bool extra = b->lbgi || b->hbgi || b->risk || b->meal || b->insulin;
-    if (persistent && minutes > 1) {
-        // a step of several minutes: state in registers across the minutes, lanes of level 2 parked and finished at the end
-        if (b->dtype == T1D_F64) rc = extra ? launch_stepn<double, true, false>(c, b, p, cap, dyn_n, minutes, n_sub, no_ctrl<double>(), s)
-                                            : launch_stepn<double, false, false>(c, b, p, cap, dyn_n, minutes, n_sub, no_ctrl<double>(), s);
-        else rc = extra ? launch_stepn<float, true, false>(c, b, p, cap, dyn_n, minutes, n_sub, no_ctrl<float>(), s)
-                        : launch_stepn<float, false, false>(c, b, p, cap, dyn_n, minutes, n_sub, no_ctrl<float>(), s);
-        if (rc) return rc;
-        T1D_HIP(hipGetLastError());
-        return T1D_OK;
-    }
-    if (persistent) {
-        // one simulated minute per launch with the split integrator: the persistent early-store kernels
-        const int stride = p.stride, nchunks = p.nchunks, blocks = p.blocks, per_block = p.per_block;
-        const size_t dyn1 = p.dyn_tables;
-        const bool tiered = c->adaptive_gut != 0;
-        // per-minute step sizes: lanes of level 2 set aside and integrated together at the end of the launch
-        // (step1d_kernel) where the list of the CU's envs fits next to the tables; adaptive_gut = 2 asks for the
-        // in-place form, 3 for the set-aside form at any batch size
-        const size_t dyn1d = dyn1 + (size_t)kS1DPark * (18 * esz + 3 * sizeof(int)) + (size_t)per_block * 64 * sizeof(uint16_t);
-        const bool defer = tiered && (c->adaptive_gut == 3 || (c->adaptive_gut == 1 && per_block >= c->defer_min_chunks)) &&
-                           stride == 32 && per_block * 64 <= 65536 && dyn1d + 512 <= (size_t)c->lds_per_block;
-#define T1D_LAUNCH_S1(TT, ST, EX, TI) do { T1D_HIP(allow_lds(c, (const void*)step1_kernel<TT, ST, EX, TI>, dyn1)); \
-        hipLaunchKernelGGL((step1_kernel<TT, ST, EX, TI>), dim3(blocks), dim3(s1_threads<TT>()), dyn1, s, make_args<TT>(c, b, minutes, n_sub), nchunks); } while (0)
-#define T1D_LAUNCH_S1D(TT, EX) do { T1D_HIP(allow_lds(c, (const void*)step1d_kernel<TT, EX>, dyn1d)); \
-        hipLaunchKernelGGL((step1d_kernel<TT, EX>), dim3(blocks), dim3(s1d_threads<TT>()), dyn1d, s, make_args<TT>(c, b, minutes, n_sub), nchunks); } while (0)
-#define T1D_S1_BY(TT, ST) do { if (tiered) { if (extra) T1D_LAUNCH_S1(TT, ST, true, true); else T1D_LAUNCH_S1(TT, ST, false, true); } \
-                               else { if (extra) T1D_LAUNCH_S1(TT, ST, true, false); else T1D_LAUNCH_S1(TT, ST, false, false); } } while (0)
-#define T1D_S1D_BY(TT) do { if (extra) T1D_LAUNCH_S1D(TT, true); else T1D_LAUNCH_S1D(TT, false); } while (0)
-        ++c->launches;
-        if (defer) {
-            if (b->dtype == T1D_F64) T1D_S1D_BY(double); else T1D_S1D_BY(float);
-        } else if (b->dtype == T1D_F64) {
-            if (stride == 32) T1D_S1_BY(double, 32); else T1D_S1_BY(double, 64);
-        } else {
-            if (stride == 32) T1D_S1_BY(float, 32); else T1D_S1_BY(float, 64);
-        }
-#undef T1D_S1D_BY
-#undef T1D_S1_BY
-#undef T1D_LAUNCH_S1D
-#undef T1D_LAUNCH_S1
-        T1D_HIP(hipGetLastError());
-        return T1D_OK;
-    }
-#define T1D_LAUNCH_STEP(V, TT, RF) do { T1D_HIP(allow_lds(c, (const void*)step_kernel<V, TT, RF>, dyn)); \
-        hipLaunchKernelGGL((step_kernel<V, TT, RF>), grid_for(b->n), dim3(kBlock), dyn, s, make_args<TT>(c, b, minutes, n_sub)); } while (0)
-#define T1D_BY_VARIANT(TT, RF, V67) do { switch (variant) { case 0: T1D_LAUNCH_STEP(0, TT, RF); break; case 3: T1D_LAUNCH_STEP(3, TT, RF); break; \
-                                                            case 4: T1D_LAUNCH_STEP(4, TT, RF); break; default: T1D_LAUNCH_STEP(V67, TT, RF); break; } } while (0)
-    if (split_refill) {          // the refill ran ahead (or none is due): the kernel compiled without it
-        if (b->dtype == T1D_F64) T1D_BY_VARIANT(double, false, 7); else T1D_BY_VARIANT(float, false, 6);
-    } else {
-        if (b->dtype == T1D_F64) T1D_BY_VARIANT(double, true, 7); else T1D_BY_VARIANT(float, true, 6);
-    }
-#undef T1D_BY_VARIANT
-#undef T1D_LAUNCH_STEP
+    rc = p.f64 ? launch_plan<double>(c, b, p, minutes, n_sub, PidArgs<double>{}, s) : launch_plan<float>(c, b, p, minutes, n_sub, PidArgs<float>{}, s);
+    if (rc) return rc;
     T1D_HIP(hipGetLastError());
     return T1D_OK;
 }
@@ -686,68 +711,35 @@ static PidArgs<T> make_bb(const t1d_bb* p, int n_steps)
     return c;
 }
 
-template <typename MK64, typename MK32>
-static int launch_rollout(const char* who, t1d_ctx* c, const t1d_batch* b, int n_steps, int minutes, int n_sub, void* stream,
-                          MK64 mk64, MK32 mk32)
+// all n_steps in one launch of rollout_pid_kernel, or one launch of stepn_kernel per step
+template <typename T>
+static int run_rollout(t1d_ctx* c, const t1d_batch* b, const Plan& p, const PidArgs<T>& pa, int n_steps, int minutes, int n_sub, hipStream_t s)
+{
+    if (!p.ctrl) return launch_plan<T>(c, b, p, minutes, n_sub, pa, s);
+    for (int k = 0; k < n_steps; ++k) {
+        PidArgs<T> one = pa;
+        one.n_steps = 1; one.trace_row += k;
+        const int rc = launch_plan<T>(c, b, p, minutes, n_sub, one, s);
+        if (rc) return rc;
+    }
+    return T1D_OK;
+}
+
+// a closed-loop roll-out under the PID controller pid or the basal-bolus controller bb (the other one NULL)
+static int launch_rollout(const char* who, t1d_ctx* c, const t1d_batch* b, const t1d_pid* pid, const t1d_bb* bb, int n_steps,
+                          int minutes, int n_sub, void* stream)
 {
     int rc = check_batch(who, c, b, false);
     if (rc) return rc;
     if (b->cho) return fail(T1D_E_INVALID, std::string(who) + ": dense cho is not supported, use the meal table");
     if (n_steps < 1) return fail(T1D_E_INVALID, std::string(who) + ": n_steps < 1");
-    if (minutes < 1 || minutes > 100000) return fail(T1D_E_INVALID, std::string(who) + ": minutes out of range");
-    if (n_sub < 1 || n_sub > 4096) return fail(T1D_E_INVALID, std::string(who) + ": n_sub out of range");
+    Plan p;
+    rc = plan_and_tables(who, c, b, minutes, n_sub, true, &p);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (c->integrator == 1 && !use_split(c, n_sub))
-        return fail(T1D_E_INVALID, std::string(who) + ": the split integrator needs math = 1 and n_sub in {2, 4, 6, 8}");
-    bool split = use_split(c, n_sub);
-    const size_t esz = b->dtype == T1D_F64 ? 8 : 4;
-    if (split) {
-        rc = ensure_split(c, n_sub);
-        if (rc) return rc;
-    }
-    int variant = pick_variant(c, split, b->dtype);
-    // Large batches: one launch of the persistent multi-minute kernel per step, the controller in its prologue -- the
-    // step-size rule's lanes of level 2 are set aside, where the all-steps-in-one-launch kernel runs each wave at the level
-    // of its most refined lane.  The noise-block refill goes ahead of every step as in t1d_step (the clocks are the envs').
-    const bool per_step = c->rollout_launches == 2 || (c->rollout_launches == 1 && b->n >= (b->dtype == T1D_F64 ? c->rollout_launches_min_envs : c->rollout_launches_min_envs_f32));
-    const bool split_refill = variant != 0 && c->split_refill && minutes <= (int)c->sensor[5];
-    if (per_step && c->multi_minute_kernel) {       // (a step of one minute too: the kernel takes any minutes >= 1)
-        const PersistPlan p = plan_persistent(c, b, n_sub, split, split_refill);
-        size_t dyn_n = 0;
-        const int cap = p.ok ? stepn_park_cap(c, p, esz, minutes, &dyn_n) : -1;
-        if (cap >= 0) {
-            for (int k = 0; k < n_steps; ++k) {
-                if (b->dtype == T1D_F64) {
-                    launch_refill<double>(c, b, minutes, n_sub, s);
-                    PidArgs<double> pa = mk64();
-                    pa.n_steps = 1; pa.trace_row += k;
-                    rc = launch_stepn<double, true, true>(c, b, p, cap, dyn_n, minutes, n_sub, pa, s);
-                } else {
-                    launch_refill<float>(c, b, minutes, n_sub, s);
-                    PidArgs<float> pa = mk32();
-                    pa.n_steps = 1; pa.trace_row += k;
-                    rc = launch_stepn<float, true, true>(c, b, p, cap, dyn_n, minutes, n_sub, pa, s);
-                }
-                if (rc) return rc;
-            }
-            T1D_HIP(hipGetLastError());
-            return T1D_OK;
-        }
-    }
-    size_t dyn = 0;
-    if (split && !generic_split_fits(c, n_sub, esz, &dyn)) {
-        if (c->integrator == 1) return fail(T1D_E_INVALID, std::string(who) + ": split tables exceed the LDS of a workgroup; use integrator 0 or -1");
-        split = false; dyn = 0;
-        variant = pick_variant(c, split, b->dtype);
-    }
-#define T1D_LAUNCH_ROLL(V, TT, MK) do { T1D_HIP(allow_lds(c, (const void*)rollout_pid_kernel<V, TT>, dyn)); \
-        hipLaunchKernelGGL((rollout_pid_kernel<V, TT>), grid_for(b->n), dim3(kBlock), dyn, s, make_args<TT>(c, b, minutes, n_sub), MK()); } while (0)
-#define T1D_BY_VARIANT(TT, MK, V67) do { switch (variant) { case 0: T1D_LAUNCH_ROLL(0, TT, MK); break; case 3: T1D_LAUNCH_ROLL(3, TT, MK); break; \
-                                                            case 4: T1D_LAUNCH_ROLL(4, TT, MK); break; default: T1D_LAUNCH_ROLL(V67, TT, MK); break; } } while (0)
-    if (b->dtype == T1D_F64) T1D_BY_VARIANT(double, mk64, 7);
-    else T1D_BY_VARIANT(float, mk32, 6);
-#undef T1D_BY_VARIANT
-#undef T1D_LAUNCH_ROLL
+    if (p.f64) rc = run_rollout<double>(c, b, p, pid ? make_pid<double>(pid, n_steps) : make_bb<double>(bb, n_steps), n_steps, minutes, n_sub, s);
+    else rc = run_rollout<float>(c, b, p, pid ? make_pid<float>(pid, n_steps) : make_bb<float>(bb, n_steps), n_steps, minutes, n_sub, s);
+    if (rc) return rc;
     T1D_HIP(hipGetLastError());
     return T1D_OK;
 }
@@ -756,8 +748,7 @@ extern "C" int t1d_rollout_pid(t1d_ctx* c, const t1d_batch* b, const t1d_pid* pi
                                int n_sub, void* stream)
 {
     if (!pid || !pid->integ || !pid->prev) return fail(T1D_E_INVALID, "t1d_rollout_pid: pid state is NULL");
-    return launch_rollout("t1d_rollout_pid", c, b, n_steps, minutes, n_sub, stream,
-                          [&] { return make_pid<double>(pid, n_steps); }, [&] { return make_pid<float>(pid, n_steps); });
+    return launch_rollout("t1d_rollout_pid", c, b, pid, nullptr, n_steps, minutes, n_sub, stream);
 }
 
 extern "C" int t1d_rollout_bb(t1d_ctx* c, const t1d_batch* b, const t1d_bb* bb, int n_steps, int minutes,
@@ -765,8 +756,7 @@ extern "C" int t1d_rollout_bb(t1d_ctx* c, const t1d_batch* b, const t1d_bb* bb, 
 {
     if (!bb || !bb->basal || !bb->cr || !bb->cf || !bb->prev_meal)
         return fail(T1D_E_INVALID, "t1d_rollout_bb: basal / cr / cf / prev_meal must be set");
-    return launch_rollout("t1d_rollout_bb", c, b, n_steps, minutes, n_sub, stream,
-                          [&] { return make_bb<double>(bb, n_steps); }, [&] { return make_bb<float>(bb, n_steps); });
+    return launch_rollout("t1d_rollout_bb", c, b, nullptr, bb, n_steps, minutes, n_sub, stream);
 }
 
 extern "C" int t1d_random_meals(int hip_device, uint64_t seed, int64_t env_offset, int64_t n, int dtype, int days,
@@ -835,6 +825,14 @@ extern "C" int t1d_philox_normals(t1d_ctx* c, uint64_t seed, int64_t env_offset,
     return T1D_OK;
 }
 
+template <typename T>
+static void launch_rhs(const t1d_ctx* c, int64_t n, int math, const void* x, const int32_t* pid, const void* cho, const void* insulin,
+                       const void* last_qsto, const void* last_food, void* dxdt, const T* par, hipStream_t s)
+{
+    hipLaunchKernelGGL((math ? rhs_kernel<1, T> : rhs_kernel<0, T>), grid_for(n), dim3(kBlock), 0, s, n, (const T*)x, pid, (const T*)cho,
+                       (const T*)insulin, (const T*)last_qsto, (const T*)last_food, (T*)dxdt, par, c->np, c->d_status);
+}
+
 extern "C" int t1d_model_rhs(t1d_ctx* c, int dtype, int64_t n, int math, const void* x, const int32_t* pid, const void* cho,
                              const void* insulin, const void* last_qsto, const void* last_food, void* dxdt, void* stream)
 {
@@ -844,11 +842,8 @@ extern "C" int t1d_model_rhs(t1d_ctx* c, int dtype, int64_t n, int math, const v
     if (math != 0 && math != 1) return fail(T1D_E_INVALID, "t1d_model_rhs: math must be 0 or 1");
     T1D_HIP(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-#define T1D_RHS(M, TT, PAR) hipLaunchKernelGGL((rhs_kernel<M, TT>), grid_for(n), dim3(kBlock), 0, s, n, (const TT*)x, pid, (const TT*)cho, \
-                                               (const TT*)insulin, (const TT*)last_qsto, (const TT*)last_food, (TT*)dxdt, (const TT*)PAR, c->np, c->d_status)
-    if (dtype == T1D_F64) { if (math) T1D_RHS(1, double, c->d_par64); else T1D_RHS(0, double, c->d_par64); }
-    else { if (math) T1D_RHS(1, float, c->d_par32); else T1D_RHS(0, float, c->d_par32); }
-#undef T1D_RHS
+    if (dtype == T1D_F64) launch_rhs<double>(c, n, math, x, pid, cho, insulin, last_qsto, last_food, dxdt, c->d_par64, s);
+    else launch_rhs<float>(c, n, math, x, pid, cho, insulin, last_qsto, last_food, dxdt, c->d_par32, s);
     T1D_HIP(hipGetLastError());
     return T1D_OK;
 }
