@@ -15,6 +15,7 @@
  *                         (replaced by fixed-step schemes built on n_sub sub-steps per minute: the split
  *                          integrator with per-minute step sizes by default, classical RK4 on request --
  *                          t1d_ctx_set_option "integrator" / "adaptive_gut")
+ *   t1d_step_dopri5  <- the same step with scipy's dopri5 itself (the exact mode)
  *                       CGMSensor.measure / CGMNoise    simglucose/sensor/cgm.py:26-36, noise_gen.py:30-97
  *                       risk_index / risk_diff          simglucose/analysis/risk.py:5-17, env.py:27-33
  *   t1d_model_rhs    <- T1DPatient.model               simglucose/patient/t1dpatient.py:119-208
@@ -62,7 +63,9 @@ enum {
     T1D_ST_NORMALS_EXHAUSTED = 1,   /* host-normals mode ran past n_normals rows; zeros were used */
     T1D_ST_NONFINITE = 2,           /* some env's state became NaN/Inf */
     T1D_ST_BAD_INDEX = 4,           /* t1d_model_rhs: a patient index outside the context's table (row 0 was used) */
-    T1D_ST_STALL = 8                /* a wave of a persistent kernel gave up waiting for its workgroup (never, by design): results invalid */
+    T1D_ST_STALL = 8,               /* a wave of a persistent kernel gave up waiting for its workgroup (never, by design): results invalid */
+    T1D_ST_SOLVER_FAILED = 16       /* t1d_step_dopri5: some env's solver gave up (step budget or step underflow; the reference raises
+                                       "ODE solver failed"): that env kept its last accepted state for the rest of the call */
 };
 
 /* columns of one row of the patient table given to t1d_ctx_create (all double):
@@ -280,6 +283,17 @@ int t1d_reset(t1d_ctx* ctx, const t1d_batch* b, const uint8_t* mask, int random_
 /* Advance every env by `minutes` (normally int(sample_time)) with one kernel launch, the same
  * action held for the whole call; integrator and step sizes as set on the context, built on n_sub sub-steps per minute. */
 int t1d_step(t1d_ctx* ctx, const t1d_batch* b, int minutes, int n_sub, void* hip_stream);
+
+/* SciPy's DOPRI5 as the reference drives it (t1dpatient.py:110-113,276; rtol 1e-6, atol 1e-12, re-entered every minute,
+ * predicted step carried between minutes).  fp64 batches only.  h_carry: device double [n], the predicted step of each env,
+ * read and written; 0 = probe for an initial step (what the reference does after reset -- the caller zeroes it for every
+ * env it resets).  nfev: device int32 [n] or NULL, RHS evaluations of each env in this call.  Any state layout.
+ * Otherwise as t1d_step (n_sub does not apply).  One lane per env runs its own accept/reject loop, so a launch lasts as long
+ * as the slowest env of each wave: on random-meal days 10.5 RHS evaluations per env-minute on average, 46.9 for the
+ * slowest lane of a wave (1 Mi fp64 envs: 3.6 ms per one-minute launch).
+ * An env whose solver gives up (500 steps in a minute, or a step below the resolution of t) keeps its last accepted
+ * state for the rest of the call and raises T1D_ST_SOLVER_FAILED.  The roll-out entry points have no DOPRI5 path. */
+int t1d_step_dopri5(t1d_ctx* ctx, const t1d_batch* b, double* h_carry, int32_t* nfev, int minutes, void* hip_stream);
 
 /* n_steps closed-loop steps in ONE launch: basal = PID(obs CGM), bolus = 0, then as t1d_step.
  * b->cgm must hold the current observation on entry (as left by t1d_reset / t1d_step). */

@@ -8,11 +8,12 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("T1D_LIB_PATH") or os.path.join(_PKG, "libt1d_hip.so")   # override: A/B builds only
 SOURCES = [os.path.join(_PKG, "csrc", "t1d_abi.hip"), os.path.join(_PKG, "csrc", "t1d_kernels.hpp"),
-           os.path.join(_PKG, "csrc", "t1d_device.hpp"),
+           os.path.join(_PKG, "csrc", "t1d_device.hpp"), os.path.join(_PKG, "csrc", "t1d_dopri5.hpp"),
            os.path.join(_ROOT, "include", "t1d.h")]
 
 T1D_F64, T1D_F32 = 0, 1
 T1D_ST_NORMALS_EXHAUSTED, T1D_ST_NONFINITE, T1D_ST_BAD_INDEX, T1D_ST_STALL = 1, 2, 4, 8
+T1D_ST_SOLVER_FAILED = 16
 ABI_VERSION = 4
 T1D_BATCH_NO_PUMP = 2
 T1D_BATCH_NO_REFILL_DUE = 4
@@ -23,7 +24,7 @@ META_EATING = 0x100
 
 EXPORTS = ("t1d_abi_version", "t1d_last_error", "t1d_ctx_create", "t1d_ctx_set_option", "t1d_ctx_destroy", "t1d_reset",
            "t1d_step", "t1d_rollout_pid", "t1d_philox_normals", "t1d_sync", "t1d_split_tables",
-           "t1d_rollout_bb", "t1d_random_meals", "t1d_outcome_stats", "t1d_model_rhs")
+           "t1d_rollout_bb", "t1d_random_meals", "t1d_outcome_stats", "t1d_model_rhs", "t1d_step_dopri5")
 
 
 class T1DError(RuntimeError):
@@ -132,6 +133,7 @@ def lib():
     L.t1d_ctx_set_option.argtypes = [vp, C.c_char_p, i64]
     L.t1d_reset.argtypes = [vp, C.POINTER(Batch), vp, C.c_int, vp]
     L.t1d_step.argtypes = [vp, C.POINTER(Batch), C.c_int, C.c_int, vp]
+    L.t1d_step_dopri5.argtypes = [vp, C.POINTER(Batch), vp, vp, C.c_int, vp]
     L.t1d_rollout_pid.argtypes = [vp, C.POINTER(Batch), C.POINTER(Pid), C.c_int, C.c_int, C.c_int, vp]
     L.t1d_rollout_bb.argtypes = [vp, C.POINTER(Batch), C.POINTER(Bb), C.c_int, C.c_int, C.c_int, vp]
     L.t1d_random_meals.argtypes = [C.c_int, u64, i64, i64, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]

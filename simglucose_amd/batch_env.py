@@ -6,6 +6,8 @@ env are those of the reference's ``simglucose/simulation/env.py`` ``T1DSimEnv.re
 of ``T1DPatient`` + ``CGMSensor`` + ``InsulinPump`` + a meal scenario; instead of SciPy's adaptive DOPRI5 the ODE is
 integrated by the library's split scheme built on ``n_sub`` sub-steps per minute, with per-minute step sizes chosen by a
 deterministic rule (``adaptive_gut``), or by classical RK4 (``set_option("integrator", 0)``).
+``integrator="dopri5"`` runs SciPy's DOPRI5 itself as the reference drives it (t1d_step_dopri5): the reference's numbers,
+at a few times the cost.
 """
 import ctypes as C
 
@@ -32,12 +34,21 @@ class BatchedT1DSimEnv:
            samples -- so that ``step(..., reward_fun=f)`` works on the batch: ``f(window)`` gets a ``[window, n]``
            tensor, oldest sample first, NaN where an episode is younger than that, and returns ``[n]`` rewards.
            Off by default: the fused default reward (risk_diff) needs only the previous sample.
+    integrator: None = the library's fixed-step schemes (above); "dopri5" = the exact mode, scipy's dopri5 with the
+           reference's tolerances re-entered every minute (t1d_step_dopri5; fp64 only, n_sub ignored).  The predicted step of
+           each env is kept in ``h_carry`` (fp64 [n], zeroed by reset) and the RHS evaluations of the last step in ``nfev``
+           (int32 [n]).  The roll-out kernels have no DOPRI5 path: loop step() instead.
     """
 
     def __init__(self, patient="adolescent#001", n_envs=None, sensor="Dexcom", pump="Insulet",
                  dtype=torch.float64, device="cuda:0", n_sub=4, seed=0, env_offset=0, noise="philox",
                  normals=None, random_init_bg=False, extra_outputs=True, sensor_row=None, pump_row=None,
-                 patient_table=None, use_pump=True, adaptive_gut=True, cgm_history=False):
+                 patient_table=None, use_pump=True, adaptive_gut=True, cgm_history=False, integrator=None):
+        if integrator not in (None, "dopri5"):
+            raise ValueError("integrator must be None or 'dopri5'")
+        if integrator == "dopri5" and dtype != torch.float64:
+            raise ValueError("integrator='dopri5' needs dtype=torch.float64")
+        self.integrator = integrator
         self._L = _lib.lib()                     # raises T1DError if the HIP extension is missing
         if not torch.cuda.is_available():
             raise _lib.T1DError("BatchedT1DSimEnv needs a ROCm GPU (torch.cuda.is_available() is False)")
@@ -108,6 +119,11 @@ class BatchedT1DSimEnv:
         else:
             self.lbgi = self.hbgi = self.risk = self.meal = self.insulin = None
         self._zero_action = z(n)
+        if integrator == "dopri5":
+            self.h_carry = z(n, dt=torch.float64)          # predicted step per env; 0 = probe for one (after reset)
+            self.nfev = z(n, dt=torch.int32)               # RHS evaluations per env in the last step
+        else:
+            self.h_carry = self.nfev = None
         self._basal_buf = z(n); self._bolus_buf = z(n)
         self.meal_time = None; self.meal_amt = None
         self.normals = None
@@ -235,6 +251,11 @@ class BatchedT1DSimEnv:
         self._clock = 0 if mask is None else None
         with torch.cuda.device(self.device):
             _lib.check(self._L.t1d_reset(self._ctx, C.byref(b), mptr, int(self.random_init_bg), self._stream()))
+        if self.h_carry is not None:                      # scipy's solver is built afresh by T1DPatient.reset
+            if mask is None:
+                self.h_carry.zero_()
+            else:
+                self.h_carry.masked_fill_(mask.bool(), 0.0)
         self._iver = self.istate._version
         b.x0_override = None
         self._keep = (keep, mask)
@@ -274,7 +295,11 @@ class BatchedT1DSimEnv:
                 b.flags = self._flags0 | _lib.T1D_BATCH_NO_REFILL_DUE
         clock, self._clock = self._clock, None        # the shadow clock survives only a call that went through
         with torch.cuda.device(self.device):
-            _lib.check(self._L.t1d_step(self._ctx, C.byref(b), minutes, self.n_sub, self._stream()))
+            if self.integrator == "dopri5":
+                _lib.check(self._L.t1d_step_dopri5(self._ctx, C.byref(b), C.c_void_p(self.h_carry.data_ptr()),
+                                                   C.c_void_p(self.nfev.data_ptr()), minutes, self._stream()))
+            else:
+                _lib.check(self._L.t1d_step(self._ctx, C.byref(b), minutes, self.n_sub, self._stream()))
         if clock is not None:
             self._clock = clock + minutes
         self._keep = (bas, cho)
@@ -332,10 +357,15 @@ class BatchedT1DSimEnv:
             tr["cgm"][0] = self.cgm0
         return tr
 
+    def _no_dopri5_rollout(self):
+        if self.integrator == "dopri5":
+            raise _lib.T1DError("the roll-out kernels have no DOPRI5 path: loop step() on an env with integrator='dopri5'")
+
     def rollout_pid(self, n_steps, P, I, D, target=140.0, pid_state=None, stats=None, trace=None):
         """n_steps closed-loop PID steps in one launch (PIDController.policy + env.step per step).
         pid_state: dict(integ, prev) tensors [n] (created zeroed if None).  stats: optional dict
         with any of sum_risk, min_bg, max_bg (float [n]) and n_low, n_high (int32 [n])."""
+        self._no_dopri5_rollout()
         if pid_state is None:
             pid_state = {"integ": torch.zeros(self.n, dtype=self.dtype, device=self.device),
                          "prev": torch.zeros(self.n, dtype=self.dtype, device=self.device)}
@@ -377,6 +407,7 @@ class BatchedT1DSimEnv:
         the previous observation and the previous step's announced meal, then env.step).  bb_state: dict with
         basal, cr, cf (see bb_constants) and prev_meal [n] (created if None; prev_meal = 0 right after reset).
         Meals come from the meal tables (set_meals).  stats as in rollout_pid."""
+        self._no_dopri5_rollout()
         if bb_state is None:
             bb_state = self.bb_constants()
             bb_state["prev_meal"] = torch.zeros(self.n, dtype=self.dtype, device=self.device)
@@ -442,6 +473,8 @@ class BatchedT1DSimEnv:
     def state_dict(self):
         sd = {k: getattr(self, k).clone() for k in _STATE_KEYS + ("cgm", "cgm0")}
         sd["format"] = self.STATE_FORMAT
+        if self.h_carry is not None:
+            sd["h_carry"] = self.h_carry.clone()
         if self._hist is not None:
             sd.update({k: getattr(self, k).clone() for k in ("_hist", "_hist_pos", "_hist_cnt")})
         return sd
@@ -451,8 +484,13 @@ class BatchedT1DSimEnv:
         if fmt != self.STATE_FORMAT or any(k not in sd for k in _STATE_KEYS + ("cgm", "cgm0")):
             raise _lib.T1DError("checkpoint format %r is not %d (checkpoints written before ABI 3 carry prev_cgm instead of "
                                 "prev_risk and no cgm0, before ABI 4 no dbar): re-create it with this version" % (fmt, self.STATE_FORMAT))
+        if self.h_carry is not None and "h_carry" not in sd:
+            raise _lib.T1DError("an env with integrator='dopri5' needs the checkpoint's h_carry (the predicted step of every env): "
+                                "take it from an env with integrator='dopri5'")
         for k in _STATE_KEYS + ("cgm", "cgm0"):
             getattr(self, k).copy_(sd[k])
+        if self.h_carry is not None:
+            self.h_carry.copy_(sd["h_carry"])
         if self._hist is not None:
             if all(k in sd for k in ("_hist", "_hist_pos", "_hist_cnt")):
                 for k in ("_hist", "_hist_pos", "_hist_cnt"):

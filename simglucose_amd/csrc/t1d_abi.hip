@@ -4,6 +4,7 @@
 // t1d_device.hpp.  This is the one translation unit of the library.
 #include "../../include/t1d.h"
 #include "t1d_kernels.hpp"
+#include "t1d_dopri5.hpp"
 
 #include <climits>
 #include <cmath>
@@ -24,6 +25,7 @@ struct t1d_ctx {
     double sensor[T1D_SENSOR_NCOLS];
     double pump[T1D_PUMP_NCOLS];
     double* d_par64 = nullptr; float* d_par32 = nullptr;
+    double* d_raw64 = nullptr;   // [kRawPars][kMaxPatients] the caller's model columns as they are (t1d_step_dopri5)
     double* d_x0 = nullptr;
     double* d_minv64 = nullptr; float* d_minv32 = nullptr;
     int* d_status = nullptr;
@@ -292,6 +294,9 @@ extern "C" int t1d_ctx_create(int hip_device, const double* ptab, int n_patients
             set(DP_CF, r[T1D_P_F] / r[T1D_P_BW]);
             for (int k = 0; k < 13; ++k) x0[(size_t)k * np + j] = r[T1D_P_X0 + k];
         }
+        std::vector<double> raw((size_t)kRawPars * kMaxPatients, 0.0);
+        for (int j = 0; j < np; ++j)
+            for (int k = 0; k < kRawPars; ++k) raw[(size_t)k * kMaxPatients + j] = ptab[(size_t)j * n_cols + T1D_P_BW + k];
         c->ptab.assign(ptab, ptab + (size_t)np * n_cols);
         c->dpar = dp;
         c->np_pad = (np + 1) & ~1;
@@ -307,6 +312,7 @@ extern "C" int t1d_ctx_create(int hip_device, const double* ptab, int n_patients
         if (e == hipSuccess) e = up((void**)&c->d_par64, dp.data(), dp.size() * 8);
         if (e == hipSuccess) e = up((void**)&c->d_par32, dpf.data(), dpf.size() * 4);
         if (e == hipSuccess) e = up((void**)&c->d_x0, x0.data(), x0.size() * 8);
+        if (e == hipSuccess) e = up((void**)&c->d_raw64, raw.data(), raw.size() * 8);
         if (e == hipSuccess) e = up((void**)&c->d_minv64, minv.data(), minv.size() * 8);
         if (e == hipSuccess) e = up((void**)&c->d_minv32, minvf.data(), minvf.size() * 4);
 #if T1D_S1_TRACE
@@ -367,7 +373,7 @@ extern "C" int t1d_ctx_destroy(t1d_ctx* c)
     (void)hipSetDevice(c->device);
     (void)hipFree(c->d_par64); (void)hipFree(c->d_par32); (void)hipFree(c->d_x0);
     (void)hipFree(c->d_minv64); (void)hipFree(c->d_minv32); (void)hipFree(c->d_status);
-    (void)hipFree(c->d_prop64); (void)hipFree(c->d_prop32); (void)hipFree(c->d_trace);
+    (void)hipFree(c->d_prop64); (void)hipFree(c->d_prop32); (void)hipFree(c->d_trace); (void)hipFree(c->d_raw64);
     delete c;
     return T1D_OK;
 }
@@ -679,6 +685,23 @@ extern "C" int t1d_step(t1d_ctx* c, const t1d_batch* b, int minutes, int n_sub, 
     hipStream_t s = (hipStream_t)stream;
     rc = p.f64 ? launch_plan<double>(c, b, p, minutes, n_sub, PidArgs<double>{}, s) : launch_plan<float>(c, b, p, minutes, n_sub, PidArgs<float>{}, s);
     if (rc) return rc;
+    T1D_HIP(hipGetLastError());
+    return T1D_OK;
+}
+
+// The exact mode (t1d_dopri5.hpp): one lane per env on the grid of the generic kernel, whatever the layout; no plan, no
+// refill ahead (the noise-block refill runs inline).
+extern "C" int t1d_step_dopri5(t1d_ctx* c, const t1d_batch* b, double* h_carry, int32_t* nfev, int minutes, void* stream)
+{
+    if (!c) return fail(T1D_E_INVALID, "t1d_step_dopri5: ctx is NULL");
+    if (!b) return fail(T1D_E_INVALID, "t1d_step_dopri5: batch is NULL");
+    if (!h_carry) return fail(T1D_E_INVALID, "t1d_step_dopri5: h_carry is NULL");
+    if (b->dtype != T1D_F64) return fail(T1D_E_INVALID, "t1d_step_dopri5: fp64 batches only");
+    if (minutes < 1 || minutes > 100000) return fail(T1D_E_INVALID, "t1d_step_dopri5: minutes out of range");
+    const int rc = check_batch("t1d_step_dopri5", c, b, true);
+    if (rc) return rc;
+    hipLaunchKernelGGL(dopri5_step_kernel, grid_for(b->n), dim3(kBlock), 0, (hipStream_t)stream, make_args<double>(c, b, minutes, 1),
+                       (const double*)c->d_raw64, h_carry, nfev);
     T1D_HIP(hipGetLastError());
     return T1D_OK;
 }

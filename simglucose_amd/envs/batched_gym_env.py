@@ -25,7 +25,7 @@ class BatchedGymT1DSimEnv(object):
     INSULIN_PUMP_HARDWARE = "Insulet"
 
     def __init__(self, n_envs, patient_name="adolescent#001", seed=0, device="cuda:0", dtype=torch.float64,
-                 exact=False, auto_reset=False, horizon_days=2, n_sub=4, env_offset=0, reward_fun=None):
+                 exact=False, auto_reset=False, horizon_days=2, n_sub=4, env_offset=0, reward_fun=None, integrator=None):
         self.n = int(n_envs)
         names = [patient_name] * self.n if isinstance(patient_name, str) else list(patient_name)
         self.patient_names = names
@@ -37,7 +37,7 @@ class BatchedGymT1DSimEnv(object):
         self.env = BatchedT1DSimEnv(patient=names, sensor=self.SENSOR_HARDWARE, pump=self.INSULIN_PUMP_HARDWARE,
                                     dtype=dtype, device=device, n_sub=n_sub, seed=self.seed_value,
                                     env_offset=env_offset, noise="philox", random_init_bg=not exact,
-                                    cgm_history=reward_fun is not None)
+                                    cgm_history=reward_fun is not None, integrator=integrator)
         self.start_hour = torch.zeros(self.n, dtype=torch.int64, device=self.env.device)
         self.max_basal = float(self.env.pump_row[4])
 

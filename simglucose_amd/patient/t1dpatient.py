@@ -25,8 +25,11 @@ class T1DPatient(Patient):
     SAMPLE_TIME = 1      # min
     EAT_RATE = 5         # g/min CHO
 
-    def __init__(self, params, init_state=None, random_init_bg=False, seed=None, t0=0):
-        self._params = params.copy()       # own copy: reset() writes random_init_bg draws back into it
+    def __init__(self, params, init_state=None, random_init_bg=False, seed=None, t0=0, integrator=None):
+        """integrator applies to the patient's own one-env batch (step() without a T1DSimEnv): None = the library's
+        fixed-step schemes, "dopri5" = scipy's dopri5 as the reference runs it."""
+        self._params = params.copy()
+        self.integrator = integrator       # own copy: reset() writes random_init_bg draws back into it
         self._init_state = init_state
         self.random_init_bg = random_init_bg
         self._seed = seed
@@ -62,7 +65,7 @@ class T1DPatient(Patient):
         if self._env is None:
             from ..batch_env import BatchedT1DSimEnv
             self._own_env = BatchedT1DSimEnv(patient="custom", n_envs=1, patient_table=self.table_row(),
-                                             sensor="Navigator", noise="philox", use_pump=False)
+                                             sensor="Navigator", noise="philox", use_pump=False, integrator=self.integrator)
             self._env = self._own_env
             self._env.reset(x0=np.asarray(self.init_state, dtype=np.float64).reshape(13, 1))
         return self._env

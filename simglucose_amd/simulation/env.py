@@ -39,12 +39,15 @@ def risk_diff(BG_last_hour):
 
 
 class T1DSimEnv(object):
-    def __init__(self, patient, sensor, pump, scenario, n_sub=4):
+    def __init__(self, patient, sensor, pump, scenario, n_sub=4, integrator=None):
+        """integrator: None = the library's fixed-step schemes on n_sub sub-steps; "dopri5" = scipy's dopri5 as the
+        reference runs it (BatchedT1DSimEnv: the reference's numbers)."""
         self.patient = patient
         self.sensor = sensor
         self.pump = pump
         self.scenario = scenario
         self.n_sub = n_sub
+        self.integrator = integrator
         self._batch = None
         self.viewer = None
         self._device_reset()
@@ -58,7 +61,8 @@ class T1DSimEnv(object):
         if self._batch is None:
             self._batch = BatchedT1DSimEnv(patient="custom", n_envs=1, patient_table=self.patient.table_row(),
                                            sensor_row=self.sensor.row(), pump_row=self.pump.row(), noise="host",
-                                           normals=self.sensor.normals(n_draws).reshape(-1, 1), n_sub=self.n_sub)
+                                           normals=self.sensor.normals(n_draws).reshape(-1, 1), n_sub=self.n_sub,
+                                           integrator=self.integrator)
         else:
             self._batch.set_normals(self.sensor.normals(n_draws).reshape(-1, 1))
         self._n_draws = n_draws
