@@ -22,6 +22,7 @@
  *   t1d_rollout_pid  <- SimObj.simulate loop with       simglucose/simulation/sim_engine.py:29-39
  *                       PIDController.policy            simglucose/controller/pid_ctrller.py:17-36
  *   t1d_rollout_bb   <- the same loop with BBController  simglucose/controller/basal_bolus_ctrller.py:34-80
+ *   t1d_rollout_pid_dopri5, t1d_rollout_bb_dopri5 <- the two loops with scipy's dopri5 itself (the exact mode)
  *   t1d_random_meals <- RandomScenario.create_scenario  simglucose/simulation/scenario_gen.py:33-60
  *   t1d_outcome_stats<- percent_stats, risk_index_trace, simglucose/analysis/report.py:74-133,198-217
  *                       CVGA_analysis
@@ -292,7 +293,8 @@ int t1d_step(t1d_ctx* ctx, const t1d_batch* b, int minutes, int n_sub, void* hip
  * as the slowest env of each wave: on random-meal days 10.5 RHS evaluations per env-minute on average, 46.9 for the
  * slowest lane of a wave (1 Mi fp64 envs: 3.6 ms per one-minute launch).
  * An env whose solver gives up (500 steps in a minute, or a step below the resolution of t) keeps its last accepted
- * state for the rest of the call and raises T1D_ST_SOLVER_FAILED.  The roll-out entry points have no DOPRI5 path. */
+ * state for the rest of the call and raises T1D_ST_SOLVER_FAILED.  Closed-loop roll-outs in this mode: t1d_rollout_pid_dopri5 /
+ * t1d_rollout_bb_dopri5 below. */
 int t1d_step_dopri5(t1d_ctx* ctx, const t1d_batch* b, double* h_carry, int32_t* nfev, int minutes, void* hip_stream);
 
 /* n_steps closed-loop steps in ONE launch: basal = PID(obs CGM), bolus = 0, then as t1d_step.
@@ -307,6 +309,28 @@ int t1d_rollout_pid(t1d_ctx* ctx, const t1d_batch* b, const t1d_pid* pid, int n_
  * meal tables.  Outputs/state as t1d_rollout_pid; bb.prev_meal is updated. */
 int t1d_rollout_bb(t1d_ctx* ctx, const t1d_batch* batch, const t1d_bb* bb, int n_steps, int minutes,
                    int n_sub, void* stream);
+
+/* SimObj.simulate (sim_engine.py:29-39) with PIDController.policy (pid_ctrller.py:17-36) and the integrator of
+ * t1d_step_dopri5, scipy's dopri5 as the reference drives it (t1dpatient.py:110-113,276): t1d_rollout_pid (controller,
+ * b->cgm on entry, accumulators, traces, the last step's reward) in the exact mode.  All n_steps steps of `minutes` minutes
+ * are ONE launch in which every env walks through its own minutes at its own pace: the body of the kernel's one loop is one
+ * step attempt of the driver, and an env that completes a minute finishes it and opens its next one without waiting for the
+ * other 63 envs of its wave.  A wave then lasts as long as the env with the largest total of step attempts over the launch,
+ * not as the per-minute maxima summed up (random-meal days, RHS evaluations per env-minute: mean 9.7, per-minute maximum of a
+ * wave 39.8, largest 240-minute total of a wave 13.8).  Envs never exchange data and the controller is evaluated without FMA
+ * contraction, like the solver: the results are those of a loop of t1d_step_dopri5 with the controller computed operation
+ * by operation between the calls, bit for bit, whatever the other envs of the batch do.
+ * h_carry: device double [n], read and written, 0 = probe (as t1d_step_dopri5); nfev: device int32 [n] or NULL, the RHS
+ * evaluations of each env over the whole call.  fp64 batches only; meals from the meal tables.  An env whose solver gives
+ * up keeps its last accepted state for the rest of the call (its clock, meals and noise go on) and raises
+ * T1D_ST_SOLVER_FAILED; the other envs are unaffected. */
+int t1d_rollout_pid_dopri5(t1d_ctx* ctx, const t1d_batch* b, const t1d_pid* pid, double* h_carry, int32_t* nfev,
+                           int n_steps, int minutes, void* hip_stream);
+
+/* The same with BBController (basal_bolus_ctrller.py:34-80; sim_engine.py:29-39; t1dpatient.py:110-113,276): t1d_rollout_bb
+ * in the exact mode -- the reference's own regression run (sim_results.csv).  bb.prev_meal is updated. */
+int t1d_rollout_bb_dopri5(t1d_ctx* ctx, const t1d_batch* b, const t1d_bb* bb, double* h_carry, int32_t* nfev,
+                          int n_steps, int minutes, void* hip_stream);
 
 /* RandomScenario.create_scenario (simulation/scenario_gen.py:33-60) for n envs on the device: fills per-env
  * meal tables meal_time int32 [6 (days + 1)][n] (minutes since the episode start, ascending, unused =

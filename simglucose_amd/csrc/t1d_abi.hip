@@ -782,6 +782,42 @@ extern "C" int t1d_rollout_bb(t1d_ctx* c, const t1d_batch* b, const t1d_bb* bb, 
     return launch_rollout("t1d_rollout_bb", c, b, nullptr, bb, n_steps, minutes, n_sub, stream);
 }
 
+// The exact mode's roll-outs (t1d_dopri5.hpp): all n_steps in one launch of dopri5_rollout_kernel on the grid of
+// dopri5_step_kernel, every lane at its own pace; no plan, no refill ahead.  Every argument is checked before any device work.
+static int launch_rollout_dopri5(const char* who, t1d_ctx* c, const t1d_batch* b, const t1d_pid* pid, const t1d_bb* bb,
+                                 double* h_carry, int32_t* nfev, int n_steps, int minutes, void* stream)
+{
+    const std::string w(who);
+    if (!c) return fail(T1D_E_INVALID, w + ": ctx is NULL");
+    if (!b) return fail(T1D_E_INVALID, w + ": batch is NULL");
+    if (!h_carry) return fail(T1D_E_INVALID, w + ": h_carry is NULL");
+    if (b->dtype != T1D_F64) return fail(T1D_E_INVALID, w + ": fp64 batches only");
+    if (n_steps < 1) return fail(T1D_E_INVALID, w + ": n_steps < 1");
+    if (minutes < 1 || minutes > 100000) return fail(T1D_E_INVALID, w + ": minutes out of range");
+    if (b->cho) return fail(T1D_E_INVALID, w + ": dense cho is not supported, use the meal table");
+    const int rc = check_batch(who, c, b, false);
+    if (rc) return rc;
+    hipLaunchKernelGGL(dopri5_rollout_kernel, grid_for(b->n), dim3(kBlock), 0, (hipStream_t)stream, make_args<double>(c, b, minutes, 1),
+                       pid ? make_pid<double>(pid, n_steps) : make_bb<double>(bb, n_steps), (const double*)c->d_raw64, h_carry, nfev);
+    T1D_HIP(hipGetLastError());
+    return T1D_OK;
+}
+
+extern "C" int t1d_rollout_pid_dopri5(t1d_ctx* c, const t1d_batch* b, const t1d_pid* pid, double* h_carry, int32_t* nfev,
+                                      int n_steps, int minutes, void* stream)
+{
+    if (!pid || !pid->integ || !pid->prev) return fail(T1D_E_INVALID, "t1d_rollout_pid_dopri5: pid state is NULL");
+    return launch_rollout_dopri5("t1d_rollout_pid_dopri5", c, b, pid, nullptr, h_carry, nfev, n_steps, minutes, stream);
+}
+
+extern "C" int t1d_rollout_bb_dopri5(t1d_ctx* c, const t1d_batch* b, const t1d_bb* bb, double* h_carry, int32_t* nfev,
+                                     int n_steps, int minutes, void* stream)
+{
+    if (!bb || !bb->basal || !bb->cr || !bb->cf || !bb->prev_meal)
+        return fail(T1D_E_INVALID, "t1d_rollout_bb_dopri5: bb is NULL, or basal / cr / cf / prev_meal is not set");
+    return launch_rollout_dopri5("t1d_rollout_bb_dopri5", c, b, nullptr, bb, h_carry, nfev, n_steps, minutes, stream);
+}
+
 extern "C" int t1d_random_meals(int hip_device, uint64_t seed, int64_t env_offset, int64_t n, int dtype, int days,
                                 const int32_t* start_minute_of_day, int start_scalar, int32_t* meal_time, void* meal_amt,
                                 void* stream)

@@ -1,5 +1,6 @@
 // t1d_dopri5.hpp -- the exact mode: scipy.integrate.ode('dopri5') as the reference drives it (t1dpatient.py:110-113,276),
-// one lane per env, fp64 only.  Included by t1d_abi.hip after t1d_kernels.hpp; launched by t1d_step_dopri5 (include/t1d.h).
+// one lane per env, fp64 only.  Included by t1d_abi.hip after t1d_kernels.hpp; launched by t1d_step_dopri5 and, for closed-loop
+// roll-outs with every lane at its own pace, by t1d_rollout_pid_dopri5 / t1d_rollout_bb_dopri5 (include/t1d.h).
 //
 // The fixed-step schemes of t1d_device.hpp are close to SciPy's solution but cannot reproduce it: part of the difference is
 // SciPy's own error (tolerance 1e-6 relative), which only SciPy's algorithm repeats.  What is restated here, line for line,
@@ -13,7 +14,8 @@
 //                  beta 0.04, uround 2.3e-16, nmax 500, hmax 1; the initial-step probe only when the carried step is 0;
 //                  FSAL; the predicted step written back on the last accepted step.
 // Both bodies are compiled with FMA contraction off, as the oracle is (oracle/Makefile: -ffp-contract=off).
-// Each lane runs its own accept/reject loop; a wave runs until its slowest lane is done.  The loop ends on every input: a
+// Each lane runs its own accept/reject loop; in dopri5_step_kernel a wave runs each minute until its slowest lane is done, in
+// dopri5_rollout_kernel until the lane with the most step attempts over the launch is.  The loop ends on every input: a
 // lane gives up after nmax steps or when the step underflows (NaN states included), which the kernel reports as
 // T1D_ST_SOLVER_FAILED -- where the reference raises "ODE solver failed".
 #pragma once
@@ -120,11 +122,34 @@ __device__ __forceinline__ double dopri5_hinit(const ParsRaw& p, const double (&
     return h;
 }
 
-// t1d_o_dopri5_minute: one integrate() from x = t_start to t_start + 1.  y: the state, advanced in place (left at the last
-// accepted point if the solver gives up); h_carry: the predicted step, read (0 = probe) and written on success; nfcn: RHS
-// evaluations of this call, added.  Returns false where the driver gives up (nmax steps, or a step below the resolution of x).
-__device__ __forceinline__ bool dopri5_minute(const ParsRaw& p, double (&y)[13], double d, double ins, double lq, double lf,
-                                              double& h_carry, double t_start, int& nfcn)
+// t1d_o_dopri5_minute: one integrate() from x = t_start to t_start + 1, in resumable form so that a kernel can walk a lane
+// through its minutes one step attempt at a time (dopri5_rollout_kernel) or run a minute to its end (dopri5_minute).
+// Dopri5Run: the words the driver carries from one step attempt to the next.
+struct Dopri5Run {
+    double x, h, facold, k1[13];
+    int nstep;
+    bool last, reject;
+};
+constexpr double kDopriRtol = 1e-6, kDopriAtol = 1e-12, kDopriHmax = 1.0;
+
+// enter a minute at x = t_start: SciPy re-enters the driver every minute -- a fresh first stage and, when the carried
+// step is 0, the initial-step probe
+__device__ __forceinline__ void dopri5_enter(const ParsRaw& p, const double (&y)[13], double d, double ins, double lq, double lf,
+                                             double h_carry, double t_start, Dopri5Run& r, int& nfcn)
+{
+#pragma clang fp contract(off)
+    r.x = t_start; r.h = h_carry; r.facold = 1e-4;
+    r.nstep = 0; r.last = false; r.reject = false;
+    rhs_scipy(p, y, d, ins, lq, lf, r.k1); nfcn++;
+    if (r.h == 0.0) { r.h = dopri5_hinit(p, y, r.k1, d, ins, lq, lf, kDopriHmax, kDopriAtol, kDopriRtol); nfcn++; }
+}
+
+// one step attempt towards xend: six RHS evaluations, the error estimate, accept or reject, the next step size.
+// y: the state, advanced in place by an accepted step.  Returns 0 = go on, 1 = the minute is done (the predicted step
+// written to h_carry), -1 = the driver gives up (nmax steps, or a step below the resolution of x): y is at the last
+// accepted point.
+__device__ __forceinline__ int dopri5_attempt(const ParsRaw& p, double (&y)[13], double d, double ins, double lq, double lf,
+                                              double& h_carry, double xend, Dopri5Run& r, int& nfcn)
 {
 #pragma clang fp contract(off)
     const double a21 = 0.2, a31 = 3.0 / 40.0, a32 = 9.0 / 40.0, a41 = 44.0 / 45.0,
@@ -134,68 +159,80 @@ __device__ __forceinline__ bool dopri5_minute(const ParsRaw& p, double (&y)[13],
         a73 = 500.0 / 1113.0, a74 = 125.0 / 192.0, a75 = -2187.0 / 6784.0, a76 = 11.0 / 84.0,
         e1 = 71.0 / 57600.0, e3 = -71.0 / 16695.0, e4 = 71.0 / 1920.0, e5 = -17253.0 / 339200.0,
         e6 = 22.0 / 525.0, e7 = -1.0 / 40.0;
-    const double rtol = 1e-6, atol = 1e-12, safe = 0.9, fac1 = 0.2, fac2 = 10.0, uround = 2.3e-16, beta = 0.04;
+    const double rtol = kDopriRtol, atol = kDopriAtol, safe = 0.9, fac1 = 0.2, fac2 = 10.0, uround = 2.3e-16, beta = 0.04;
     const int nmax = 500;
     const double expo1 = 0.2 - beta * 0.75, facc1 = 1.0 / fac1, facc2 = 1.0 / fac2;
-    const double xend = t_start + 1.0, hmax = 1.0;
-    double x = t_start, h = h_carry, facold = 1e-4;
-    double k1[13], k2[13], k3[13], k4[13], k5[13], k6[13], y1[13], ysti[13];
-    int nstep = 0;
-    bool last = false, reject = false;
+    const double hmax = kDopriHmax;
+    double k2[13], k3[13], k4[13], k5[13], k6[13], y1[13], ysti[13];
+    double (&k1)[13] = r.k1;
+    double h = r.h;
 
-    rhs_scipy(p, y, d, ins, lq, lf, k1); nfcn++;          // SciPy re-enters the driver every minute: a fresh first stage
-    if (h == 0.0) { h = dopri5_hinit(p, y, k1, d, ins, lq, lf, hmax, atol, rtol); nfcn++; }
+    if (r.nstep > nmax) return -1;
+    if (0.1 * fabs(h) <= fabs(r.x) * uround) return -1;
+    if ((r.x + 1.01 * h - xend) > 0.0) { h = xend - r.x; r.last = true; }
+    r.nstep++;
+#pragma unroll
+    for (int i = 0; i < 13; ++i) y1[i] = y[i] + h * a21 * k1[i];
+    rhs_scipy(p, y1, d, ins, lq, lf, k2);
+#pragma unroll
+    for (int i = 0; i < 13; ++i) y1[i] = y[i] + h * (a31 * k1[i] + a32 * k2[i]);
+    rhs_scipy(p, y1, d, ins, lq, lf, k3);
+#pragma unroll
+    for (int i = 0; i < 13; ++i) y1[i] = y[i] + h * (a41 * k1[i] + a42 * k2[i] + a43 * k3[i]);
+    rhs_scipy(p, y1, d, ins, lq, lf, k4);
+#pragma unroll
+    for (int i = 0; i < 13; ++i) y1[i] = y[i] + h * (a51 * k1[i] + a52 * k2[i] + a53 * k3[i] + a54 * k4[i]);
+    rhs_scipy(p, y1, d, ins, lq, lf, k5);
+#pragma unroll
+    for (int i = 0; i < 13; ++i) ysti[i] = y[i] + h * (a61 * k1[i] + a62 * k2[i] + a63 * k3[i] + a64 * k4[i] + a65 * k5[i]);
+    rhs_scipy(p, ysti, d, ins, lq, lf, k6);
+#pragma unroll
+    for (int i = 0; i < 13; ++i) y1[i] = y[i] + h * (a71 * k1[i] + a73 * k3[i] + a74 * k4[i] + a75 * k5[i] + a76 * k6[i]);
+    rhs_scipy(p, y1, d, ins, lq, lf, k2);              // k2 <- k7 (the first stage of the next step: FSAL)
+    nfcn += 6;
+    double err = 0.0;
+#pragma unroll
+    for (int i = 0; i < 13; ++i) {
+        const double ke = (e1 * k1[i] + e3 * k3[i] + e4 * k4[i] + e5 * k5[i] + e6 * k6[i] + e7 * k2[i]) * h;
+        const double sk = atol + rtol * fmax(fabs(y[i]), fabs(y1[i]));
+        err += (ke / sk) * (ke / sk);
+    }
+    err = sqrt(err / 13.0);
+    const double fac11 = pow(err, expo1);
+    double fac = fac11 / pow(r.facold, beta);
+    fac = fmax(facc2, fmin(facc1, fac / safe));
+    double hnew = h / fac;
+    if (err <= 1.0) {
+        r.facold = fmax(err, 1e-4);
+#pragma unroll
+        for (int i = 0; i < 13; ++i) { k1[i] = k2[i]; y[i] = y1[i]; }
+        r.x += h;
+        if (r.last) { h_carry = hnew; return 1; }
+        if (fabs(hnew) > hmax) hnew = hmax;
+        if (r.reject) hnew = fmin(fabs(hnew), fabs(h));
+        r.reject = false;
+    } else {
+        hnew = h / fmin(facc1, fac11 / safe);
+        r.reject = true;
+        r.last = false;
+    }
+    r.h = hnew;
+    return 0;
+}
+
+// one minute to its end.  y: the state, advanced in place (left at the last accepted point if the solver gives up);
+// h_carry: the predicted step, read (0 = probe) and written on success; nfcn: RHS evaluations of this call, added.
+// Returns false where the driver gives up.
+__device__ __forceinline__ bool dopri5_minute(const ParsRaw& p, double (&y)[13], double d, double ins, double lq, double lf,
+                                              double& h_carry, double t_start, int& nfcn)
+{
+#pragma clang fp contract(off)
+    Dopri5Run r;
+    dopri5_enter(p, y, d, ins, lq, lf, h_carry, t_start, r, nfcn);
+    const double xend = t_start + 1.0;
     for (;;) {
-        if (nstep > nmax) return false;
-        if (0.1 * fabs(h) <= fabs(x) * uround) return false;
-        if ((x + 1.01 * h - xend) > 0.0) { h = xend - x; last = true; }
-        nstep++;
-#pragma unroll
-        for (int i = 0; i < 13; ++i) y1[i] = y[i] + h * a21 * k1[i];
-        rhs_scipy(p, y1, d, ins, lq, lf, k2);
-#pragma unroll
-        for (int i = 0; i < 13; ++i) y1[i] = y[i] + h * (a31 * k1[i] + a32 * k2[i]);
-        rhs_scipy(p, y1, d, ins, lq, lf, k3);
-#pragma unroll
-        for (int i = 0; i < 13; ++i) y1[i] = y[i] + h * (a41 * k1[i] + a42 * k2[i] + a43 * k3[i]);
-        rhs_scipy(p, y1, d, ins, lq, lf, k4);
-#pragma unroll
-        for (int i = 0; i < 13; ++i) y1[i] = y[i] + h * (a51 * k1[i] + a52 * k2[i] + a53 * k3[i] + a54 * k4[i]);
-        rhs_scipy(p, y1, d, ins, lq, lf, k5);
-#pragma unroll
-        for (int i = 0; i < 13; ++i) ysti[i] = y[i] + h * (a61 * k1[i] + a62 * k2[i] + a63 * k3[i] + a64 * k4[i] + a65 * k5[i]);
-        rhs_scipy(p, ysti, d, ins, lq, lf, k6);
-#pragma unroll
-        for (int i = 0; i < 13; ++i) y1[i] = y[i] + h * (a71 * k1[i] + a73 * k3[i] + a74 * k4[i] + a75 * k5[i] + a76 * k6[i]);
-        rhs_scipy(p, y1, d, ins, lq, lf, k2);              // k2 <- k7 (the first stage of the next step: FSAL)
-        nfcn += 6;
-        double err = 0.0;
-#pragma unroll
-        for (int i = 0; i < 13; ++i) {
-            const double ke = (e1 * k1[i] + e3 * k3[i] + e4 * k4[i] + e5 * k5[i] + e6 * k6[i] + e7 * k2[i]) * h;
-            const double sk = atol + rtol * fmax(fabs(y[i]), fabs(y1[i]));
-            err += (ke / sk) * (ke / sk);
-        }
-        err = sqrt(err / 13.0);
-        const double fac11 = pow(err, expo1);
-        double fac = fac11 / pow(facold, beta);
-        fac = fmax(facc2, fmin(facc1, fac / safe));
-        double hnew = h / fac;
-        if (err <= 1.0) {
-            facold = fmax(err, 1e-4);
-#pragma unroll
-            for (int i = 0; i < 13; ++i) { k1[i] = k2[i]; y[i] = y1[i]; }
-            x += h;
-            if (last) { h_carry = hnew; return true; }
-            if (fabs(hnew) > hmax) hnew = hmax;
-            if (reject) hnew = fmin(fabs(hnew), fabs(h));
-            reject = false;
-        } else {
-            hnew = h / fmin(facc1, fac11 / safe);
-            reject = true;
-            last = false;
-        }
-        h = hnew;
+        const int rc = dopri5_attempt(p, y, d, ins, lq, lf, h_carry, xend, r, nfcn);
+        if (rc) return rc > 0;
     }
 }
 
@@ -254,6 +291,151 @@ __global__ __launch_bounds__(kBlock, 1) void dopri5_step_kernel(const KArgs<doub
         o.meal += meal / div; o.ins += insulin / div; o.bg += gsub / div; o.cgm += cgm / div;   // env.py:78-81
     }
     write_outputs<0>(a, i, e, o, rp);
+    store_env(a, i, pid, e);
+    at(h_carry, i) = hc;
+    if (nfev) at(nfev, i) = nf;
+    if (failed) atomicOr(a.status, T1D_ST_SOLVER_FAILED);
+}
+
+// ---- closed-loop roll-outs in the exact mode (t1d_rollout_pid_dopri5 / t1d_rollout_bb_dopri5) ---------------------------
+// PIDController.policy (pid_ctrller.py:17-36) / BBController._bb_policy (basal_bolus_ctrller.py:64-79): the arithmetic of
+// rollout_body (t1d_kernels.hpp), restated with FMA contraction off like everything else the exact mode computes, so that
+// a roll-out gives what a step() loop with the controller evaluated operation by operation gives.  The controller's state
+// lives in memory: it is touched once per step.  obs: the previous step's observation; st: the sensor's sample time.
+__device__ __forceinline__ void dopri5_controller(const PidArgs<double>& c, unsigned i, double obs, double st, double& u, double& bolus)
+{
+#pragma clang fp contract(off)
+    bolus = 0.0;
+    if (c.kind == 1) {
+        u = at(c.bb_basal, i);
+        const double prev_meal = at(c.bb_prev_meal, i);
+        if (prev_meal > 0.0) {
+            const double corr = obs > 150.0 ? (obs - c.target) / at(c.bb_cf, i) : 0.0;
+            bolus = ((prev_meal * st) / at(c.bb_cr, i) + corr) / st;
+        }
+    } else {
+        const double integ = at(c.integ, i), prev = at(c.prev, i);
+        u = c.P * (obs - c.target) + c.I * integ + c.D * (obs - prev) / st;
+        at(c.prev, i) = obs;
+        at(c.integ, i) = integ + (obs - c.target) * st;
+    }
+}
+
+// The words of a lane that only its minute boundaries touch, kept in LDS between them ([word][lane]: no bank conflict):
+// dopri5_attempt needs every register of the unified file for its stage vectors (dopri5_step_kernel: 256 VGPRs + 220
+// AGPRs), and what is reloaded at the top of the boundary block is not alive across the step attempts.
+struct RollCold {
+    enum { PLANNED, LAST_CGM, PREV_RISK, CUR0, CUR1, CUR2, CUR3, NOISE, O_CGM, O_BG, O_MEAL, O_INS, HC, NF };
+    enum { CURSOR, NEXT_MEAL, NEXT_MEAL_LOADED, NI };
+    double* f; int* w;
+    __device__ __forceinline__ void save(const Env<double>& e, const StepOut<double>& o, double noise, double hc) const
+    {
+        f[PLANNED * kBlock] = e.planned; f[LAST_CGM * kBlock] = e.last_cgm; f[PREV_RISK * kBlock] = e.prev_risk;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) f[(CUR0 + k) * kBlock] = e.cur[k];
+        f[NOISE * kBlock] = noise; f[HC * kBlock] = hc;
+        f[O_CGM * kBlock] = o.cgm; f[O_BG * kBlock] = o.bg; f[O_MEAL * kBlock] = o.meal; f[O_INS * kBlock] = o.ins;
+        w[CURSOR * kBlock] = e.cursor; w[NEXT_MEAL * kBlock] = e.next_meal; w[NEXT_MEAL_LOADED * kBlock] = e.next_meal_loaded;
+    }
+    __device__ __forceinline__ void load(Env<double>& e, StepOut<double>& o, double& noise, double& hc) const
+    {
+        e.planned = f[PLANNED * kBlock]; e.last_cgm = f[LAST_CGM * kBlock]; e.prev_risk = f[PREV_RISK * kBlock];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) e.cur[k] = f[(CUR0 + k) * kBlock];
+        noise = f[NOISE * kBlock]; hc = f[HC * kBlock];
+        o.cgm = f[O_CGM * kBlock]; o.bg = f[O_BG * kBlock]; o.meal = f[O_MEAL * kBlock]; o.ins = f[O_INS * kBlock];
+        e.cursor = w[CURSOR * kBlock]; e.next_meal = w[NEXT_MEAL * kBlock]; e.next_meal_loaded = w[NEXT_MEAL_LOADED * kBlock];
+    }
+};
+
+// c.n_steps closed-loop steps of a.minutes minutes in one launch, every lane at its own pace.  The body of the one loop is
+// ONE step attempt of the driver for every lane that still has work; ahead of it, only the lanes that have just completed a
+// minute (or enter their first) run the boundary block: finish the minute as dopri5_step_kernel does, at the end of a step
+// the outputs, the trace rows, the statistics and the controller, then open the next minute.  Inside a launch nothing
+// forces the 64 envs of a wave to be in the same minute, so a wave pays for the lane with the largest TOTAL of step
+// attempts, not for the per-minute maximum summed over the minutes.  Lanes never exchange data, and a lane executes the
+// operations dopri5_step_kernel and the controller would execute for its env, in the same order: its results do not depend
+// on its neighbours, and are those of a step() loop, bit for bit.  What a step leaves behind once per step (observation,
+// reward, risk, controller state, statistics) goes through memory as in that loop; what a minute needs is in RollCold.
+// The loop ends: a lane either completes a minute or spends one of the driver's nmax step attempts of that minute.
+// A lane whose solver gives up keeps its last accepted state for the rest of the launch; its clock, meals and noise go on.
+// Grid, block, tables and arguments as dopri5_step_kernel; nfev: RHS evaluations of each env in this launch.
+__global__ __launch_bounds__(kBlock, 1) void dopri5_rollout_kernel(const KArgs<double> a, const PidArgs<double> c,
+                                                                   const double* __restrict__ raw, double* h_carry, int32_t* nfev)
+{
+    __shared__ double lds[kRawPars * kMaxPatients];
+    __shared__ double cold_f[RollCold::NF * kBlock];
+    __shared__ int cold_w[RollCold::NI * kBlock];
+    for (int j = threadIdx.x; j < kRawPars * kMaxPatients; j += blockDim.x) lds[j] = raw[j];
+    __syncthreads();
+    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
+    __builtin_assume(i < (1u << 28));          // host guarantees n <= 2^28: i * sizeof(T) fits a 32-bit voffset
+    if ((int64_t)i >= a.n) return;
+    const uint32_t meta = at(a.meta, i);
+    const uint32_t pid = T1D_META_PID(meta);
+    Env<double> e;
+    load_env(a, i, meta, e);
+    const ParsRaw p{lds, (int)pid};
+    NoDerivedPars nop;
+    const RollCold cold{cold_f + threadIdx.x, cold_w + threadIdx.x};
+    const double div = double(a.minutes), st = double(a.sen.st);
+    double hc = at(h_carry, i), noise = 0.0, insulin = 0.0, d_mg = 0.0;
+    StepOut<double> o{0.0, 0.0, 0.0, 0.0};
+    Dopri5Run r{};
+    int nf = 0, m = 0, s = 0;
+    bool due = false, failed = false, boundary = true, fresh = true;
+    cold.save(e, o, noise, hc);
+    for (;;) {
+        if (boundary) {
+            cold.load(e, o, noise, hc);
+            if (!fresh) {
+                e.t += 1;
+                const double gsub = e.x[12] / p(T1D_P_VG);                                    // t1dpatient.py:217-218
+                const double cgm = measure_apply(a, e, gsub, noise, due);                     // env.py:62
+                o.bg += gsub / div; o.cgm += cgm / div;                                       // env.py:80-81
+                if (++m == a.minutes) {                  // the step is complete: what t1d_step_dopri5 leaves, then the roll-out's own
+                    const double rp = e.prev_risk;
+                    write_outputs<0>(a, i, e, o, rp);
+                    const int64_t tr = (c.trace_row + s) * a.n + i;
+                    if (c.bg_trace) c.bg_trace[tr] = o.bg;
+                    if (c.cgm_trace) c.cgm_trace[tr] = o.cgm;
+                    if (c.cho_trace) c.cho_trace[tr] = o.meal;
+                    if (c.ins_trace) c.ins_trace[tr] = o.ins;
+                    if (c.kind == 1) at(c.bb_prev_meal, i) = o.meal;
+                    if (c.sum_risk) { double l, h, rk; risk_index1<0>(o.bg, l, h, rk); at(c.sum_risk, i) = at(c.sum_risk, i) + rk; }
+                    if (c.min_bg) { const double v = at(c.min_bg, i); at(c.min_bg, i) = o.bg < v ? o.bg : v; }
+                    if (c.max_bg) { const double v = at(c.max_bg, i); at(c.max_bg, i) = o.bg > v ? o.bg : v; }
+                    if (c.n_low) at(c.n_low, i) = at(c.n_low, i) + (o.bg < 70.0);
+                    if (c.n_high) at(c.n_high, i) = at(c.n_high, i) + (o.bg > 180.0);
+                    m = 0; ++s;
+                }
+            }
+            if (s == c.n_steps) break;
+            if (m == 0) {                                // a step opens: the controller on the last observation, then the pump
+                double u, bolus;
+                dopri5_controller(c, i, at(a.cgm, i), st, u, bolus);
+                double q_basal = u, q_bolus = bolus;     // as step_body with a bolus given: env.py:51-52
+                if (!(a.flags & T1D_BATCH_NO_PUMP)) {
+                    q_basal = pump_quantise(u, a.pump.inc_basal, a.pump.min_basal, a.pump.max_basal);
+                    q_bolus = pump_quantise(bolus, a.pump.inc_bolus, a.pump.min_bolus, a.pump.max_bolus);
+                }
+                insulin = q_basal + q_bolus;
+                o = StepOut<double>{0.0, 0.0, 0.0, 0.0};
+            }
+            const double meal = meal_lookup(a, i, e);                                         // env.py:50
+            noise = measure_noise<true>(a, i, e, due);
+            const MinuteIn<double> u = eat_minute<0, double>(nop, e.x, meal, insulin, e.planned, e.lq, e.lf, e.eating);
+            d_mg = u.d_mg;
+            o.meal += meal / div; o.ins += insulin / div;                                     // env.py:78-79
+            if (!failed) dopri5_enter(p, e.x, d_mg, insulin, e.lq, e.lf, hc, (double)e.t, r, nf);
+            cold.save(e, o, noise, hc);
+            fresh = false; boundary = false;
+        }
+        if (failed) { boundary = true; continue; }
+        const int rc = dopri5_attempt(p, e.x, d_mg, insulin, e.lq, e.lf, cold.f[RollCold::HC * kBlock], (double)e.t + 1.0, r, nf);
+        failed = rc < 0;
+        boundary = rc != 0;
+    }
     store_env(a, i, pid, e);
     at(h_carry, i) = hc;
     if (nfev) at(nfev, i) = nf;

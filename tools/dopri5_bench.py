@@ -8,7 +8,14 @@ costs, since it runs until its slowest lane is done.  Accuracy leg: 1 024 env-da
 dopri (the reference's numbers) and on a tight solve (classical RK4, 48 sub-steps): max / p99 / median of each env-day's
 max |BG difference|.  The kernel's registers come from a resource-usage compile.
 
-usage: dopri5_bench.py [--out FILE] [--launches N] [--no-accuracy]   (GPU box; prints one JSON document)"""
+--rollout: the closed-loop leg instead (Dexcom steps, BB controller and PID with mild gains, 160 steps = 8 h, 1 Mi and 256 Ki
+envs): a step() loop with the controller in torch on the device between the launches (what the exact mode offered before
+the roll-out kernel; no host synchronisation inside the loop) against rollout_*_dopri5 for the same steps from the same
+state, alternated --reps times in one process, every repetition reported; and the count model (tools/dopri5_counts.py)
+on per-minute RHS counts of the same closed loop.
+
+usage: dopri5_bench.py [--out FILE] [--launches N] [--no-accuracy]   (GPU box; prints one JSON document)
+       dopri5_bench.py --rollout [--out FILE] [--reps 3] [--sizes 1048576,262144]"""
 import argparse
 import json
 import os
@@ -23,13 +30,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from simglucose_amd.batch_env import BatchedT1DSimEnv  # noqa: E402
 from simglucose_amd import params, scenario_batch  # noqa: E402
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from dopri5_counts import wave_costs  # noqa: E402
 
 
-def make(n, days=2, seed=5, random_start=True):
+def make(n, days=2, seed=5, random_start=True, sensor="Navigator", extra_outputs=False):
     """random_start: every env's episode starts at a random minute of the day (as the bench's workload), so that a window
     of a few hundred minutes sees every phase of a day -- night, meals, the hours after them"""
     pid = np.arange(n) % 30
-    env = BatchedT1DSimEnv(patient=pid, sensor="Navigator", seed=seed, extra_outputs=False, integrator="dopri5")
+    env = BatchedT1DSimEnv(patient=pid, sensor=sensor, seed=seed, extra_outputs=extra_outputs, integrator="dopri5")
     start = 0
     if random_start:
         g0 = torch.Generator(device=env.device); g0.manual_seed(11)
@@ -106,12 +115,100 @@ def accuracy(n=1024, minutes=1440):
     return {"env_days": n, "vs_scipy_dopri": st(w_ref), "vs_tight_rk4_48": st(w_tight), "scipy_vs_tight": st(ref_tight)}
 
 
-def resources():
+PID_MILD = (1.5e-4, 4e-7, 5e-4)
+ROLLOUT_STEPS, ROLLOUT_WARMUP = 160, 10
+
+
+def step_loop(env, kind, steps, per_minute=None):
+    """the closed loop as a step() loop, the controller in torch on the device between the launches.  per_minute: a list
+    that receives every minute's nfev (the step is then made of one-minute launches with the action held: the same
+    integration, the step's means formed as the kernel forms them)"""
+    st = float(env.minutes_per_step)
+    zero = torch.zeros(env.n, dtype=torch.float64, device=env.device)
+    obs = env.cgm.clone()
+    if kind == "bb":
+        c = env.bb_constants()
+        meal = zero.clone()
+    else:
+        P, I, D = PID_MILD
+        integ, prev = zero.clone(), zero.clone()
+    for _ in range(steps):
+        if kind == "bb":
+            corr = torch.where(obs > 150.0, (obs - 140.0) / c["cf"], zero)
+            basal, bolus = c["basal"], torch.where(meal > 0, ((meal * st) / c["cr"] + corr) / st, zero)
+        else:
+            basal, bolus = P * (obs - 140.0) + I * integ + D * (obs - prev) / st, zero
+            prev = obs
+            integ = integ + (obs - 140.0) * st
+        if per_minute is None:
+            env.step(basal, bolus)
+            obs, meal = env.cgm.clone(), env.meal.clone()
+        else:
+            obs, meal = zero.clone(), zero.clone()
+            for _m in range(env.minutes_per_step):
+                env.step(basal, bolus, minutes=1)
+                per_minute.append(env.nfev.to(torch.int16).cpu().numpy())
+                obs = obs + env.cgm / st
+                meal = meal + env.meal / st
+
+
+def rollout_leg(n, reps):
+    """both controllers at n envs: events around ROLLOUT_STEPS steps after ROLLOUT_WARMUP steps, the two legs alternated"""
+    res = {"n_envs": n, "steps": ROLLOUT_STEPS, "warmup_steps": ROLLOUT_WARMUP}
+    for kind in ("bb", "pid"):
+        runs = {"step_loop_ms": [], "rollout_ms": []}
+        for rep in range(reps):
+            for leg in ("step_loop_ms", "rollout_ms"):
+                env, *_ = make(n, sensor="Dexcom", extra_outputs=True)
+                state = None
+                if leg == "step_loop_ms":
+                    step_loop(env, kind, ROLLOUT_WARMUP)
+                elif kind == "bb":
+                    state = env.rollout_bb_dopri5(ROLLOUT_WARMUP)
+                else:
+                    state = env.rollout_pid_dopri5(ROLLOUT_WARMUP, *PID_MILD)
+                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize(); s.record()
+                if leg == "step_loop_ms":
+                    step_loop(env, kind, ROLLOUT_STEPS)
+                elif kind == "bb":
+                    env.rollout_bb_dopri5(ROLLOUT_STEPS, bb_state=state)
+                else:
+                    env.rollout_pid_dopri5(ROLLOUT_STEPS, *PID_MILD, pid_state=state)
+                e.record(); torch.cuda.synchronize()
+                assert env.sync() == 0
+                runs[leg].append(round(s.elapsed_time(e), 2))
+                del env
+        a, b = np.array(runs["step_loop_ms"]), np.array(runs["rollout_ms"])
+        runs["ratio_of_medians"] = round(float(np.median(a) / np.median(b)), 3)
+        runs["ratio_worst_case"] = round(float(a.min() / b.max()), 3)
+        res[kind] = runs
+        print(json.dumps({"n_envs": n, kind: runs}), flush=True)
+    return res
+
+
+def rollout_counts(n, launch_minutes=240):
+    """the three count figures for the closed loop of the timing legs (after the same warm-up), from per-minute nfev"""
+    out = {"n_envs": n, "launch_minutes": launch_minutes}
+    for kind in ("bb", "pid"):
+        env, *_ = make(n, sensor="Dexcom", extra_outputs=True)
+        step_loop(env, kind, ROLLOUT_WARMUP)
+        rows = []
+        step_loop(env, kind, ROLLOUT_STEPS, per_minute=rows)
+        assert env.sync() == 0
+        c = wave_costs(np.stack(rows), launch_minutes)
+        c["count_ratio_lockstep_over_free_running"] = round(c["lockstep_wave_cost"] / c["free_running_wave_cost"], 3)
+        out[kind] = {k: round(v, 3) for k, v in c.items()}
+        del env
+    return out
+
+
+def resources(kernel="_ZN3t1d18dopri5_step_kernel"):
     out = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-fno-slp-vectorize", "-std=c++17", "--cuda-device-only",
                           "-c", "-Rpass-analysis=kernel-resource-usage", "-o", os.devnull,
                           os.path.join(ROOT, "simglucose_amd", "csrc", "t1d_abi.hip")],
                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT).stdout.decode()
-    blk = [b for b in out.split("Function Name: ") if b.startswith("_ZN3t1d18dopri5_step_kernel")][0]
+    blk = [b for b in out.split("Function Name: ") if b.startswith(kernel)][0]
     get = lambda key: int(re.search(re.escape(key) + r": (\d+)", blk).group(1))
     return {"vgprs": get("VGPRs"), "agprs": get("AGPRs"), "scratch_bytes_per_lane": get("ScratchSize [bytes/lane]"),
             "occupancy_waves_per_simd": get("Occupancy [waves/SIMD]")}
@@ -124,7 +221,27 @@ def main():
     ap.add_argument("--sizes", default="1048576,262144,131072")
     ap.add_argument("--no-accuracy", action="store_true")
     ap.add_argument("--no-resources", action="store_true")
+    ap.add_argument("--rollout", action="store_true")
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--count-envs", type=int, default=262144)
     a = ap.parse_args()
+    if a.rollout:
+        sizes = "1048576,262144" if a.sizes == ap.get_default("sizes") else a.sizes
+        res = {"workload": "Dexcom 3-min steps, fp64, random meal tables (episodes start at a random minute of the day), Philox "
+                           "noise; BBController and PID %r; step() loop with the controller in torch against rollout_*_dopri5" % (PID_MILD,),
+               "device": torch.cuda.get_device_name(0)}
+        res["timing"] = [rollout_leg(int(n), a.reps) for n in sizes.split(",")]
+        res["counts"] = rollout_counts(a.count_envs)
+        print(json.dumps(res["counts"]), flush=True)
+        if not a.no_resources:
+            res["kernels"] = {"dopri5_rollout_kernel": resources("_ZN3t1d21dopri5_rollout_kernel"),
+                              "dopri5_step_kernel": resources()}
+        txt = json.dumps(res, indent=1)
+        print(txt)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(txt + "\n")
+        return
     res = {"workload": "Navigator 1-min steps, fp64, random meal tables, random basal pool (8), Philox noise, t1d_step_dopri5",
            "device": torch.cuda.get_device_name(0)}
     res["timing"] = [timing(int(n), a.launches) for n in a.sizes.split(",")]
