@@ -24,6 +24,8 @@
  *   t1d_rollout_bb   <- the same loop with BBController  simglucose/controller/basal_bolus_ctrller.py:34-80
  *   t1d_rollout_pid_dopri5, t1d_rollout_bb_dopri5 <- the two loops with scipy's dopri5 itself (the exact mode)
  *   t1d_random_meals <- RandomScenario.create_scenario  simglucose/simulation/scenario_gen.py:33-60
+ *   t1d_restart_done <- the reset() a gym training loop calls when done comes back true (T1DSimEnv.reset + a new
+ *                       RandomScenario and start hour, simglucose/envs/simglucose_gym_env.py:58-73), for the finished envs only
  *   t1d_outcome_stats<- percent_stats, risk_index_trace, simglucose/analysis/report.py:74-133,198-217
  *                       CVGA_analysis
  *
@@ -208,6 +210,25 @@ typedef struct t1d_outcome {
     int32_t chunk;
 } t1d_outcome;
 
+/* t1d_restart_done: what a restarted env needs besides the batch.  Floating arrays have the batch's dtype. */
+typedef struct t1d_restart {
+    int32_t days;             /* horizon of the meal tables: rows = 6 (days + 1) = batch.n_meals */
+    int32_t random_init_bg;   /* as t1d_reset */
+    int32_t reset_outputs;    /* 0 = of the outputs only cgm is written for a restarted env; bg, reward, done, lbgi, hbgi, risk,
+                                 meal, insulin keep what the finished step left (the terminal transition a gym caller gets
+                                 back with the new observation).  non-zero = they are written as t1d_reset writes them */
+    int32_t reserved;         /* 0 */
+    int32_t* meal_time;       /* the batch's own tables, writable: [rows][n] (== batch.meal_time) */
+    void* meal_amt;           /* (== batch.meal_amt) */
+    int32_t* start_minute;    /* [n] minute of day at which the env's current episode started; written for restarted envs */
+    double* h_carry;          /* [n] or NULL: zeroed for restarted envs (t1d_step_dopri5) */
+    void* terminal_cgm;       /* [n] or NULL: observation of the finished step, written for restarted envs only */
+    void* ep_return;          /* [n] or NULL: running sum of reward over the env's current episode, += batch.reward in every call */
+    int32_t* ep_length;       /* [n], with ep_return: steps of the current episode, += 1 in every call */
+    void* last_return;        /* [n] or NULL (needs ep_return): ep_return of the env's last finished episode */
+    int32_t* last_length;     /* [n] or NULL (needs ep_return): ep_length of it */
+} t1d_restart;
+
 int t1d_abi_version(void);
 const char* t1d_last_error(void);
 
@@ -361,6 +382,28 @@ int t1d_philox_normals(t1d_ctx* ctx, uint64_t seed, int64_t env_offset, int64_t 
  * All device arrays of `dtype`; pid int32 [n]. */
 int t1d_model_rhs(t1d_ctx* ctx, int dtype, int64_t n, int math, const void* x, const int32_t* pid, const void* cho,
                   const void* insulin, const void* last_qsto, const void* last_food, void* dxdt, void* hip_stream);
+
+/* Start the next episode of the envs whose mask byte is non-zero (mask == NULL: batch.done), where they are: one launch, one
+ * lane per env, meant to follow every t1d_step of a gym-style loop -- no host round trip, nothing allocated, the other envs
+ * untouched (one byte read each; with the accumulators below 33 bytes more).  Everything the new episode draws is keyed by
+ * the env's OWN episode index k = its batch.episode counter before the call (0 for an env never reset) and its global id
+ * g = env_offset + i, so an env's k-th episode is one thing however it was reached and whatever the rest of the batch did
+ * (shards of a multi-GPU job = slices of one batch, through every restart).  A restarted env
+ *   1. gets cgm[i] stored to terminal_cgm[i]; ep_return / ep_length move to last_return / last_length and restart at 0
+ *      (every env, restarted or not, first adds this step's reward and 1 to them);
+ *   2. draws its start hour: h = (z >> 11) mod 24 with z = splitmix64 finaliser of g * 0x9E3779B97F4A7C15 +
+ *      (seed * 1000003 + k), all mod 2^64; start_minute[i] = 60 h;
+ *   3. writes its column of the meal tables with what t1d_random_meals(seed * 7919 + k mod 2^64, env_offset = g, n = 1, days,
+ *      start 60 h) writes;
+ *   4. is reset as by t1d_reset (patient state, random_init_bg draws, noise state, CGM samples #0 and #1, prev_risk, cgm0,
+ *      cursor 0, next_meal = its new row 0, episode = k + 1 -- the `ep` of the Philox draws), and h_carry[i] = 0.
+ * With k = 0 and seed s this is the first episode BatchedGymT1DSimEnv(seed = s).reset() builds.  Batches with host normals or
+ * x0_override have no per-episode source on the device: T1D_E_INVALID, as are tables that are not the batch's own, n_meals
+ * != 6 (days + 1) and a NULL batch.episode.  fp64 and fp32, any state layout.  Option "restart_compact": 1 (default) = a workgroup
+ * collects the finished envs of 4 096 in LDS and restarts them with full waves; 0 = every lane restarts its own env, in waves
+ * with one or two live lanes (same results; gym step at 1 Mi fp64 envs with 1.5 % of the envs finishing per step: 0.35 ms
+ * against 1.05 ms, 0.21 ms without any restart: profiles/autoreset). */
+int t1d_restart_done(t1d_ctx* ctx, const t1d_batch* b, const uint8_t* mask, const t1d_restart* r, void* hip_stream);
 
 /* Wait for the stream and return the accumulated status bits through *status (then clear them). */
 int t1d_sync(t1d_ctx* ctx, void* hip_stream, int32_t* status);

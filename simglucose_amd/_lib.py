@@ -25,7 +25,7 @@ META_EATING = 0x100
 EXPORTS = ("t1d_abi_version", "t1d_last_error", "t1d_ctx_create", "t1d_ctx_set_option", "t1d_ctx_destroy", "t1d_reset",
            "t1d_step", "t1d_rollout_pid", "t1d_philox_normals", "t1d_sync", "t1d_split_tables",
            "t1d_rollout_bb", "t1d_random_meals", "t1d_outcome_stats", "t1d_model_rhs", "t1d_step_dopri5",
-           "t1d_rollout_pid_dopri5", "t1d_rollout_bb_dopri5")
+           "t1d_rollout_pid_dopri5", "t1d_rollout_bb_dopri5", "t1d_restart_done")
 
 
 class T1DError(RuntimeError):
@@ -70,6 +70,14 @@ class Outcome(C.Structure):
     """struct t1d_outcome (include/t1d.h)"""
     _fields_ = [("counts", C.c_void_p), ("pct", C.c_void_p), ("zone", C.c_void_p), ("risk_trace", C.c_void_p),
                 ("q_lo", C.c_double), ("q_hi", C.c_double), ("chunk", C.c_int32)]
+
+
+class Restart(C.Structure):
+    """struct t1d_restart (include/t1d.h)"""
+    _fields_ = [("days", C.c_int32), ("random_init_bg", C.c_int32), ("reset_outputs", C.c_int32), ("reserved", C.c_int32),
+                ("meal_time", C.c_void_p), ("meal_amt", C.c_void_p), ("start_minute", C.c_void_p), ("h_carry", C.c_void_p),
+                ("terminal_cgm", C.c_void_p), ("ep_return", C.c_void_p), ("ep_length", C.c_void_p),
+                ("last_return", C.c_void_p), ("last_length", C.c_void_p)]
 
 
 def _stale():
@@ -139,6 +147,7 @@ def lib():
     L.t1d_rollout_bb.argtypes = [vp, C.POINTER(Batch), C.POINTER(Bb), C.c_int, C.c_int, C.c_int, vp]
     L.t1d_rollout_pid_dopri5.argtypes = [vp, C.POINTER(Batch), C.POINTER(Pid), vp, vp, C.c_int, C.c_int, vp]
     L.t1d_rollout_bb_dopri5.argtypes = [vp, C.POINTER(Batch), C.POINTER(Bb), vp, vp, C.c_int, C.c_int, vp]
+    L.t1d_restart_done.argtypes = [vp, C.POINTER(Batch), vp, C.POINTER(Restart), vp]
     L.t1d_random_meals.argtypes = [C.c_int, u64, i64, i64, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]
     L.t1d_outcome_stats.argtypes = [C.c_int, C.c_int, i64, i64, vp, C.POINTER(Outcome), vp]
     L.t1d_philox_normals.argtypes = [vp, u64, i64, i64, u32, i32, i32, vp, vp]

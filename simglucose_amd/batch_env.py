@@ -130,6 +130,7 @@ class BatchedT1DSimEnv:
             self.h_carry = self.nfev = None
         self._basal_buf = z(n); self._bolus_buf = z(n)
         self.meal_time = None; self.meal_amt = None
+        self.start_minute = None   # int32 [n], minute of day at which each env's current episode started (restart_done)
         self.normals = None
         self._b = _lib.Batch()
         b = self._b
@@ -213,6 +214,16 @@ class BatchedT1DSimEnv:
         self._hist_cnt[m] = 1
         self._hist[0, m] = self.cgm0[m]
 
+    def _hist_restart(self, m):
+        """_hist_reset for the envs of the bool mask m without boolean indexing (nothing here waits for the device)"""
+        if self._hist is None:
+            return
+        nan = torch.full((), float("nan"), dtype=self.dtype, device=self.device)
+        self._hist.copy_(torch.where(m.unsqueeze(0), nan, self._hist))
+        self._hist[0].copy_(torch.where(m, self.cgm0, self._hist[0]))
+        self._hist_pos.masked_fill_(m, 0)
+        self._hist_cnt.masked_fill_(m, 1)
+
     def _hist_push(self):
         """CGM_hist.append(CGM) (env.py:94) for every env"""
         self._hist_pos = (self._hist_pos + 1) % self.window
@@ -264,6 +275,65 @@ class BatchedT1DSimEnv:
         b.x0_override = None
         self._keep = (keep, mask)
         self._hist_reset(mask)
+        return self.cgm
+
+    def restart_done(self, mask=None, days=2, terminal_obs=None, episode_stats=None, reset_outputs=False):
+        """Start the next episode of the finished envs where they are (t1d_restart_done, include/t1d.h): one launch after a
+        step(), no host round trip.  mask: uint8 / bool [n], None = ``done``.  A restarted env draws its start hour, its column
+        of the meal tables (RandomScenario over ``days`` days) and its reset from its own episode index (``episode`` before the
+        call) and global id, so its k-th episode does not depend on the rest of the batch.  Of the outputs only ``cgm`` (the new
+        episode's first observation) changes; reward, done, bg ... keep the terminal step's values unless reset_outputs.
+        The env owns meal tables of 6 (days + 1) rows (created on the first call if it has none) and ``start_minute``.
+        terminal_obs: tensor [n] that receives the finished step's observation of the restarted envs.  episode_stats: dict
+        with ep_return, ep_length (int32) and optionally last_return, last_length (int32), tensors [n]: every call adds the
+        step's reward and 1 to the running pair, a restart moves it to last_* and zeroes it."""
+        if self.noise == "host" or self.normals is not None:
+            raise _lib.T1DError("restart_done draws every episode on the device: not available with host normals")
+        days = int(days)
+        rows = 6 * (days + 1)
+        if self.meal_time is None:
+            self.set_meals(torch.full((rows, self.n), _lib.MEAL_UNUSED, dtype=torch.int32, device=self.device),
+                           torch.zeros(rows, self.n, dtype=self.dtype, device=self.device))
+        if self.meal_time.shape[0] != rows:
+            raise _lib.T1DError("restart_done(days=%d) needs meal tables of %d rows; the env's have %d"
+                                % (days, rows, self.meal_time.shape[0]))
+        if self.start_minute is None:
+            self.start_minute = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        r = _lib.Restart()
+        r.days, r.random_init_bg, r.reset_outputs, r.reserved = days, int(self.random_init_bg), int(bool(reset_outputs)), 0
+        r.meal_time, r.meal_amt = self.meal_time.data_ptr(), self.meal_amt.data_ptr()
+        r.start_minute = self.start_minute.data_ptr()
+        r.h_carry = self.h_carry.data_ptr() if self.h_carry is not None else None
+
+        def ptr(t, dt):
+            if t is None:
+                return None
+            if t.dtype != dt or t.device != self.device or t.shape != (self.n,) or not t.is_contiguous():
+                raise ValueError("restart_done buffers must be contiguous [n] tensors of %s on the env's device" % dt)
+            return t.data_ptr()
+        r.terminal_cgm = ptr(terminal_obs, self.dtype)
+        st = episode_stats or {}
+        r.ep_return, r.ep_length = ptr(st.get("ep_return"), self.dtype), ptr(st.get("ep_length"), torch.int32)
+        r.last_return, r.last_length = ptr(st.get("last_return"), self.dtype), ptr(st.get("last_length"), torch.int32)
+        mptr = None
+        if mask is not None:
+            mask = torch.as_tensor(mask)
+            if mask.dtype == torch.bool and mask.device == self.device and mask.is_contiguous():
+                mask = mask.view(torch.uint8)
+            else:
+                mask = mask.to(self.device).to(torch.uint8).contiguous()
+            if mask.shape != (self.n,):
+                raise ValueError("mask must have n entries")
+            mptr = C.c_void_p(mask.data_ptr())
+        self._b.x0_override = None
+        self._clock = None                         # the envs no longer share one clock
+        # the ring is reset from the mask as it is before the launch (reset_outputs clears `done`)
+        hist_mask = None if self._hist is None else (self.done if mask is None else mask).bool()
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.t1d_restart_done(self._ctx, C.byref(self._b), mptr, C.byref(r), self._stream()))
+        self._keep = (mask, terminal_obs, st)
+        if hist_mask is not None:
+            self._hist_restart(hist_mask)
         return self.cgm
 
     def step(self, basal, bolus=None, cho=None, minutes=None, reward_fun=None):

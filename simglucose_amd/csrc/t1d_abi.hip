@@ -51,6 +51,7 @@ struct t1d_ctx {
     int record_group_min = 64;       // the multi-minute kernel: that many waiting records go ahead of a wave's next chunk
     int rollout_launches = 1;        // closed-loop roll-outs as one launch of that kernel per step: 0 never (all steps inside one launch of the generic kernel), 1 from rollout_launches_min_envs envs up, 2 always
     int rollout_launches_min_envs = 524288, rollout_launches_min_envs_f32 = 786432;
+    int restart_compact = 1;         // t1d_restart_done: 1 = a workgroup collects the finished envs of 4 096 in LDS and restarts them with full waves; 0 = every lane its own env
     std::vector<double> ptab;    // the caller's table, kept for rebuilding the split tables
     std::vector<double> dpar;    // host copy of the derived-parameter table
 };
@@ -352,6 +353,7 @@ extern "C" int t1d_ctx_set_option(t1d_ctx* c, const char* name, int64_t value)
         {"rollout_launches", &t1d_ctx::rollout_launches, 0, 2},
         {"rollout_launches_min_envs", &t1d_ctx::rollout_launches_min_envs, 0, 1 << 28},
         {"rollout_launches_min_envs_f32", &t1d_ctx::rollout_launches_min_envs_f32, 0, 1 << 28},
+        {"restart_compact", &t1d_ctx::restart_compact, 0, 1},
         {"s1_blocks", &t1d_ctx::s1_blocks, 0, 65535},
         {"adaptive_gut", &t1d_ctx::adaptive_gut, 0, 3},
         {"single_minute_kernel", &t1d_ctx::single_minute_kernel, 0, 1},
@@ -818,17 +820,9 @@ extern "C" int t1d_rollout_bb_dopri5(t1d_ctx* c, const t1d_batch* b, const t1d_b
     return launch_rollout_dopri5("t1d_rollout_bb_dopri5", c, b, nullptr, bb, h_carry, nfev, n_steps, minutes, stream);
 }
 
-extern "C" int t1d_random_meals(int hip_device, uint64_t seed, int64_t env_offset, int64_t n, int dtype, int days,
-                                const int32_t* start_minute_of_day, int start_scalar, int32_t* meal_time, void* meal_amt,
-                                void* stream)
+// the six meal windows of RandomScenario.create_scenario (scenario_gen.py:38-45) as the kernels take them
+static MealSlots meal_slots()
 {
-    if (!meal_time || !meal_amt) return fail(T1D_E_INVALID, "t1d_random_meals: output pointer is NULL");
-    if (n < 1 || n > (int64_t)1 << 28) return fail(T1D_E_INVALID, "t1d_random_meals: n out of range");
-    if (days < 1 || days > 10000) return fail(T1D_E_INVALID, "t1d_random_meals: days out of range");
-    if (dtype != T1D_F64 && dtype != T1D_F32) return fail(T1D_E_INVALID, "t1d_random_meals: bad dtype");
-    if (!start_minute_of_day && (start_scalar < 0 || start_scalar >= 1440))
-        return fail(T1D_E_INVALID, "t1d_random_meals: start minute of day must be in [0, 1440)");
-    T1D_HIP(hipSetDevice(hip_device));
     MealSlots ms;
     const double prob[6] = {0.95, 0.3, 0.95, 0.3, 0.95, 0.3};          // scenario_gen.py:38-45
     const double lb[6] = {5, 9, 10, 14, 16, 20}, ub[6] = {9, 10, 14, 16, 20, 23}, mu[6] = {7, 9.5, 12, 15, 18, 21.5};
@@ -840,6 +834,67 @@ extern "C" int t1d_random_meals(int hip_device, uint64_t seed, int64_t env_offse
         const double cb = 0.5 * std::erfc(-((ms.ub[k] - ms.mu[k]) / sd[k]) / std::sqrt(2.0));
         ms.cdf_a[k] = ca; ms.cdf_w[k] = cb - ca;
     }
+    return ms;
+}
+
+template <typename T>
+static void launch_restart(const t1d_ctx* c, const t1d_batch* b, const uint8_t* mask, const t1d_restart* r, hipStream_t s)
+{
+    RestartArgs<T> ra;
+    ra.days = r->days; ra.random_init_bg = r->random_init_bg; ra.reset_outputs = r->reset_outputs;
+    ra.meal_time = r->meal_time; ra.meal_amt = (T*)r->meal_amt; ra.start_minute = r->start_minute; ra.h_carry = r->h_carry;
+    ra.terminal_cgm = (T*)r->terminal_cgm; ra.ep_return = (T*)r->ep_return; ra.ep_length = r->ep_length;
+    ra.last_return = (T*)r->last_return; ra.last_length = r->last_length;
+    const uint8_t* m = mask ? mask : b->done;
+    if (c->restart_compact) {
+        const int64_t per = (int64_t)kBlock * kRestartTile;
+        hipLaunchKernelGGL((restart_kernel<true, T>), dim3((unsigned)((b->n + per - 1) / per)), dim3(kBlock), 0, s,
+                           make_args<T>(c, b, 1, 1), ra, m, meal_slots());
+    } else {
+        hipLaunchKernelGGL((restart_kernel<false, T>), grid_for(b->n), dim3(kBlock), 0, s, make_args<T>(c, b, 1, 1), ra, m, meal_slots());
+    }
+}
+
+extern "C" int t1d_restart_done(t1d_ctx* c, const t1d_batch* b, const uint8_t* mask, const t1d_restart* r, void* stream)
+{
+    // what needs no device is checked first, so that a bad call is refused on any machine
+    if (!b) return fail(T1D_E_INVALID, "t1d_restart_done: batch is NULL");
+    if (!r) return fail(T1D_E_INVALID, "t1d_restart_done: restart is NULL");
+    if (r->days < 1 || r->days > 10000) return fail(T1D_E_INVALID, "t1d_restart_done: days out of range");
+    if (r->reserved != 0) return fail(T1D_E_INVALID, "t1d_restart_done: reserved must be 0");
+    if (b->normals || b->n_normals != 0)
+        return fail(T1D_E_INVALID, "t1d_restart_done: host-normals batches have no per-episode source on the device");
+    if (b->x0_override) return fail(T1D_E_INVALID, "t1d_restart_done: x0_override has no per-episode source on the device");
+    if (!r->meal_time || !r->meal_amt || !r->start_minute)
+        return fail(T1D_E_INVALID, "t1d_restart_done: meal_time / meal_amt / start_minute is NULL");
+    if (r->meal_time != b->meal_time || r->meal_amt != b->meal_amt)
+        return fail(T1D_E_INVALID, "t1d_restart_done: meal_time / meal_amt must be the tables the batch names");
+    if (b->n_meals != 6 * (r->days + 1)) return fail(T1D_E_INVALID, "t1d_restart_done: batch.n_meals must be 6 (days + 1)");
+    if (!b->episode) return fail(T1D_E_INVALID, "t1d_restart_done: batch.episode is NULL (the episode index keys the new episode)");
+    if (!r->ep_return != !r->ep_length) return fail(T1D_E_INVALID, "t1d_restart_done: ep_return and ep_length go together");
+    if ((r->last_return || r->last_length) && !r->ep_return)
+        return fail(T1D_E_INVALID, "t1d_restart_done: last_return / last_length need ep_return and ep_length");
+    if (r->h_carry && b->dtype != T1D_F64) return fail(T1D_E_INVALID, "t1d_restart_done: h_carry belongs to fp64 batches");
+    int rc = check_batch("t1d_restart_done", c, b, false);
+    if (rc) return rc;
+    if (b->dtype == T1D_F64) launch_restart<double>(c, b, mask, r, (hipStream_t)stream);
+    else launch_restart<float>(c, b, mask, r, (hipStream_t)stream);
+    T1D_HIP(hipGetLastError());
+    return T1D_OK;
+}
+
+extern "C" int t1d_random_meals(int hip_device, uint64_t seed, int64_t env_offset, int64_t n, int dtype, int days,
+                                const int32_t* start_minute_of_day, int start_scalar, int32_t* meal_time, void* meal_amt,
+                                void* stream)
+{
+    if (!meal_time || !meal_amt) return fail(T1D_E_INVALID, "t1d_random_meals: output pointer is NULL");
+    if (n < 1 || n > (int64_t)1 << 28) return fail(T1D_E_INVALID, "t1d_random_meals: n out of range");
+    if (days < 1 || days > 10000) return fail(T1D_E_INVALID, "t1d_random_meals: days out of range");
+    if (dtype != T1D_F64 && dtype != T1D_F32) return fail(T1D_E_INVALID, "t1d_random_meals: bad dtype");
+    if (!start_minute_of_day && (start_scalar < 0 || start_scalar >= 1440))
+        return fail(T1D_E_INVALID, "t1d_random_meals: start minute of day must be in [0, 1440)");
+    T1D_HIP(hipSetDevice(hip_device));
+    const MealSlots ms = meal_slots();
     hipStream_t s = (hipStream_t)stream;
     if (dtype == T1D_F64)
         hipLaunchKernelGGL(random_meals_kernel<double>, grid_for(n), dim3(kBlock), 0, s, seed, env_offset, n, days,

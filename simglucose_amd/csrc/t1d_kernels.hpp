@@ -16,6 +16,7 @@
 //   rollout_pid_kernel n_steps x (PID or basal-bolus policy + step) with state in registers.
 //   reset_kernel       masked T1DSimEnv.reset().                                              (env.py:119-155)
 //   random_meals_kernel  RandomScenario.create_scenario for the whole batch.          (scenario_gen.py:33-60)
+//   restart_kernel     after a step: new start hour, meal table and reset() for the envs whose episode ended, in place.
 //   outcome_kernel     time in range, CVGA percentiles and risk means of a BG history.   (analysis/report.py:74-217)
 //   philox_normals_kernel  replays the Philox stream for tests.
 #pragma once
@@ -1478,13 +1479,12 @@ __global__ __launch_bounds__(kBlock, T1D_WAVES) void rollout_pid_kernel(const KA
     }
 }
 
+// T1DSimEnv.reset() of env i (env.py:119-155): the body of reset_kernel, and of restart_kernel for an env whose episode
+// ended.  next_meal0 = minute of the env's first meal-table entry.  outputs = false leaves bg, reward, done, lbgi, hbgi,
+// risk, meal and insulin as the step before left them (they describe the terminal transition); cgm is written either way.
 template <typename T>
-__global__ __launch_bounds__(kBlock) void reset_kernel(const KArgs<T> a, const uint8_t* mask, int random_init_bg)
+__device__ __forceinline__ void reset_env(const KArgs<T>& a, unsigned i, int random_init_bg, int next_meal0, bool outputs)
 {
-    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
-    __builtin_assume(i < (1u << 28));          // host guarantees n <= 2^28: i * sizeof(T) fits a 32-bit voffset
-    if ((int64_t)i >= a.n) return;
-    if (mask && !at(mask, i)) return;
     const int64_t n = a.n;
     const uint32_t pid = T1D_META_PID(at(a.meta, i));
     uint32_t ep = 0;
@@ -1502,7 +1502,7 @@ __global__ __launch_bounds__(kBlock) void reset_kernel(const KArgs<T> a, const u
         e.x[12] += t_sqrt(T(0.1) * e.x[12]) * (T)r2.x;
     }
     e.planned = T(0); e.lq = e.x[0] + e.x[1]; e.lf = T(0); e.eating = false; e.cursor = 0; e.t = 0;
-    e.next_meal = (a.n_meals > 0) ? at(a.meal_time, i) : INT_MAX;      // first table row; entries before t = 0 are skipped lazily
+    e.next_meal = next_meal0;                                           // first table row; entries before t = 0 are skipped lazily
     e.next_meal_loaded = e.next_meal - 1;                               // force the store
     // CGMSensor.reset -> CGMNoise(): first AR value and first 15-min point (noise_gen.py:24,86)
     T z0;
@@ -1527,14 +1527,27 @@ __global__ __launch_bounds__(kBlock) void reset_kernel(const KArgs<T> a, const u
     { T l0, h0; risk_index1<0>(c[0], l0, h0, e.prev_risk); }    // CGM_hist = [sample #0]: what the first reward is formed against
     if (a.cgm0) at(a.cgm0, i) = c[0];
     store_env(a, i, pid, e);
-    T l, h, r;
-    risk_index1<0>(bg0, l, h, r);
-    at(a.cgm, i) = c[1]; at(a.bg, i) = bg0; at(a.reward, i) = T(0); at(a.done, i) = 0;
-    if (a.lbgi) at(a.lbgi, i) = l;
-    if (a.hbgi) at(a.hbgi, i) = h;
-    if (a.risk) at(a.risk, i) = r;
-    if (a.meal) at(a.meal, i) = T(0);
-    if (a.insulin) at(a.insulin, i) = T(0);
+    at(a.cgm, i) = c[1];
+    if (outputs) {
+        T l, h, r;
+        risk_index1<0>(bg0, l, h, r);
+        at(a.bg, i) = bg0; at(a.reward, i) = T(0); at(a.done, i) = 0;
+        if (a.lbgi) at(a.lbgi, i) = l;
+        if (a.hbgi) at(a.hbgi, i) = h;
+        if (a.risk) at(a.risk, i) = r;
+        if (a.meal) at(a.meal, i) = T(0);
+        if (a.insulin) at(a.insulin, i) = T(0);
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void reset_kernel(const KArgs<T> a, const uint8_t* mask, int random_init_bg)
+{
+    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
+    __builtin_assume(i < (1u << 28));          // host guarantees n <= 2^28: i * sizeof(T) fits a 32-bit voffset
+    if ((int64_t)i >= a.n) return;
+    if (mask && !at(mask, i)) return;
+    reset_env(a, i, random_init_bg, (a.n_meals > 0) ? (int)at(a.meal_time, i) : INT_MAX, true);
 }
 
 // T1DPatient.model at n independent points (t1d_model_rhs): the RHS of the step kernels, on its own
@@ -1606,17 +1619,13 @@ struct MealSlots {
 };
 constexpr uint64_t kScenarioKey = 0x5ce9a7105ce9a710ull;
 
+// the meal table of one env: column `mt` / `ma` of a [6 (days + 1)][n] table pair (row stride n); -> its row 0
 template <typename T>
-__global__ __launch_bounds__(kBlock) void random_meals_kernel(uint64_t seed, int64_t env_offset, int64_t n, int days,
-                                                              const int32_t* start_tab, int start_scalar,
-                                                              int32_t* meal_time, T* meal_amt, MealSlots ms)
+__device__ __forceinline__ int random_meals_env(uint64_t seed, uint64_t gid, int days, int start, int32_t* mt, T* ma, int64_t n,
+                                                const MealSlots& ms)
 {
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
     const int rows = 6 * (days + 1);
-    const int start = start_tab ? start_tab[i] : start_scalar;
-    const uint64_t gid = (uint64_t)(env_offset + i);
-    int w = 0, last = -1;
+    int w = 0, last = -1, first = INT_MAX;
     for (int day = 0; day <= days; ++day) {
 #pragma unroll 1
         for (int k = 0; k < 6; ++k) {
@@ -1632,13 +1641,111 @@ __global__ __launch_bounds__(kBlock) void random_meals_kernel(uint64_t seed, int
             const double grams = fmax(rint(ms.amu[k] + ms.asd[k] * g.x), 0.0);          // :56-57
             const int minute = day * 1440 + (int)tod - start;
             if (present && minute >= 0 && minute < days * 1440 && minute != last) {
-                meal_time[(int64_t)w * n + i] = minute;
-                meal_amt[(int64_t)w * n + i] = (T)grams;
+                mt[(int64_t)w * n] = minute;
+                ma[(int64_t)w * n] = (T)grams;
+                if (w == 0) first = minute;
                 last = minute; ++w;
             }
         }
     }
-    for (; w < rows; ++w) { meal_time[(int64_t)w * n + i] = INT_MAX; meal_amt[(int64_t)w * n + i] = T(0); }
+    for (; w < rows; ++w) { mt[(int64_t)w * n] = INT_MAX; ma[(int64_t)w * n] = T(0); }
+    return first;                                  // row 0: the minute of the env's first meal (INT_MAX = none)
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void random_meals_kernel(uint64_t seed, int64_t env_offset, int64_t n, int days,
+                                                              const int32_t* start_tab, int start_scalar,
+                                                              int32_t* meal_time, T* meal_amt, MealSlots ms)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    random_meals_env<T>(seed, (uint64_t)(env_offset + i), days, start_tab ? start_tab[i] : start_scalar, meal_time + i, meal_amt + i, n, ms);
+}
+
+// ---- restart of finished episodes where they are (t1d_restart_done) -------------------------------------
+// One lane = one env, after every step: a lane whose mask byte is set starts the env's next episode -- start hour, meal
+// table column, T1DSimEnv.reset() -- all keyed by the env's OWN episode index (its `episode` counter before the call) and
+// its global id, so that an env's k-th episode does not depend on what the rest of the batch did.
+template <typename T> struct RestartArgs {
+    int days, random_init_bg, reset_outputs;
+    int32_t* meal_time; T* meal_amt; int32_t* start_minute; double* h_carry;
+    T* terminal_cgm; T* ep_return; int32_t* ep_length; T* last_return; int32_t* last_length;
+};
+
+// start hour of episode `ep` of env `gid`: splitmix64 of the global env id, keyed with seed * 1000003 + ep
+// (envs/batched_gym_env.py start_hours)
+__device__ __forceinline__ int start_hour_of(uint64_t seed, uint64_t gid, uint32_t ep)
+{
+    uint64_t z = gid * 0x9E3779B97F4A7C15ull + (seed * 1000003ull + ep);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return (int)((z >> 11) % 24u);
+}
+
+// the cheap part, every lane: episode accumulators and the terminal observation.  -> does env i restart?
+template <typename T>
+__device__ __forceinline__ bool restart_front(const KArgs<T>& a, const RestartArgs<T>& r, const uint8_t* mask, unsigned i)
+{
+    if ((int64_t)i >= a.n) return false;
+    const bool fin = at(mask, i) != 0;
+    if (r.ep_return) {
+        T sum = at(r.ep_return, i) + at(a.reward, i);
+        int len = at(r.ep_length, i) + 1;
+        if (fin) {
+            if (r.last_return) at(r.last_return, i) = sum;
+            if (r.last_length) at(r.last_length, i) = len;
+            sum = T(0); len = 0;
+        }
+        at(r.ep_return, i) = sum; at(r.ep_length, i) = len;
+    }
+    if (fin && r.terminal_cgm) { const T obs = at(a.cgm, i); at(r.terminal_cgm, i) = obs; }
+    return fin;
+}
+
+template <typename T>
+__device__ __forceinline__ void restart_env(const KArgs<T>& a, const RestartArgs<T>& r, const MealSlots& ms, unsigned i)
+{
+    const uint32_t ep = at(a.episode, i);                      // the episode index; reset_env leaves the counter at ep + 1
+    const uint64_t gid = (uint64_t)(a.env_offset + i);
+    const int start = 60 * start_hour_of(a.seed, gid, ep);
+    at(r.start_minute, i) = start;
+    const int first = random_meals_env<T>(a.seed * 7919ull + ep, gid, r.days, start, r.meal_time + i, r.meal_amt + i, a.n, ms);
+    reset_env(a, i, r.random_init_bg, first, r.reset_outputs != 0);
+    if (r.h_carry) at(r.h_carry, i) = 0.0;
+}
+
+// COMPACT = true (the default): a workgroup looks at kRestartTile x 256 envs, collects the finished ones in LDS and works
+// the list off with full waves -- finished envs are scattered (1.5 % of the envs per step on the hypo workload) and an env's
+// restart depends on nothing but itself.  COMPACT = false: every lane restarts its own env, so the 18 Philox set-ups and
+// the reset run in waves with one or two live lanes: 0.84 ms instead of 0.14 ms on top of a 0.21 ms step at 1 Mi fp64 envs.
+constexpr int kRestartTile = 16;
+template <bool COMPACT, typename T>
+__global__ __launch_bounds__(kBlock) void restart_kernel(const KArgs<T> a, const RestartArgs<T> r, const uint8_t* mask, MealSlots ms)
+{
+    if constexpr (!COMPACT) {
+        const unsigned i = blockIdx.x * kBlock + threadIdx.x;
+        __builtin_assume(i < (1u << 28));
+        if (restart_front(a, r, mask, i)) restart_env(a, r, ms, i);
+    } else {
+        __shared__ unsigned list[kBlock * kRestartTile];
+        __shared__ unsigned count;
+        if (threadIdx.x == 0) count = 0;
+        __syncthreads();
+        const unsigned base = blockIdx.x * (unsigned)(kBlock * kRestartTile) + threadIdx.x;
+#pragma unroll 4
+        for (int k = 0; k < kRestartTile; ++k) {
+            const unsigned i = base + (unsigned)(k * kBlock);
+            if (restart_front(a, r, mask, i)) list[atomicAdd(&count, 1u)] = i;
+        }
+        __syncthreads();
+        const unsigned m = count;
+        for (unsigned j = threadIdx.x; j < m; j += kBlock) {
+            const unsigned i = list[j];
+            __builtin_assume(i < (1u << 28));
+            restart_env(a, r, ms, i);
+        }
+    }
 }
 
 // ---- outcome statistics of a BG history on the device (analysis/report.py) ------------------------------

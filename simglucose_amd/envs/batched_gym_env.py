@@ -9,6 +9,14 @@ Two ways to build the episodes:
     gym's seeding chain, numpy's RandomState streams for sensor noise, scenario and initial glucose
     (``simglucose/envs/simglucose_gym_env.py:58-73``) -- through host-side set-up and the kernel's
     host-normals mode.
+
+``auto_reset``: False = the caller resets; True = ``step()`` looks at ``done`` on the host and rebuilds the finished envs'
+episodes through ``reset(mask)`` (start hours and meal seeds keyed by the wrapper's global episode counter);
+``"device"`` = ``step()`` is the step launch plus one launch of ``t1d_restart_done``: finished envs start their next episode
+where they are, keyed by their OWN episode index and global env id (an env's k-th episode is the same whatever its
+neighbours did, in a shard as in a slice of one batch), nothing is read back or allocated, and the tensors handed out keep
+their addresses.  ``info["terminal_observation"]`` (valid where ``done``) and ``info["episode"]`` (``"r"`` / ``"l"``: return and
+length of each env's last finished episode) are filled by that launch.
 """
 from datetime import datetime, timedelta
 
@@ -20,6 +28,24 @@ from ..batch_env import BatchedT1DSimEnv
 from . import seeding
 
 
+def start_hours(seed, episode, gid):
+    """start hour (0..23) of episode index `episode` of the envs with GLOBAL ids `gid` (int64 tensor): splitmix64 of the id,
+    keyed with seed * 1000003 + episode -- a function of nothing else, so that the shards of a multi-GPU job draw what the
+    slices of one big batch would.  episode: an int, or an int64 tensor like gid (every env its own index: what
+    t1d_restart_done computes on the device)."""
+    lsr = lambda v, s: (v >> s) & ((1 << (64 - s)) - 1)               # logical shift on two's-complement int64
+    wrap = lambda c: c - (1 << 64) if c >= (1 << 63) else c
+    if isinstance(episode, torch.Tensor):
+        key = episode.to(torch.int64) + wrap((int(seed) * 1000003) & 0xFFFFFFFFFFFFFFFF)
+    else:
+        key = wrap((int(seed) * 1000003 + int(episode)) & 0xFFFFFFFFFFFFFFFF)
+    z = gid * wrap(0x9E3779B97F4A7C15) + key
+    z = (z ^ lsr(z, 30)) * wrap(0xBF58476D1CE4E5B9)
+    z = (z ^ lsr(z, 27)) * wrap(0x94D049BB133111EB)
+    z = z ^ lsr(z, 31)
+    return lsr(z, 11) % 24
+
+
 class BatchedGymT1DSimEnv(object):
     SENSOR_HARDWARE = "Dexcom"
     INSULIN_PUMP_HARDWARE = "Insulet"
@@ -29,6 +55,12 @@ class BatchedGymT1DSimEnv(object):
         self.n = int(n_envs)
         names = [patient_name] * self.n if isinstance(patient_name, str) else list(patient_name)
         self.patient_names = names
+        self.device_restart = isinstance(auto_reset, str) and auto_reset == "device"
+        if isinstance(auto_reset, str) and not self.device_restart:
+            raise ValueError("auto_reset must be False, True or 'device'")
+        if self.device_restart and exact:
+            raise ValueError("auto_reset='device' draws every episode on the device; exact=True replays the reference's numpy "
+                             "streams on the host: the two do not combine")
         self.seed_value, self.exact, self.auto_reset = int(seed), bool(exact), bool(auto_reset)
         self.horizon_days = int(horizon_days)
         # as the reference wrapper's reward_fun (simglucose_gym_env.py:27-46), for the batch: f(window [20, n]) -> [n]
@@ -38,8 +70,30 @@ class BatchedGymT1DSimEnv(object):
                                     dtype=dtype, device=device, n_sub=n_sub, seed=self.seed_value,
                                     env_offset=env_offset, noise="philox", random_init_bg=not exact,
                                     cgm_history=reward_fun is not None, integrator=integrator)
-        self.start_hour = torch.zeros(self.n, dtype=torch.int64, device=self.env.device)
+        self._start_hour = torch.zeros(self.n, dtype=torch.int64, device=self.env.device)
         self.max_basal = float(self.env.pump_row[4])
+        if self.device_restart:
+            # what t1d_restart_done fills, allocated once: the buffers handed out by step() keep their addresses
+            dv, n = self.env.device, self.n
+            self.terminal_observation = torch.zeros(n, dtype=dtype, device=dv)
+            self.episode_stats = {"ep_return": torch.zeros(n, dtype=dtype, device=dv),
+                                  "ep_length": torch.zeros(n, dtype=torch.int32, device=dv),
+                                  "last_return": torch.zeros(n, dtype=dtype, device=dv),
+                                  "last_length": torch.zeros(n, dtype=torch.int32, device=dv)}
+            self._episode_info = {"r": self.episode_stats["last_return"], "l": self.episode_stats["last_length"]}
+            self._all = torch.ones(n, dtype=torch.uint8, device=dv)
+            self._done_b = torch.zeros(n, dtype=torch.bool, device=dv)
+
+    @property
+    def start_hour(self):
+        """start hour of every env's current episode, int64 [n]"""
+        if self.device_restart and self.env.start_minute is not None:
+            return (self.env.start_minute // 60).long()
+        return self._start_hour
+
+    @start_hour.setter
+    def start_hour(self, v):
+        self._start_hour = v
 
     # ------------------------------------------------------------------ episode construction
     def _build_exact(self):
@@ -78,13 +132,7 @@ class BatchedGymT1DSimEnv(object):
         """start hour of every env of this episode, a function of (seed, episode, GLOBAL env id) only -- splitmix64 of the
         id, keyed -- so that the shards of a multi-GPU job draw what the slices of one big batch would"""
         gid = torch.arange(self.n, dtype=torch.int64, device=self.env.device) + int(self.env.env_offset)
-        lsr = lambda v, s: (v >> s) & ((1 << (64 - s)) - 1)               # logical shift on two's-complement int64
-        wrap = lambda c: c - (1 << 64) if c >= (1 << 63) else c
-        z = gid * wrap(0x9E3779B97F4A7C15) + wrap((self.seed_value * 1000003 + self._episode) & 0xFFFFFFFFFFFFFFFF)
-        z = (z ^ lsr(z, 30)) * wrap(0xBF58476D1CE4E5B9)
-        z = (z ^ lsr(z, 27)) * wrap(0x94D049BB133111EB)
-        z = z ^ lsr(z, 31)
-        return lsr(z, 11) % 24
+        return start_hours(self.seed_value, self._episode, gid)
 
     def _build_device(self, mask=None):
         hours = self._start_hours()
@@ -109,10 +157,23 @@ class BatchedGymT1DSimEnv(object):
         self.env.seed = self.seed_value & 0xFFFFFFFFFFFFFFFF
         self.env._b.seed = self.env.seed
         self._episode = 0
+        if self.device_restart:
+            self.env.episode.zero_()              # every env is back at its episode 0
         return [self.seed_value]
 
     def reset(self, mask=None):
         """-> observation CGM [n].  mask (optional, device-built episodes only): reset just those envs."""
+        if self.device_restart:
+            # every env (or every masked env) goes on to ITS next episode: index = its own episode counter
+            m = self._all if mask is None else torch.as_tensor(mask, device=self.env.device)
+            obs = self.env.restart_done(mask=m, days=self.horizon_days, reset_outputs=True)
+            for k in ("ep_return", "ep_length"):
+                if mask is None:
+                    self.episode_stats[k].zero_()
+                else:
+                    self.episode_stats[k].masked_fill_(m.bool(), 0)
+            self._episode += 1
+            return obs
         if self.exact:
             if mask is not None:
                 raise ValueError("masked reset is not available with exact=True")
@@ -131,6 +192,18 @@ class BatchedGymT1DSimEnv(object):
         if a.numel() == 1:
             a = a.expand(self.n)
         obs, reward, done, info = self.env.step(a.contiguous(), reward_fun=self.reward_fun)
+        if self.device_restart:
+            # one more launch, nothing read back: where done, obs (env.cgm) now holds the new episode's first observation;
+            # reward and done are the terminal step's
+            torch.ne(done, 0, out=self._done_b)
+            if self.reward_fun is not None:           # the episode return sums what the caller is handed
+                self.env.reward.copy_(reward)
+                reward = self.env.reward
+            self.env.restart_done(days=self.horizon_days, terminal_obs=self.terminal_observation,
+                                  episode_stats=self.episode_stats)
+            info["terminal_observation"] = self.terminal_observation      # valid where done
+            info["episode"] = self._episode_info                          # return / length of each env's last finished episode
+            return obs, reward, self._done_b, info
         done_b = done.bool()
         if self.auto_reset and not self.exact and bool(done_b.any()):
             info = dict(info, terminal_observation=obs.clone())
@@ -141,6 +214,8 @@ class BatchedGymT1DSimEnv(object):
 
     def time(self):
         """per-env wall-clock as minutes since 2018-01-01 00:00."""
+        if self.device_restart and self.env.start_minute is not None:
+            return self.env.start_minute.long() + self.env.t.long()
         return self.start_hour * 60 + self.env.t.long()
 
     @property
