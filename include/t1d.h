@@ -22,6 +22,9 @@
  *   t1d_rollout_pid  <- SimObj.simulate loop with       simglucose/simulation/sim_engine.py:29-39
  *                       PIDController.policy            simglucose/controller/pid_ctrller.py:17-36
  *   t1d_rollout_bb   <- the same loop with BBController  simglucose/controller/basal_bolus_ctrller.py:34-80
+ *   t1d_rollout_mlp  <- the same loop with a learned policy: a small feed-forward network on the recent CGM, insulin
+ *                       and meal history (no counterpart in the reference, whose controllers are hand-written; it is
+ *                       what a user of simglucose/envs/simglucose_gym_env.py:14-106 trains)
  *   t1d_rollout_pid_dopri5, t1d_rollout_bb_dopri5 <- the two loops with scipy's dopri5 itself (the exact mode)
  *   t1d_random_meals <- RandomScenario.create_scenario  simglucose/simulation/scenario_gen.py:33-60
  *   t1d_restart_done <- the reset() a gym training loop calls when done comes back true (T1DSimEnv.reset + a new
@@ -195,6 +198,51 @@ typedef struct t1d_bb {
     void* bg_trace; void* cgm_trace; void* cho_trace; void* insulin_trace; int64_t trace_row;
 } t1d_bb;
 
+/* A feed-forward policy for closed-loop roll-outs (t1d_rollout_mlp), evaluated once per env and step from what the roll-out
+ * holds: the controller slot of SimObj.simulate (sim_engine.py:29-39) filled by a network instead of PIDController.policy
+ * (pid_ctrller.py:17-36) or BBController.policy (basal_bolus_ctrller.py:34-80).  Floating arrays have the batch's dtype.
+ * Features, H = history, F = 2 H + 3, in this order:
+ *   k = 0 .. H-1   (CGM[-k] - cgm_mean) * cgm_scale: CGM[0] the observation the step starts from (batch.cgm on entry, as for
+ *                  t1d_rollout_pid; env.py:81,142), CGM[-k] the observation k steps earlier
+ *   k = 0 .. H-1   INS[-1-k] * ins_scale: the mean pump output of the k-th previous step, U/min -- info["insulin"], after
+ *                  the quantiser (env.py:79; pump.py:23-39)
+ *   prev_meal * cho_scale: the previous step's mean announced CHO, g/min (info["meal"], env.py:78; the word
+ *                  basal_bolus_ctrller.py:38 reads; 0 after reset)
+ *   sin(2 pi m / 1440), cos(2 pi m / 1440), m = (start_minute[i] + t[i]) mod 1440 at the start of the step
+ * Layers: n_layers dense layers of width[l] outputs; width[n_layers - 1] == 1.  params holds, for each policy, the layers in
+ * order, each as row-major W[out][in] followed by b[out]: n_params = sum over l of width[l] * (in_l + 1), in_0 = F, in_l =
+ * width[l - 1].  Accumulation order, part of the contract so that a host can restate it: acc = b[o], then for j = 0, 1, ..
+ * ascending acc = fma(W[o][j], in[j], acc).  Hidden activation (one for the whole net): tanh(v) = sign(v) (1 - E) / (1 + E),
+ * E = exp(-2 |v|), or relu(v) = max(v, 0).  Output: basal = fma(out_scale, g(y), out_bias), g(y) = y or the logistic
+ * 1 / (1 + exp(-y)); bolus = 0; then the pump quantiser and the step exactly as in t1d_step.
+ * Env i uses policy i / envs_per_policy; batch.n == n_policies * envs_per_policy; envs_per_policy is a multiple of 64 (a
+ * wave, and a 64-env chunk, has one weight set).
+ * State: cgm_hist [H][n] and ins_hist [H][n], row k = CGM[-k] / INS[-1-k], read and written, shifted once per step (row 0 of
+ * cgm_hist is taken from batch.cgm on entry); prev_meal [n].  A roll-out cut anywhere and resumed with them gives the same
+ * words.  After t1d_reset: every row of cgm_hist = the reset observation, ins_hist = 0, prev_meal = 0. */
+enum { T1D_MLP_TANH = 0, T1D_MLP_RELU = 1 };          /* t1d_mlp.hidden_act */
+enum { T1D_MLP_IDENTITY = 0, T1D_MLP_LOGISTIC = 1 };  /* t1d_mlp.out_act */
+typedef struct t1d_mlp {
+    int32_t history;          /* H, 1 .. 12 */
+    int32_t n_layers;         /* 1 .. 4 */
+    int32_t width[4];         /* 1 .. 32 each, the last used one == 1; unused entries 0 */
+    int32_t hidden_act;       /* T1D_MLP_TANH | T1D_MLP_RELU */
+    int32_t out_act;          /* T1D_MLP_IDENTITY | T1D_MLP_LOGISTIC */
+    int64_t n_policies;
+    int64_t envs_per_policy;
+    int64_t n_params;         /* words of one policy's weight set (checked against the widths) */
+    double cgm_mean, cgm_scale, ins_scale, cho_scale, out_scale, out_bias;
+    const void* params;       /* [n_policies][n_params] */
+    void* cgm_hist;           /* [H][n] state */
+    void* ins_hist;           /* [H][n] state */
+    void* prev_meal;          /* [n] state */
+    const int32_t* start_minute;   /* [n] minute of day at which the env's episode started, NULL = 0 */
+    /* optional per-env accumulators over the roll-out (NULL to skip), as in t1d_pid */
+    void* sum_risk; void* min_bg; void* max_bg; int32_t* n_low; int32_t* n_high;
+    /* optional history on the device, as in t1d_pid; action_trace [rows][n]: the basal the network asked for, before the pump */
+    void* bg_trace; void* cgm_trace; void* cho_trace; void* insulin_trace; void* action_trace; int64_t trace_row;
+} t1d_mlp;
+
 /* Per-env outcome statistics of a BG history kept on the device (analysis/report.py), one lane per env:
  *   counts     int32 [5][n]: samples with BG > 180, BG < 70, 70 <= BG <= 180, BG > 250, BG < 50  (percent_stats,
  *              report.py:74-92; divide by n_rows for the percentages)
@@ -330,6 +378,15 @@ int t1d_rollout_pid(t1d_ctx* ctx, const t1d_batch* b, const t1d_pid* pid, int n_
  * meal tables.  Outputs/state as t1d_rollout_pid; bb.prev_meal is updated. */
 int t1d_rollout_bb(t1d_ctx* ctx, const t1d_batch* batch, const t1d_bb* bb, int n_steps, int minutes,
                    int n_sub, void* stream);
+
+/* SimObj.simulate (sim_engine.py:29-39) with the policy of t1d_mlp for n_steps env.steps in ONE launch, the env state in
+ * registers, the two windows and the layer activations in LDS, the weights through the scalar data cache.  fp64 and fp32, any
+ * state layout, the fixed-step integrators as configured on the context (the exact mode has no such roll-out), meals from the
+ * meal tables.  Outputs, state and the last step's reward as t1d_rollout_pid; mlp.cgm_hist / ins_hist / prev_meal are
+ * updated.  Anything out of range -- history, n_layers, a width, an activation code, a NULL array, n_params, or
+ * n != n_policies * envs_per_policy -- is T1D_E_INVALID before anything is launched. */
+int t1d_rollout_mlp(t1d_ctx* ctx, const t1d_batch* batch, const t1d_mlp* mlp, int n_steps, int minutes,
+                    int n_sub, void* stream);
 
 /* SimObj.simulate (sim_engine.py:29-39) with PIDController.policy (pid_ctrller.py:17-36) and the integrator of
  * t1d_step_dopri5, scipy's dopri5 as the reference drives it (t1dpatient.py:110-113,276): t1d_rollout_pid (controller,

@@ -9,7 +9,7 @@ _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("T1D_LIB_PATH") or os.path.join(_PKG, "libt1d_hip.so")   # override: A/B builds only
 SOURCES = [os.path.join(_PKG, "csrc", "t1d_abi.hip"), os.path.join(_PKG, "csrc", "t1d_kernels.hpp"),
            os.path.join(_PKG, "csrc", "t1d_device.hpp"), os.path.join(_PKG, "csrc", "t1d_dopri5.hpp"),
-           os.path.join(_ROOT, "include", "t1d.h")]
+           os.path.join(_PKG, "csrc", "t1d_policy.hpp"), os.path.join(_ROOT, "include", "t1d.h")]
 
 T1D_F64, T1D_F32 = 0, 1
 T1D_ST_NORMALS_EXHAUSTED, T1D_ST_NONFINITE, T1D_ST_BAD_INDEX, T1D_ST_STALL = 1, 2, 4, 8
@@ -21,11 +21,14 @@ META_PLANNED = 0x200
 P_NCOLS = 45
 MEAL_UNUSED = 0x7FFFFFFF
 META_EATING = 0x100
+T1D_MLP_TANH, T1D_MLP_RELU = 0, 1
+T1D_MLP_IDENTITY, T1D_MLP_LOGISTIC = 0, 1
+MLP_MAX_HISTORY, MLP_MAX_LAYERS, MLP_MAX_WIDTH = 12, 4, 32
 
 EXPORTS = ("t1d_abi_version", "t1d_last_error", "t1d_ctx_create", "t1d_ctx_set_option", "t1d_ctx_destroy", "t1d_reset",
            "t1d_step", "t1d_rollout_pid", "t1d_philox_normals", "t1d_sync", "t1d_split_tables",
            "t1d_rollout_bb", "t1d_random_meals", "t1d_outcome_stats", "t1d_model_rhs", "t1d_step_dopri5",
-           "t1d_rollout_pid_dopri5", "t1d_rollout_bb_dopri5", "t1d_restart_done")
+           "t1d_rollout_pid_dopri5", "t1d_rollout_bb_dopri5", "t1d_restart_done", "t1d_rollout_mlp")
 
 
 class T1DError(RuntimeError):
@@ -64,6 +67,19 @@ class Bb(C.Structure):
                 ("n_low", C.c_void_p), ("n_high", C.c_void_p),
                 ("bg_trace", C.c_void_p), ("cgm_trace", C.c_void_p), ("cho_trace", C.c_void_p),
                 ("insulin_trace", C.c_void_p), ("trace_row", C.c_int64)]
+
+
+class Mlp(C.Structure):
+    """struct t1d_mlp (include/t1d.h)"""
+    _fields_ = [("history", C.c_int32), ("n_layers", C.c_int32), ("width", C.c_int32 * 4), ("hidden_act", C.c_int32),
+                ("out_act", C.c_int32), ("n_policies", C.c_int64), ("envs_per_policy", C.c_int64), ("n_params", C.c_int64),
+                ("cgm_mean", C.c_double), ("cgm_scale", C.c_double), ("ins_scale", C.c_double), ("cho_scale", C.c_double),
+                ("out_scale", C.c_double), ("out_bias", C.c_double),
+                ("params", C.c_void_p), ("cgm_hist", C.c_void_p), ("ins_hist", C.c_void_p), ("prev_meal", C.c_void_p),
+                ("start_minute", C.c_void_p), ("sum_risk", C.c_void_p), ("min_bg", C.c_void_p), ("max_bg", C.c_void_p),
+                ("n_low", C.c_void_p), ("n_high", C.c_void_p),
+                ("bg_trace", C.c_void_p), ("cgm_trace", C.c_void_p), ("cho_trace", C.c_void_p),
+                ("insulin_trace", C.c_void_p), ("action_trace", C.c_void_p), ("trace_row", C.c_int64)]
 
 
 class Outcome(C.Structure):
@@ -145,6 +161,7 @@ def lib():
     L.t1d_step_dopri5.argtypes = [vp, C.POINTER(Batch), vp, vp, C.c_int, vp]
     L.t1d_rollout_pid.argtypes = [vp, C.POINTER(Batch), C.POINTER(Pid), C.c_int, C.c_int, C.c_int, vp]
     L.t1d_rollout_bb.argtypes = [vp, C.POINTER(Batch), C.POINTER(Bb), C.c_int, C.c_int, C.c_int, vp]
+    L.t1d_rollout_mlp.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), C.c_int, C.c_int, C.c_int, vp]
     L.t1d_rollout_pid_dopri5.argtypes = [vp, C.POINTER(Batch), C.POINTER(Pid), vp, vp, C.c_int, C.c_int, vp]
     L.t1d_rollout_bb_dopri5.argtypes = [vp, C.POINTER(Batch), C.POINTER(Bb), vp, vp, C.c_int, C.c_int, vp]
     L.t1d_restart_done.argtypes = [vp, C.POINTER(Batch), vp, C.POINTER(Restart), vp]

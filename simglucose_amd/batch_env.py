@@ -404,12 +404,16 @@ class BatchedT1DSimEnv:
     @staticmethod
     def _set_trace(p, trace, n_steps):
         """trace: None or dict with any of bg, cgm, cho, insulin (tensors [rows, n]) and row = first row to write
-        (see new_trace)"""
+        (see new_trace); rollout_mlp also takes action"""
         p.bg_trace = p.cgm_trace = p.cho_trace = p.insulin_trace = None
         p.trace_row = 0
+        cols = (("bg", "bg_trace"), ("cgm", "cgm_trace"), ("cho", "cho_trace"), ("insulin", "insulin_trace"))
+        if hasattr(p, "action_trace"):
+            p.action_trace = None
+            cols += (("action", "action_trace"),)
         if trace:
             row = int(trace.get("row", 0))
-            for k, f in (("bg", "bg_trace"), ("cgm", "cgm_trace"), ("cho", "cho_trace"), ("insulin", "insulin_trace")):
+            for k, f in cols:
                 if trace.get(k) is not None:
                     if trace[k].shape[0] < row + n_steps or not trace[k].is_contiguous():
                         raise ValueError("trace['%s'] needs at least row + n_steps contiguous rows" % k)
@@ -421,6 +425,7 @@ class BatchedT1DSimEnv:
         """Device-resident history for the next `n_steps` roll-out steps, laid out as T1DSimEnv's history lists
         (simulation/env.py:119-155,169-180): row 0 holds what reset() recorded (BG0 and CGM sample #0; CHO and
         insulin have no row for the last time stamp, so their row r is the action of step r), row r >= 1 step r.
+        "action" (rollout_mlp only) is the basal the policy asked for in step r, before the pump.
         Call right after reset(); pass the dict as rollout_*(trace=...)."""
         tr = {"row": 1}
         for k in columns:
@@ -433,7 +438,7 @@ class BatchedT1DSimEnv:
 
     def _no_dopri5_rollout(self):
         if self.integrator == "dopri5":
-            raise _lib.T1DError("rollout_pid / rollout_bb run the fixed-step kernels, which have no DOPRI5 path: an env with "
+            raise _lib.T1DError("rollout_pid / rollout_bb / rollout_mlp run the fixed-step kernels, which have no DOPRI5 path: an env with "
                                 "integrator='dopri5' takes rollout_pid_dopri5 / rollout_bb_dopri5")
 
     def rollout_pid(self, n_steps, P, I, D, target=140.0, pid_state=None, stats=None, trace=None):
@@ -504,6 +509,60 @@ class BatchedT1DSimEnv:
             self._clock = clock + int(n_steps) * self.minutes_per_step
         self._hist_after_rollout()
         return bb_state
+
+    def new_policy_state(self, policy):
+        """The state rollout_mlp carries for an MLPController, as it is right after reset(): every row of the CGM window
+        holds the current observation, the insulin window and prev_meal are zero.  -> dict(cgm_hist [H, n], ins_hist [H, n],
+        prev_meal [n])"""
+        H = int(policy.history)
+        return {"cgm_hist": self.cgm.unsqueeze(0).repeat(H, 1).contiguous(),
+                "ins_hist": torch.zeros(H, self.n, dtype=self.dtype, device=self.device),
+                "prev_meal": torch.zeros(self.n, dtype=self.dtype, device=self.device)}
+
+    def rollout_mlp(self, n_steps, policy, policy_state=None, stats=None, trace=None):
+        """n_steps closed-loop steps in one launch under a feed-forward policy evaluated inside the kernel (t1d_rollout_mlp,
+        include/t1d.h): policy is a controller.MLPController with one weight set, or with P of them -- env i then uses
+        set i // (n // P), and n // P must be a multiple of 64.  policy_state: dict(cgm_hist, ins_hist, prev_meal) as
+        new_policy_state() makes it (created if None: call right after reset()), updated in place and returned, so a
+        roll-out can be cut anywhere and resumed.  The time-of-day features use the env's start_minute (0 if it has none).
+        stats as in rollout_pid; trace may also hold "action" (new_trace)."""
+        self._no_dopri5_rollout()
+        n_steps = int(n_steps)
+        if n_steps < 1:
+            raise ValueError("n_steps must be at least 1")
+        npol = int(policy.n_policies)
+        if self.n % npol or (self.n // npol) % 64:
+            raise ValueError("rollout_mlp: %d envs do not split into %d policies of a multiple of 64 envs each" % (self.n, npol))
+        if policy_state is None:
+            policy_state = self.new_policy_state(policy)
+        H = int(policy.history)
+        for k, shape in (("cgm_hist", (H, self.n)), ("ins_hist", (H, self.n)), ("prev_meal", (self.n,))):
+            t = policy_state.get(k)
+            if t is None or tuple(t.shape) != shape or t.dtype != self.dtype or t.device != self.device or not t.is_contiguous():
+                raise ValueError("policy_state['%s'] must be a contiguous %s tensor of the env's dtype on its device" % (k, shape))
+        params = policy.device_params(self.device, self.dtype)          # uploaded once per policy, device and dtype
+        p = _lib.Mlp()
+        policy.fill_struct(p)
+        p.n_policies, p.envs_per_policy, p.n_params = npol, self.n // npol, params.shape[1]
+        p.params = params.data_ptr()
+        for k in ("cgm_hist", "ins_hist", "prev_meal"):
+            setattr(p, k, policy_state[k].data_ptr())
+        p.start_minute = self.start_minute.data_ptr() if self.start_minute is not None else None
+        stats = stats or {}
+        for k in ("sum_risk", "min_bg", "max_bg", "n_low", "n_high"):
+            setattr(p, k, stats[k].data_ptr() if k in stats else None)
+        self._set_trace(p, trace, n_steps)
+        self._b.cho = None
+        self._b.flags = self._flags0
+        clock, self._clock = self._clock, None
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.t1d_rollout_mlp(self._ctx, C.byref(self._b), C.byref(p), n_steps,
+                                               self.minutes_per_step, self.n_sub, self._stream()))
+        if clock is not None:
+            self._clock = clock + n_steps * self.minutes_per_step
+        self._keep = (params, policy_state)
+        self._hist_after_rollout()
+        return policy_state
 
     def _rollout_dopri5(self, fn, p, n_steps, trace, max_minutes_per_launch):
         """the launches of one exact-mode roll-out: whole steps, at most max_minutes_per_launch simulated minutes each.

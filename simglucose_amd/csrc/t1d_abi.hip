@@ -5,6 +5,7 @@
 #include "../../include/t1d.h"
 #include "t1d_kernels.hpp"
 #include "t1d_dopri5.hpp"
+#include "t1d_policy.hpp"
 
 #include <climits>
 #include <cmath>
@@ -503,8 +504,10 @@ static bool is_packed(const t1d_batch* b, size_t esz)
 }
 
 // The plan of a step (rollout = false) or of a closed-loop roll-out.  On an error *out still says whether the split tables
-// are asked for (the caller builds them either way).
-static int plan_call(const char* who, const t1d_ctx* c, const t1d_batch* b, int minutes, int n_sub, bool rollout, Plan* out)
+// are asked for (the caller builds them either way).  one_launch: a roll-out that has no launch-per-step form
+// (t1d_rollout_mlp) -- all its steps in one launch of the generic grid, whatever "rollout_launches" says.
+static int plan_call(const char* who, const t1d_ctx* c, const t1d_batch* b, int minutes, int n_sub, bool rollout, Plan* out,
+                     bool one_launch = false)
 {
     Plan& p = *out;
     p = Plan();
@@ -539,7 +542,7 @@ static int plan_call(const char* who, const t1d_ctx* c, const t1d_batch* b, int 
     // step-size rule's lanes of level 2 are set aside, where the all-steps-in-one-launch kernel runs each wave at the level
     // of its most refined lane (a step of one minute too: the kernel takes any minutes >= 1).
     const bool want_n = rollout
-        ? c->multi_minute_kernel != 0 && (c->rollout_launches == 2 || (c->rollout_launches == 1 &&
+        ? !one_launch && c->multi_minute_kernel != 0 && (c->rollout_launches == 2 || (c->rollout_launches == 1 &&
               b->n >= (p.f64 ? c->rollout_launches_min_envs : c->rollout_launches_min_envs_f32)))
         : minutes > 1 && (c->multi_minute_kernel == 2 || (c->multi_minute_kernel == 1 &&
               b->n >= (p.f64 ? c->multi_minute_min_envs : c->multi_minute_min_envs_f32)));
@@ -603,9 +606,10 @@ static int plan_call(const char* who, const t1d_ctx* c, const t1d_batch* b, int 
 
 // plan_call, then the split tables wherever the split integrator is asked for: also where the plan then fails for want
 // of LDS or falls back to RK4
-static int plan_and_tables(const char* who, t1d_ctx* c, const t1d_batch* b, int minutes, int n_sub, bool rollout, Plan* p)
+static int plan_and_tables(const char* who, t1d_ctx* c, const t1d_batch* b, int minutes, int n_sub, bool rollout, Plan* p,
+                           bool one_launch = false)
 {
-    const int rc = plan_call(who, c, b, minutes, n_sub, rollout, p);
+    const int rc = plan_call(who, c, b, minutes, n_sub, rollout, p, one_launch);
     const int e = p->tables ? ensure_split(c, n_sub) : T1D_OK;
     return e ? e : rc;
 }
@@ -782,6 +786,109 @@ extern "C" int t1d_rollout_bb(t1d_ctx* c, const t1d_batch* b, const t1d_bb* bb, 
     if (!bb || !bb->basal || !bb->cr || !bb->cf || !bb->prev_meal)
         return fail(T1D_E_INVALID, "t1d_rollout_bb: basal / cr / cf / prev_meal must be set");
     return launch_rollout("t1d_rollout_bb", c, b, nullptr, bb, n_steps, minutes, n_sub, stream);
+}
+
+// ---- t1d_rollout_mlp (t1d_policy.hpp) ---------------------------------------------------------------------------------
+template <typename T>
+static KernelFn<T, MlpArgs<T>> mlp_rollout_fn(int variant)
+{
+    switch (variant) {
+    case 0: return mlp_rollout_kernel<0, T>;
+    case 3: return mlp_rollout_kernel<3, T>;
+    case 4: return mlp_rollout_kernel<4, T>;
+    default: return mlp_rollout_kernel<sizeof(T) == 8 ? 7 : 6, T>;
+    }
+}
+
+template <typename T>
+static MlpArgs<T> make_mlp(const t1d_mlp* m, int n_steps)
+{
+    MlpArgs<T> c;
+    c.params = (const T*)m->params;
+    c.cgm_hist = (T*)m->cgm_hist; c.ins_hist = (T*)m->ins_hist; c.prev_meal = (T*)m->prev_meal; c.start_minute = m->start_minute;
+    c.cgm_mean = (T)m->cgm_mean; c.cgm_scale = (T)m->cgm_scale; c.ins_scale = (T)m->ins_scale; c.cho_scale = (T)m->cho_scale;
+    c.out_scale = (T)m->out_scale; c.out_bias = (T)m->out_bias;
+    c.sum_risk = (T*)m->sum_risk; c.min_bg = (T*)m->min_bg; c.max_bg = (T*)m->max_bg; c.n_low = m->n_low; c.n_high = m->n_high;
+    c.bg_trace = (T*)m->bg_trace; c.cgm_trace = (T*)m->cgm_trace; c.cho_trace = (T*)m->cho_trace; c.ins_trace = (T*)m->insulin_trace;
+    c.act_trace = (T*)m->action_trace; c.trace_row = m->trace_row;
+    c.envs_per_policy = (unsigned)m->envs_per_policy;
+    c.widths = 0;
+    for (int l = 0; l < m->n_layers; ++l) c.widths |= (unsigned)m->width[l] << (8 * l);
+    c.n_params = (int)m->n_params; c.history = m->history; c.n_layers = m->n_layers;
+    c.hidden_act = m->hidden_act; c.out_act = m->out_act; c.n_steps = n_steps;
+    c.lds_off = 0; c.cols = 0;
+    return c;
+}
+
+// every field of the policy that has a range; -> the rows of a wave's column block in *cols
+static int check_mlp(const t1d_batch* b, const t1d_mlp* m, int* cols)
+{
+    const std::string w = "t1d_rollout_mlp: ";
+    if (!m) return fail(T1D_E_INVALID, w + "mlp is NULL");
+    if (m->history < 1 || m->history > kMlpMaxHistory) return fail(T1D_E_INVALID, w + "history must be in [1, 12]");
+    if (m->n_layers < 1 || m->n_layers > kMlpMaxLayers) return fail(T1D_E_INVALID, w + "n_layers must be in [1, 4]");
+    const int F = 2 * m->history + 3;
+    int64_t count = 0;
+    int in_w = F, widest = F;
+    for (int l = 0; l < m->n_layers; ++l) {
+        if (m->width[l] < 1 || m->width[l] > kMlpMaxWidth) return fail(T1D_E_INVALID, w + "every width must be in [1, 32]");
+        count += (int64_t)m->width[l] * (in_w + 1);
+        in_w = m->width[l];
+        if (l + 1 < m->n_layers) widest = std::max(widest, in_w);
+    }
+    if (m->width[m->n_layers - 1] != 1) return fail(T1D_E_INVALID, w + "the last layer's width must be 1");
+    if (m->n_params != count) return fail(T1D_E_INVALID, w + "n_params must be " + std::to_string(count) + " for these widths");
+    if (m->hidden_act != T1D_MLP_TANH && m->hidden_act != T1D_MLP_RELU) return fail(T1D_E_INVALID, w + "unknown hidden_act");
+    if (m->out_act != T1D_MLP_IDENTITY && m->out_act != T1D_MLP_LOGISTIC) return fail(T1D_E_INVALID, w + "unknown out_act");
+    if (!m->params || !m->cgm_hist || !m->ins_hist || !m->prev_meal)
+        return fail(T1D_E_INVALID, w + "params / cgm_hist / ins_hist / prev_meal must be set");
+    if (m->n_policies < 1) return fail(T1D_E_INVALID, w + "n_policies < 1");
+    if (m->envs_per_policy < 64 || m->envs_per_policy % 64) return fail(T1D_E_INVALID, w + "envs_per_policy must be a multiple of 64");
+    if (m->envs_per_policy > ((int64_t)1 << 28) || m->n_policies > ((int64_t)1 << 28) || b->n != m->n_policies * m->envs_per_policy)
+        return fail(T1D_E_INVALID, w + "batch.n must be n_policies * envs_per_policy");
+    *cols = 2 * m->history + widest;
+    return T1D_OK;
+}
+
+template <typename T>
+static int run_rollout_mlp(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* m, Plan p, int cols, int n_steps, int minutes, int n_sub, hipStream_t s)
+{
+    MlpArgs<T> ma = make_mlp<T>(m, n_steps);
+    // dynamic LDS: the propagator table as the plan sized it, then the columns of every wave; the workgroup is the
+    // largest whose columns fit beside the tables (the LDS-parameter variants hold theirs in static LDS)
+    ma.lds_off = (int)((p.lds + 15) & ~(size_t)15);
+    ma.cols = cols;
+    const size_t fixed = (p.variant == 0 || p.variant == 7 ? (size_t)DP_COUNT * kMaxPatients * sizeof(T) : 0) + 256;   // static LDS
+    const size_t per_wave = (size_t)cols * 64 * sizeof(T);
+    int threads = T1D_POLICY_THREADS;
+    while (threads > 64 && fixed + ma.lds_off + per_wave * (threads / 64) > (size_t)c->lds_per_block) threads /= 2;
+    if (fixed + ma.lds_off + per_wave * (threads / 64) > (size_t)c->lds_per_block)
+        return fail(T1D_E_INVALID, "t1d_rollout_mlp: the integrator's tables leave no room in LDS for one wave of this policy");
+    p.lds = ma.lds_off + per_wave * (threads / 64);
+    p.block = threads; p.grid = (unsigned)((b->n + threads - 1) / threads);
+    return launch(c, b, p, minutes, n_sub, s, mlp_rollout_fn<T>(p.variant), ma);
+}
+
+extern "C" int t1d_rollout_mlp(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, int n_steps, int minutes,
+                               int n_sub, void* stream)
+{
+    int rc = check_batch("t1d_rollout_mlp", c, b, false);
+    if (rc) return rc;
+    if (b->cho) return fail(T1D_E_INVALID, "t1d_rollout_mlp: dense cho is not supported, use the meal table");
+    if (n_steps < 1) return fail(T1D_E_INVALID, "t1d_rollout_mlp: n_steps < 1");
+    int cols = 0;
+    rc = check_mlp(b, mlp, &cols);
+    if (rc) return rc;
+    // the plan of a roll-out that keeps all its steps in one launch: variant, refill and the propagator table's LDS
+    Plan p;
+    rc = plan_and_tables("t1d_rollout_mlp", c, b, minutes, n_sub, true, &p, true);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    rc = p.f64 ? run_rollout_mlp<double>(c, b, mlp, p, cols, n_steps, minutes, n_sub, s)
+               : run_rollout_mlp<float>(c, b, mlp, p, cols, n_steps, minutes, n_sub, s);
+    if (rc) return rc;
+    T1D_HIP(hipGetLastError());
+    return T1D_OK;
 }
 
 // The exact mode's roll-outs (t1d_dopri5.hpp): all n_steps in one launch of dopri5_rollout_kernel on the grid of

@@ -1,0 +1,231 @@
+// t1d_policy.hpp -- closed-loop roll-outs under a small feed-forward policy evaluated inside the kernel (gfx950 only):
+// t1d_rollout_mlp of include/t1d.h.  Included by t1d_abi.hip after t1d_kernels.hpp, whose step_body / load_env /
+// store_env / write_outputs it calls as they are.
+//
+//   mlp_rollout_kernel   n_steps x (features -> dense layers -> basal, then step_body) in ONE launch, the env state in
+//                        registers as in rollout_pid_kernel.  What does not fit beside the integrator's registers lives
+//                        in LDS, one column of 64 lanes per word (word k of lane l at k * 64 + l: every access of a wave
+//                        covers 64 consecutive words, so no two lanes of a group meet on a bank):
+//                          rows 0 .. H-1     the CGM window as a ring: CGM[-k] sits in row (head + k) mod H
+//                          rows H .. 2H-1    the insulin window, same ring: INS[-1-k] in row H + (head + k) mod H
+//                          rows 2H ..        the layer input: the F = 2H + 3 features, then each hidden layer's output
+//                        `head` is wave-uniform (every lane takes a step per iteration), so a step overwrites the oldest row
+//                        instead of moving 2H words; the arrays in memory are in window order on entry and on exit.
+//                        A layer's outputs are accumulated four at a time in registers and written back over its inputs
+//                        once the layer is complete.
+//   weights              one set per wave (envs_per_policy is a multiple of 64): read through the scalar data cache from
+//                        the constant address space (s_load_dword*), straight into the FMA's scalar operand -- no LDS,
+//                        no vector register; nothing is ever stored through the scalar unit.
+//   block size           64 .. 256 threads, chosen per launch (t1d_rollout_mlp): the most waves whose columns fit in a
+//                        workgroup's LDS beside the integrator's tables.  The launch bound is one wave per SIMD: a roll-out
+//                        step with the noise-block refill inline needs more than the 256 registers two waves would leave
+//                        each (rollout_pid_kernel, bound to two, keeps ~300 bytes per lane in scratch); with the whole
+//                        file seven of the eight instances report no scratch (profiles/policy).
+#pragma once
+#include "t1d_kernels.hpp"
+
+namespace t1d {
+
+constexpr int kMlpMaxHistory = 12, kMlpMaxLayers = 4, kMlpMaxWidth = 32;
+#ifndef T1D_POLICY_THREADS
+#define T1D_POLICY_THREADS 256            // launch bound: 4 waves per workgroup = 1 per SIMD, the whole register file each
+#endif
+
+template <typename T> struct MlpArgs {
+    const T* params;                      // [n_policies][n_params]
+    T* cgm_hist; T* ins_hist; T* prev_meal; const int32_t* start_minute;
+    T cgm_mean, cgm_scale, ins_scale, cho_scale, out_scale, out_bias;
+    T* sum_risk; T* min_bg; T* max_bg; int32_t* n_low; int32_t* n_high;
+    T* bg_trace; T* cgm_trace; T* cho_trace; T* ins_trace; T* act_trace; int64_t trace_row;
+    unsigned envs_per_policy, widths;     // widths: width[l] in bits 8 l .. 8 l + 7
+    int n_params, history, n_layers, hidden_act, out_act, n_steps;
+    int lds_off;                          // bytes of dynamic LDS ahead of the columns (the propagator table)
+    int cols;                             // rows of a wave's column block: 2 H + the widest layer input
+};
+
+// ---- activations on the fast exp of t1d_device.hpp ----------------------------------------------------------------
+// tanh(v) = sign(v) (1 - E) / (1 + E) with E = exp(-2 |v|) <= 1: no overflow, absolute error ~2 ulp of 1 (the relative
+// error grows towards v = 0, where 1 - E cancels: |error| stays below 3e-16 in fp64).
+template <typename T>
+__device__ __forceinline__ T mlp_tanh(T v)
+{
+    const T lim = sizeof(T) == 8 ? T(20) : T(10);            // tanh(20) = 1 - 3e-18, tanh(10) = 1 - 8e-9: both round to 1
+    const T a = t_min(v < T(0) ? -v : v, lim);
+    const T E = exp_core(T(-2) * a);
+    const T r = fdiv(T(1) - E, T(1) + E);
+    return v != v ? v : (v < T(0) ? -r : r);                 // fmin would turn a NaN into the limit: it is handed on instead
+}
+// logistic(v) = 1 / (1 + exp(-v)), the argument clamped to where the result has already reached 0 or 1
+template <typename T>
+__device__ __forceinline__ T mlp_logistic(T v)
+{
+    const T lim = sizeof(T) == 8 ? T(700) : T(80);
+    const T E = exp_core(t_max(t_min(-v, lim), -lim));
+    return v != v ? v : fdiv(T(1), T(1) + E);                // a NaN stays a NaN (the step then raises T1D_ST_NONFINITE)
+}
+
+// sin and cos of 2 pi m / 1440 for the minute of day m in [0, 1440): sinpi / cospi of m / 720 -- their argument
+// reduction is exact and has no large-argument path to pay registers for
+__device__ __forceinline__ void mlp_time_of_day(int m, double& s, double& c) { const double x = (double)m / 720.0; s = sinpi(x); c = cospi(x); }
+__device__ __forceinline__ void mlp_time_of_day(int m, float& s, float& c) { const float x = (float)m / 720.0f; s = sinpif(x); c = cospif(x); }
+
+// The dense layers on the lane's column.  buf: rows of the layer input (row j at buf[j * 64]); w: this wave's weight set,
+// layer after layer, each as row-major W[out][in] followed by b[out].  Accumulation order (include/t1d.h): acc = b[o],
+// then acc = fma(W[o][j], in[j], acc) for j ascending.  -> the last layer's single output, before the output function.
+template <typename T>
+__device__ __forceinline__ T mlp_layers(const MlpArgs<T>& c, const __attribute__((address_space(4))) T* w, T* buf, int in_w)
+{
+    T y = T(0);
+#pragma unroll 1
+    for (int l = 0; l < c.n_layers; ++l) {
+        const int out_w = (int)((c.widths >> (8 * l)) & 0xffu);
+        const __attribute__((address_space(4))) T* bias = w + out_w * in_w;
+        T out[kMlpMaxWidth];
+#pragma unroll
+        for (int ob = 0; ob < kMlpMaxWidth; ob += 4) {
+            if (ob < out_w) {                                            // wave-uniform
+                // four outputs share every input word read from LDS; beyond the layer's width the last row is computed
+                // again and dropped
+                const int last = out_w - 1;
+                const int o0 = ob, o1 = ob + 1 < last ? ob + 1 : last, o2 = ob + 2 < last ? ob + 2 : last, o3 = ob + 3 < last ? ob + 3 : last;
+                const __attribute__((address_space(4))) T* r0 = w + o0 * in_w;
+                const __attribute__((address_space(4))) T* r1 = w + o1 * in_w;
+                const __attribute__((address_space(4))) T* r2 = w + o2 * in_w;
+                const __attribute__((address_space(4))) T* r3 = w + o3 * in_w;
+                T a0 = bias[o0], a1 = bias[o1], a2 = bias[o2], a3 = bias[o3];
+#pragma unroll 1
+                for (int j = 0; j < in_w; ++j) {
+                    const T x = buf[j * 64];
+                    a0 = fma((T)r0[j], x, a0); a1 = fma((T)r1[j], x, a1); a2 = fma((T)r2[j], x, a2); a3 = fma((T)r3[j], x, a3);
+                }
+                out[ob] = a0; out[ob + 1] = a1; out[ob + 2] = a2; out[ob + 3] = a3;
+            }
+        }
+        if (l + 1 == c.n_layers) { y = out[0]; break; }
+        // the layer is complete: its outputs replace its inputs, then the activation runs over them in place
+#pragma unroll
+        for (int o = 0; o < kMlpMaxWidth; ++o)
+            if (o < out_w) buf[o * 64] = out[o];
+#pragma unroll 1
+        for (int o = 0; o < out_w; ++o) {
+            const T v = buf[o * 64];
+            buf[o * 64] = c.hidden_act == 0 ? mlp_tanh(v) : (v < T(0) ? T(0) : v);      // relu; a NaN stays a NaN
+        }
+        w = bias + out_w;
+        in_w = out_w;
+    }
+    return y;
+}
+
+// rollout_body (t1d_kernels.hpp) with the policy in place of the two hand-written controllers.  col: the lane's column.
+template <int VARIANT, typename T, typename P, typename PR = NoProp>
+__device__ __forceinline__ void mlp_rollout_body(const KArgs<T>& a, const MlpArgs<T>& c, P& p, unsigned i, uint32_t pid, Env<T>& e,
+                                                 T* col, PR pr = PR())
+{
+    constexpr int MATH = VariantMath<VARIANT>::value;
+    typedef const __attribute__((address_space(4))) T* WPtr;
+    const int H = c.history;
+    T* const buf = col + 2 * H * 64;
+    // the wave's weight set: a scalar base, whatever the compiler can prove about the lane index
+    const unsigned wave0 = __builtin_amdgcn_readfirstlane(i & ~63u);
+    const WPtr w = (WPtr)(c.params + (size_t)(wave0 / c.envs_per_policy) * (size_t)c.n_params);
+    T obs = at(a.cgm, i);
+    col[0] = obs;                                               // CGM[0] is the observation the step starts from
+    for (int k = 1; k < H; ++k) col[k * 64] = at(rowv(c.cgm_hist, a.n, k), i);
+    for (int k = 0; k < H; ++k) col[(H + k) * 64] = at(rowv(c.ins_hist, a.n, k), i);
+    int head = 0;
+    T prev_meal = at(c.prev_meal, i);
+    const int start = c.start_minute ? (int)at(c.start_minute, i) : 0;
+    T sum_risk = c.sum_risk ? at(c.sum_risk, i) : T(0);
+    T min_bg = c.min_bg ? at(c.min_bg, i) : T(0), max_bg = c.max_bg ? at(c.max_bg, i) : T(0);
+    int n_low = c.n_low ? at(c.n_low, i) : 0, n_high = c.n_high ? at(c.n_high, i) : 0;
+    StepOut<T> o{obs, T(0), T(0), T(0)};
+    T cgm_before = T(0);                        // CGM of the step before the last one, once two steps have run
+#pragma unroll 1
+    for (int s = 0; s < c.n_steps; ++s) {
+        // the features, in the order of include/t1d.h
+        for (int k = 0, r = head; k < H; ++k) {
+            buf[k * 64] = (col[r * 64] - c.cgm_mean) * c.cgm_scale;
+            buf[(H + k) * 64] = col[(H + r) * 64] * c.ins_scale;
+            r = r + 1 == H ? 0 : r + 1;
+        }
+        buf[2 * H * 64] = prev_meal * c.cho_scale;
+        {
+            int m = (start + e.t) % 1440;
+            m = m < 0 ? m + 1440 : m;
+            T sn, cs;
+            mlp_time_of_day(m, sn, cs);
+            buf[(2 * H + 1) * 64] = sn; buf[(2 * H + 2) * 64] = cs;
+        }
+        const T y = mlp_layers(c, w, buf, 2 * H + 3);
+        const T u = fma(c.out_scale, c.out_act == 0 ? y : mlp_logistic(y), c.out_bias);
+        o = step_body<MATH, T, P, true, PR, VariantInfo<VARIANT>::tiered>(a, p, i, e, u, T(0), true, pr);
+        obs = o.cgm;
+        prev_meal = o.meal;
+        head = head == 0 ? H - 1 : head - 1;                    // the oldest row becomes the newest
+        col[head * 64] = o.cgm; col[(H + head) * 64] = o.ins;
+        if (c.bg_trace) c.bg_trace[(c.trace_row + s) * a.n + i] = o.bg;
+        if (c.cgm_trace) c.cgm_trace[(c.trace_row + s) * a.n + i] = o.cgm;
+        if (c.cho_trace) c.cho_trace[(c.trace_row + s) * a.n + i] = o.meal;
+        if (c.ins_trace) c.ins_trace[(c.trace_row + s) * a.n + i] = o.ins;
+        if (c.act_trace) c.act_trace[(c.trace_row + s) * a.n + i] = u;
+        if (s + 1 < c.n_steps) cgm_before = o.cgm;  // CGM history advances every step
+        if (c.sum_risk) { T l, h, r; risk_index1<MATH>(o.bg, l, h, r); sum_risk += r; }
+        min_bg = o.bg < min_bg ? o.bg : min_bg;
+        max_bg = o.bg > max_bg ? o.bg : max_bg;
+        n_low += o.bg < T(70); n_high += o.bg > T(180);
+    }
+    // the last step's reward: against the step before it, or against what the state carried in (one step)
+    T rp = e.prev_risk;
+    if (c.n_steps > 1) { T l, h; risk_index1<MATH>(cgm_before, l, h, rp); }
+    write_outputs<MATH>(a, i, e, o, rp);
+    store_env(a, i, pid, e);
+    for (int k = 0, r = head; k < H; ++k) {                     // the windows back in window order
+        at(rowv(c.cgm_hist, a.n, k), i) = col[r * 64];
+        at(rowv(c.ins_hist, a.n, k), i) = col[(H + r) * 64];
+        r = r + 1 == H ? 0 : r + 1;
+    }
+    at(c.prev_meal, i) = prev_meal;
+    if (c.sum_risk) at(c.sum_risk, i) = sum_risk;
+    if (c.min_bg) at(c.min_bg, i) = min_bg;
+    if (c.max_bg) at(c.max_bg, i) = max_bg;
+    if (c.n_low) at(c.n_low, i) = n_low;
+    if (c.n_high) at(c.n_high, i) = n_high;
+}
+
+// VARIANT as for rollout_pid_kernel.  blockDim.x is any multiple of 64 up to T1D_POLICY_THREADS; dynamic LDS: the
+// propagator table (split variants), then cols * 64 words for each wave.
+template <int VARIANT, typename T>
+__global__ __launch_bounds__(T1D_POLICY_THREADS) void mlp_rollout_kernel(const KArgs<T> a, const MlpArgs<T> c)
+{
+    using VI = VariantInfo<VARIANT>;
+    constexpr int kParRows = VI::split ? DP_COUNT : DP_RK4_COUNT;
+    __shared__ T lds[VI::lds_pars ? kParRows * kMaxPatients : 1];
+    if (VI::lds_pars) stage_pars(a, lds, kParRows);
+    if (VI::split) stage_prop(a, (T*)t1d_dyn_lds);
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    __builtin_assume(i < (1u << 28));          // host guarantees n <= 2^28: i * sizeof(T) fits a 32-bit voffset
+    if ((int64_t)i >= a.n) return;
+    T* const col = (T*)(t1d_dyn_lds + c.lds_off) + (threadIdx.x >> 6) * (c.cols * 64) + (threadIdx.x & 63u);
+    const uint32_t meta = at(a.meta, i);
+    const uint32_t pid = T1D_META_PID(meta);
+    Env<T> e;
+    load_env(a, i, meta, e);
+    if constexpr (VARIANT == 4 || VARIANT == 6) {
+        ParsReg<T> p;
+        p.load(a.dpar, (int)pid);
+        mlp_rollout_body<VARIANT>(a, c, p, i, pid, e, col, PropLds<T>{(const T*)t1d_dyn_lds, a.np_pad, (int)pid});
+    } else if constexpr (VARIANT == 7) {
+        ParsLds<T> p{lds, (int)pid};
+        mlp_rollout_body<VARIANT>(a, c, p, i, pid, e, col, PropLds<T>{(const T*)t1d_dyn_lds, a.np_pad, (int)pid});
+    } else if constexpr (VARIANT == 3) {
+        ParsReg<T> p;
+        p.load(a.dpar, (int)pid);
+        mlp_rollout_body<VARIANT>(a, c, p, i, pid, e, col);
+    } else {
+        ParsLds<T> p{lds, (int)pid};
+        mlp_rollout_body<VARIANT>(a, c, p, i, pid, e, col);
+    }
+}
+
+} // namespace t1d

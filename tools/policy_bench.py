@@ -1,0 +1,126 @@
+"""Cost of a closed loop under a learned policy: 160 Dexcom steps, random-meal days, all 30 patients, with
+  mlp      BatchedT1DSimEnv.rollout_mlp: features, network and step fused in one launch (t1d_rollout_mlp)
+  host     the same policy as torch ops around one step() launch per step -- what a user does without rollout_mlp
+  pid      rollout_pid: the no-network floor
+Every leg: fresh env, reset, one warm-up pass of `warmup` steps, then `steps` steps between two device synchronisations
+(host clock).  The legs are alternated `reps` times.  `net_share` is 1 - pid / mlp: the part of the fused launch the network,
+the windows and the wider register budget cost.  One JSON line per (dtype, batch size); --out writes them as a list.
+
+    python tools/policy_bench.py --out profiles/policy/policy_bench.json
+"""
+import argparse
+import json
+import math
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+START = 360
+
+
+def make_policy(history, widths, seed=0):
+    import torch
+    from simglucose_amd.controller.mlp_ctrller import MLPController
+    g = torch.Generator().manual_seed(seed)
+    layers, n_in = [], 2 * history + 3
+    for w in widths:
+        layers.append((torch.randn(1, w, n_in, generator=g, dtype=torch.float64) / math.sqrt(n_in),
+                       0.1 * torch.randn(1, w, generator=g, dtype=torch.float64)))
+        n_in = w
+    return MLPController(layers, history=history, hidden="tanh", output="logistic", out_scale=0.06)
+
+
+def make_env(n, dtype, seed):
+    import numpy as np
+    import torch
+    from simglucose_amd.batch_env import BatchedT1DSimEnv
+    from simglucose_amd.scenario_batch import random_meal_tables
+    e = BatchedT1DSimEnv(patient=np.arange(n) % 30, sensor="Dexcom", dtype=dtype, seed=seed)
+    e.set_meals(*random_meal_tables(n, days=1, start_minute_of_day=START, seed=seed, dtype=dtype))
+    e.start_minute = torch.full((n,), START, dtype=torch.int32, device=e.device)
+    e.reset()
+    return e
+
+
+def run_leg(leg, n, dtype, pol, steps, warmup, seed):
+    import torch
+    e = make_env(n, dtype, seed)
+    zero = torch.zeros(n, dtype=dtype, device=e.device)
+    state = e.new_policy_state(pol)
+    pid_state = None
+
+    def go(k):
+        nonlocal pid_state
+        if leg == "mlp":
+            e.rollout_mlp(k, pol, policy_state=state)
+        elif leg == "pid":
+            pid_state = e.rollout_pid(k, 1.5e-4, 4e-7, 5e-4, pid_state=pid_state)
+        else:
+            for _ in range(k):
+                feat = pol.features(state["cgm_hist"], state["ins_hist"], state["prev_meal"], e.start_minute + e.t)
+                e.step(pol.forward(feat), zero)
+                pol.shift(state["cgm_hist"], state["ins_hist"], e.cgm, e.insulin)
+                state["prev_meal"].copy_(e.meal)
+    go(warmup)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    go(steps)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    status = e.sync(raise_on_status=False)
+    mean_bg = float(e.bg.mean())
+    e.close()
+    del e
+    torch.cuda.empty_cache()
+    return {"us_per_step": 1e6 * dt / steps, "status": status, "mean_bg": mean_bg}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, nargs="+", default=[1 << 16, 1 << 20])
+    ap.add_argument("--dtypes", nargs="+", default=["float64", "float32"])
+    ap.add_argument("--steps", type=int, default=160)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--legs", nargs="+", default=["mlp", "host", "pid"], choices=["mlp", "host", "pid"])
+    ap.add_argument("--history", type=int, default=4)
+    ap.add_argument("--widths", type=int, nargs="+", default=[16, 16, 1])
+    ap.add_argument("--seed", type=int, default=5)
+    ap.add_argument("--label", default=None, help="free text kept in the output (e.g. which build was measured)")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("policy_bench.py measures on the GPU: none found")
+    pol = make_policy(args.history, args.widths)
+    results = []
+    for name in args.dtypes:
+        dtype = getattr(torch, name)
+        for n in args.n:
+            runs = {leg: [] for leg in args.legs}
+            for _ in range(args.reps):
+                for leg in args.legs:
+                    runs[leg].append(run_leg(leg, n, dtype, pol, args.steps, args.warmup, args.seed))
+            res = {"n_envs": n, "dtype": name, "steps": args.steps, "warmup": args.warmup, "sensor": "Dexcom", "history": args.history,
+                   "widths": args.widths, "label": args.label, "device": torch.cuda.get_device_name(0), "legs": {}}
+            for leg, rr in runs.items():
+                us = sorted(r["us_per_step"] for r in rr)
+                res["legs"][leg] = {"us_per_step_median": us[len(us) // 2], "us_per_step_runs": [r["us_per_step"] for r in rr],
+                                    "status": max(r["status"] for r in rr), "mean_bg": rr[-1]["mean_bg"]}
+            med = {leg: v["us_per_step_median"] for leg, v in res["legs"].items()}
+            if "mlp" in med and "host" in med:
+                res["host_over_mlp"] = med["host"] / med["mlp"]
+            if "mlp" in med and "pid" in med:
+                res["net_share"] = 1.0 - med["pid"] / med["mlp"]
+            print(json.dumps(res), flush=True)
+            results.append(res)
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(results, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
