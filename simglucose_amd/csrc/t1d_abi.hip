@@ -42,6 +42,9 @@ struct t1d_ctx {
     int split_nsub = 0;      // n_sub the split tables on the device were built for (0 = none yet)
     int np_pad = 0;
     double* d_prop64 = nullptr; float* d_prop32 = nullptr;   // [kPropRows(split_nsub)][np_pad]
+    // both tables as the persistent kernels keep them in LDS at row stride 32, the pump and sensor limits behind them
+    // (s1_stage_image); rebuilt with the tables, by ensure_split alone; null for more than 32 patients
+    double* d_img64 = nullptr; float* d_img32 = nullptr;
     long long* d_trace = nullptr;    // T1D_S1_TRACE builds
     int defer_min_chunks = 1;        // adaptive_gut = 1: one-minute launches set lanes of level 2 aside from this many chunks per CU up
     int multi_minute_kernel = 1;     // steps of several minutes (minutes <= sample_time) on the packed layout through the persistent kernel with the state in registers across the minutes: 0 never (generic kernel), 1 = fp64 batches of multi_minute_min_envs envs or more, 2 always
@@ -230,6 +233,24 @@ static int ensure_split(t1d_ctx* c, int ng)
     T1D_HIP(hipMemcpy(c->d_prop32, propf.data(), propf.size() * 4, hipMemcpyHostToDevice));
     T1D_HIP(hipMemcpy(c->d_par64, c->dpar.data(), c->dpar.size() * 8, hipMemcpyHostToDevice));
     T1D_HIP(hipMemcpy(c->d_par32, dpf.data(), dpf.size() * 4, hipMemcpyHostToDevice));
+    (void)hipFree(c->d_img64); (void)hipFree(c->d_img32); c->d_img64 = nullptr; c->d_img32 = nullptr;
+    if (c->np <= 32) {
+        // [DP_COUNT + rows][32]: the words the kernels would gather from dpar and prop, zero beyond np; then lconst's eight
+        std::vector<double> img((size_t)(DP_COUNT + rows) * 32 + kImgConst, 0.0);
+        for (int j = 0; j < c->np; ++j) {
+            for (int k = 0; k < DP_COUNT; ++k) img[(size_t)k * 32 + j] = c->dpar[(size_t)k * kMaxPatients + j];
+            for (int k = 0; k < rows; ++k) img[(size_t)(DP_COUNT + k) * 32 + j] = prop[(size_t)k * npp + j];
+        }
+        double* const lc = img.data() + (size_t)(DP_COUNT + rows) * 32;
+        lc[0] = c->pump[5]; lc[1] = c->pump[3]; lc[2] = c->pump[4];      // inc_basal, min_basal, max_basal
+        lc[3] = c->pump[2]; lc[4] = c->pump[0]; lc[5] = c->pump[1];      // inc_bolus, min_bolus, max_bolus
+        lc[6] = c->sensor[6]; lc[7] = c->sensor[7];                      // vmin, vmax
+        std::vector<float> imgf(img.begin(), img.end());
+        T1D_HIP(hipMalloc((void**)&c->d_img64, img.size() * 8));
+        T1D_HIP(hipMalloc((void**)&c->d_img32, imgf.size() * 4));
+        T1D_HIP(hipMemcpy(c->d_img64, img.data(), img.size() * 8, hipMemcpyHostToDevice));
+        T1D_HIP(hipMemcpy(c->d_img32, imgf.data(), imgf.size() * 4, hipMemcpyHostToDevice));
+    }
     c->split_nsub = ng;
     return T1D_OK;
 }
@@ -377,6 +398,7 @@ extern "C" int t1d_ctx_destroy(t1d_ctx* c)
     (void)hipFree(c->d_par64); (void)hipFree(c->d_par32); (void)hipFree(c->d_x0);
     (void)hipFree(c->d_minv64); (void)hipFree(c->d_minv32); (void)hipFree(c->d_status);
     (void)hipFree(c->d_prop64); (void)hipFree(c->d_prop32); (void)hipFree(c->d_trace); (void)hipFree(c->d_raw64);
+    (void)hipFree(c->d_img64); (void)hipFree(c->d_img32);
     delete c;
     return T1D_OK;
 }
@@ -432,6 +454,7 @@ static KArgs<T> make_args(const t1d_ctx* c, const t1d_batch* b, int minutes, int
     a.np = c->np; a.S = c->S; a.n_meals = b->n_meals; a.n_normals = b->n_normals;
     a.minutes = minutes; a.n_sub = n_sub; a.flags = b->flags | (c->pingpong && (c->launches & 1) ? kFlagReverse : 0);
     a.prop = sizeof(T) == 8 ? (const T*)c->d_prop64 : (const T*)c->d_prop32;
+    a.img = sizeof(T) == 8 ? (const T*)c->d_img64 : (const T*)c->d_img32;
     a.prop_rows = c->split_nsub ? kPropRows(c->split_nsub) : 0; a.np_pad = c->np_pad;
     return a;
 }

@@ -732,10 +732,23 @@ __device__ __forceinline__ T pump_quantise(T amount, T inc, T lo, T hi)
 // risk_index([bg], 1) (risk.py:5-17); NaN -> 0 and Inf -> max as numpy.nan_to_num does.
 // MATH 1: log(bg)**1.084 = exp(1.084 log(log bg)) with the fast log/exp above; arguments outside
 // (1, inf) are resolved by case analysis with numpy's semantics.
-template <int MATH, typename T>
+// CLAMPED (MATH 1): the caller vouches for 1 < bg < inf (a CGM value just clamped to a sensor range above 1 mg/dL, which
+// also maps NaN to its lower end): none of the special cases can occur, f is finite and 10 f^2 far below `big`, so the
+// selects that resolve them drop out; the results are the same bits (ri = l + h = 10 f^2, one of the two being 0).
+template <int MATH, typename T, bool CLAMPED = false>
 __device__ __forceinline__ void risk_index1(T bg, T& lbgi, T& hbgi, T& ri)
 {
     T f;
+    if (MATH == 1 && CLAMPED) {
+        const T u = log_core<true>(bg);
+        const T pw = exp_core<12, true>(T(1.084) * log_core<true>(u));
+        f = T(1.509) * (pw - T(5.381));
+        const T ff = T(10) * f * f;
+        lbgi = f < T(0) ? ff : T(0);
+        hbgi = f > T(0) ? ff : T(0);
+        ri = ff;
+        return;
+    }
     if (MATH == 0) {
         f = T(1.509) * (t_pow(t_log(bg), T(1.084)) - T(5.381));
     } else {

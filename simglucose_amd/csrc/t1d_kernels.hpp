@@ -57,6 +57,7 @@ template <typename T> struct KArgs {
     T* cgm; T* bg; T* reward; uint8_t* done; T* lbgi; T* hbgi; T* risk; T* meal; T* insulin; T* cgm0;
     const T* dpar;          // [DP_COUNT][kMaxPatients] derived patient constants
     const T* prop;          // [prop_rows][np_pad] insulin propagator of the split integrator (kPropRows(n_sub) rows)
+    const T* img;           // both tables as the persistent kernels keep them in LDS at row stride 32 (s1_stage_image); np <= 32
     const double* x0tab;    // [13][np]
     const T* minv;          // [11][11] knot second derivatives of the noise spline: M = minv . y
     int* status;
@@ -705,11 +706,13 @@ __device__ __forceinline__ void s1_chunk(const KArgs<T>& a, T* ldp, T* lpr, T* l
         for (int k = 0; k < 4; ++k) at(X(40 + k), i) = e.cur[k];
     }
     const T gsub = e.x[12] * pl(DP_IVG);                                                       // t1dpatient.py:217-218
+    bool in_range = false;                                    // this lane's CGM has just been clamped to a range inside (1, inf)
     if (due) {                                                                                 // cgm.py:26-36
         T c = gsub + noise;
         int z = 0;
         asm volatile("" : "+v"(z));
         const T vmin = lconst[6 + z], vmax = lconst[7 + z];
+        in_range = vmin > T(1) && vmax < T(__builtin_huge_val());
         c = c > vmin ? c : vmin;
         c = c < vmax ? c : vmax;
         last_cgm = c;
@@ -719,7 +722,12 @@ __device__ __forceinline__ void s1_chunk(const KArgs<T>& a, T* ldp, T* lpr, T* l
     at(a.cgm, i) = cgm_out; at(a.bg, i) = bg_out;
     if (!(fabs((double)e.x[12]) <= 1.0e300)) atomicOr(a.status, T1D_ST_NONFINITE);
     T l, h, r, rc = T(0);
-    if (!ab_flag(a, 0x100)) risk_index1<1>(cgm_out, l, h, rc);
+    if (!ab_flag(a, 0x100)) {
+        // every sensor of sensor_params.csv clamps to a range far above 1 mg/dL: the risk index then meets none of numpy's
+        // special cases.  A held value (no sample due) is state, and takes the full form with the rest of its wave.
+        if (__builtin_amdgcn_ballot_w64(!in_range) == 0ull) risk_index1<1, T, true>(cgm_out, l, h, rc);
+        else risk_index1<1>(cgm_out, l, h, rc);
+    }
     at(a.reward, i) = rp - rc;                                                                 // env.py:27-33
     at(X(17), i) = rc;
     at(a.done, i) = (bg_out < T(70) || bg_out > T(350)) ? 1 : 0;                               // env.py:103
@@ -736,6 +744,36 @@ __device__ __forceinline__ void s1_chunk(const KArgs<T>& a, T* ldp, T* lpr, T* l
 }
 
 struct S1NoLevel { __device__ __forceinline__ void operator()(bool) const {} };
+
+// words of the table image behind its rows: pump and sensor limits in lconst's order
+constexpr int kImgConst = 8;
+// The tables of a CU at row stride 32 from their image (KArgs.img: [DP_COUNT + prop_rows][32], zero beyond np, then
+// kImgConst words; t1d_abi.hip builds it with the tables): a straight copy, 16 bytes per lane and load, four loads in flight
+// before the first is waited for -- one round trip for the tables of n_sub = 4 where s1_stage_tables makes eight dependent
+// ones with a division per element.  ldp and lpr are contiguous in LDS.
+template <typename T, int NT>
+__device__ __forceinline__ void s1_stage_image(const KArgs<T>& a, T* ldp, T* lconst)
+{
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    const int words = (DP_COUNT + a.prop_rows) * 32;
+    const int units = words * (int)sizeof(T) / 16;
+    const u32x4* __restrict__ src = (const u32x4*)a.img;
+    u32x4* dst = (u32x4*)ldp;
+    for (int j0 = 0; j0 < units; j0 += 4 * NT) {
+        u32x4 v[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int j = j0 + k * NT + (int)threadIdx.x;
+            v[k] = j < units ? src[j] : u32x4{0u, 0u, 0u, 0u};
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int j = j0 + k * NT + (int)threadIdx.x;
+            if (j < units) dst[j] = v[k];
+        }
+    }
+    if (threadIdx.x < kImgConst) lconst[threadIdx.x] = a.img[words + threadIdx.x];
+}
 
 // tables of one CU, staged once per launch: ldp = [DP_COUNT][STRIDE], lpr = [prop_rows][STRIDE]
 template <typename T, int STRIDE>
@@ -768,7 +806,8 @@ __global__ __launch_bounds__(s1_threads<T>(), 1) void step1_kernel(const KArgs<T
     __shared__ int queue;
     __shared__ T lconst[8];                              // pump and sensor limits: read from LDS where used, so that they
                                                          // do not sit in (spilled) scalar registers across the whole kernel
-    s1_stage_tables<T, STRIDE>(a, ldp, lpr, lconst);
+    if constexpr (STRIDE == 32) s1_stage_image<T, s1_threads<T>()>(a, ldp, lconst);
+    else s1_stage_tables<T, STRIDE>(a, ldp, lpr, lconst);
     if (threadIdx.x == 0) queue = 0;
     __syncthreads();
     // This workgroup owns a contiguous run of 64-env chunks; its waves draw them from a queue in LDS.  The
@@ -830,7 +869,7 @@ __global__ __launch_bounds__(s1d_threads<T>(), 1) void step1d_kernel(const KArgs
     uint16_t* const list = (uint16_t*)(park_i + 3 * kS1DPark);
     __shared__ int queue, taken, listed, passed;
     __shared__ T lconst[8];
-    s1_stage_tables<T, STRIDE>(a, ldp, lpr, lconst);
+    s1_stage_image<T, s1d_threads<T>()>(a, ldp, lconst);
     if (threadIdx.x == 0) { queue = 0; taken = 0; listed = 0; passed = 0; }
     __syncthreads();
     const int first = (int)blockIdx.x * per_block;
