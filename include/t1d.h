@@ -25,6 +25,9 @@
  *   t1d_rollout_mlp  <- the same loop with a learned policy: a small feed-forward network on the recent CGM, insulin
  *                       and meal history (no counterpart in the reference, whose controllers are hand-written; it is
  *                       what a user of simglucose/envs/simglucose_gym_env.py:14-106 trains)
+ *   t1d_collect_mlp  <- that loop as a gym training loop runs it: the action sampled around the network's output, the
+ *                       reward and done of every step kept, reset() when done comes back true
+ *                       (simglucose/envs/simglucose_gym_env.py:39-73)
  *   t1d_rollout_pid_dopri5, t1d_rollout_bb_dopri5 <- the two loops with scipy's dopri5 itself (the exact mode)
  *   t1d_random_meals <- RandomScenario.create_scenario  simglucose/simulation/scenario_gen.py:33-60
  *   t1d_restart_done <- the reset() a gym training loop calls when done comes back true (T1DSimEnv.reset + a new
@@ -277,6 +280,25 @@ typedef struct t1d_restart {
     int32_t* last_length;     /* [n] or NULL (needs ep_return): ep_length of it */
 } t1d_restart;
 
+/* t1d_collect_mlp: what a policy-gradient trainer needs of a roll-out under t1d_mlp besides the roll-out itself.  Floating
+ * arrays have the batch's dtype. */
+enum { T1D_COLLECT_CONTINUE = 0, T1D_COLLECT_RESTART = 1 };   /* t1d_collect.on_done */
+typedef struct t1d_collect {
+    uint64_t explore_seed;    /* Philox key of the exploration draws; its own key, not batch.seed */
+    const void* sigma;        /* [n_policies]: std of the noise added to the network's output before the output function;
+                                 NULL = no noise (no draw is made) */
+    int32_t on_done;          /* T1D_COLLECT_CONTINUE: episodes never end (as t1d_rollout_mlp); T1D_COLLECT_RESTART: an env whose
+                                 step comes back done starts its next episode before its next step, exactly as
+                                 t1d_restart_done would */
+    int32_t reserved;         /* 0 */
+    const t1d_restart* restart;   /* on_done = T1D_COLLECT_RESTART: as for t1d_restart_done (h_carry must be NULL); else ignored */
+    /* optional histories, rows as the traces of t1d_mlp (row mlp.trace_row + s = step s of this call), NULL to skip */
+    void* reward_trace;       /* [rows][n]    risk_diff of every step: what batch.reward would hold after that step */
+    uint8_t* done_trace;      /* [rows][n]    batch.done of every step */
+    void* eps_trace;          /* [rows][n]    the standard normal drawn for the step (0 where sigma is NULL) */
+    void* feat_trace;         /* [rows][F][n] the F = 2 H + 3 features the network was given, in t1d_mlp's order */
+} t1d_collect;
+
 int t1d_abi_version(void);
 const char* t1d_last_error(void);
 
@@ -387,6 +409,35 @@ int t1d_rollout_bb(t1d_ctx* ctx, const t1d_batch* batch, const t1d_bb* bb, int n
  * n != n_policies * envs_per_policy -- is T1D_E_INVALID before anything is launched. */
 int t1d_rollout_mlp(t1d_ctx* ctx, const t1d_batch* batch, const t1d_mlp* mlp, int n_steps, int minutes,
                     int n_sub, void* stream);
+
+/* t1d_rollout_mlp as a policy-gradient trainer collects a batch of trajectories: n_steps steps in ONE launch, the env state in
+ * registers, windows and activations in LDS, the weights through the scalar data cache, with exploration noise, the reward and
+ * done of every step, the features the network saw, and episodes that end and start again without leaving the device.
+ * Action: y = the last layer's output as in t1d_rollout_mlp; z = fma(sigma[p], eps, y) for the env's policy p (z = y with sigma
+ *   NULL); basal = fma(out_scale, g(z), out_bias), bolus = 0.  action_trace holds that basal, before the pump.  The Gaussian
+ *   lives in the pre-output space; the log-probability is the host's business, from eps and sigma.
+ * Draw: eps = (T) philox_pair(explore_seed, g, k, m).x -- the first normal of Philox block m of episode k of subsequence g (the
+ *   layout of t1d_philox_normals) -- with g = env_offset + i, k the env's batch.episode counter at that step (0 with a NULL
+ *   array) and m the env's t at the start of the step, minutes since its episode began (m < 2^24: an episode of 31 years).  It
+ *   depends on nothing else, so a roll-out cut anywhere, sharded anywhere or with other neighbours draws the same numbers.
+ *   A caller who passes batch.seed as explore_seed makes eps the normal the sensor noise takes from the same block: exploration
+ *   then correlates with the CGM noise.
+ * on_done = T1D_COLLECT_RESTART: after a step with done != 0 the env goes through what t1d_restart_done(mask = done,
+ *   reset_outputs as given) does to it -- the episode accumulators of t1d_restart advance every step for every env,
+ *   terminal_cgm is written, the env gets a new start hour, a new column of the meal tables, a reset and episode + 1 -- and
+ *   its policy state becomes what follows a reset: every cgm_hist row the new first observation, ins_hist = 0, prev_meal = 0,
+ *   the time-of-day features from the new start_minute (mlp.start_minute is restart.start_minute, or NULL).  Trace rows of
+ *   step s always describe step s: cgm_trace[s] is the terminal observation of an env that finished there, the new episode's
+ *   first observation shows in feat_trace[s + 1] and in batch.cgm.
+ * After the call batch.*, the env state, mlp.cgm_hist / ins_hist / prev_meal and the sum_risk .. n_high accumulators (which run
+ *   on across episodes) are what n_steps x (t1d_rollout_mlp(1), t1d_restart_done, the reset of the policy state of the envs
+ *   that were done) leave, bit for bit; with sigma NULL and T1D_COLLECT_CONTINUE, what t1d_rollout_mlp leaves.
+ * T1D_E_INVALID before anything is launched, nothing changed: whatever t1d_rollout_mlp rejects; with T1D_COLLECT_RESTART
+ *   whatever t1d_restart_done rejects (a NULL batch.episode, tables that are not the batch's own, n_meals != 6 (days + 1), host
+ *   normals, x0_override), a NULL restart and a non-NULL restart->h_carry (the exact mode has no collector); on_done outside
+ *   {0, 1}; reserved != 0. */
+int t1d_collect_mlp(t1d_ctx* ctx, const t1d_batch* batch, const t1d_mlp* mlp, const t1d_collect* collect, int n_steps,
+                    int minutes, int n_sub, void* stream);
 
 /* SimObj.simulate (sim_engine.py:29-39) with PIDController.policy (pid_ctrller.py:17-36) and the integrator of
  * t1d_step_dopri5, scipy's dopri5 as the reference drives it (t1dpatient.py:110-113,276): t1d_rollout_pid (controller,

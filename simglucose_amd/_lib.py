@@ -23,12 +23,14 @@ MEAL_UNUSED = 0x7FFFFFFF
 META_EATING = 0x100
 T1D_MLP_TANH, T1D_MLP_RELU = 0, 1
 T1D_MLP_IDENTITY, T1D_MLP_LOGISTIC = 0, 1
+T1D_COLLECT_CONTINUE, T1D_COLLECT_RESTART = 0, 1
 MLP_MAX_HISTORY, MLP_MAX_LAYERS, MLP_MAX_WIDTH = 12, 4, 32
 
 EXPORTS = ("t1d_abi_version", "t1d_last_error", "t1d_ctx_create", "t1d_ctx_set_option", "t1d_ctx_destroy", "t1d_reset",
            "t1d_step", "t1d_rollout_pid", "t1d_philox_normals", "t1d_sync", "t1d_split_tables",
            "t1d_rollout_bb", "t1d_random_meals", "t1d_outcome_stats", "t1d_model_rhs", "t1d_step_dopri5",
-           "t1d_rollout_pid_dopri5", "t1d_rollout_bb_dopri5", "t1d_restart_done", "t1d_rollout_mlp")
+           "t1d_rollout_pid_dopri5", "t1d_rollout_bb_dopri5", "t1d_restart_done", "t1d_rollout_mlp",
+           "t1d_collect_mlp")
 
 
 class T1DError(RuntimeError):
@@ -94,6 +96,13 @@ class Restart(C.Structure):
                 ("meal_time", C.c_void_p), ("meal_amt", C.c_void_p), ("start_minute", C.c_void_p), ("h_carry", C.c_void_p),
                 ("terminal_cgm", C.c_void_p), ("ep_return", C.c_void_p), ("ep_length", C.c_void_p),
                 ("last_return", C.c_void_p), ("last_length", C.c_void_p)]
+
+
+class Collect(C.Structure):
+    """struct t1d_collect (include/t1d.h)"""
+    _fields_ = [("explore_seed", C.c_uint64), ("sigma", C.c_void_p), ("on_done", C.c_int32), ("reserved", C.c_int32),
+                ("restart", C.POINTER(Restart)), ("reward_trace", C.c_void_p), ("done_trace", C.c_void_p),
+                ("eps_trace", C.c_void_p), ("feat_trace", C.c_void_p)]
 
 
 def _stale():
@@ -162,6 +171,7 @@ def lib():
     L.t1d_rollout_pid.argtypes = [vp, C.POINTER(Batch), C.POINTER(Pid), C.c_int, C.c_int, C.c_int, vp]
     L.t1d_rollout_bb.argtypes = [vp, C.POINTER(Batch), C.POINTER(Bb), C.c_int, C.c_int, C.c_int, vp]
     L.t1d_rollout_mlp.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), C.c_int, C.c_int, C.c_int, vp]
+    L.t1d_collect_mlp.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), C.POINTER(Collect), C.c_int, C.c_int, C.c_int, vp]
     L.t1d_rollout_pid_dopri5.argtypes = [vp, C.POINTER(Batch), C.POINTER(Pid), vp, vp, C.c_int, C.c_int, vp]
     L.t1d_rollout_bb_dopri5.argtypes = [vp, C.POINTER(Batch), C.POINTER(Bb), vp, vp, C.c_int, C.c_int, vp]
     L.t1d_restart_done.argtypes = [vp, C.POINTER(Batch), vp, C.POINTER(Restart), vp]

@@ -15,6 +15,8 @@ in ``include/t1d.h``, ``csrc/t1d_policy.hpp``) for a whole batch:
 
 The kernel accumulates ``b[o]`` first and then ``W[o][j] x[j]`` for j ascending with one fused multiply-add each;
 ``forward(..., ordered=True)`` adds in that order, ``ordered=False`` is a plain ``torch.matmul``.
+``BatchedT1DSimEnv.collect_mlp`` adds ``sigma * eps`` to the last layer's output before ``g``; ``log_prob`` is the
+density of that sample.
 """
 import math
 
@@ -194,6 +196,18 @@ class MLPController(Controller):
         y = x.reshape(n)
         g = torch.sigmoid(y) if self.output == "logistic" else y
         return self.out_scale * g + self.out_bias
+
+    @staticmethod
+    def log_prob(eps, sigma):
+        """Log-density of the pre-output sample z = y + sigma eps that collect_mlp acted on, under N(y, sigma^2):
+        -eps^2 / 2 - log sigma - log(2 pi) / 2 per env and step.  eps: the "eps" trace [..., n]; sigma: a float, or a tensor
+        that broadcasts against eps (one value per env: sigma_per_policy.repeat_interleave(n // P)).  Plain torch,
+        differentiable in sigma.  For the likelihood of an old sample under a new network y' and sigma' pass
+        eps' = (z - y') / sigma' with y' = the new network's pre-output value on the recorded features (see the example in
+        BatchedT1DSimEnv.collect_mlp)."""
+        eps = torch.as_tensor(eps)
+        sigma = torch.as_tensor(sigma, dtype=eps.dtype, device=eps.device)
+        return -0.5 * eps * eps - torch.log(sigma) - 0.5 * math.log(2.0 * math.pi)
 
     # ------------------------------------------------------------------ the reference's controller surface, one env
     def reset(self):

@@ -30,6 +30,7 @@ struct t1d_ctx {
     double* d_x0 = nullptr;
     double* d_minv64 = nullptr; float* d_minv32 = nullptr;
     int* d_status = nullptr;
+    MealSlots* d_slots = nullptr;    // meal_slots() on the device, for kernels that restart an env themselves (t1d_collect_mlp)
     int math = 1;            // RHS arithmetic variant (t1d_ctx_set_option "math")
     int n_cu = 256;
     int lds_per_block = 65536;   // hipDeviceAttributeMaxSharedMemoryPerBlock (160 KiB on gfx950)
@@ -60,6 +61,7 @@ struct t1d_ctx {
     std::vector<double> dpar;    // host copy of the derived-parameter table
 };
 
+static MealSlots meal_slots();
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) { g_err = msg; return code; }
 #define T1D_HIP(call)                                                                         \
@@ -342,6 +344,8 @@ extern "C" int t1d_ctx_create(int hip_device, const double* ptab, int n_patients
         if (e == hipSuccess) e = hipMalloc((void**)&c->d_trace, 128 * 4 * 64 * sizeof(long long));
         if (e == hipSuccess) e = hipMemset(c->d_trace, 0, 128 * 4 * 64 * sizeof(long long));
 #endif
+        const MealSlots slots = meal_slots();
+        if (e == hipSuccess) e = up((void**)&c->d_slots, &slots, sizeof(slots));
         if (e == hipSuccess) e = hipMalloc((void**)&c->d_status, sizeof(int));
         if (e == hipSuccess) e = hipMemset(c->d_status, 0, sizeof(int));
         if (e != hipSuccess) {
@@ -398,7 +402,7 @@ extern "C" int t1d_ctx_destroy(t1d_ctx* c)
     (void)hipFree(c->d_par64); (void)hipFree(c->d_par32); (void)hipFree(c->d_x0);
     (void)hipFree(c->d_minv64); (void)hipFree(c->d_minv32); (void)hipFree(c->d_status);
     (void)hipFree(c->d_prop64); (void)hipFree(c->d_prop32); (void)hipFree(c->d_trace); (void)hipFree(c->d_raw64);
-    (void)hipFree(c->d_img64); (void)hipFree(c->d_img32);
+    (void)hipFree(c->d_img64); (void)hipFree(c->d_img32); (void)hipFree(c->d_slots);
     delete c;
     return T1D_OK;
 }
@@ -844,9 +848,9 @@ static MlpArgs<T> make_mlp(const t1d_mlp* m, int n_steps)
 }
 
 // every field of the policy that has a range; -> the rows of a wave's column block in *cols
-static int check_mlp(const t1d_batch* b, const t1d_mlp* m, int* cols)
+static int check_mlp(const char* who, const t1d_batch* b, const t1d_mlp* m, int* cols)
 {
-    const std::string w = "t1d_rollout_mlp: ";
+    const std::string w = std::string(who) + ": ";
     if (!m) return fail(T1D_E_INVALID, w + "mlp is NULL");
     if (m->history < 1 || m->history > kMlpMaxHistory) return fail(T1D_E_INVALID, w + "history must be in [1, 12]");
     if (m->n_layers < 1 || m->n_layers > kMlpMaxLayers) return fail(T1D_E_INVALID, w + "n_layers must be in [1, 4]");
@@ -873,10 +877,10 @@ static int check_mlp(const t1d_batch* b, const t1d_mlp* m, int* cols)
     return T1D_OK;
 }
 
+// the launch shape of the policy kernels, into the plan and the policy's arguments
 template <typename T>
-static int run_rollout_mlp(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* m, Plan p, int cols, int n_steps, int minutes, int n_sub, hipStream_t s)
+static int shape_mlp(const char* who, const t1d_ctx* c, const t1d_batch* b, int cols, Plan& p, MlpArgs<T>& ma)
 {
-    MlpArgs<T> ma = make_mlp<T>(m, n_steps);
     // dynamic LDS: the propagator table as the plan sized it, then the columns of every wave; the workgroup is the
     // largest whose columns fit beside the tables (the LDS-parameter variants hold theirs in static LDS)
     ma.lds_off = (int)((p.lds + 15) & ~(size_t)15);
@@ -886,9 +890,18 @@ static int run_rollout_mlp(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* m, Pla
     int threads = T1D_POLICY_THREADS;
     while (threads > 64 && fixed + ma.lds_off + per_wave * (threads / 64) > (size_t)c->lds_per_block) threads /= 2;
     if (fixed + ma.lds_off + per_wave * (threads / 64) > (size_t)c->lds_per_block)
-        return fail(T1D_E_INVALID, "t1d_rollout_mlp: the integrator's tables leave no room in LDS for one wave of this policy");
+        return fail(T1D_E_INVALID, std::string(who) + ": the integrator's tables leave no room in LDS for one wave of this policy");
     p.lds = ma.lds_off + per_wave * (threads / 64);
     p.block = threads; p.grid = (unsigned)((b->n + threads - 1) / threads);
+    return T1D_OK;
+}
+
+template <typename T>
+static int run_rollout_mlp(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* m, Plan p, int cols, int n_steps, int minutes, int n_sub, hipStream_t s)
+{
+    MlpArgs<T> ma = make_mlp<T>(m, n_steps);
+    const int rc = shape_mlp<T>("t1d_rollout_mlp", c, b, cols, p, ma);
+    if (rc) return rc;
     return launch(c, b, p, minutes, n_sub, s, mlp_rollout_fn<T>(p.variant), ma);
 }
 
@@ -900,7 +913,7 @@ extern "C" int t1d_rollout_mlp(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* ml
     if (b->cho) return fail(T1D_E_INVALID, "t1d_rollout_mlp: dense cho is not supported, use the meal table");
     if (n_steps < 1) return fail(T1D_E_INVALID, "t1d_rollout_mlp: n_steps < 1");
     int cols = 0;
-    rc = check_mlp(b, mlp, &cols);
+    rc = check_mlp("t1d_rollout_mlp", b, mlp, &cols);
     if (rc) return rc;
     // the plan of a roll-out that keeps all its steps in one launch: variant, refill and the propagator table's LDS
     Plan p;
@@ -968,13 +981,20 @@ static MealSlots meal_slots()
 }
 
 template <typename T>
-static void launch_restart(const t1d_ctx* c, const t1d_batch* b, const uint8_t* mask, const t1d_restart* r, hipStream_t s)
+static RestartArgs<T> make_restart(const t1d_restart* r)
 {
     RestartArgs<T> ra;
     ra.days = r->days; ra.random_init_bg = r->random_init_bg; ra.reset_outputs = r->reset_outputs;
     ra.meal_time = r->meal_time; ra.meal_amt = (T*)r->meal_amt; ra.start_minute = r->start_minute; ra.h_carry = r->h_carry;
     ra.terminal_cgm = (T*)r->terminal_cgm; ra.ep_return = (T*)r->ep_return; ra.ep_length = r->ep_length;
     ra.last_return = (T*)r->last_return; ra.last_length = r->last_length;
+    return ra;
+}
+
+template <typename T>
+static void launch_restart(const t1d_ctx* c, const t1d_batch* b, const uint8_t* mask, const t1d_restart* r, hipStream_t s)
+{
+    const RestartArgs<T> ra = make_restart<T>(r);
     const uint8_t* m = mask ? mask : b->done;
     if (c->restart_compact) {
         const int64_t per = (int64_t)kBlock * kRestartTile;
@@ -985,30 +1005,101 @@ static void launch_restart(const t1d_ctx* c, const t1d_batch* b, const uint8_t* 
     }
 }
 
+// what a batch and a t1d_restart must be for an env to be restarted on the device; needs no device
+static int check_restart(const char* who, const t1d_batch* b, const t1d_restart* r)
+{
+    const std::string w = std::string(who) + ": ";
+    if (!b) return fail(T1D_E_INVALID, w + "batch is NULL");
+    if (!r) return fail(T1D_E_INVALID, w + "restart is NULL");
+    if (r->days < 1 || r->days > 10000) return fail(T1D_E_INVALID, w + "days out of range");
+    if (r->reserved != 0) return fail(T1D_E_INVALID, w + "reserved must be 0");
+    if (b->normals || b->n_normals != 0)
+        return fail(T1D_E_INVALID, w + "host-normals batches have no per-episode source on the device");
+    if (b->x0_override) return fail(T1D_E_INVALID, w + "x0_override has no per-episode source on the device");
+    if (!r->meal_time || !r->meal_amt || !r->start_minute)
+        return fail(T1D_E_INVALID, w + "meal_time / meal_amt / start_minute is NULL");
+    if (r->meal_time != b->meal_time || r->meal_amt != b->meal_amt)
+        return fail(T1D_E_INVALID, w + "meal_time / meal_amt must be the tables the batch names");
+    if (b->n_meals != 6 * (r->days + 1)) return fail(T1D_E_INVALID, w + "batch.n_meals must be 6 (days + 1)");
+    if (!b->episode) return fail(T1D_E_INVALID, w + "batch.episode is NULL (the episode index keys the new episode)");
+    if (!r->ep_return != !r->ep_length) return fail(T1D_E_INVALID, w + "ep_return and ep_length go together");
+    if ((r->last_return || r->last_length) && !r->ep_return)
+        return fail(T1D_E_INVALID, w + "last_return / last_length need ep_return and ep_length");
+    return T1D_OK;
+}
+
 extern "C" int t1d_restart_done(t1d_ctx* c, const t1d_batch* b, const uint8_t* mask, const t1d_restart* r, void* stream)
 {
     // what needs no device is checked first, so that a bad call is refused on any machine
-    if (!b) return fail(T1D_E_INVALID, "t1d_restart_done: batch is NULL");
-    if (!r) return fail(T1D_E_INVALID, "t1d_restart_done: restart is NULL");
-    if (r->days < 1 || r->days > 10000) return fail(T1D_E_INVALID, "t1d_restart_done: days out of range");
-    if (r->reserved != 0) return fail(T1D_E_INVALID, "t1d_restart_done: reserved must be 0");
-    if (b->normals || b->n_normals != 0)
-        return fail(T1D_E_INVALID, "t1d_restart_done: host-normals batches have no per-episode source on the device");
-    if (b->x0_override) return fail(T1D_E_INVALID, "t1d_restart_done: x0_override has no per-episode source on the device");
-    if (!r->meal_time || !r->meal_amt || !r->start_minute)
-        return fail(T1D_E_INVALID, "t1d_restart_done: meal_time / meal_amt / start_minute is NULL");
-    if (r->meal_time != b->meal_time || r->meal_amt != b->meal_amt)
-        return fail(T1D_E_INVALID, "t1d_restart_done: meal_time / meal_amt must be the tables the batch names");
-    if (b->n_meals != 6 * (r->days + 1)) return fail(T1D_E_INVALID, "t1d_restart_done: batch.n_meals must be 6 (days + 1)");
-    if (!b->episode) return fail(T1D_E_INVALID, "t1d_restart_done: batch.episode is NULL (the episode index keys the new episode)");
-    if (!r->ep_return != !r->ep_length) return fail(T1D_E_INVALID, "t1d_restart_done: ep_return and ep_length go together");
-    if ((r->last_return || r->last_length) && !r->ep_return)
-        return fail(T1D_E_INVALID, "t1d_restart_done: last_return / last_length need ep_return and ep_length");
+    int rc = check_restart("t1d_restart_done", b, r);
+    if (rc) return rc;
     if (r->h_carry && b->dtype != T1D_F64) return fail(T1D_E_INVALID, "t1d_restart_done: h_carry belongs to fp64 batches");
-    int rc = check_batch("t1d_restart_done", c, b, false);
+    rc = check_batch("t1d_restart_done", c, b, false);
     if (rc) return rc;
     if (b->dtype == T1D_F64) launch_restart<double>(c, b, mask, r, (hipStream_t)stream);
     else launch_restart<float>(c, b, mask, r, (hipStream_t)stream);
+    T1D_HIP(hipGetLastError());
+    return T1D_OK;
+}
+
+// ---- t1d_collect_mlp (t1d_policy.hpp) ---------------------------------------------------------------------------------
+template <typename T>
+static KernelFn<T, MlpArgs<T>, CollectArgs<T>, RestartArgs<T>> mlp_collect_fn(int variant)
+{
+    switch (variant) {
+    case 0: return mlp_collect_kernel<0, T>;
+    case 3: return mlp_collect_kernel<3, T>;
+    case 4: return mlp_collect_kernel<4, T>;
+    default: return mlp_collect_kernel<sizeof(T) == 8 ? 7 : 6, T>;
+    }
+}
+
+template <typename T>
+static int run_collect_mlp(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* m, const t1d_collect* g, Plan p, int cols, int n_steps,
+                           int minutes, int n_sub, hipStream_t s)
+{
+    MlpArgs<T> ma = make_mlp<T>(m, n_steps);
+    const int rc = shape_mlp<T>("t1d_collect_mlp", c, b, cols, p, ma);
+    if (rc) return rc;
+    CollectArgs<T> ga;
+    ga.explore_seed = g->explore_seed; ga.sigma = (const T*)g->sigma; ga.on_done = g->on_done;
+    ga.reward_trace = (T*)g->reward_trace; ga.done_trace = g->done_trace; ga.eps_trace = (T*)g->eps_trace; ga.feat_trace = (T*)g->feat_trace;
+    ga.slots = c->d_slots;
+    const RestartArgs<T> ra = g->on_done == T1D_COLLECT_RESTART ? make_restart<T>(g->restart) : RestartArgs<T>{};
+    return launch(c, b, p, minutes, n_sub, s, mlp_collect_fn<T>(p.variant), ma, ga, ra);
+}
+
+extern "C" int t1d_collect_mlp(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_collect* g, int n_steps, int minutes,
+                               int n_sub, void* stream)
+{
+    const char* who = "t1d_collect_mlp";
+    if (!g) return fail(T1D_E_INVALID, "t1d_collect_mlp: collect is NULL");
+    if (g->on_done != T1D_COLLECT_CONTINUE && g->on_done != T1D_COLLECT_RESTART)
+        return fail(T1D_E_INVALID, "t1d_collect_mlp: on_done must be T1D_COLLECT_CONTINUE or T1D_COLLECT_RESTART");
+    if (g->reserved != 0) return fail(T1D_E_INVALID, "t1d_collect_mlp: reserved must be 0");
+    if (g->on_done == T1D_COLLECT_RESTART) {
+        if (!g->restart) return fail(T1D_E_INVALID, "t1d_collect_mlp: on_done = T1D_COLLECT_RESTART needs restart");
+        int rr = check_restart(who, b, g->restart);
+        if (rr) return rr;
+        if (g->restart->h_carry) return fail(T1D_E_INVALID, "t1d_collect_mlp: restart.h_carry must be NULL (the exact mode has no collector)");
+    }
+    int rc = check_batch(who, c, b, false);
+    if (rc) return rc;
+    if (b->cho) return fail(T1D_E_INVALID, "t1d_collect_mlp: dense cho is not supported, use the meal table");
+    if (n_steps < 1) return fail(T1D_E_INVALID, "t1d_collect_mlp: n_steps < 1");
+    int cols = 0;
+    rc = check_mlp(who, b, mlp, &cols);
+    if (rc) return rc;
+    // a restarted env's time-of-day features follow its new start: the array the restart writes is the one the policy reads
+    if (g->on_done == T1D_COLLECT_RESTART && mlp->start_minute && mlp->start_minute != g->restart->start_minute)
+        return fail(T1D_E_INVALID, "t1d_collect_mlp: mlp.start_minute must be restart.start_minute (or NULL)");
+    Plan p;
+    rc = plan_and_tables(who, c, b, minutes, n_sub, true, &p, true);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    rc = p.f64 ? run_collect_mlp<double>(c, b, mlp, g, p, cols, n_steps, minutes, n_sub, s)
+               : run_collect_mlp<float>(c, b, mlp, g, p, cols, n_steps, minutes, n_sub, s);
+    if (rc) return rc;
     T1D_HIP(hipGetLastError());
     return T1D_OK;
 }

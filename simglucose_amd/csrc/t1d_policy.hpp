@@ -228,4 +228,196 @@ __global__ __launch_bounds__(T1D_POLICY_THREADS) void mlp_rollout_kernel(const K
     }
 }
 
+// ---- t1d_collect_mlp: trajectories for a policy-gradient trainer --------------------------------------------------------
+//   mlp_collect_kernel   mlp_rollout_kernel with what a trainer needs of every step: exploration noise on the network's
+//                        output, the reward and done of every step, the features the network was given, and episodes that
+//                        end (include/t1d.h).  The env state stays in registers, windows and activations in the LDS
+//                        columns, the weights (and the policy's sigma) go through the scalar data cache, as above.
+//   draw                 eps = philox_pair(explore_seed, global env id, the env's episode counter, the env's t).x: one
+//                        Philox set-up per lane and step, none without sigma.  Keyed by what the env is and where it
+//                        stands, so cuts, shards and neighbours do not show in it.
+//   a finished env       on_done = 1: the lane writes its outputs and its state as the end of the launch would, then
+//                        collect_restart -- restart_front / restart_env on the words in memory, what restart_kernel runs
+//                        for it -- then loads the new episode and fills its window rows with the new first observation.
+//                        A lane that did not finish writes nothing of its state between the steps.  collect_restart is
+//                        written to be kept out of line, as noise_refill is (T1D_COLLECT_RESTART_INLINE=0: eighteen Philox
+//                        set-ups, erfinv and the reset then cost code and registers on that path only), and like
+//                        noise_refill it is inlined by default, on measurement: around a call the register allocator
+//                        keeps part of the step's state in scratch in every step (0.8 - 1.3 KB per lane against 0.6 - 0.9,
+//                        and 12 - 22 % on a launch in which no env finishes; profiles/collect).  Inside the branch the env
+//                        state is dead between store_env and load_env, so the restart's registers overlap it.
+template <typename T> struct CollectArgs {
+    uint64_t explore_seed;
+    const T* sigma;                       // [n_policies], null = no noise
+    T* reward_trace; uint8_t* done_trace; T* eps_trace; T* feat_trace;
+    const MealSlots* slots;               // the meal windows in device memory (on_done = 1)
+    int on_done;
+};
+
+#ifndef T1D_COLLECT_RESTART_INLINE
+#define T1D_COLLECT_RESTART_INLINE 1
+#endif
+#if T1D_COLLECT_RESTART_INLINE
+#define T1D_COLLECT_RESTART_ATTR __forceinline__
+#else
+#define T1D_COLLECT_RESTART_ATTR __noinline__
+#endif
+
+// The next episode of env i, whose finished step is in memory (outputs and state): t1d_restart_done for one env.  All
+// arguments by value: out of line, a reference would pin the caller's copy of the kernel arguments in scratch.
+template <typename T>
+__device__ T1D_COLLECT_RESTART_ATTR void collect_restart(KArgs<T> a, RestartArgs<T> r, const MealSlots* ms, unsigned i)
+{
+    if (restart_front(a, r, a.done, i)) restart_env(a, r, *ms, i);
+}
+
+// mlp_rollout_body with the exploration draw, the per-step reward / done / feature histories and the restart of finished
+// envs.  Without sigma and with on_done = 0 it computes what mlp_rollout_body computes, word for word.
+template <int VARIANT, typename T, typename P, typename PR = NoProp>
+__device__ __forceinline__ void mlp_collect_body(const KArgs<T>& a, const MlpArgs<T>& c, const CollectArgs<T>& g, const RestartArgs<T>& r,
+                                                 P& p, unsigned i, uint32_t pid, Env<T>& e, T* col, PR pr = PR())
+{
+    constexpr int MATH = VariantMath<VARIANT>::value;
+    typedef const __attribute__((address_space(4))) T* WPtr;
+    const int H = c.history, F = 2 * H + 3;
+    T* const buf = col + 2 * H * 64;
+    const unsigned wave0 = __builtin_amdgcn_readfirstlane(i & ~63u);
+    const unsigned pol = wave0 / c.envs_per_policy;
+    const WPtr w = (WPtr)(c.params + (size_t)pol * (size_t)c.n_params);
+    const T sg = g.sigma ? (T)((WPtr)g.sigma)[pol] : T(0);      // one sigma per wave, as the weights
+    col[0] = at(a.cgm, i);                                      // CGM[0] is the observation the step starts from
+    for (int k = 1; k < H; ++k) col[k * 64] = at(rowv(c.cgm_hist, a.n, k), i);
+    for (int k = 0; k < H; ++k) col[(H + k) * 64] = at(rowv(c.ins_hist, a.n, k), i);
+    int head = 0;
+    T prev_meal = at(c.prev_meal, i);
+    int start = c.start_minute ? (int)at(c.start_minute, i) : 0;
+    uint32_t ep = (g.sigma && a.episode) ? at(a.episode, i) : 0u;
+    T sum_risk = c.sum_risk ? at(c.sum_risk, i) : T(0);
+    T min_bg = c.min_bg ? at(c.min_bg, i) : T(0), max_bg = c.max_bg ? at(c.max_bg, i) : T(0);
+    int n_low = c.n_low ? at(c.n_low, i) : 0, n_high = c.n_high ? at(c.n_high, i) : 0;
+    StepOut<T> o{T(0), T(0), T(0), T(0)};
+    T rp = e.prev_risk;                         // risk of the observation the last step started from
+    bool fresh = false;                         // the last step ended the episode: outputs and state are in memory already
+#pragma unroll 1
+    for (int s = 0; s < c.n_steps; ++s) {
+        const int64_t trow = (c.trace_row + s) * a.n + i;
+        // the features, in the order of include/t1d.h
+        for (int k = 0, q = head; k < H; ++k) {
+            buf[k * 64] = (col[q * 64] - c.cgm_mean) * c.cgm_scale;
+            buf[(H + k) * 64] = col[(H + q) * 64] * c.ins_scale;
+            q = q + 1 == H ? 0 : q + 1;
+        }
+        buf[2 * H * 64] = prev_meal * c.cho_scale;
+        {
+            int m = (start + e.t) % 1440;
+            m = m < 0 ? m + 1440 : m;
+            T sn, cs;
+            mlp_time_of_day(m, sn, cs);
+            buf[(2 * H + 1) * 64] = sn; buf[(2 * H + 2) * 64] = cs;
+        }
+        if (g.feat_trace)
+            for (int j = 0; j < F; ++j) g.feat_trace[((c.trace_row + s) * F + j) * a.n + i] = buf[j * 64];
+        T y = mlp_layers(c, w, buf, F);
+        T eps = T(0);
+        if (g.sigma) {                          // wave-uniform
+            eps = (T)philox_pair(g.explore_seed, (uint64_t)(a.env_offset + i), ep, (uint32_t)e.t).x;
+            y = fma(sg, eps, y);
+        }
+        const T u = fma(c.out_scale, c.out_act == 0 ? y : mlp_logistic(y), c.out_bias);
+        rp = e.prev_risk;
+        o = step_body<MATH, T, P, true, PR, VariantInfo<VARIANT>::tiered>(a, p, i, e, u, T(0), true, pr);
+        // the step's reward and done, as write_outputs forms them
+        T rl, rh, rc;
+        risk_index1<MATH>(o.cgm, rl, rh, rc);
+        e.prev_risk = rc;
+        const T reward = rp - rc;
+        const bool fin = o.bg < T(70) || o.bg > T(350);
+        prev_meal = o.meal;
+        head = head == 0 ? H - 1 : head - 1;                    // the oldest row becomes the newest
+        col[head * 64] = o.cgm; col[(H + head) * 64] = o.ins;
+        if (c.bg_trace) c.bg_trace[trow] = o.bg;
+        if (c.cgm_trace) c.cgm_trace[trow] = o.cgm;
+        if (c.cho_trace) c.cho_trace[trow] = o.meal;
+        if (c.ins_trace) c.ins_trace[trow] = o.ins;
+        if (c.act_trace) c.act_trace[trow] = u;
+        if (g.reward_trace) g.reward_trace[trow] = reward;
+        if (g.done_trace) g.done_trace[trow] = fin ? 1 : 0;
+        if (g.eps_trace) g.eps_trace[trow] = eps;
+        if (c.sum_risk) { T l, h, q; risk_index1<MATH>(o.bg, l, h, q); sum_risk += q; }
+        min_bg = o.bg < min_bg ? o.bg : min_bg;
+        max_bg = o.bg > max_bg ? o.bg : max_bg;
+        n_low += o.bg < T(70); n_high += o.bg > T(180);
+        fresh = false;
+        if (g.on_done) {
+            if (fin) {
+                // the finished step goes to memory as the end of a launch leaves it; the restart works on those words
+                write_outputs<MATH>(a, i, e, o, rp);
+                store_env(a, i, pid, e);
+                collect_restart<T>(a, r, g.slots, i);
+                load_env(a, i, at(a.meta, i), e);
+                const T first = at(a.cgm, i);                   // the new episode's first observation
+                for (int k = 0; k < H; ++k) { col[k * 64] = first; col[(H + k) * 64] = T(0); }
+                prev_meal = T(0);
+                if (c.start_minute) start = (int)at(c.start_minute, i);
+                if (g.sigma) ep = at(a.episode, i);
+                fresh = true;
+            } else if (r.ep_return) {                           // restart_front's accumulators for an env that goes on
+                const T sum = at(r.ep_return, i) + reward;
+                const int len = at(r.ep_length, i) + 1;
+                at(r.ep_return, i) = sum; at(r.ep_length, i) = len;
+            }
+        }
+    }
+    if (!fresh) {
+        write_outputs<MATH>(a, i, e, o, rp);
+        store_env(a, i, pid, e);
+    }
+    for (int k = 0, q = head; k < H; ++k) {                     // the windows back in window order
+        at(rowv(c.cgm_hist, a.n, k), i) = col[q * 64];
+        at(rowv(c.ins_hist, a.n, k), i) = col[(H + q) * 64];
+        q = q + 1 == H ? 0 : q + 1;
+    }
+    at(c.prev_meal, i) = prev_meal;
+    if (c.sum_risk) at(c.sum_risk, i) = sum_risk;
+    if (c.min_bg) at(c.min_bg, i) = min_bg;
+    if (c.max_bg) at(c.max_bg, i) = max_bg;
+    if (c.n_low) at(c.n_low, i) = n_low;
+    if (c.n_high) at(c.n_high, i) = n_high;
+}
+
+// Launch shape, LDS and VARIANT as for mlp_rollout_kernel.
+template <int VARIANT, typename T>
+__global__ __launch_bounds__(T1D_POLICY_THREADS) void mlp_collect_kernel(const KArgs<T> a, const MlpArgs<T> c, const CollectArgs<T> g,
+                                                                         const RestartArgs<T> r)
+{
+    using VI = VariantInfo<VARIANT>;
+    constexpr int kParRows = VI::split ? DP_COUNT : DP_RK4_COUNT;
+    __shared__ T lds[VI::lds_pars ? kParRows * kMaxPatients : 1];
+    if (VI::lds_pars) stage_pars(a, lds, kParRows);
+    if (VI::split) stage_prop(a, (T*)t1d_dyn_lds);
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    __builtin_assume(i < (1u << 28));          // host guarantees n <= 2^28: i * sizeof(T) fits a 32-bit voffset
+    if ((int64_t)i >= a.n) return;
+    T* const col = (T*)(t1d_dyn_lds + c.lds_off) + (threadIdx.x >> 6) * (c.cols * 64) + (threadIdx.x & 63u);
+    const uint32_t meta = at(a.meta, i);
+    const uint32_t pid = T1D_META_PID(meta);
+    Env<T> e;
+    load_env(a, i, meta, e);
+    if constexpr (VARIANT == 4 || VARIANT == 6) {
+        ParsReg<T> p;
+        p.load(a.dpar, (int)pid);
+        mlp_collect_body<VARIANT>(a, c, g, r, p, i, pid, e, col, PropLds<T>{(const T*)t1d_dyn_lds, a.np_pad, (int)pid});
+    } else if constexpr (VARIANT == 7) {
+        ParsLds<T> p{lds, (int)pid};
+        mlp_collect_body<VARIANT>(a, c, g, r, p, i, pid, e, col, PropLds<T>{(const T*)t1d_dyn_lds, a.np_pad, (int)pid});
+    } else if constexpr (VARIANT == 3) {
+        ParsReg<T> p;
+        p.load(a.dpar, (int)pid);
+        mlp_collect_body<VARIANT>(a, c, g, r, p, i, pid, e, col);
+    } else {
+        ParsLds<T> p{lds, (int)pid};
+        mlp_collect_body<VARIANT>(a, c, g, r, p, i, pid, e, col);
+    }
+}
+
 } // namespace t1d

@@ -1,0 +1,474 @@
+"""The trajectory collector on the GPU (BatchedT1DSimEnv.collect_mlp -> t1d_collect_mlp, csrc/t1d_policy.hpp): pinned bit
+for bit to rollout_mlp (no noise, no episode ends) and to the per-step loop of rollout_mlp(1), restart_done and the torch
+reset of the policy state (episodes that end); the exploration draws replayed through t1d_philox_normals; the action and the
+recorded features against the host's forward pass; cut and shard invariance with noise and restarts on; the argument checks.
+The helpers are those of test_gpu_policy.py and test_gpu_autoreset.py, copied."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+ST = 3                                   # Dexcom
+START = 360
+DAYS = 2
+STATE = ("state", "istate", "ar_e", "cgm", "bg", "reward", "done", "lbgi", "hbgi", "risk", "meal", "insulin")
+STATS = ("sum_risk", "min_bg", "max_bg", "n_low", "n_high")
+POLICY_STATE = ("cgm_hist", "ins_hist", "prev_meal")
+TRACES = ("bg", "cgm", "cho", "insulin", "action", "reward", "done", "eps", "features")
+EPISODE_STATS = ("ep_return", "ep_length", "last_return", "last_length")
+
+
+def _torch():
+    import torch
+    assert torch.cuda.is_available()
+    return torch
+
+
+def _mk(n, dtype, env_offset=0, seed=5, meals=True, start=None, **kw):
+    """all 30 patients, random-meal day from START (or per-env start minutes), reset: the envs of test_gpu_policy.py"""
+    torch = _torch()
+    from simglucose_amd.batch_env import BatchedT1DSimEnv
+    from simglucose_amd.scenario_batch import random_meal_tables
+    pid = (np.arange(n) + env_offset) % 30
+    e = BatchedT1DSimEnv(patient=pid, sensor="Dexcom", dtype=dtype, seed=seed, env_offset=env_offset, **kw)
+    e.start_minute = torch.full((n,), START, dtype=torch.int32, device=e.device) if start is None else \
+        torch.as_tensor(start, dtype=torch.int32).to(e.device).contiguous()
+    if meals:
+        e.set_meals(*random_meal_tables(n, days=1, start_minute_of_day=e.start_minute, seed=seed, dtype=dtype, env_offset=env_offset))
+    e.reset()
+    return e
+
+
+def _mk_gym(n, dtype, seed=3, env_offset=0):
+    """child#001 / adult#001 alternating, random initial glucose, Philox noise, every env in episode 0 of the device's own
+    episode stream: the envs of test_gpu_autoreset.py"""
+    torch = _torch()
+    from simglucose_amd.batch_env import BatchedT1DSimEnv
+    e = BatchedT1DSimEnv(patient=["child#001", "adult#001"] * (n // 2), sensor="Dexcom", pump="Insulet", dtype=dtype, n_sub=4,
+                         seed=seed, env_offset=env_offset, noise="philox", random_init_bg=True)
+    e.restart_done(mask=torch.ones(n, dtype=torch.uint8, device=e.device), days=DAYS, reset_outputs=True)
+    return e
+
+
+def _stats(e):
+    torch = _torch()
+    z = lambda dt=e.dtype: torch.zeros(e.n, dtype=dt, device=e.device)
+    return {"sum_risk": z(), "min_bg": z() + 1000.0, "max_bg": z(), "n_low": z(torch.int32), "n_high": z(torch.int32)}
+
+
+def _episode_stats(e):
+    torch = _torch()
+    z = lambda dt=e.dtype: torch.zeros(e.n, dtype=dt, device=e.device)
+    return {"ep_return": z(), "ep_length": z(torch.int32), "last_return": z(), "last_length": z(torch.int32)}
+
+
+def _policy(history=4, widths=(16, 16, 1), n_policies=1, seed=0, hidden="tanh", output="logistic", gain=1.0, **kw):
+    torch = _torch()
+    from simglucose_amd.controller.mlp_ctrller import MLPController
+    g = torch.Generator().manual_seed(seed)
+    layers, n_in = [], 2 * history + 3
+    for w in widths:
+        layers.append((gain * torch.randn(n_policies, w, n_in, generator=g, dtype=torch.float64) / math.sqrt(n_in),
+                       gain * 0.1 * torch.randn(n_policies, w, generator=g, dtype=torch.float64)))
+        n_in = w
+    kw.setdefault("out_scale", 0.06)
+    return MLPController(layers, history=history, hidden=hidden, output=output, **kw)
+
+
+def _constant_policy(basal, history=4):
+    """a one-layer net with zero weights and identity output: `basal` U/min whatever it sees"""
+    torch = _torch()
+    from simglucose_amd.controller.mlp_ctrller import MLPController
+    return MLPController([(torch.zeros(1, 2 * history + 3, dtype=torch.float64), torch.zeros(1, dtype=torch.float64))],
+                         history=history, output="identity", out_scale=1.0, out_bias=basal)
+
+
+def _bits(t):
+    """the words of a tensor as integers: equal bit patterns compare equal, also the NaN rows new_trace leaves unwritten"""
+    torch = _torch()
+    t = t.contiguous()
+    return t.view({8: torch.int64, 4: torch.int32, 1: torch.uint8}[t.element_size()]) if t.is_floating_point() else t
+
+
+def _same_env(a, b, sl=slice(None), keys=STATE):
+    torch = _torch()
+    for k in keys:
+        assert torch.equal(_bits(getattr(a, k)[..., sl]), _bits(getattr(b, k))), k
+
+
+def _same_dicts(a, b, keys, sl=slice(None)):
+    torch = _torch()
+    for k in keys:
+        assert torch.equal(_bits(a[k][..., sl]), _bits(b[k])), k
+
+
+# ---------------------------------------------------------------------------------------------------------- 1
+@pytest.mark.parametrize("dtype_name", ["float64", "float32"])
+def test_without_noise_and_episode_ends_it_is_rollout_mlp_bit_for_bit(dtype_name):
+    torch = _torch()
+    dtype = getattr(torch, dtype_name)
+    n, K = 192, 60
+    pol = _policy()
+    cols = ("bg", "cgm", "cho", "insulin", "action")
+    a, b, c = _mk(n, dtype), _mk(n, dtype), _mk(n, dtype)
+    sa, ta = _stats(a), a.new_trace(K, columns=cols)
+    st = a.rollout_mlp(20, pol, stats=sa, trace=ta)
+    a.rollout_mlp(K - 20, pol, policy_state=st, stats=sa, trace=ta)
+    assert a.sync() == 0
+    sb, tb = _stats(b), b.new_trace(K, columns=cols + ("reward", "done"))
+    sb2 = b.collect_mlp(20, pol, stats=sb, trace=tb)
+    assert b.collect_mlp(K - 20, pol, policy_state=sb2, stats=sb, trace=tb, sigma=None, on_done="continue") is sb2
+    assert b.sync() == 0
+    _same_env(a, b)
+    _same_dicts(st, sb2, POLICY_STATE)
+    _same_dicts(sa, sb, STATS)
+    _same_dicts(ta, tb, cols)
+    assert tb["row"] == K + 1 and float(tb["insulin"][1:].max()) > 0 and float(tb["cgm"].std()) > 0
+    # the reward and done of every step: what the env holds after each of K one-step roll-outs
+    sc = None
+    for s in range(1, K + 1):
+        sc = c.rollout_mlp(1, pol, policy_state=sc)
+        assert torch.equal(_bits(tb["reward"][s]), _bits(c.reward)), s
+        assert torch.equal(tb["done"][s], c.done), s
+    assert c.sync() == 0
+    _same_env(a, c)
+    assert float(tb["reward"][1:].abs().max()) > 0
+
+
+# ---------------------------------------------------------------------------------------------------------- 2
+def _loop_of_entry_points(e, pol, K, stats, tr, term, es):
+    """what a trainer does without collect_mlp: per step rollout_mlp(1), restart_done, the torch reset of the policy state"""
+    torch = _torch()
+    st = e.new_policy_state(pol)
+    low = high = 0
+    zero = torch.zeros((), dtype=e.dtype, device=e.device)
+    for _ in range(K):
+        row = tr["row"]
+        e.rollout_mlp(1, pol, policy_state=st, stats=stats, trace=tr)
+        done = e.done.bool()
+        tr["reward"][row] = e.reward; tr["done"][row] = e.done
+        low = low + (done & (e.bg < 70)).sum(); high = high + (done & (e.bg > 350)).sum()
+        e.restart_done(days=DAYS, terminal_obs=term, episode_stats=es)
+        st["cgm_hist"].copy_(torch.where(done, e.cgm, st["cgm_hist"]))           # new_policy_state for the envs that restarted
+        st["ins_hist"].copy_(torch.where(done, zero, st["ins_hist"]))
+        st["prev_meal"].copy_(torch.where(done, zero, st["prev_meal"]))
+    assert e.sync() == 0
+    return st, int(low), int(high)
+
+
+def _restart_pair(dtype, basal, cuts):
+    torch = _torch()
+    n, K = 256, sum(cuts)
+    pol = _constant_policy(basal)
+    cols = ("bg", "cgm", "cho", "insulin", "action", "reward", "done", "eps")
+    A, B = _mk_gym(n, dtype), _mk_gym(n, dtype)
+    z = lambda: torch.zeros(n, dtype=dtype, device=A.device)
+    sa, ta, terma, esa = _stats(A), A.new_trace(K, columns=cols), z(), _episode_stats(A)
+    sb, tb, termb, esb = _stats(B), B.new_trace(K, columns=cols[:5] + ("reward", "done")), z(), _episode_stats(B)
+    sta = None
+    for k in cuts:
+        sta = A.collect_mlp(k, pol, policy_state=sta, stats=sa, trace=ta, on_done="restart", days=DAYS, terminal_obs=terma,
+                            episode_stats=esa)
+    assert A.sync() == 0
+    stb, low, high = _loop_of_entry_points(B, pol, K, sb, tb, termb, esb)
+    _same_env(B, A, keys=STATE + ("meal_time", "meal_amt", "start_minute", "episode", "cgm0"))
+    _same_dicts(stb, sta, POLICY_STATE)
+    _same_dicts(sb, sa, STATS)
+    _same_dicts(esb, esa, EPISODE_STATS)
+    assert torch.equal(_bits(termb), _bits(terma))
+    _same_dicts(tb, ta, cols[:7])
+    assert bool((ta["eps"][1:] == 0).all())
+    assert A._clock is None
+    return (B.episode - 1).cpu().numpy(), low, high
+
+
+@pytest.mark.parametrize("dtype_name", ["float64", "float32"])
+def test_restart_is_the_loop_of_existing_entry_points_bit_for_bit(dtype_name):
+    """400 Dexcom steps under a constant 0.05 U/min (episodes end low) in launches of 150 and 250 steps, and 400 steps without
+    insulin (episodes end high)."""
+    torch = _torch()
+    dtype = getattr(torch, dtype_name)
+    restarts_lo, low_lo, high_lo = _restart_pair(dtype, 0.05, (150, 250))
+    restarts_hi, low_hi, high_hi = _restart_pair(dtype, 0.0, (400,))
+    print("\n[%s] restarted envs %d / %d of 256, max restarts per env %d / %d, endings < 70: %d / %d, > 350: %d / %d"
+          % (dtype_name, (restarts_lo > 0).sum(), (restarts_hi > 0).sum(), restarts_lo.max(), restarts_hi.max(), low_lo, low_hi,
+             high_lo, high_hi))
+    # asserted on the reference loop, so that the comparison cannot pass on nothing
+    assert (restarts_lo > 0).sum() >= 0.05 * 256
+    assert restarts_lo.max() >= 2
+    assert high_lo + high_hi > 0
+
+
+# ---------------------------------------------------------------------------------------------------------- 3
+def _draw_of_pair(m):
+    """the draw index of t1d_philox_normals whose value is philox_pair(.., pair = m).x"""
+    return np.where(m >= 3, 1 + 10 * ((m - 3) // 5) + 2 * ((m - 3) % 5), 0)
+
+
+@pytest.mark.parametrize("dtype_name", ["float64", "float32"])
+def test_exploration_draws_are_keyed_by_env_episode_and_clock(dtype_name):
+    torch = _torch()
+    dtype = getattr(torch, dtype_name)
+    n, K, warm, explore_seed = 256, 40, 150, 0x1234ABCD5678
+    pol = _constant_policy(0.05)
+    e = _mk_gym(n, dtype)
+    st = e.collect_mlp(warm, pol, on_done="restart", days=DAYS)          # far enough for episodes to end in the window below
+    ep0, t0 = e.episode.cpu().numpy().astype(np.int64), e.t.cpu().numpy().astype(np.int64)
+    tr = e.new_trace(K, columns=("done", "eps"))
+    e.collect_mlp(K, pol, sigma=0.3, explore_seed=explore_seed, policy_state=st, trace=tr, on_done="restart", days=DAYS)
+    assert e.sync() == 0
+    done = tr["done"][1:].cpu().numpy().astype(np.int64)
+    eps = tr["eps"][1:]
+    # the episode counter and the clock every env had at the start of every step, from the done history
+    k, m = np.empty((K, n), np.int64), np.empty((K, n), np.int64)
+    ep, t = ep0.copy(), t0.copy()
+    for s in range(K):
+        k[s], m[s] = ep, t
+        ep = ep + done[s]
+        t = np.where(done[s] != 0, 0, t + ST)
+    assert np.array_equal(ep, e.episode.cpu().numpy()) and np.array_equal(t, e.t.cpu().numpy())
+    assert done.sum() > 0 and k.max() >= 2 and (m == 0).any()            # episodes after the first one, and first steps
+    d = _draw_of_pair(m)
+    want = np.empty((K, n))
+    normals = {}
+    for kk in np.unique(k):
+        out = torch.empty(int(d.max()) + 1, n, dtype=torch.float64, device=e.device)
+        with torch.cuda.device(e.device):
+            assert e._L.t1d_philox_normals(e._ctx, explore_seed, e.env_offset, n, int(kk), 0, out.shape[0],
+                                           C.c_void_p(out.data_ptr()), e._stream()) == 0
+        normals[int(kk)] = out.cpu().numpy()
+        sel = k == kk
+        want[sel] = normals[int(kk)][d[sel], np.broadcast_to(np.arange(n), (K, n))[sel]]
+    assert torch.equal(_bits(eps), _bits(torch.as_tensor(want, dtype=torch.float64).to(dtype).to(e.device)))
+    # no two envs, steps or episodes share their draws
+    assert not torch.equal(eps[:, 0], eps[:, 1]) and not torch.equal(eps[0], eps[1])
+    assert len(torch.unique(eps)) > 0.99 * eps.numel()
+    ks = sorted(normals)
+    assert len(ks) >= 2 and not np.array_equal(normals[ks[0]][:8], normals[ks[1]][:8])
+    assert 0.9 < float(eps.double().std()) < 1.1 and abs(float(eps.double().mean())) < 0.05
+    # without sigma no draw is made and the rows are 0
+    tr0 = e.new_trace(3, columns=("eps",))
+    e.collect_mlp(3, pol, policy_state=st, trace=tr0, on_done="restart", days=DAYS)
+    assert e.sync() == 0 and bool((tr0["eps"][1:] == 0).all())
+
+
+# ---------------------------------------------------------------------------------------------------------- 4
+@pytest.mark.parametrize("shape", ["small", "top"])
+@pytest.mark.parametrize("dtype_name", ["float64", "float32"])
+def test_action_and_features_are_what_the_contract_says(dtype_name, shape):
+    """Teacher-forced on the kernel's own traces, so nothing is amplified by the closed loop: the action against the host's
+    ordered forward pass on the recorded features plus sigma eps (bound: the rounding of a few dozen fused multiply-adds per
+    layer and of the exp-based activations, 1e-13 of the output range in fp64, 1e-5 in fp32 -- test_top_of_the_range of
+    test_gpu_policy.py); features 0 .. 2 H bit for bit MLPController.features of the windows rebuilt from the traces; the two
+    time-of-day features within 1e-14 / 2e-6 of sin and cos (test_feature_semantics)."""
+    torch = _torch()
+    from simglucose_amd.controller.mlp_ctrller import MLPController
+    dtype = getattr(torch, dtype_name)
+    n, K, P = 256, 24, 2
+    if shape == "small":
+        pol = _policy(history=4, widths=(16, 16, 1), n_policies=P, seed=3, output="identity")
+    else:
+        pol = _policy(history=12, widths=(32, 32, 32, 1), n_policies=P, seed=7, output="logistic")
+    H = pol.history
+    pre = MLPController(list(zip(pol.W, pol.b)), history=H, hidden=pol.hidden, output="identity", out_scale=1.0, out_bias=0.0)
+    starts = 17 * np.arange(n) % 1440
+    e = _mk(n, dtype, start=starts)
+    st0 = {k: v.clone() for k, v in e.new_policy_state(pol).items()}
+    sigma = torch.tensor([0.1, 0.5], dtype=torch.float64)
+    tr = e.new_trace(K, columns=TRACES, history=H)
+    e.collect_mlp(K, pol, sigma=sigma, trace=tr)
+    assert e.sync() == 0
+    sg = sigma.repeat_interleave(n // P).to(e.device)
+    cgm_hist, ins_hist, meal = st0["cgm_hist"], st0["ins_hist"], st0["prev_meal"]
+    worst = worst_tod = 0.0
+    for s in range(1, K + 1):
+        feat = tr["features"][s]
+        y = pre.forward(feat.double(), ordered=True)
+        z = y + sg * tr["eps"][s].double()
+        want = pol.out_scale * (torch.sigmoid(z) if pol.output == "logistic" else z) + pol.out_bias
+        worst = max(worst, float((tr["action"][s].double() - want).abs().max()))
+        minute = e.start_minute + ST * (s - 1)
+        ref = pol.features(cgm_hist, ins_hist, meal, minute)
+        assert torch.equal(_bits(feat[:2 * H + 1]), _bits(ref[:2 * H + 1])), s
+        ang = (minute % 1440).double() * (2.0 * math.pi / 1440.0)
+        worst_tod = max(worst_tod, float((feat[2 * H + 1].double() - torch.sin(ang)).abs().max()),
+                        float((feat[2 * H + 2].double() - torch.cos(ang)).abs().max()))
+        pol.shift(cgm_hist, ins_hist, tr["cgm"][s], tr["insulin"][s])
+        meal = tr["cho"][s]
+    print("\n[%s %s] max |action - host| = %.3e U/min (out_scale %.2f), max |time-of-day feature - sin, cos| = %.3e"
+          % (dtype_name, shape, worst, pol.out_scale, worst_tod))
+    assert worst <= pol.out_scale * (1e-13 if dtype == torch.float64 else 1e-5)
+    assert worst_tod <= (1e-14 if dtype == torch.float64 else 2e-6)
+    assert float(tr["action"][1:].std()) > 0 and float(tr["eps"][1:].std()) > 0.5
+
+
+# ---------------------------------------------------------------------------------------------------------- 5
+def _noisy_run(e, pol, sigma, warm, chunks, explore_seed=99):
+    """`warm` steps in one launch (far enough for episodes to end in what follows), then the traced chunks"""
+    stats, es, term = _stats(e), _episode_stats(e), _torch().zeros(e.n, dtype=e.dtype, device=e.device)
+    kw = dict(sigma=sigma, explore_seed=explore_seed, stats=stats, on_done="restart", days=DAYS, terminal_obs=term, episode_stats=es)
+    st = e.collect_mlp(warm, pol, **kw)
+    tr = e.new_trace(sum(chunks), columns=TRACES, history=pol.history)
+    for ch in chunks:
+        e.collect_mlp(ch, pol, policy_state=st, trace=tr, **kw)
+    assert e.sync() == 0
+    es["terminal_obs"] = term
+    return st, stats, es, tr
+
+
+def _hypo_leaning_policies(P, seed=11):
+    """small random weights around a constant 0.05 U/min"""
+    return _policy(history=4, widths=(8, 1), n_policies=P, seed=seed, output="identity", gain=0.02, out_scale=1.0, out_bias=0.05)
+
+
+GYM_STATE = STATE + ("meal_time", "meal_amt", "start_minute", "cgm0")
+
+
+def test_cuts_change_nothing_with_noise_and_restarts_on():
+    torch = _torch()
+    pol = _hypo_leaning_policies(1)
+    runs = []
+    for chunks in ((40,), (10,) * 4, (1,) * 40):
+        e = _mk_gym(256, torch.float64)
+        runs.append((e,) + _noisy_run(e, pol, 0.3, 150, chunks))
+    e0, st0, stats0, es0, tr0 = runs[0]
+    assert int(tr0["done"][1:].sum()) > 0 and int(e0.episode.max()) >= 2
+    for e, st, stats, es, tr in runs[1:]:
+        _same_env(e0, e, keys=GYM_STATE)
+        _same_dicts(st0, st, POLICY_STATE)
+        _same_dicts(stats0, stats, STATS)
+        _same_dicts(es0, es, EPISODE_STATS + ("terminal_obs",))
+        _same_dicts(tr0, tr, TRACES)
+
+
+def test_shards_are_slices_of_the_big_batch_with_noise_and_restarts_on():
+    torch = _torch()
+    from simglucose_amd.controller.mlp_ctrller import MLPController
+    n, epp = 1024, 128
+    pol = _hypo_leaning_policies(n // epp)
+    sigma = torch.linspace(0.05, 0.4, n // epp, dtype=torch.float64)
+    big = _mk_gym(n, torch.float64)
+    st, stats, es, tr = _noisy_run(big, pol, sigma, 150, (40,))
+    assert int(tr["done"][1:].sum()) > 0
+    for a, b in ((0, 128), (256, 640), (896, 1024)):
+        pa, pb = a // epp, b // epp
+        sub = MLPController([(W[pa:pb], bb[pa:pb]) for W, bb in zip(pol.W, pol.b)], history=pol.history, hidden=pol.hidden,
+                            output=pol.output, out_scale=pol.out_scale, out_bias=pol.out_bias)
+        e = _mk_gym(b - a, torch.float64, env_offset=a)
+        s2, stats2, es2, tr2 = _noisy_run(e, sub, sigma[pa:pb], 150, (40,))
+        sl = slice(a, b)
+        _same_env(big, e, sl, keys=GYM_STATE)
+        _same_dicts(st, s2, POLICY_STATE, sl)
+        _same_dicts(stats, stats2, STATS, sl)
+        _same_dicts(es, es2, EPISODE_STATS + ("terminal_obs",), sl)
+        _same_dicts(tr, tr2, TRACES, sl)
+
+
+# ---------------------------------------------------------------------------------------------------------- 6
+def test_rejections_change_nothing():
+    torch = _torch()
+    from simglucose_amd import _lib
+    from simglucose_amd.batch_env import BatchedT1DSimEnv
+    e = _mk_gym(128, torch.float64)
+    pol = _policy(history=3, widths=(8, 1))
+    st = e.new_policy_state(pol)
+    params = pol.flat_params().to(e.device)
+    other_time, other_amt = e.meal_time.clone(), e.meal_amt.clone()
+    scratch = torch.zeros(13, e.n, dtype=torch.float64, device=e.device)
+    before = {k: getattr(e, k).clone() for k in GYM_STATE}
+    before.update({k: v.clone() for k, v in st.items()})
+    L = e._L
+
+    def mlp():
+        p = _lib.Mlp()
+        pol.fill_struct(p)
+        p.n_policies, p.envs_per_policy, p.n_params = 1, e.n, params.shape[1]
+        p.params = params.data_ptr()
+        for k in ("cgm_hist", "ins_hist", "prev_meal"):
+            setattr(p, k, st[k].data_ptr())
+        p.start_minute = e.start_minute.data_ptr()
+        return p
+
+    def restart():
+        r = _lib.Restart()
+        r.days, r.random_init_bg, r.reset_outputs, r.reserved = DAYS, 1, 0, 0
+        r.meal_time, r.meal_amt, r.start_minute = e.meal_time.data_ptr(), e.meal_amt.data_ptr(), e.start_minute.data_ptr()
+        return r
+
+    def collect(r, on_done=1):
+        g = _lib.Collect()
+        g.explore_seed, g.on_done, g.reserved = 7, on_done, 0
+        g.restart = C.pointer(r) if r is not None else None
+        return g
+
+    def batch(**kw):
+        b = _lib.Batch()
+        C.memmove(C.byref(b), C.byref(e._b), C.sizeof(b))
+        for k, v in kw.items():
+            setattr(b, k, v)
+        return b
+
+    def call(p, g, b=None, n_steps=2, minutes=3, n_sub=4):
+        with torch.cuda.device(e.device):
+            return L.t1d_collect_mlp(e._ctx, C.byref(b if b is not None else e._b), C.byref(p) if p is not None else None,
+                                     C.byref(g) if g is not None else None, n_steps, minutes, n_sub, e._stream())
+    bad = []
+    # everything t1d_rollout_mlp rejects
+    for field, value in (("history", 0), ("history", 13), ("n_layers", 0), ("n_layers", 5), ("hidden_act", 2), ("out_act", -1),
+                         ("params", None), ("cgm_hist", None), ("ins_hist", None), ("prev_meal", None), ("n_policies", 0),
+                         ("n_policies", 2), ("envs_per_policy", 64), ("envs_per_policy", 100), ("n_params", params.shape[1] + 1)):
+        p = mlp(); setattr(p, field, value)
+        for on_done in (0, 1):
+            r = restart(); bad.append(("mlp." + field, value, p, collect(r, on_done), None, {}, r))
+    for l, wv in ((0, 0), (0, 33), (1, 2)):
+        p = mlp(); p.width[l] = wv; r = restart(); bad.append(("mlp.width[%d]" % l, wv, p, collect(r), None, {}, r))
+    r = restart()
+    bad += [("mlp", None, None, collect(r), None, {}, r), ("n_steps", 0, mlp(), collect(r), None, {"n_steps": 0}, r),
+            ("minutes", 0, mlp(), collect(r), None, {"minutes": 0}, r), ("n_sub", 0, mlp(), collect(r), None, {"n_sub": 0}, r),
+            ("batch.cho", "set", mlp(), collect(r), batch(cho=scratch.data_ptr()), {}, r)]
+    # everything t1d_restart_done rejects, with on_done = 1
+    bad += [("batch.episode", None, mlp(), collect(r), batch(episode=None), {}, r),
+            ("batch.normals", "set", mlp(), collect(r), batch(normals=scratch.data_ptr(), n_normals=13), {}, r),
+            ("batch.x0_override", "set", mlp(), collect(r), batch(x0_override=scratch.data_ptr()), {}, r)]
+    for field, value in (("meal_time", other_time.data_ptr()), ("meal_amt", other_amt.data_ptr()), ("meal_time", None),
+                         ("start_minute", None), ("days", 3), ("days", 0), ("reserved", 1), ("h_carry", scratch.data_ptr())):
+        r2 = restart(); setattr(r2, field, value); bad.append(("restart." + field, value, mlp(), collect(r2), None, {}, r2))
+    es = _episode_stats(e)
+    r3 = restart(); r3.ep_return = es["ep_return"].data_ptr(); bad.append(("restart.ep_return alone", "set", mlp(), collect(r3), None, {}, r3))
+    r4 = restart(); r4.last_return = es["last_return"].data_ptr(); bad.append(("restart.last_return alone", "set", mlp(), collect(r4), None, {}, r4))
+    # the collector's own
+    bad += [("collect.on_done", 2, mlp(), collect(r, 2), None, {}, r), ("collect.on_done", -1, mlp(), collect(r, -1), None, {}, r),
+            ("collect.restart", None, mlp(), collect(None, 1), None, {}, None), ("collect", None, mlp(), None, None, {}, None)]
+    p = mlp(); p.start_minute = scratch.data_ptr()                # a restarted env's time of day would not follow its new start
+    bad.append(("mlp.start_minute", "not restart.start_minute", p, collect(r), None, {}, r))
+    for on_done in (0, 1):
+        g = collect(r, on_done); g.reserved = 1; bad.append(("collect.reserved", 1, mlp(), g, None, {}, r))
+    for what, value, p, g, b, kw, _keep in bad:
+        assert call(p, g, b, **kw) == -1, (what, value)
+        assert L.t1d_last_error().startswith(b"t1d_collect_mlp: "), (what, value, L.t1d_last_error())
+        assert len(L.t1d_last_error()) > len(b"t1d_collect_mlp: "), (what, value)
+    assert e.sync() == 0
+    for k in GYM_STATE:
+        assert torch.equal(getattr(e, k), before[k]), k
+    for k in st:
+        assert torch.equal(st[k], before[k]), k
+    with pytest.raises(ValueError):
+        e.collect_mlp(2, _policy(n_policies=4))                 # 128 envs / 4 = 32 per policy
+    with pytest.raises(ValueError):
+        e.collect_mlp(0, pol)
+    with pytest.raises(ValueError):
+        e.collect_mlp(2, pol, on_done="stop")
+    with pytest.raises(ValueError):
+        e.collect_mlp(2, pol, trace={"row": 0, "done": torch.zeros(4, e.n, dtype=torch.float64, device=e.device)})
+    for k in GYM_STATE:
+        assert torch.equal(getattr(e, k), before[k]), k
+    # and the good ones run
+    r = restart()
+    assert call(mlp(), collect(r, 1)) == 0 and call(mlp(), collect(None, 0)) == 0 and e.sync() == 0
+    assert int(e.t.max()) == 4 * ST
+    ex = BatchedT1DSimEnv(patient=np.arange(64) % 30, integrator="dopri5")
+    ex.reset()
+    with pytest.raises(_lib.T1DError):
+        ex.collect_mlp(2, pol)
