@@ -403,7 +403,7 @@ int t1d_rollout_bb(t1d_ctx* ctx, const t1d_batch* batch, const t1d_bb* bb, int n
 
 /* SimObj.simulate (sim_engine.py:29-39) with the policy of t1d_mlp for n_steps env.steps in ONE launch, the env state in
  * registers, the two windows and the layer activations in LDS, the weights through the scalar data cache.  fp64 and fp32, any
- * state layout, the fixed-step integrators as configured on the context (the exact mode has no such roll-out), meals from the
+ * state layout, the fixed-step integrators as configured on the context (the exact mode: t1d_rollout_mlp_dopri5), meals from the
  * meal tables.  Outputs, state and the last step's reward as t1d_rollout_pid; mlp.cgm_hist / ins_hist / prev_meal are
  * updated.  Anything out of range -- history, n_layers, a width, an activation code, a NULL array, n_params, or
  * n != n_policies * envs_per_policy -- is T1D_E_INVALID before anything is launched. */
@@ -460,6 +460,33 @@ int t1d_rollout_pid_dopri5(t1d_ctx* ctx, const t1d_batch* b, const t1d_pid* pid,
  * in the exact mode -- the reference's own regression run (sim_results.csv).  bb.prev_meal is updated. */
 int t1d_rollout_bb_dopri5(t1d_ctx* ctx, const t1d_batch* b, const t1d_bb* bb, double* h_carry, int32_t* nfev,
                           int n_steps, int minutes, void* hip_stream);
+
+/* SimObj.simulate (sim_engine.py:29-39) with the policy of t1d_mlp and the integrator of t1d_step_dopri5: t1d_rollout_mlp
+ * (features, layers, output function, bolus = 0, windows, prev_meal, accumulators, the five trace columns with action_trace,
+ * the last step's reward) in the exact mode, with the solver and the free-running lanes of t1d_rollout_pid_dopri5.  All
+ * n_steps steps are ONE launch in which every env walks through its minutes at its own pace; an env that opens a step
+ * evaluates the network then, whatever the other 63 envs of its wave are doing.  The two windows (a ring whose head each
+ * env keeps for itself) and the layer activations are in LDS, the weights go through the scalar data cache, one set per wave.
+ * The action of a step is the word t1d_rollout_mlp and t1d_mlp_action compute from the same windows, prev_meal, clock,
+ * start_minute and weights; everything else is what t1d_rollout_pid_dopri5 does.  The results are those of a loop of
+ * t1d_mlp_action, t1d_step_dopri5 (bolus = 0), the shift of the windows and prev_meal = batch.meal, bit for bit, whatever
+ * the other envs of the batch do and wherever the roll-out is cut.
+ * fp64 batches only; meals from the meal tables; every policy t1d_rollout_mlp accepts is accepted (the workgroup shrinks from
+ * four waves to two or one where the columns need the room).  h_carry, nfev and T1D_ST_SOLVER_FAILED as in
+ * t1d_rollout_pid_dopri5; mlp.cgm_hist / ins_hist / prev_meal are updated (row 0 of cgm_hist is taken from batch.cgm on entry).
+ * T1D_E_INVALID before anything is launched, nothing changed: whatever t1d_rollout_mlp rejects and whatever
+ * t1d_rollout_pid_dopri5 rejects (an fp32 batch, a NULL h_carry, dense cho, n_steps < 1, minutes out of range). */
+int t1d_rollout_mlp_dopri5(t1d_ctx* ctx, const t1d_batch* b, const t1d_mlp* mlp, double* h_carry, int32_t* nfev,
+                           int n_steps, int minutes, void* hip_stream);
+
+/* The policy of t1d_mlp alone, one lane per env: action[i] (device [n], the batch's dtype) = the basal, before the pump,
+ * that the next step of t1d_rollout_mlp / t1d_rollout_mlp_dopri5 would ask for env i -- from batch.cgm (CGM[0]), rows 1 ..
+ * of mlp.cgm_hist, mlp.ins_hist, mlp.prev_meal, batch.t and mlp.start_minute, with the arithmetic of the roll-outs, word for
+ * word.  It changes nothing: no state is written and no step is taken (the accumulators and trace pointers of mlp are not
+ * used).  fp64 and fp32, any integrator, any state layout.  What a step() loop needs to drive the env with the roll-outs'
+ * policy: action, t1d_step / t1d_step_dopri5, then cgm_hist and ins_hist shifted by one row with batch.cgm / batch.insulin
+ * in row 0 and prev_meal = batch.meal.  T1D_E_INVALID: a NULL action, and whatever t1d_rollout_mlp rejects of the policy. */
+int t1d_mlp_action(t1d_ctx* ctx, const t1d_batch* b, const t1d_mlp* mlp, void* action, void* hip_stream);
 
 /* RandomScenario.create_scenario (simulation/scenario_gen.py:33-60) for n envs on the device: fills per-env
  * meal tables meal_time int32 [6 (days + 1)][n] (minutes since the episode start, ascending, unused =

@@ -453,7 +453,7 @@ class BatchedT1DSimEnv:
     def _no_dopri5_rollout(self):
         if self.integrator == "dopri5":
             raise _lib.T1DError("rollout_pid / rollout_bb / rollout_mlp run the fixed-step kernels, which have no DOPRI5 path: an env with "
-                                "integrator='dopri5' takes rollout_pid_dopri5 / rollout_bb_dopri5")
+                                "integrator='dopri5' takes rollout_pid_dopri5 / rollout_bb_dopri5 / rollout_mlp_dopri5")
 
     def rollout_pid(self, n_steps, P, I, D, target=140.0, pid_state=None, stats=None, trace=None):
         """n_steps closed-loop PID steps in one launch (PIDController.policy + env.step per step).
@@ -533,22 +533,11 @@ class BatchedT1DSimEnv:
                 "ins_hist": torch.zeros(H, self.n, dtype=self.dtype, device=self.device),
                 "prev_meal": torch.zeros(self.n, dtype=self.dtype, device=self.device)}
 
-    def rollout_mlp(self, n_steps, policy, policy_state=None, stats=None, trace=None):
-        """n_steps closed-loop steps in one launch under a feed-forward policy evaluated inside the kernel (t1d_rollout_mlp,
-        include/t1d.h): policy is a controller.MLPController with one weight set, or with P of them -- env i then uses
-        set i // (n // P), and n // P must be a multiple of 64.  policy_state: dict(cgm_hist, ins_hist, prev_meal) as
-        new_policy_state() makes it (created if None: call right after reset()), updated in place and returned, so a
-        roll-out can be cut anywhere and resumed.  The time-of-day features use the env's start_minute (0 if it has none).
-        stats as in rollout_pid; trace may also hold "action" (new_trace)."""
-        self._no_dopri5_rollout()
-        n_steps = int(n_steps)
-        if n_steps < 1:
-            raise ValueError("n_steps must be at least 1")
+    def _mlp_struct(self, who, policy, policy_state, stats=None):
+        """the t1d_mlp of a policy and its state on this env, checked -> (struct, params tensor)"""
         npol = int(policy.n_policies)
         if self.n % npol or (self.n // npol) % 64:
-            raise ValueError("rollout_mlp: %d envs do not split into %d policies of a multiple of 64 envs each" % (self.n, npol))
-        if policy_state is None:
-            policy_state = self.new_policy_state(policy)
+            raise ValueError("%s: %d envs do not split into %d policies of a multiple of 64 envs each" % (who, self.n, npol))
         H = int(policy.history)
         for k, shape in (("cgm_hist", (H, self.n)), ("ins_hist", (H, self.n)), ("prev_meal", (self.n,))):
             t = policy_state.get(k)
@@ -565,6 +554,59 @@ class BatchedT1DSimEnv:
         stats = stats or {}
         for k in ("sum_risk", "min_bg", "max_bg", "n_low", "n_high"):
             setattr(p, k, stats[k].data_ptr() if k in stats else None)
+        return p, params
+
+    def policy_action(self, policy, policy_state):
+        """The basal [n], before the pump, that the next step of rollout_mlp / rollout_mlp_dopri5 would ask for
+        (t1d_mlp_action, include/t1d.h): the network on the current observation (env.cgm), rows 1 .. of
+        policy_state["cgm_hist"], its ins_hist and prev_meal, the env's clock and start_minute -- the roll-outs' own device
+        code, so the word is theirs.  Nothing is changed and no step is taken; works in every mode.  A step() loop under
+        the roll-outs' policy:
+
+            st = env.new_policy_state(pol)
+            u = env.policy_action(pol, st); env.step(u, 0 * u)
+            pol.shift(st["cgm_hist"], st["ins_hist"], env.cgm, env.insulin); st["prev_meal"] = env.meal.clone()
+        """
+        p, params = self._mlp_struct("policy_action", policy, policy_state)
+        self._set_trace(p, None, 0)
+        out = torch.empty(self.n, dtype=self.dtype, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.t1d_mlp_action(self._ctx, C.byref(self._b), C.byref(p), C.c_void_p(out.data_ptr()), self._stream()))
+        self._keep = (params, policy_state, out)
+        return out
+
+    def rollout_mlp_dopri5(self, n_steps, policy, policy_state=None, stats=None, trace=None, max_minutes_per_launch=240):
+        """rollout_mlp in the exact mode (t1d_rollout_mlp_dopri5): n_steps closed-loop steps under the in-kernel network with
+        scipy's dopri5, every env at its own pace inside a launch -- SimObj.simulate as the reference would run it with that
+        policy.  Results as a loop of policy_action(), step(u, 0) and the shift of the policy state, bit for bit.  Arguments
+        and return value as rollout_mlp; h_carry, nfev and max_minutes_per_launch as in rollout_pid_dopri5.  Measured on an
+        MI355X (160 steps, 1 Mi envs, H = 4, width 16; profiles/policy): 502 ms against 1 260 ms for that loop and 246 ms for
+        rollout_pid_dopri5 -- lanes open their steps at different moments, and each moment runs the network for the few
+        lanes that are there."""
+        self._need_dopri5("rollout_mlp_dopri5")
+        if int(n_steps) < 1:
+            raise ValueError("n_steps must be at least 1")
+        if policy_state is None:
+            policy_state = self.new_policy_state(policy)
+        p, params = self._mlp_struct("rollout_mlp_dopri5", policy, policy_state, stats)
+        self._rollout_dopri5(self._L.t1d_rollout_mlp_dopri5, p, n_steps, trace, max_minutes_per_launch)
+        self._keep = (params, policy_state)
+        return policy_state
+
+    def rollout_mlp(self, n_steps, policy, policy_state=None, stats=None, trace=None):
+        """n_steps closed-loop steps in one launch under a feed-forward policy evaluated inside the kernel (t1d_rollout_mlp,
+        include/t1d.h): policy is a controller.MLPController with one weight set, or with P of them -- env i then uses
+        set i // (n // P), and n // P must be a multiple of 64.  policy_state: dict(cgm_hist, ins_hist, prev_meal) as
+        new_policy_state() makes it (created if None: call right after reset()), updated in place and returned, so a
+        roll-out can be cut anywhere and resumed.  The time-of-day features use the env's start_minute (0 if it has none).
+        stats as in rollout_pid; trace may also hold "action" (new_trace)."""
+        self._no_dopri5_rollout()
+        n_steps = int(n_steps)
+        if n_steps < 1:
+            raise ValueError("n_steps must be at least 1")
+        if policy_state is None:
+            policy_state = self.new_policy_state(policy)
+        p, params = self._mlp_struct("rollout_mlp", policy, policy_state, stats)
         self._set_trace(p, trace, n_steps)
         self._b.cho = None
         self._b.flags = self._flags0

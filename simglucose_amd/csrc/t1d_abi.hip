@@ -929,8 +929,7 @@ extern "C" int t1d_rollout_mlp(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* ml
 
 // The exact mode's roll-outs (t1d_dopri5.hpp): all n_steps in one launch of dopri5_rollout_kernel on the grid of
 // dopri5_step_kernel, every lane at its own pace; no plan, no refill ahead.  Every argument is checked before any device work.
-static int launch_rollout_dopri5(const char* who, t1d_ctx* c, const t1d_batch* b, const t1d_pid* pid, const t1d_bb* bb,
-                                 double* h_carry, int32_t* nfev, int n_steps, int minutes, void* stream)
+static int check_rollout_dopri5(const char* who, const t1d_ctx* c, const t1d_batch* b, const double* h_carry, int n_steps, int minutes)
 {
     const std::string w(who);
     if (!c) return fail(T1D_E_INVALID, w + ": ctx is NULL");
@@ -940,7 +939,13 @@ static int launch_rollout_dopri5(const char* who, t1d_ctx* c, const t1d_batch* b
     if (n_steps < 1) return fail(T1D_E_INVALID, w + ": n_steps < 1");
     if (minutes < 1 || minutes > 100000) return fail(T1D_E_INVALID, w + ": minutes out of range");
     if (b->cho) return fail(T1D_E_INVALID, w + ": dense cho is not supported, use the meal table");
-    const int rc = check_batch(who, c, b, false);
+    return check_batch(who, c, b, false);
+}
+
+static int launch_rollout_dopri5(const char* who, t1d_ctx* c, const t1d_batch* b, const t1d_pid* pid, const t1d_bb* bb,
+                                 double* h_carry, int32_t* nfev, int n_steps, int minutes, void* stream)
+{
+    const int rc = check_rollout_dopri5(who, c, b, h_carry, n_steps, minutes);
     if (rc) return rc;
     hipLaunchKernelGGL(dopri5_rollout_kernel, grid_for(b->n), dim3(kBlock), 0, (hipStream_t)stream, make_args<double>(c, b, minutes, 1),
                        pid ? make_pid<double>(pid, n_steps) : make_bb<double>(bb, n_steps), (const double*)c->d_raw64, h_carry, nfev);
@@ -961,6 +966,63 @@ extern "C" int t1d_rollout_bb_dopri5(t1d_ctx* c, const t1d_batch* b, const t1d_b
     if (!bb || !bb->basal || !bb->cr || !bb->cf || !bb->prev_meal)
         return fail(T1D_E_INVALID, "t1d_rollout_bb_dopri5: bb is NULL, or basal / cr / cf / prev_meal is not set");
     return launch_rollout_dopri5("t1d_rollout_bb_dopri5", c, b, nullptr, bb, h_carry, nfev, n_steps, minutes, stream);
+}
+
+// The exact mode's roll-out under the policy of t1d_mlp (dopri5_mlp_rollout_kernel, t1d_dopri5.hpp).  Dynamic LDS: for every
+// wave RollCold's words and the policy's columns; the workgroup is the most waves (4, 2 or 1) whose pieces fit beside the raw
+// patient rows.
+extern "C" int t1d_rollout_mlp_dopri5(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, double* h_carry, int32_t* nfev,
+                                      int n_steps, int minutes, void* stream)
+{
+    const char* who = "t1d_rollout_mlp_dopri5";
+    int rc = check_rollout_dopri5(who, c, b, h_carry, n_steps, minutes);
+    if (rc) return rc;
+    int cols = 0;
+    rc = check_mlp(who, b, mlp, &cols);
+    if (rc) return rc;
+    MlpArgs<double> ma = make_mlp<double>(mlp, n_steps);
+    ma.cols = cols;
+    const size_t fixed = (size_t)kRawPars * kMaxPatients * sizeof(double) + 256;           // static LDS
+    const size_t per_wave = (size_t)kRollColdWaveBytes + (size_t)cols * 64 * sizeof(double);
+    int threads = kBlock;
+    while (threads > 64 && fixed + per_wave * (threads / 64) > (size_t)c->lds_per_block) threads /= 2;
+    if (fixed + per_wave * (threads / 64) > (size_t)c->lds_per_block)
+        return fail(T1D_E_INVALID, std::string(who) + ": the patient rows leave no room in LDS for one wave of this policy");
+    const size_t dyn = per_wave * (threads / 64);
+    T1D_HIP(allow_lds(c, (const void*)dopri5_mlp_rollout_kernel, dyn));
+    hipLaunchKernelGGL(dopri5_mlp_rollout_kernel, dim3((unsigned)((b->n + threads - 1) / threads)), dim3(threads), dyn, (hipStream_t)stream,
+                       make_args<double>(c, b, minutes, 1), ma, (const double*)c->d_raw64, h_carry, nfev);
+    T1D_HIP(hipGetLastError());
+    return T1D_OK;
+}
+
+// The policy alone (mlp_action_kernel, t1d_dopri5.hpp): dynamic LDS is the columns of every wave, within the 64 KiB any
+// kernel may have without asking.
+template <typename T>
+static void launch_mlp_action(const t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, int cols, void* action, hipStream_t s)
+{
+    MlpArgs<T> ma = make_mlp<T>(mlp, 0);
+    ma.cols = cols;
+    const size_t per_wave = (size_t)cols * 64 * sizeof(T), room = std::min<size_t>((size_t)c->lds_per_block, 65536) - 256;
+    int threads = T1D_POLICY_THREADS;
+    while (threads > 64 && per_wave * (threads / 64) > room) threads /= 2;
+    hipLaunchKernelGGL(mlp_action_kernel<T>, dim3((unsigned)((b->n + threads - 1) / threads)), dim3(threads), per_wave * (threads / 64), s,
+                       make_args<T>(c, b, 1, 1), ma, (T*)action);
+}
+
+extern "C" int t1d_mlp_action(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, void* action, void* stream)
+{
+    const char* who = "t1d_mlp_action";
+    int rc = check_batch(who, c, b, false);
+    if (rc) return rc;
+    if (!action) return fail(T1D_E_INVALID, "t1d_mlp_action: action is NULL");
+    int cols = 0;
+    rc = check_mlp(who, b, mlp, &cols);
+    if (rc) return rc;
+    if (b->dtype == T1D_F64) launch_mlp_action<double>(c, b, mlp, cols, action, (hipStream_t)stream);
+    else launch_mlp_action<float>(c, b, mlp, cols, action, (hipStream_t)stream);
+    T1D_HIP(hipGetLastError());
+    return T1D_OK;
 }
 
 // the six meal windows of RandomScenario.create_scenario (scenario_gen.py:38-45) as the kernels take them

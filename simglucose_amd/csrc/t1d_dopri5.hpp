@@ -20,6 +20,7 @@
 // T1D_ST_SOLVER_FAILED -- where the reference raises "ODE solver failed".
 #pragma once
 #include "t1d_kernels.hpp"
+#include "t1d_policy.hpp"
 
 namespace t1d {
 
@@ -323,30 +324,32 @@ __device__ __forceinline__ void dopri5_controller(const PidArgs<double>& c, unsi
 
 // The words of a lane that only its minute boundaries touch, kept in LDS between them ([word][lane]: no bank conflict):
 // dopri5_attempt needs every register of the unified file for its stage vectors (dopri5_step_kernel: 256 VGPRs + 220
-// AGPRs), and what is reloaded at the top of the boundary block is not alive across the step attempts.
-struct RollCold {
+// AGPRs), and what is reloaded at the top of the boundary block is not alive across the step attempts.  STRIDE: the lanes
+// that share a block of words -- the workgroup (RollCold) or, where the workgroup's size is chosen per launch, the wave.
+template <int STRIDE> struct RollColdT {
     enum { PLANNED, LAST_CGM, PREV_RISK, CUR0, CUR1, CUR2, CUR3, NOISE, O_CGM, O_BG, O_MEAL, O_INS, HC, NF };
     enum { CURSOR, NEXT_MEAL, NEXT_MEAL_LOADED, NI };
     double* f; int* w;
     __device__ __forceinline__ void save(const Env<double>& e, const StepOut<double>& o, double noise, double hc) const
     {
-        f[PLANNED * kBlock] = e.planned; f[LAST_CGM * kBlock] = e.last_cgm; f[PREV_RISK * kBlock] = e.prev_risk;
+        f[PLANNED * STRIDE] = e.planned; f[LAST_CGM * STRIDE] = e.last_cgm; f[PREV_RISK * STRIDE] = e.prev_risk;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) f[(CUR0 + k) * kBlock] = e.cur[k];
-        f[NOISE * kBlock] = noise; f[HC * kBlock] = hc;
-        f[O_CGM * kBlock] = o.cgm; f[O_BG * kBlock] = o.bg; f[O_MEAL * kBlock] = o.meal; f[O_INS * kBlock] = o.ins;
-        w[CURSOR * kBlock] = e.cursor; w[NEXT_MEAL * kBlock] = e.next_meal; w[NEXT_MEAL_LOADED * kBlock] = e.next_meal_loaded;
+        for (int k = 0; k < 4; ++k) f[(CUR0 + k) * STRIDE] = e.cur[k];
+        f[NOISE * STRIDE] = noise; f[HC * STRIDE] = hc;
+        f[O_CGM * STRIDE] = o.cgm; f[O_BG * STRIDE] = o.bg; f[O_MEAL * STRIDE] = o.meal; f[O_INS * STRIDE] = o.ins;
+        w[CURSOR * STRIDE] = e.cursor; w[NEXT_MEAL * STRIDE] = e.next_meal; w[NEXT_MEAL_LOADED * STRIDE] = e.next_meal_loaded;
     }
     __device__ __forceinline__ void load(Env<double>& e, StepOut<double>& o, double& noise, double& hc) const
     {
-        e.planned = f[PLANNED * kBlock]; e.last_cgm = f[LAST_CGM * kBlock]; e.prev_risk = f[PREV_RISK * kBlock];
+        e.planned = f[PLANNED * STRIDE]; e.last_cgm = f[LAST_CGM * STRIDE]; e.prev_risk = f[PREV_RISK * STRIDE];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) e.cur[k] = f[(CUR0 + k) * kBlock];
-        noise = f[NOISE * kBlock]; hc = f[HC * kBlock];
-        o.cgm = f[O_CGM * kBlock]; o.bg = f[O_BG * kBlock]; o.meal = f[O_MEAL * kBlock]; o.ins = f[O_INS * kBlock];
-        e.cursor = w[CURSOR * kBlock]; e.next_meal = w[NEXT_MEAL * kBlock]; e.next_meal_loaded = w[NEXT_MEAL_LOADED * kBlock];
+        for (int k = 0; k < 4; ++k) e.cur[k] = f[(CUR0 + k) * STRIDE];
+        noise = f[NOISE * STRIDE]; hc = f[HC * STRIDE];
+        o.cgm = f[O_CGM * STRIDE]; o.bg = f[O_BG * STRIDE]; o.meal = f[O_MEAL * STRIDE]; o.ins = f[O_INS * STRIDE];
+        e.cursor = w[CURSOR * STRIDE]; e.next_meal = w[NEXT_MEAL * STRIDE]; e.next_meal_loaded = w[NEXT_MEAL_LOADED * STRIDE];
     }
 };
+typedef RollColdT<kBlock> RollCold;
 
 // c.n_steps closed-loop steps of a.minutes minutes in one launch, every lane at its own pace.  The body of the one loop is
 // ONE step attempt of the driver for every lane that still has work; ahead of it, only the lanes that have just completed a
@@ -440,6 +443,147 @@ __global__ __launch_bounds__(kBlock, 1) void dopri5_rollout_kernel(const KArgs<d
     at(h_carry, i) = hc;
     if (nfev) at(nfev, i) = nf;
     if (failed) atomicOr(a.status, T1D_ST_SOLVER_FAILED);
+}
+
+// ---- closed-loop roll-outs in the exact mode under the policy of t1d_mlp (t1d_rollout_mlp_dopri5) -----------------------
+// dopri5_rollout_kernel with the network of t1d_policy.hpp where dopri5_controller stands: solver, eat_minute, measure_*,
+// the pump and the outputs are that kernel's, line for line; the action is mlp_action, the function mlp_rollout_kernel
+// calls, so a step asks for the word t1d_rollout_mlp would ask for from the same windows, prev_meal, clock and weights
+// (the functions of t1d_policy.hpp carry no contract(off): the pragma of this file is set per function and stays in the
+// solver's).  Where the policy's words live:
+//   windows      2 H rows of the lane's LDS column ([row][lane], no bank conflict), a ring as in mlp_rollout_body.  The
+//                lanes of a wave are in different steps, so the head is per lane: after s steps of this launch CGM[0] sits
+//                in row (H - s mod H) mod H, worked out from the lane's own step counter when a step ends.  In window
+//                order in mlp.cgm_hist / ins_hist on entry and on exit.
+//   layer buffer the rows behind the windows; live, like mlp_layers' out[] registers, only inside the boundary block of a
+//                lane that opens a step.  Nothing of the policy is in a register across dopri5_attempt.
+//   weights      one set per wave through the scalar data cache, as in mlp_rollout_kernel; only the lanes that open a step
+//                at that moment are active while the network runs.
+//   prev_meal, accumulators   through memory once per step, as dopri5_rollout_kernel passes the controller's state.
+// LDS: the raw patient rows (static), then for each wave RollCold's words (stride 64) and the column block -- the workgroup
+// is 4, 2 or 1 waves, the most that fit (t1d_rollout_mlp_dopri5), so every wave owns a contiguous piece of dynamic LDS
+// whose layout does not depend on the workgroup's size.
+constexpr int kRollColdWaveBytes = (int)(RollColdT<64>::NF * sizeof(double) + RollColdT<64>::NI * sizeof(int)) * 64;
+
+__global__ __launch_bounds__(kBlock, 1) void dopri5_mlp_rollout_kernel(const KArgs<double> a, const MlpArgs<double> c,
+                                                                       const double* __restrict__ raw, double* h_carry, int32_t* nfev)
+{
+    typedef RollColdT<64> Cold;
+    __shared__ double lds[kRawPars * kMaxPatients];
+    for (int j = threadIdx.x; j < kRawPars * kMaxPatients; j += blockDim.x) lds[j] = raw[j];
+    __syncthreads();
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    __builtin_assume(i < (1u << 28));          // host guarantees n <= 2^28: i * sizeof(T) fits a 32-bit voffset
+    if ((int64_t)i >= a.n) return;             // n is a multiple of 64: whole waves leave
+    // the wave's piece of dynamic LDS: Cold's doubles, Cold's ints, the columns
+    unsigned char* const piece = t1d_dyn_lds + (threadIdx.x >> 6) * (kRollColdWaveBytes + c.cols * 64 * (int)sizeof(double));
+    const unsigned lane = threadIdx.x & 63u;
+    const Cold cold{(double*)piece + lane, (int*)(piece + Cold::NF * 64 * sizeof(double)) + lane};
+    double* const col = (double*)(piece + kRollColdWaveBytes) + lane;
+    const int H = c.history;
+    double* const buf = col + 2 * H * 64;
+    const uint32_t meta = at(a.meta, i);
+    const uint32_t pid = T1D_META_PID(meta);
+    Env<double> e;
+    load_env(a, i, meta, e);
+    const ParsRaw p{lds, (int)pid};
+    NoDerivedPars nop;
+    const double div = double(a.minutes);
+    col[0] = at(a.cgm, i);                                      // CGM[0] is the observation the first step starts from
+    for (int k = 1; k < H; ++k) col[k * 64] = at(rowv(c.cgm_hist, a.n, k), i);
+    for (int k = 0; k < H; ++k) col[(H + k) * 64] = at(rowv(c.ins_hist, a.n, k), i);
+    double hc = at(h_carry, i), noise = 0.0, insulin = 0.0, d_mg = 0.0;
+    StepOut<double> o{0.0, 0.0, 0.0, 0.0};
+    Dopri5Run r{};
+    int nf = 0, m = 0, s = 0;
+    bool due = false, failed = false, boundary = true, fresh = true;
+    cold.save(e, o, noise, hc);
+    for (;;) {
+        if (boundary) {
+            cold.load(e, o, noise, hc);
+            if (!fresh) {
+                e.t += 1;
+                const double gsub = e.x[12] / p(T1D_P_VG);                                    // t1dpatient.py:217-218
+                const double cgm = measure_apply(a, e, gsub, noise, due);                     // env.py:62
+                o.bg += gsub / div; o.cgm += cgm / div;                                       // env.py:80-81
+                if (++m == a.minutes) {                  // the step is complete: what t1d_step_dopri5 leaves, then the roll-out's own
+                    const double rp = e.prev_risk;
+                    write_outputs<0>(a, i, e, o, rp);
+                    const int64_t tr = (c.trace_row + s) * a.n + i;
+                    if (c.bg_trace) c.bg_trace[tr] = o.bg;
+                    if (c.cgm_trace) c.cgm_trace[tr] = o.cgm;
+                    if (c.cho_trace) c.cho_trace[tr] = o.meal;
+                    if (c.ins_trace) c.ins_trace[tr] = o.ins;
+                    at(c.prev_meal, i) = o.meal;
+                    if (c.sum_risk) { double l, h, rk; risk_index1<0>(o.bg, l, h, rk); at(c.sum_risk, i) = at(c.sum_risk, i) + rk; }
+                    if (c.min_bg) { const double v = at(c.min_bg, i); at(c.min_bg, i) = o.bg < v ? o.bg : v; }
+                    if (c.max_bg) { const double v = at(c.max_bg, i); at(c.max_bg, i) = o.bg > v ? o.bg : v; }
+                    if (c.n_low) at(c.n_low, i) = at(c.n_low, i) + (o.bg < 70.0);
+                    if (c.n_high) at(c.n_high, i) = at(c.n_high, i) + (o.bg > 180.0);
+                    m = 0; ++s;
+                    const int q = s % H, head = q ? H - q : 0;  // the oldest row becomes the newest
+                    col[head * 64] = o.cgm; col[(H + head) * 64] = o.ins;
+                }
+            }
+            if (s == c.n_steps) break;
+            if (m == 0) {                                // a step opens: the network on the windows, then the pump
+                const int q = s % H, head = q ? H - q : 0;
+                const int start = c.start_minute ? (int)at(c.start_minute, i) : 0;
+                const double prev_meal = at(c.prev_meal, i);
+                const double u = mlp_action(c, mlp_wave_weights(c, i), col, buf, head, prev_meal, start + e.t);
+                if (c.act_trace) c.act_trace[(c.trace_row + s) * a.n + i] = u;
+                double q_basal = u, q_bolus = 0.0;       // as step_body with a bolus given: env.py:51-52
+                if (!(a.flags & T1D_BATCH_NO_PUMP)) {
+                    q_basal = pump_quantise(u, a.pump.inc_basal, a.pump.min_basal, a.pump.max_basal);
+                    q_bolus = pump_quantise(0.0, a.pump.inc_bolus, a.pump.min_bolus, a.pump.max_bolus);
+                }
+                insulin = q_basal + q_bolus;
+                o = StepOut<double>{0.0, 0.0, 0.0, 0.0};
+            }
+            const double meal = meal_lookup(a, i, e);                                         // env.py:50
+            noise = measure_noise<true>(a, i, e, due);
+            const MinuteIn<double> u = eat_minute<0, double>(nop, e.x, meal, insulin, e.planned, e.lq, e.lf, e.eating);
+            d_mg = u.d_mg;
+            o.meal += meal / div; o.ins += insulin / div;                                     // env.py:78-79
+            if (!failed) dopri5_enter(p, e.x, d_mg, insulin, e.lq, e.lf, hc, (double)e.t, r, nf);
+            cold.save(e, o, noise, hc);
+            fresh = false; boundary = false;
+        }
+        if (failed) { boundary = true; continue; }
+        const int rc = dopri5_attempt(p, e.x, d_mg, insulin, e.lq, e.lf, cold.f[Cold::HC * 64], (double)e.t + 1.0, r, nf);
+        failed = rc < 0;
+        boundary = rc != 0;
+    }
+    store_env(a, i, pid, e);
+    at(h_carry, i) = hc;
+    if (nfev) at(nfev, i) = nf;
+    if (failed) atomicOr(a.status, T1D_ST_SOLVER_FAILED);
+    const int q = s % H;
+    for (int k = 0, row = q ? H - q : 0; k < H; ++k) {         // the windows back in window order
+        at(rowv(c.cgm_hist, a.n, k), i) = col[row * 64];
+        at(rowv(c.ins_hist, a.n, k), i) = col[(H + row) * 64];
+        row = row + 1 == H ? 0 : row + 1;
+    }
+}
+
+// t1d_mlp_action: the policy alone, one lane per env -- the action the next step of a roll-out would ask for, from
+// batch.cgm (CGM[0]), rows 1 .. of cgm_hist, ins_hist, prev_meal, batch.t and start_minute.  Reads only; writes action [n].
+// Dynamic LDS: cols * 64 words for each wave, the lane's column in window order (head 0).
+template <typename T>
+__global__ __launch_bounds__(T1D_POLICY_THREADS) void mlp_action_kernel(const KArgs<T> a, const MlpArgs<T> c, T* action)
+{
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    __builtin_assume(i < (1u << 28));          // host guarantees n <= 2^28: i * sizeof(T) fits a 32-bit voffset
+    if ((int64_t)i >= a.n) return;
+    T* const col = (T*)t1d_dyn_lds + (threadIdx.x >> 6) * (c.cols * 64) + (threadIdx.x & 63u);
+    const int H = c.history;
+    col[0] = at(a.cgm, i);
+    for (int k = 1; k < H; ++k) col[k * 64] = at(rowv(c.cgm_hist, a.n, k), i);
+    for (int k = 0; k < H; ++k) col[(H + k) * 64] = at(rowv(c.ins_hist, a.n, k), i);
+    const int start = c.start_minute ? (int)at(c.start_minute, i) : 0;
+    const T prev_meal = at(c.prev_meal, i);
+    const int t = at(a.t, i);
+    action[i] = mlp_action(c, mlp_wave_weights(c, i), col, col + 2 * H * 64, 0, prev_meal, start + t);
 }
 
 } // namespace t1d

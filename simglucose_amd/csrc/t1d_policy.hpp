@@ -117,6 +117,51 @@ __device__ __forceinline__ T mlp_layers(const MlpArgs<T>& c, const __attribute__
     return y;
 }
 
+// The F = 2 H + 3 features of a step, in the order of include/t1d.h, into buf (the rows behind the lane's two windows).
+// col: the lane's column; head: the ring row of CGM[0] / INS[-1] (wave-uniform in mlp_rollout_kernel, per lane where the
+// lanes of a wave are in different steps); clock: start_minute + t at the start of the step.
+template <typename T>
+__device__ __forceinline__ void mlp_features(const MlpArgs<T>& c, const T* col, T* buf, int head, T prev_meal, int clock)
+{
+    const int H = c.history;
+    for (int k = 0, r = head; k < H; ++k) {
+        buf[k * 64] = (col[r * 64] - c.cgm_mean) * c.cgm_scale;
+        buf[(H + k) * 64] = col[(H + r) * 64] * c.ins_scale;
+        r = r + 1 == H ? 0 : r + 1;
+    }
+    buf[2 * H * 64] = prev_meal * c.cho_scale;
+    int m = clock % 1440;
+    m = m < 0 ? m + 1440 : m;
+    T sn, cs;
+    mlp_time_of_day(m, sn, cs);
+    buf[(2 * H + 1) * 64] = sn; buf[(2 * H + 2) * 64] = cs;
+}
+
+// the basal the policy asks for, from the last layer's output (plus the exploration term, where there is one)
+template <typename T>
+__device__ __forceinline__ T mlp_output(const MlpArgs<T>& c, T y)
+{
+    return fma(c.out_scale, c.out_act == 0 ? y : mlp_logistic(y), c.out_bias);
+}
+
+// features -> layers -> output function: the action of one step.  Every kernel that evaluates the policy calls this (or its
+// three parts, where something goes in between), so that they all give the same word for the same windows, clock and weights.
+template <typename T>
+__device__ __forceinline__ T mlp_action(const MlpArgs<T>& c, const __attribute__((address_space(4))) T* w, const T* col, T* buf,
+                                        int head, T prev_meal, int clock)
+{
+    mlp_features(c, col, buf, head, prev_meal, clock);
+    return mlp_output(c, mlp_layers(c, w, buf, 2 * c.history + 3));
+}
+
+// the weight set of the wave of env i: a scalar base, whatever the compiler can prove about the lane index
+template <typename T>
+__device__ __forceinline__ const __attribute__((address_space(4))) T* mlp_wave_weights(const MlpArgs<T>& c, unsigned i)
+{
+    const unsigned wave0 = __builtin_amdgcn_readfirstlane(i & ~63u);
+    return (const __attribute__((address_space(4))) T*)(c.params + (size_t)(wave0 / c.envs_per_policy) * (size_t)c.n_params);
+}
+
 // rollout_body (t1d_kernels.hpp) with the policy in place of the two hand-written controllers.  col: the lane's column.
 template <int VARIANT, typename T, typename P, typename PR = NoProp>
 __device__ __forceinline__ void mlp_rollout_body(const KArgs<T>& a, const MlpArgs<T>& c, P& p, unsigned i, uint32_t pid, Env<T>& e,
@@ -126,9 +171,7 @@ __device__ __forceinline__ void mlp_rollout_body(const KArgs<T>& a, const MlpArg
     typedef const __attribute__((address_space(4))) T* WPtr;
     const int H = c.history;
     T* const buf = col + 2 * H * 64;
-    // the wave's weight set: a scalar base, whatever the compiler can prove about the lane index
-    const unsigned wave0 = __builtin_amdgcn_readfirstlane(i & ~63u);
-    const WPtr w = (WPtr)(c.params + (size_t)(wave0 / c.envs_per_policy) * (size_t)c.n_params);
+    const WPtr w = mlp_wave_weights(c, i);
     T obs = at(a.cgm, i);
     col[0] = obs;                                               // CGM[0] is the observation the step starts from
     for (int k = 1; k < H; ++k) col[k * 64] = at(rowv(c.cgm_hist, a.n, k), i);
@@ -143,22 +186,7 @@ __device__ __forceinline__ void mlp_rollout_body(const KArgs<T>& a, const MlpArg
     T cgm_before = T(0);                        // CGM of the step before the last one, once two steps have run
 #pragma unroll 1
     for (int s = 0; s < c.n_steps; ++s) {
-        // the features, in the order of include/t1d.h
-        for (int k = 0, r = head; k < H; ++k) {
-            buf[k * 64] = (col[r * 64] - c.cgm_mean) * c.cgm_scale;
-            buf[(H + k) * 64] = col[(H + r) * 64] * c.ins_scale;
-            r = r + 1 == H ? 0 : r + 1;
-        }
-        buf[2 * H * 64] = prev_meal * c.cho_scale;
-        {
-            int m = (start + e.t) % 1440;
-            m = m < 0 ? m + 1440 : m;
-            T sn, cs;
-            mlp_time_of_day(m, sn, cs);
-            buf[(2 * H + 1) * 64] = sn; buf[(2 * H + 2) * 64] = cs;
-        }
-        const T y = mlp_layers(c, w, buf, 2 * H + 3);
-        const T u = fma(c.out_scale, c.out_act == 0 ? y : mlp_logistic(y), c.out_bias);
+        const T u = mlp_action(c, w, col, buf, head, prev_meal, start + e.t);
         o = step_body<MATH, T, P, true, PR, VariantInfo<VARIANT>::tiered>(a, p, i, e, u, T(0), true, pr);
         obs = o.cgm;
         prev_meal = o.meal;
@@ -301,20 +329,7 @@ __device__ __forceinline__ void mlp_collect_body(const KArgs<T>& a, const MlpArg
 #pragma unroll 1
     for (int s = 0; s < c.n_steps; ++s) {
         const int64_t trow = (c.trace_row + s) * a.n + i;
-        // the features, in the order of include/t1d.h
-        for (int k = 0, q = head; k < H; ++k) {
-            buf[k * 64] = (col[q * 64] - c.cgm_mean) * c.cgm_scale;
-            buf[(H + k) * 64] = col[(H + q) * 64] * c.ins_scale;
-            q = q + 1 == H ? 0 : q + 1;
-        }
-        buf[2 * H * 64] = prev_meal * c.cho_scale;
-        {
-            int m = (start + e.t) % 1440;
-            m = m < 0 ? m + 1440 : m;
-            T sn, cs;
-            mlp_time_of_day(m, sn, cs);
-            buf[(2 * H + 1) * 64] = sn; buf[(2 * H + 2) * 64] = cs;
-        }
+        mlp_features(c, col, buf, head, prev_meal, start + e.t);
         if (g.feat_trace)
             for (int j = 0; j < F; ++j) g.feat_trace[((c.trace_row + s) * F + j) * a.n + i] = buf[j * 64];
         T y = mlp_layers(c, w, buf, F);
@@ -323,7 +338,7 @@ __device__ __forceinline__ void mlp_collect_body(const KArgs<T>& a, const MlpArg
             eps = (T)philox_pair(g.explore_seed, (uint64_t)(a.env_offset + i), ep, (uint32_t)e.t).x;
             y = fma(sg, eps, y);
         }
-        const T u = fma(c.out_scale, c.out_act == 0 ? y : mlp_logistic(y), c.out_bias);
+        const T u = mlp_output(c, y);
         rp = e.prev_risk;
         o = step_body<MATH, T, P, true, PR, VariantInfo<VARIANT>::tiered>(a, p, i, e, u, T(0), true, pr);
         // the step's reward and done, as write_outputs forms them

@@ -1,0 +1,389 @@
+"""Exact-mode roll-outs under the in-kernel MLP policy on the GPU (BatchedT1DSimEnv.rollout_mlp_dopri5 ->
+t1d_rollout_mlp_dopri5, csrc/t1d_dopri5.hpp) and the policy alone (policy_action -> t1d_mlp_action): bit for bit the step()
+loop driven by policy_action, independent of the other envs of the batch, pinned to rollout_pid_dopri5 and to the oracle's
+DOPRI5 on the recorded actions, the top of the policy's range, the argument checks and a solver failure.
+
+All cases: Dexcom (3-minute steps), host normals and explicit meal tables."""
+import ctypes as C
+import math
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+ST = 3                       # Dexcom
+START = 360                  # the time-of-day features: every episode starts at 06:00
+STATE = ("x", "t", "cgm", "bg", "reward", "last_cgm", "prev_risk", "planned", "h_carry")      # test_gpu_dopri5_rollout.py::STATE
+POLICY_STATE = ("cgm_hist", "ins_hist", "prev_meal")
+TRACE = ("bg", "cgm", "cho", "insulin", "action")
+
+
+def _torch():
+    import torch
+    assert torch.cuda.is_available()
+    return torch
+
+
+def _inputs(n, K, seed=3):
+    """per-env inputs that do not depend on the env's index in a batch: patient row, host normals, a meal table"""
+    rs = np.random.RandomState(seed)
+    pid = np.arange(n) % 30
+    z = rs.randn(1 + 10 * (2 + K * ST // 150), n)
+    mt = np.sort(rs.choice(np.arange(2, max(8, K * ST - 2)), size=(n, 4)), axis=1).T.copy()      # [4][n], ascending
+    for j in range(1, 4):                                            # at most one entry per minute
+        mt[j] = np.maximum(mt[j], mt[j - 1] + 1)
+    ma = rs.uniform(15.0, 90.0, size=(4, n))
+    return pid, z, mt.astype(np.int64), ma
+
+
+def _env(pid, z, mt, ma, cols=None, exact=True, **kw):
+    torch = _torch()
+    from simglucose_amd.batch_env import BatchedT1DSimEnv
+    if cols is not None:
+        pid, z, mt, ma = pid[cols], z[:, cols], mt[:, cols], ma[:, cols]
+    e = BatchedT1DSimEnv(patient=pid, sensor="Dexcom", noise="host", normals=z, integrator="dopri5" if exact else None, **kw)
+    e.set_meals(torch.as_tensor(mt), torch.as_tensor(ma))
+    e.start_minute = torch.full((e.n,), START, dtype=torch.int32, device=e.device)
+    e.reset()
+    return e
+
+
+def _policy(history=4, widths=(16, 1), n_policies=1, seed=0, hidden="tanh", output="logistic", **kw):
+    torch = _torch()
+    from simglucose_amd.controller.mlp_ctrller import MLPController
+    g = torch.Generator().manual_seed(seed)
+    layers, n_in = [], 2 * history + 3
+    for w in widths:
+        layers.append((torch.randn(n_policies, w, n_in, generator=g, dtype=torch.float64) / math.sqrt(n_in),
+                       0.1 * torch.randn(n_policies, w, generator=g, dtype=torch.float64)))
+        n_in = w
+    # the logistic output spans [0, 0.06] U/min, about four times a basal rate and far below the pump's 0.5 U/min
+    kw.setdefault("out_scale", 0.06)
+    return MLPController(layers, history=history, hidden=hidden, output=output, **kw)
+
+
+def _step_loop(e, pol, K):
+    """A: one launch per step, the action from policy_action between the launches -> policy state, trace rows, summed nfev"""
+    torch = _torch()
+    st = e.new_policy_state(pol)
+    zero = torch.zeros(e.n, dtype=e.dtype, device=e.device)
+    rows = {k: [] for k in TRACE}
+    nf = torch.zeros(e.n, dtype=torch.int64, device=e.device)
+    for _ in range(K):
+        u = e.policy_action(pol, st)
+        e.step(u, zero)
+        pol.shift(st["cgm_hist"], st["ins_hist"], e.cgm, e.insulin)
+        st["prev_meal"] = e.meal.clone()
+        nf += e.nfev
+        for key, t in (("bg", e.bg), ("cgm", e.cgm), ("cho", e.meal), ("insulin", e.insulin), ("action", u)):
+            rows[key].append(t.clone())
+    return st, {k: torch.stack(v) for k, v in rows.items()}, nf
+
+
+def _rollout(e, pol, chunks, **kw):
+    """the roll-out in calls of the given lengths -> policy state, trace, summed nfev"""
+    torch = _torch()
+    tr = e.new_trace(sum(chunks), columns=TRACE)
+    st = None
+    nf = torch.zeros(e.n, dtype=torch.int64, device=e.device)
+    for ch in chunks:
+        st = e.rollout_mlp_dopri5(ch, pol, policy_state=st, trace=tr, **kw)
+        nf += e.nfev
+    return st, tr, nf
+
+
+def _same(a, b, keys=STATE, sl=slice(None)):
+    torch = _torch()
+    for k in keys:
+        assert torch.equal(getattr(a, k)[..., sl], getattr(b, k)), k
+
+
+def _same_dicts(a, b, keys, sl=slice(None)):
+    torch = _torch()
+    for k in keys:
+        assert torch.equal(a[k][..., sl], b[k]), k
+
+
+def _meals_and_moving_actions(rows):
+    assert bool((rows["cho"] > 0).any())
+    assert float(rows["action"].std(dim=0).max()) > 0            # the action trace is not constant
+
+
+# ---------------------------------------------------------------------------------------------------------- 1
+def test_rollout_equals_step_loop_bit_for_bit():
+    """In A the 64 envs of a wave are in the same step in every launch, in B .. D each lane is wherever its own step sizes
+    have taken it and evaluates the network on its own: every word must still be equal, however the roll-out is cut."""
+    torch = _torch()
+    n, K = 192, 60
+    inp = _inputs(n, K)
+    pol = _policy(n_policies=3, seed=1)                              # three weight sets of 64 envs
+    ea = _env(*inp)
+    sa, rows, nfa = _step_loop(ea, pol, K)
+    _meals_and_moving_actions(rows)
+    assert float(rows["insulin"].min()) < float(rows["insulin"].max()) < 0.4     # the pump is not saturated everywhere
+    for chunks, kw in (((1, 9, 50), {}), ((K,), {"max_minutes_per_launch": 10 ** 6}), ((K,), {"max_minutes_per_launch": 30})):
+        e = _env(*inp)
+        st, tr, nf = _rollout(e, pol, chunks, **kw)
+        _same(ea, e)
+        _same_dicts(sa, st, POLICY_STATE)
+        for k in TRACE:
+            assert torch.equal(rows[k], tr[k][1:]), (k, chunks, kw)
+        assert torch.equal(nfa, nf)
+        assert e.sync() == 0
+        assert int(e.t.min()) == K * ST == int(e.t.max())
+    assert ea.sync() == 0
+
+
+# ---------------------------------------------------------------------------------------------------------- 2
+@pytest.mark.parametrize("dtype_name", ["float64", "float32"])
+def test_policy_action_is_the_rollouts_policy(dtype_name):
+    """On a fixed-step env, a few steps into an episode: policy_action gives the word rollout_mlp(1) records as its action
+    from the same state, and leaves the env and the policy state as they were."""
+    torch = _torch()
+    dtype = getattr(torch, dtype_name)
+    n, K = 128, 8
+    e = _env(*_inputs(n, K, seed=5), exact=False, dtype=dtype)
+    pol = _policy(n_policies=2, seed=2)
+    tr = e.new_trace(K, columns=TRACE)
+    st = e.rollout_mlp(K - 1, pol, trace=tr)
+    keys = ("state", "istate", "ar_e", "cgm", "bg", "reward", "done", "meal", "insulin")
+    before = {k: getattr(e, k).clone() for k in keys}
+    before.update({k: v.clone() for k, v in st.items()})
+    u = e.policy_action(pol, st)
+    assert e.sync() == 0
+    for k in keys:
+        assert torch.equal(getattr(e, k), before[k]), k
+    for k in st:
+        assert torch.equal(st[k], before[k]), k
+    e.rollout_mlp(1, pol, policy_state=st, trace=tr)
+    assert e.sync() == 0
+    assert u.dtype == dtype and u.shape == (n,)
+    assert torch.equal(u, tr["action"][K])
+    _meals_and_moving_actions({k: tr[k][1:] for k in TRACE})
+
+
+# ---------------------------------------------------------------------------------------------------------- 3
+def test_the_same_envs_in_different_company():
+    """Envs 0 .. 63 of a 128-env batch, and as a batch of their own with the same weight set: the per-lane ring head, and
+    lanes that never exchange data."""
+    torch = _torch()
+    from simglucose_amd.controller.mlp_ctrller import MLPController
+    n, K = 128, 40
+    inp = _inputs(n, K, seed=11)
+    pol = _policy(n_policies=2, seed=3, history=5)
+    one = MLPController([(W[:1], b[:1]) for W, b in zip(pol.W, pol.b)], history=pol.history, hidden=pol.hidden, output=pol.output,
+                        out_scale=pol.out_scale)
+    big, small = _env(*inp), _env(*inp, cols=np.arange(64))
+    sb, trb, nfb = _rollout(big, pol, (K,))
+    ss, trs, nfs = _rollout(small, one, (K,))
+    sl = slice(0, 64)
+    _same(big, small, sl=sl)
+    _same_dicts(sb, ss, POLICY_STATE, sl)
+    for k in TRACE:
+        assert torch.equal(trb[k][1:, sl], trs[k][1:]), k
+    assert torch.equal(nfb[sl], nfs)
+    assert not torch.equal(trb["action"][1:, :64], trb["action"][1:, 64:])
+    _meals_and_moving_actions({k: trs[k][1:] for k in TRACE})
+    assert big.sync() == 0 and small.sync() == 0
+
+
+# ---------------------------------------------------------------------------------------------------------- 4
+def test_one_weight_on_cgm0_is_rollout_pid_dopri5_bit_for_bit():
+    """A one-layer net with cgm_mean = target, cgm_scale = 1, weight P on CGM[0] and identity output asks for P (CGM - target):
+    acc = fma(P, x, 0) is the rounded product, every other fma adds an exact zero, and fma(1, y, 0) = y -- the word of
+    PIDController with I = D = 0, whose two other terms are exact zeros as well."""
+    torch = _torch()
+    from simglucose_amd.controller.mlp_ctrller import MLPController
+    n, K, P, target = 128, 40, 1.5e-4, 140.0
+    inp = _inputs(n, K, seed=7)
+    W = torch.zeros(1, 5, dtype=torch.float64); W[0, 0] = P
+    pol = MLPController([(W, torch.zeros(1))], history=1, output="identity", cgm_mean=target, cgm_scale=1.0)
+    a, b = _env(*inp), _env(*inp)
+    ta = a.new_trace(K)
+    ps = a.rollout_pid_dopri5(15, P, 0.0, 0.0, target=target, trace=ta)
+    nfa = a.nfev.long().clone()
+    a.rollout_pid_dopri5(K - 15, P, 0.0, 0.0, target=target, pid_state=ps, trace=ta)
+    nfa += a.nfev
+    _, tb, nfb = _rollout(b, pol, (15, K - 15))
+    assert a.sync() == 0 and b.sync() == 0
+    _same(a, b)
+    for k in ("bg", "cgm", "cho", "insulin"):
+        assert torch.equal(ta[k][1:], tb[k][1:]), k              # row 0: what reset() recorded (NaN for cho and insulin)
+    assert torch.equal(nfa, nfb)
+    _meals_and_moving_actions({k: tb[k][1:] for k in TRACE})
+    assert float(tb["insulin"][1:].max()) > 0
+
+
+# ---------------------------------------------------------------------------------------------------------- 5
+def test_integration_is_the_oracles_on_the_recorded_actions():
+    """Every env replayed on the oracle's dopri, open loop, with the device's own action trace as basal (through the pump)
+    and the kernel's normals and meals: BG / CGM at the bars of test_large_batch_sampled_envs_match_oracle
+    (tests/test_gpu_dopri5_rollout.py) for such a replay.  The actions against the host's ordered forward pass in fp64 on
+    the features rebuilt from the recorded cgm / insulin / cho rows: within out_scale * 1e-13, the bound of
+    test_top_of_the_range (tests/test_gpu_policy.py) for the same comparison.  Teacher-forced on both sides, so a
+    pump-quantiser tie cannot turn a 1-ulp tanh difference into a diverged closed loop: no env is left out."""
+    torch = _torch()
+    from oracle import t1d_oracle as O
+    n, K = 64, 40
+    pid, z, mt, ma = _inputs(n, K, seed=13)
+    pol = _policy(seed=4)
+    e = _env(pid, z, mt, ma)
+    obs0 = e.cgm.clone()
+    _, tr, _ = _rollout(e, pol, (K,))
+    assert e.sync() == 0
+    _meals_and_moving_actions({k: tr[k][1:] for k in TRACE})
+    cho = np.zeros((K * ST, n))
+    for j in range(n):
+        for tt, aa in zip(mt[:, j], ma[:, j]):
+            if 0 <= tt < K * ST:
+                cho[tt, j] = aa
+    orc = O.OracleEnv(pid, sensor="Dexcom", normals=z, integrator="dopri")
+    orc.reset()
+    act = tr["action"][1:].cpu().numpy()
+    bg_d, cgm_d = tr["bg"][1:].cpu().numpy(), tr["cgm"][1:].cpu().numpy()
+    worst = np.zeros(n)
+    for k in range(K):
+        o = orc.step(act[k], None, cho[k * ST:(k + 1) * ST])
+        worst = np.maximum(worst, np.maximum(np.abs(bg_d[k] - o["bg"]), np.abs(cgm_d[k] - o["cgm"])))
+    print("\n%.1f %% of %d traces within 1e-8 of the oracle, max %.3e mg/dL" % (100 * (worst <= 1e-8).mean(), n, worst.max()))
+    assert (worst <= 1e-8).mean() >= 0.95 and worst.max() <= 5e-4, ((worst <= 1e-8).mean(), worst.max())
+    cgm_hist = obs0.unsqueeze(0).repeat(pol.history, 1)
+    ins_hist = torch.zeros(pol.history, n, dtype=torch.float64, device=e.device)
+    meal = torch.zeros(n, dtype=torch.float64, device=e.device)
+    worst_u = 0.0
+    for s in range(1, K + 1):
+        feat = pol.features(cgm_hist, ins_hist, meal, e.start_minute + ST * (s - 1))
+        want = pol.forward(feat, ordered=True)
+        worst_u = max(worst_u, float((tr["action"][s] - want).abs().max()))
+        pol.shift(cgm_hist, ins_hist, tr["cgm"][s], tr["insulin"][s])
+        meal = tr["cho"][s]
+    print("max |action - host forward| = %.3e U/min" % worst_u)
+    assert worst_u <= pol.out_scale * 1e-13
+
+
+# ---------------------------------------------------------------------------------------------------------- 6
+def test_top_of_the_range():
+    """H = 12, widths (32, 32, 32, 1), relu: 56 rows per lane, 28 KiB of columns per wave beside the solver's words -- the
+    LDS fit and the choice of the workgroup's size.  Accepted, and the step loop bit for bit."""
+    torch = _torch()
+    n, K = 128, 12
+    inp = _inputs(n, K, seed=17)
+    pol = _policy(history=12, widths=(32, 32, 32, 1), hidden="relu", seed=7)
+    ea, eb = _env(*inp), _env(*inp)
+    sa, rows, nfa = _step_loop(ea, pol, K)
+    sb, tr, nfb = _rollout(eb, pol, (5, 7))
+    _same(ea, eb)
+    _same_dicts(sa, sb, POLICY_STATE)
+    for k in TRACE:
+        assert torch.equal(rows[k], tr[k][1:]), k
+    assert torch.equal(nfa, nfb)
+    _meals_and_moving_actions(rows)
+    assert ea.sync() == 0 and eb.sync() == 0
+
+
+# ---------------------------------------------------------------------------------------------------------- 7
+def test_rejections_change_nothing():
+    torch = _torch()
+    from simglucose_amd import _lib
+    n, K = 128, 4
+    inp = _inputs(n, K, seed=19)
+    e = _env(*inp)
+    pol = _policy(history=3, widths=(8, 1))
+    e.rollout_mlp_dopri5(2, pol)                                 # a state with a carried step in it
+    st = e.new_policy_state(pol)
+    params = pol.flat_params().to(e.device)
+    before = {k: getattr(e, k).clone() for k in STATE}
+    before.update({k: v.clone() for k, v in st.items()})
+    assert bool((before["h_carry"] != 0).all())
+    L = e._L
+
+    def good(env=e, state=st, prm=params):
+        p = _lib.Mlp()
+        pol.fill_struct(p)
+        p.n_policies, p.envs_per_policy, p.n_params = 1, env.n, prm.shape[1]
+        p.params = prm.data_ptr()
+        for k in POLICY_STATE:
+            setattr(p, k, state[k].data_ptr())
+        return p
+
+    def call(p, env=e, h_carry=e.h_carry, n_steps=2):
+        with torch.cuda.device(env.device):
+            return L.t1d_rollout_mlp_dopri5(env._ctx, C.byref(env._b), C.byref(p), C.c_void_p(h_carry.data_ptr() if h_carry is not None else None),
+                                            None, n_steps, ST, env._stream())
+    bad = []
+    for field, value in (("n_policies", 2), ("envs_per_policy", 64), ("history", 13), ("cgm_hist", None), ("ins_hist", None)):
+        p = good(); setattr(p, field, value); bad.append((field, value, p))
+    for field, value, p in bad:
+        assert call(p) == -1, (field, value)
+        assert L.t1d_last_error().startswith(b"t1d_rollout_mlp_dopri5: "), (field, value)
+    assert call(good(), h_carry=None) == -1 and b"h_carry" in L.t1d_last_error()
+    assert call(good(), n_steps=0) == -1 and b"n_steps" in L.t1d_last_error()
+    # an fp32 batch
+    f32 = _env(*inp, exact=False, dtype=torch.float32)
+    st32 = f32.new_policy_state(pol)
+    prm32 = params.float()
+    keys32 = ("state", "istate", "cgm", "bg")
+    before32 = {k: getattr(f32, k).clone() for k in keys32}
+    hc32 = torch.full((n,), 0.25, dtype=torch.float64, device=f32.device)
+    assert call(good(f32, st32, prm32), env=f32, h_carry=hc32) == -1 and b"fp64" in L.t1d_last_error()
+    assert f32.sync() == 0
+    for k in keys32:
+        assert torch.equal(getattr(f32, k), before32[k]), k
+    assert bool((hc32 == 0.25).all())
+    assert torch.equal(st32["cgm_hist"], f32.cgm.unsqueeze(0).repeat(3, 1)) and not bool(st32["ins_hist"].any())
+    # a fixed-step env through the Python method
+    with pytest.raises(_lib.T1DError, match="dopri5"):
+        f32.rollout_mlp_dopri5(2, pol)
+    with pytest.raises(_lib.T1DError, match="rollout_mlp_dopri5"):
+        e.rollout_mlp(2, pol)
+    with pytest.raises(ValueError):
+        e.rollout_mlp_dopri5(0, pol)
+    with pytest.raises(ValueError):
+        e.rollout_mlp_dopri5(2, _policy(n_policies=4))           # 128 envs / 4 = 32 per policy
+    assert e.sync() == 0
+    for k in STATE:
+        assert torch.equal(getattr(e, k), before[k]), k
+    for k in st:
+        assert torch.equal(st[k], before[k]), k
+    assert call(good()) == 0 and e.sync() == 0                   # and the good one runs
+    assert int(e.t.min()) == 4 * ST
+
+
+# ---------------------------------------------------------------------------------------------------------- 8
+def test_solver_failure_inside_a_rollout():
+    """The stiff-patient construction of test_gpu_dopri5_rollout.py::test_solver_failure_inside_a_rollout (kabs x 1e6: DOPRI5
+    would need far more than its 500 steps in a minute), one env in three: the status bit, a finite state, and the normal
+    envs as if the stiff ones were not there."""
+    torch = _torch()
+    from simglucose_amd import _lib
+    from simglucose_amd.batch_env import BatchedT1DSimEnv
+    from oracle import t1d_oracle as O
+    names, tab = O.patient_table()
+    rows = tab[[names.index("adult#001"), names.index("adult#001")]].copy()
+    rows[1, O.IDX["kabs"]] *= 1e6
+    n, K = 192, 10
+    pid = (np.arange(n) % 3 == 1).astype(np.int64)
+    normal = np.where(pid == 0)[0]                               # 128 envs, spread over all three waves
+    rs = np.random.RandomState(9)
+    z = rs.randn(21, n)
+    mt = np.stack([np.full(n, 4), np.full(n, 17)]).astype(np.int64)
+    ma = rs.uniform(30.0, 60.0, size=(2, n))
+    pol = _policy(seed=5)
+    out = []
+    for cols in (np.arange(n), normal):
+        e = BatchedT1DSimEnv(patient=pid[cols], patient_table=rows, sensor="Dexcom", noise="host", normals=z[:, cols], integrator="dopri5")
+        e.set_meals(torch.as_tensor(mt[:, cols]), torch.as_tensor(ma[:, cols]))
+        e.reset()
+        tr = e.new_trace(K, columns=TRACE)
+        e.rollout_mlp_dopri5(K, pol, trace=tr)
+        out.append((e, tr, e.sync(raise_on_status=False)))
+    (ea, tra, sta), (eb, trb, stb) = out
+    assert sta & _lib.T1D_ST_SOLVER_FAILED and not (sta & _lib.T1D_ST_NONFINITE), sta
+    assert stb == 0
+    assert bool(torch.isfinite(ea.x).all()) and int(ea.t.min()) == K * ST == int(ea.t.max())
+    nidx = torch.as_tensor(normal, device=ea.device)
+    for k in TRACE:
+        assert torch.equal(tra[k][1:, nidx], trb[k][1:]), k
+    for k in STATE:
+        assert torch.equal(getattr(ea, k)[..., nidx], getattr(eb, k)), k
+    _meals_and_moving_actions({k: trb[k][1:] for k in TRACE})

@@ -1,0 +1,42 @@
+"""CPU suite: the surface of the exact-mode policy roll-out (t1d_rollout_mlp_dopri5) and of the policy alone
+(t1d_mlp_action) -- declared, bound, exported, and refusing a NULL context without a device."""
+import ctypes as C
+import os
+import re
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ("t1d_rollout_mlp_dopri5", "t1d_mlp_action")
+
+
+def test_symbols_are_declared_bound_and_exported():
+    from simglucose_amd import _lib
+    src = open(os.path.join(ROOT, "include", "t1d.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    L = _lib.lib()
+    for name in NEW:
+        assert re.search(r"\bint\s+%s\s*\(" % name, src), name
+        assert name in _lib.EXPORTS, name
+        assert hasattr(L, name), name
+        assert getattr(L, name).argtypes is not None and getattr(L, name).restype is C.c_int, name
+    assert L.t1d_abi_version() == 4                             # functions only: the structs did not move
+
+
+def test_null_ctx_is_refused_without_a_device():
+    from simglucose_amd import _lib
+    L = _lib.lib()
+    b, m = _lib.Batch(), _lib.Mlp()
+    assert L.t1d_rollout_mlp_dopri5(None, C.byref(b), C.byref(m), None, None, 1, 3, None) == -1
+    assert L.t1d_last_error().startswith(b"t1d_rollout_mlp_dopri5") and b"ctx is NULL" in L.t1d_last_error()
+    assert L.t1d_mlp_action(None, C.byref(b), C.byref(m), None, None) == -1
+    assert L.t1d_last_error().startswith(b"t1d_mlp_action") and b"ctx is NULL" in L.t1d_last_error()
+
+
+def test_env_has_both_methods():
+    import inspect
+    from simglucose_amd.batch_env import BatchedT1DSimEnv
+    sig = inspect.signature(BatchedT1DSimEnv.rollout_mlp_dopri5)
+    assert list(sig.parameters)[1:] == ["n_steps", "policy", "policy_state", "stats", "trace", "max_minutes_per_launch"]
+    assert sig.parameters["max_minutes_per_launch"].default == 240
+    assert list(inspect.signature(BatchedT1DSimEnv.policy_action).parameters)[1:] == ["policy", "policy_state"]
+    # rollout_mlp still refuses exact-mode envs, and now says where to go
+    assert "rollout_mlp_dopri5" in inspect.getsource(BatchedT1DSimEnv._no_dopri5_rollout)
