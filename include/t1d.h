@@ -29,6 +29,7 @@
  *                       reward and done of every step kept, reset() when done comes back true
  *                       (simglucose/envs/simglucose_gym_env.py:39-73)
  *   t1d_rollout_pid_dopri5, t1d_rollout_bb_dopri5 <- the two loops with scipy's dopri5 itself (the exact mode)
+ *   t1d_rollout_mlp_dopri5, t1d_collect_mlp_dopri5 <- t1d_rollout_mlp and t1d_collect_mlp in the exact mode
  *   t1d_random_meals <- RandomScenario.create_scenario  simglucose/simulation/scenario_gen.py:33-60
  *   t1d_restart_done <- the reset() a gym training loop calls when done comes back true (T1DSimEnv.reset + a new
  *                       RandomScenario and start hour, simglucose/envs/simglucose_gym_env.py:58-73), for the finished envs only
@@ -291,7 +292,8 @@ typedef struct t1d_collect {
                                  step comes back done starts its next episode before its next step, exactly as
                                  t1d_restart_done would */
     int32_t reserved;         /* 0 */
-    const t1d_restart* restart;   /* on_done = T1D_COLLECT_RESTART: as for t1d_restart_done (h_carry must be NULL); else ignored */
+    const t1d_restart* restart;   /* on_done = T1D_COLLECT_RESTART: as for t1d_restart_done (h_carry must be NULL; in
+                                     t1d_collect_mlp_dopri5 NULL or the call's h_carry); else ignored */
     /* optional histories, rows as the traces of t1d_mlp (row mlp.trace_row + s = step s of this call), NULL to skip */
     void* reward_trace;       /* [rows][n]    risk_diff of every step: what batch.reward would hold after that step */
     uint8_t* done_trace;      /* [rows][n]    batch.done of every step */
@@ -434,8 +436,8 @@ int t1d_rollout_mlp(t1d_ctx* ctx, const t1d_batch* batch, const t1d_mlp* mlp, in
  *   that were done) leave, bit for bit; with sigma NULL and T1D_COLLECT_CONTINUE, what t1d_rollout_mlp leaves.
  * T1D_E_INVALID before anything is launched, nothing changed: whatever t1d_rollout_mlp rejects; with T1D_COLLECT_RESTART
  *   whatever t1d_restart_done rejects (a NULL batch.episode, tables that are not the batch's own, n_meals != 6 (days + 1), host
- *   normals, x0_override), a NULL restart and a non-NULL restart->h_carry (the exact mode has no collector); on_done outside
- *   {0, 1}; reserved != 0. */
+ *   normals, x0_override), a NULL restart and a non-NULL restart->h_carry (the exact mode's collector is
+ *   t1d_collect_mlp_dopri5); on_done outside {0, 1}; reserved != 0. */
 int t1d_collect_mlp(t1d_ctx* ctx, const t1d_batch* batch, const t1d_mlp* mlp, const t1d_collect* collect, int n_steps,
                     int minutes, int n_sub, void* stream);
 
@@ -478,6 +480,40 @@ int t1d_rollout_bb_dopri5(t1d_ctx* ctx, const t1d_batch* b, const t1d_bb* bb, do
  * t1d_rollout_pid_dopri5 rejects (an fp32 batch, a NULL h_carry, dense cho, n_steps < 1, minutes out of range). */
 int t1d_rollout_mlp_dopri5(t1d_ctx* ctx, const t1d_batch* b, const t1d_mlp* mlp, double* h_carry, int32_t* nfev,
                            int n_steps, int minutes, void* hip_stream);
+
+/* t1d_collect_mlp in the exact mode: the gym training loop of simglucose/envs/simglucose_gym_env.py:39-73 (the action sampled
+ * around the network's output, reward and done of every step, reset() when done comes back true) with the integrator of
+ * t1d_step_dopri5, scipy's dopri5 as the reference drives it (t1dpatient.py:110-113,276).  All of t1d_collect_mlp's
+ * contract -- action, draw, traces, on_done, the accumulators -- on the solver and the free-running lanes of
+ * t1d_rollout_mlp_dopri5: ONE launch in which every env walks through its minutes, its steps and its episodes at its own pace.
+ * Action: y, z = fma(sigma[p], eps, y) (z = y with sigma NULL), basal = fma(out_scale, g(z), out_bias), bolus = 0, as in
+ *   t1d_collect_mlp; y is the word t1d_rollout_mlp_dopri5 and t1d_mlp_action compute.  action_trace holds that basal.
+ * Draw: eps = philox_pair(explore_seed, env_offset + i, k, m).x with k the env's batch.episode counter at that step (0 with a
+ *   NULL array) and m its t at the start of the step, exactly as in t1d_collect_mlp; no draw and eps_trace = 0 with sigma NULL.
+ * Traces: row trace_row + s of reward_trace, done_trace, eps_trace, feat_trace and of the five t1d_mlp columns describes step
+ *   s of this call for every env, although the envs reach step s at different moments of the launch.
+ * on_done = T1D_COLLECT_RESTART: after a step with done != 0 the env goes through what t1d_restart_done(mask = done,
+ *   reset_outputs as given) does to it with restart->h_carry = h_carry: its predicted solver step becomes 0, so the first
+ *   minute of the new episode probes, as the reference's solver does after T1DPatient.reset.  Its policy state becomes that of a
+ *   fresh reset (every cgm_hist row the new first observation, ins_hist = 0, prev_meal = 0), the time-of-day features come
+ *   from the new start_minute and the draw key from the new episode counter.  The episode accumulators of t1d_restart advance
+ *   every step for every env.  restart->h_carry must be NULL or h_carry: either way the env's entry of h_carry is zeroed.
+ * After the call batch.*, the env state, h_carry, mlp.cgm_hist / ins_hist / prev_meal, the accumulators, the restart outputs
+ *   and every trace row are what n_steps x (t1d_rollout_mlp_dopri5(1), t1d_restart_done with h_carry, the reset of the policy
+ *   state of the envs that were done) leave, bit for bit, whatever the other envs of the batch do and wherever the call is
+ *   cut; with sigma NULL and T1D_COLLECT_CONTINUE, what t1d_rollout_mlp_dopri5 leaves.  nfev: the RHS evaluations of each env
+ *   over the whole call, across its episodes.
+ * An env whose solver gives up raises T1D_ST_SOLVER_FAILED and keeps its last accepted state while its clock, meals and noise
+ *   go on, as in t1d_rollout_mlp_dopri5 -- until the end of the call or of its episode: a restarted env starts its new episode
+ *   with a working solver.  The bit-for-bit equivalence above is for envs whose solver does not fail (the loop of one-step
+ *   calls tries the solver again in every step).
+ * T1D_E_INVALID before anything is launched, nothing changed: whatever t1d_rollout_mlp_dopri5 rejects (an fp32 batch, a NULL
+ *   h_carry, dense cho, n_steps < 1, minutes out of range, a bad policy); whatever t1d_collect_mlp rejects of collect (on_done
+ *   outside {0, 1}, reserved != 0, with T1D_COLLECT_RESTART a NULL restart, a NULL batch.episode, tables that are not the
+ *   batch's own, n_meals != 6 (days + 1), host normals, x0_override); a restart->h_carry that is neither NULL nor h_carry;
+ *   with T1D_COLLECT_RESTART an mlp.start_minute that is neither NULL nor restart->start_minute, as in t1d_collect_mlp. */
+int t1d_collect_mlp_dopri5(t1d_ctx* ctx, const t1d_batch* b, const t1d_mlp* mlp, const t1d_collect* collect,
+                           double* h_carry, int32_t* nfev, int n_steps, int minutes, void* hip_stream);
 
 /* The policy of t1d_mlp alone, one lane per env: action[i] (device [n], the batch's dtype) = the basal, before the pump,
  * that the next step of t1d_rollout_mlp / t1d_rollout_mlp_dopri5 would ask for env i -- from batch.cgm (CGM[0]), rows 1 ..

@@ -452,8 +452,9 @@ class BatchedT1DSimEnv:
 
     def _no_dopri5_rollout(self):
         if self.integrator == "dopri5":
-            raise _lib.T1DError("rollout_pid / rollout_bb / rollout_mlp run the fixed-step kernels, which have no DOPRI5 path: an env with "
-                                "integrator='dopri5' takes rollout_pid_dopri5 / rollout_bb_dopri5 / rollout_mlp_dopri5")
+            raise _lib.T1DError("rollout_pid / rollout_bb / rollout_mlp / collect_mlp run the fixed-step kernels, which have no DOPRI5 "
+                                "path: an env with integrator='dopri5' takes rollout_pid_dopri5 / rollout_bb_dopri5 / "
+                                "rollout_mlp_dopri5 / collect_mlp_dopri5")
 
     def rollout_pid(self, n_steps, P, I, D, target=140.0, pid_state=None, stats=None, trace=None):
         """n_steps closed-loop PID steps in one launch (PIDController.policy + env.step per step).
@@ -654,13 +655,37 @@ class BatchedT1DSimEnv:
         """
         self._no_dopri5_rollout()
         n_steps = int(n_steps)
+        policy_state, p, g, keep = self._collect_structs("collect_mlp", n_steps, policy, sigma, explore_seed, policy_state, stats,
+                                                         trace, on_done, days, terminal_obs, episode_stats, reset_outputs)
+        if g.restart:
+            g.restart.contents.h_carry = None
+        self._set_trace(p, trace, n_steps)
+        self._b.cho = None
+        self._b.flags = self._flags0
+        clock, self._clock = self._clock, None
+        ep0 = self.episode.clone() if (on_done == "restart" and self._hist is not None) else None
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.t1d_collect_mlp(self._ctx, C.byref(self._b), C.byref(p), C.byref(g), n_steps,
+                                               self.minutes_per_step, self.n_sub, self._stream()))
+        if clock is not None and on_done != "restart":         # restarted envs no longer share the clock
+            self._clock = clock + n_steps * self.minutes_per_step
+        self._keep = keep
+        self._hist_after_rollout()
+        if ep0 is not None:                                     # CGM_hist of an env whose last step ended its episode = [sample #0]
+            self._hist_restart((self.episode != ep0) & (self.t == 0))
+        return policy_state
+
+    def _collect_structs(self, who, n_steps, policy, sigma, explore_seed, policy_state, stats, trace, on_done, days,
+                         terminal_obs, episode_stats, reset_outputs):
+        """the t1d_mlp and t1d_collect of collect_mlp / collect_mlp_dopri5, checked; the five t1d_mlp trace columns are left to
+        _set_trace.  -> (policy_state, t1d_mlp, t1d_collect, what must stay alive until the launch has run)"""
         if n_steps < 1:
             raise ValueError("n_steps must be at least 1")
         if on_done not in ("continue", "restart"):
             raise ValueError("on_done must be 'continue' or 'restart'")
         npol = int(policy.n_policies)
         if self.n % npol or (self.n // npol) % 64:
-            raise ValueError("collect_mlp: %d envs do not split into %d policies of a multiple of 64 envs each" % (self.n, npol))
+            raise ValueError("%s: %d envs do not split into %d policies of a multiple of 64 envs each" % (who, self.n, npol))
         if policy_state is None:
             policy_state = self.new_policy_state(policy)
         H = int(policy.history)
@@ -677,9 +702,8 @@ class BatchedT1DSimEnv:
         r = None
         if on_done == "restart":
             if self.noise == "host" or self.normals is not None:
-                raise _lib.T1DError("collect_mlp(on_done='restart') draws every episode on the device: not available with host normals")
-            r = self._restart_struct(int(days), terminal_obs, episode_stats or {}, reset_outputs, "collect_mlp")
-            r.h_carry = None
+                raise _lib.T1DError("%s(on_done='restart') draws every episode on the device: not available with host normals" % who)
+            r = self._restart_struct(int(days), terminal_obs, episode_stats or {}, reset_outputs, who)
             g.restart = C.pointer(r)
             self._b.x0_override = None
         params = policy.device_params(self.device, self.dtype)
@@ -701,25 +725,36 @@ class BatchedT1DSimEnv:
                 if t.dtype != dt or tuple(t.shape[1:]) != shape or t.shape[0] < int(trace.get("row", 0)) + n_steps or not t.is_contiguous():
                     raise ValueError("trace['%s'] must be contiguous [rows >= row + n_steps, %s] of %s" % (k, ", ".join(map(str, shape)), dt))
                 setattr(g, f, t.data_ptr())
-        self._set_trace(p, trace, n_steps)
-        self._b.cho = None
-        self._b.flags = self._flags0
-        clock, self._clock = self._clock, None
+        return policy_state, p, g, (params, policy_state, sigma, r, terminal_obs, episode_stats, trace)
+
+    def collect_mlp_dopri5(self, n_steps, policy, sigma=None, explore_seed=None, policy_state=None, stats=None, trace=None,
+                           on_done="continue", days=2, terminal_obs=None, episode_stats=None, reset_outputs=False,
+                           max_minutes_per_launch=240):
+        """collect_mlp in the exact mode (t1d_collect_mlp_dopri5, include/t1d.h): trajectories for a policy-gradient trainer
+        with scipy's dopri5, every env at its own pace inside a launch -- through its minutes, its steps and, with
+        on_done="restart", its episodes.  Arguments, draws, trace columns and return value as collect_mlp; h_carry, nfev (summed
+        over the whole call, across an env's episodes) and max_minutes_per_launch as in rollout_pid_dopri5 -- the cut changes no
+        result.  A restarted env's h_carry becomes 0: its first minute probes the step size, as after reset().  The result is
+        that of a loop of rollout_mlp_dopri5(1), restart_done() and the torch reset of policy_state, bit for bit (for envs
+        whose solver does not give up); with sigma=None and on_done="continue" it is rollout_mlp_dopri5's.  Measurements:
+        profiles/collect (exact_collect_bench.json)."""
+        self._need_dopri5("collect_mlp_dopri5")
+        n_steps = int(n_steps)
+        policy_state, p, g, keep = self._collect_structs("collect_mlp_dopri5", n_steps, policy, sigma, explore_seed, policy_state,
+                                                         stats, trace, on_done, days, terminal_obs, episode_stats, reset_outputs)
         ep0 = self.episode.clone() if (on_done == "restart" and self._hist is not None) else None
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.t1d_collect_mlp(self._ctx, C.byref(self._b), C.byref(p), C.byref(g), n_steps,
-                                               self.minutes_per_step, self.n_sub, self._stream()))
-        if clock is not None and on_done != "restart":         # restarted envs no longer share the clock
-            self._clock = clock + n_steps * self.minutes_per_step
-        self._keep = (params, policy_state, sigma, r, terminal_obs, episode_stats, trace)
-        self._hist_after_rollout()
+        self._rollout_dopri5(self._L.t1d_collect_mlp_dopri5, p, n_steps, trace, max_minutes_per_launch, extra=(C.byref(g),))
+        if on_done == "restart":                                # restarted envs no longer share the clock
+            self._clock = None
+        self._keep = keep
         if ep0 is not None:                                     # CGM_hist of an env whose last step ended its episode = [sample #0]
             self._hist_restart((self.episode != ep0) & (self.t == 0))
         return policy_state
 
-    def _rollout_dopri5(self, fn, p, n_steps, trace, max_minutes_per_launch):
+    def _rollout_dopri5(self, fn, p, n_steps, trace, max_minutes_per_launch, extra=()):
         """the launches of one exact-mode roll-out: whole steps, at most max_minutes_per_launch simulated minutes each.
-        State, controller state and h_carry carry over, so the cut changes no result; nfev is summed over the launches."""
+        State, controller state and h_carry carry over, so the cut changes no result; nfev is summed over the launches.
+        extra: the arguments between the controller's struct and h_carry (the collector's t1d_collect)."""
         n_steps = int(n_steps)
         if n_steps < 1:
             raise ValueError("n_steps must be at least 1")
@@ -733,7 +768,7 @@ class BatchedT1DSimEnv:
             done = 0
             while done < n_steps:
                 k = min(per, n_steps - done)
-                _lib.check(fn(self._ctx, C.byref(self._b), C.byref(p), C.c_void_p(self.h_carry.data_ptr()),
+                _lib.check(fn(self._ctx, C.byref(self._b), C.byref(p), *extra, C.c_void_p(self.h_carry.data_ptr()),
                               C.c_void_p(self.nfev.data_ptr()), k, self.minutes_per_step, self._stream()))
                 if total is not None:
                     total += self.nfev

@@ -1131,21 +1131,33 @@ static int run_collect_mlp(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* m, con
     return launch(c, b, p, minutes, n_sub, s, mlp_collect_fn<T>(p.variant), ma, ga, ra);
 }
 
+// what a t1d_collect must be, for both collectors; needs no device.  h_carry: the exact mode's array (NULL: fixed-step)
+static int check_collect(const char* who, const t1d_batch* b, const t1d_collect* g, const double* h_carry)
+{
+    const std::string w = std::string(who) + ": ";
+    if (!g) return fail(T1D_E_INVALID, w + "collect is NULL");
+    if (g->on_done != T1D_COLLECT_CONTINUE && g->on_done != T1D_COLLECT_RESTART)
+        return fail(T1D_E_INVALID, w + "on_done must be T1D_COLLECT_CONTINUE or T1D_COLLECT_RESTART");
+    if (g->reserved != 0) return fail(T1D_E_INVALID, w + "reserved must be 0");
+    if (g->on_done == T1D_COLLECT_RESTART) {
+        if (!g->restart) return fail(T1D_E_INVALID, w + "on_done = T1D_COLLECT_RESTART needs restart");
+        int rr = check_restart(who, b, g->restart);
+        if (rr) return rr;
+        if (!h_carry && g->restart->h_carry)
+            return fail(T1D_E_INVALID, w + "restart.h_carry must be NULL (the exact mode's collector is t1d_collect_mlp_dopri5)");
+        if (h_carry && g->restart->h_carry && g->restart->h_carry != h_carry)
+            return fail(T1D_E_INVALID, w + "restart.h_carry must be NULL or the call's h_carry");
+    }
+    return T1D_OK;
+}
+
 extern "C" int t1d_collect_mlp(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_collect* g, int n_steps, int minutes,
                                int n_sub, void* stream)
 {
     const char* who = "t1d_collect_mlp";
-    if (!g) return fail(T1D_E_INVALID, "t1d_collect_mlp: collect is NULL");
-    if (g->on_done != T1D_COLLECT_CONTINUE && g->on_done != T1D_COLLECT_RESTART)
-        return fail(T1D_E_INVALID, "t1d_collect_mlp: on_done must be T1D_COLLECT_CONTINUE or T1D_COLLECT_RESTART");
-    if (g->reserved != 0) return fail(T1D_E_INVALID, "t1d_collect_mlp: reserved must be 0");
-    if (g->on_done == T1D_COLLECT_RESTART) {
-        if (!g->restart) return fail(T1D_E_INVALID, "t1d_collect_mlp: on_done = T1D_COLLECT_RESTART needs restart");
-        int rr = check_restart(who, b, g->restart);
-        if (rr) return rr;
-        if (g->restart->h_carry) return fail(T1D_E_INVALID, "t1d_collect_mlp: restart.h_carry must be NULL (the exact mode has no collector)");
-    }
-    int rc = check_batch(who, c, b, false);
+    int rc = check_collect(who, b, g, nullptr);
+    if (rc) return rc;
+    rc = check_batch(who, c, b, false);
     if (rc) return rc;
     if (b->cho) return fail(T1D_E_INVALID, "t1d_collect_mlp: dense cho is not supported, use the meal table");
     if (n_steps < 1) return fail(T1D_E_INVALID, "t1d_collect_mlp: n_steps < 1");
@@ -1162,6 +1174,45 @@ extern "C" int t1d_collect_mlp(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* ml
     rc = p.f64 ? run_collect_mlp<double>(c, b, mlp, g, p, cols, n_steps, minutes, n_sub, s)
                : run_collect_mlp<float>(c, b, mlp, g, p, cols, n_steps, minutes, n_sub, s);
     if (rc) return rc;
+    T1D_HIP(hipGetLastError());
+    return T1D_OK;
+}
+
+// The exact mode's collector (dopri5_mlp_collect_kernel, t1d_dopri5.hpp): the checks of t1d_rollout_mlp_dopri5 and of
+// t1d_collect_mlp, then one launch with the LDS pieces and the workgroup of t1d_rollout_mlp_dopri5.
+extern "C" int t1d_collect_mlp_dopri5(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_collect* g, double* h_carry,
+                                      int32_t* nfev, int n_steps, int minutes, void* stream)
+{
+    const char* who = "t1d_collect_mlp_dopri5";
+    int rc = check_rollout_dopri5(who, c, b, h_carry, n_steps, minutes);
+    if (rc) return rc;
+    rc = check_collect(who, b, g, h_carry);
+    if (rc) return rc;
+    int cols = 0;
+    rc = check_mlp(who, b, mlp, &cols);
+    if (rc) return rc;
+    // a restarted env's time-of-day features follow its new start: the array the restart writes is the one the policy reads
+    if (g->on_done == T1D_COLLECT_RESTART && mlp->start_minute && mlp->start_minute != g->restart->start_minute)
+        return fail(T1D_E_INVALID, std::string(who) + ": mlp.start_minute must be restart.start_minute (or NULL)");
+    MlpArgs<double> ma = make_mlp<double>(mlp, n_steps);
+    ma.cols = cols;
+    CollectArgs<double> ga;
+    ga.explore_seed = g->explore_seed; ga.sigma = (const double*)g->sigma; ga.on_done = g->on_done;
+    ga.reward_trace = (double*)g->reward_trace; ga.done_trace = g->done_trace; ga.eps_trace = (double*)g->eps_trace;
+    ga.feat_trace = (double*)g->feat_trace;
+    ga.slots = c->d_slots;
+    RestartArgs<double> ra = g->on_done == T1D_COLLECT_RESTART ? make_restart<double>(g->restart) : RestartArgs<double>{};
+    if (g->on_done == T1D_COLLECT_RESTART) ra.h_carry = h_carry;      // the env's predicted step is part of what restarts
+    const size_t fixed = (size_t)kRawPars * kMaxPatients * sizeof(double) + 256;           // static LDS
+    const size_t per_wave = (size_t)kRollColdWaveBytes + (size_t)cols * 64 * sizeof(double);
+    int threads = kBlock;
+    while (threads > 64 && fixed + per_wave * (threads / 64) > (size_t)c->lds_per_block) threads /= 2;
+    if (fixed + per_wave * (threads / 64) > (size_t)c->lds_per_block)
+        return fail(T1D_E_INVALID, std::string(who) + ": the patient rows leave no room in LDS for one wave of this policy");
+    const size_t dyn = per_wave * (threads / 64);
+    T1D_HIP(allow_lds(c, (const void*)dopri5_mlp_collect_kernel, dyn));
+    hipLaunchKernelGGL(dopri5_mlp_collect_kernel, dim3((unsigned)((b->n + threads - 1) / threads)), dim3(threads), dyn, (hipStream_t)stream,
+                       make_args<double>(c, b, minutes, 1), ma, ga, ra, (const double*)c->d_raw64, h_carry, nfev);
     T1D_HIP(hipGetLastError());
     return T1D_OK;
 }

@@ -465,6 +465,67 @@ __global__ __launch_bounds__(kBlock, 1) void dopri5_rollout_kernel(const KArgs<d
 // whose layout does not depend on the workgroup's size.
 constexpr int kRollColdWaveBytes = (int)(RollColdT<64>::NF * sizeof(double) + RollColdT<64>::NI * sizeof(int)) * 64;
 
+// dopri5_mlp_rollout_kernel's pieces outside the solver loop as functions, for dopri5_mlp_collect_kernel (below): the same
+// lines, inlined there.  The roll-out kernel keeps them written out: calling these from it changed its register
+// allocation and cost it 0.5 - 0.7 % at 1 Mi envs when tried (profiles/policy/kernel_resources_collect_exact.txt).  A
+// change to one of them is a change to the matching lines of that kernel.
+// The lane's piece of dynamic LDS: Cold's doubles, Cold's ints, then the columns.
+struct MlpLaneLds { RollColdT<64> cold; double* col; };
+__device__ __forceinline__ MlpLaneLds dopri5_mlp_lane_lds(const MlpArgs<double>& c)
+{
+    typedef RollColdT<64> Cold;
+    unsigned char* const piece = t1d_dyn_lds + (threadIdx.x >> 6) * (kRollColdWaveBytes + c.cols * 64 * (int)sizeof(double));
+    const unsigned lane = threadIdx.x & 63u;
+    return MlpLaneLds{Cold{(double*)piece + lane, (int*)(piece + Cold::NF * 64 * sizeof(double)) + lane},
+                      (double*)(piece + kRollColdWaveBytes) + lane};
+}
+
+// the windows into the lane's column, in window order (head 0)
+__device__ __forceinline__ void dopri5_mlp_load_windows(const KArgs<double>& a, const MlpArgs<double>& c, unsigned i, double* col)
+{
+    const int H = c.history;
+    col[0] = at(a.cgm, i);                                      // CGM[0] is the observation the first step starts from
+    for (int k = 1; k < H; ++k) col[k * 64] = at(rowv(c.cgm_hist, a.n, k), i);
+    for (int k = 0; k < H; ++k) col[(H + k) * 64] = at(rowv(c.ins_hist, a.n, k), i);
+}
+
+// the windows back in window order after s steps of this launch
+__device__ __forceinline__ void dopri5_mlp_store_windows(const KArgs<double>& a, const MlpArgs<double>& c, unsigned i, const double* col, int s)
+{
+    const int H = c.history, q = s % H;
+    for (int k = 0, row = q ? H - q : 0; k < H; ++k) {
+        at(rowv(c.cgm_hist, a.n, k), i) = col[row * 64];
+        at(rowv(c.ins_hist, a.n, k), i) = col[(H + row) * 64];
+        row = row + 1 == H ? 0 : row + 1;
+    }
+}
+
+// a step closes: its four trace columns (row tr), prev_meal and the statistics
+__device__ __forceinline__ void dopri5_mlp_step_words(const MlpArgs<double>& c, unsigned i, int64_t tr, const StepOut<double>& o)
+{
+    if (c.bg_trace) c.bg_trace[tr] = o.bg;
+    if (c.cgm_trace) c.cgm_trace[tr] = o.cgm;
+    if (c.cho_trace) c.cho_trace[tr] = o.meal;
+    if (c.ins_trace) c.ins_trace[tr] = o.ins;
+    at(c.prev_meal, i) = o.meal;
+    if (c.sum_risk) { double l, h, rk; risk_index1<0>(o.bg, l, h, rk); at(c.sum_risk, i) = at(c.sum_risk, i) + rk; }
+    if (c.min_bg) { const double v = at(c.min_bg, i); at(c.min_bg, i) = o.bg < v ? o.bg : v; }
+    if (c.max_bg) { const double v = at(c.max_bg, i); at(c.max_bg, i) = o.bg > v ? o.bg : v; }
+    if (c.n_low) at(c.n_low, i) = at(c.n_low, i) + (o.bg < 70.0);
+    if (c.n_high) at(c.n_high, i) = at(c.n_high, i) + (o.bg > 180.0);
+}
+
+// a step opens with the action u: the pump, as step_body with a bolus of 0 given (env.py:51-52); the insulin of its minutes
+__device__ __forceinline__ double dopri5_mlp_pump(const KArgs<double>& a, double u)
+{
+    double q_basal = u, q_bolus = 0.0;
+    if (!(a.flags & T1D_BATCH_NO_PUMP)) {
+        q_basal = pump_quantise(u, a.pump.inc_basal, a.pump.min_basal, a.pump.max_basal);
+        q_bolus = pump_quantise(0.0, a.pump.inc_bolus, a.pump.min_bolus, a.pump.max_bolus);
+    }
+    return q_basal + q_bolus;
+}
+
 __global__ __launch_bounds__(kBlock, 1) void dopri5_mlp_rollout_kernel(const KArgs<double> a, const MlpArgs<double> c,
                                                                        const double* __restrict__ raw, double* h_carry, int32_t* nfev)
 {
@@ -564,6 +625,141 @@ __global__ __launch_bounds__(kBlock, 1) void dopri5_mlp_rollout_kernel(const KAr
         at(rowv(c.ins_hist, a.n, k), i) = col[(H + row) * 64];
         row = row + 1 == H ? 0 : row + 1;
     }
+}
+
+// ---- trajectories for a policy-gradient trainer in the exact mode (t1d_collect_mlp_dopri5) ------------------------------
+// dopri5_mlp_rollout_kernel with the collector's work (mlp_collect_body, t1d_policy.hpp) in the boundary block; solver
+// loop, Cold words, columns, per-lane ring head and weights are that kernel's, line for line.  A kernel of its own: the
+// roll-out keeps its registers and its arguments.
+//   a step opens    mlp_action in its three parts: the features (to feat_trace), the layers, then the draw -- keyed by the
+//                   env's global id, its episode counter and its clock, as in mlp_collect_body -- and sigma on the last
+//                   layer's output, the output function, the pump.  eps_trace is written here: the step that uses the
+//                   draw is the row it describes, and nothing of it has to wait for the step's end.
+//   a step closes   reward and done as write_outputs forms them, to their trace rows; ep_return / ep_length advance.
+//   done, restart   the lane writes its state as the end of the launch would, runs collect_restart -- t1d_restart_done for
+//                   this env alone, on the words in memory -- loads the new episode, fills its window rows with the new
+//                   first observation, and starts again with prev_meal = 0, a carried step of 0 (the first minute probes)
+//                   and a working solver.  The ring head stays where the lane's step counter puts it: every row holds the
+//                   same word.  start_minute, the episode counter and prev_meal are read from memory where a step opens, so
+//                   the new ones are picked up there; the Cold words are saved again at the end of the boundary block.
+//                   The other lanes of the wave are inactive meanwhile and go on with their step attempts afterwards.
+// Nothing of the policy, the draw or the restart is in a register across dopri5_attempt.
+__global__ __launch_bounds__(kBlock, 1) void dopri5_mlp_collect_kernel(const KArgs<double> a, const MlpArgs<double> c,
+                                                                       const CollectArgs<double> g, const RestartArgs<double> ra,
+                                                                       const double* __restrict__ raw, double* h_carry, int32_t* nfev)
+{
+    typedef RollColdT<64> Cold;
+    typedef const __attribute__((address_space(4))) double* WPtr;
+    __shared__ double lds[kRawPars * kMaxPatients];
+    for (int j = threadIdx.x; j < kRawPars * kMaxPatients; j += blockDim.x) lds[j] = raw[j];
+    __syncthreads();
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    __builtin_assume(i < (1u << 28));          // host guarantees n <= 2^28: i * sizeof(T) fits a 32-bit voffset
+    if ((int64_t)i >= a.n) return;             // n is a multiple of 64: whole waves leave
+    const MlpLaneLds piece = dopri5_mlp_lane_lds(c);
+    const Cold cold = piece.cold;
+    double* const col = piece.col;
+    const int H = c.history, F = 2 * H + 3;
+    double* const buf = col + 2 * H * 64;
+    const uint32_t meta = at(a.meta, i);
+    const uint32_t pid = T1D_META_PID(meta);
+    Env<double> e;
+    load_env(a, i, meta, e);
+    const ParsRaw p{lds, (int)pid};
+    NoDerivedPars nop;
+    const double div = double(a.minutes);
+    dopri5_mlp_load_windows(a, c, i, col);
+    double hc = at(h_carry, i), noise = 0.0, insulin = 0.0, d_mg = 0.0;
+    StepOut<double> o{0.0, 0.0, 0.0, 0.0};
+    Dopri5Run r{};
+    int nf = 0, m = 0, s = 0;
+    bool due = false, failed = false, boundary = true, fresh = true;
+    bool stored = false;                        // the last step ended the episode: the state in memory is the new episode's
+    cold.save(e, o, noise, hc);
+    for (;;) {
+        if (boundary) {
+            cold.load(e, o, noise, hc);
+            if (!fresh) {
+                e.t += 1;
+                const double gsub = e.x[12] / p(T1D_P_VG);                                    // t1dpatient.py:217-218
+                const double cgm = measure_apply(a, e, gsub, noise, due);                     // env.py:62
+                o.bg += gsub / div; o.cgm += cgm / div;                                       // env.py:80-81
+                if (++m == a.minutes) {                  // the step is complete: what t1d_step_dopri5 leaves, then the collector's own
+                    const double rp = e.prev_risk;
+                    write_outputs<0>(a, i, e, o, rp);
+                    const double reward = rp - e.prev_risk;     // the word write_outputs stored in batch.reward
+                    const bool fin = o.bg < 70.0 || o.bg > 350.0;
+                    const int64_t tr = (c.trace_row + s) * a.n + i;
+                    if (g.reward_trace) g.reward_trace[tr] = reward;
+                    if (g.done_trace) g.done_trace[tr] = fin ? 1 : 0;
+                    dopri5_mlp_step_words(c, i, tr, o);
+                    m = 0; ++s;
+                    const int q = s % H, head = q ? H - q : 0;  // the oldest row becomes the newest
+                    col[head * 64] = o.cgm; col[(H + head) * 64] = o.ins;
+                    if (g.on_done) {
+                        if (fin) {
+                            // the finished step is in memory (write_outputs); the state follows, and the restart works on those words
+                            store_env(a, i, pid, e);
+                            if (failed) atomicOr(a.status, T1D_ST_SOLVER_FAILED);
+                            collect_restart<double>(a, ra, g.slots, i);
+                            load_env(a, i, at(a.meta, i), e);
+                            const double first = at(a.cgm, i);  // the new episode's first observation
+                            for (int k = 0; k < H; ++k) { col[k * 64] = first; col[(H + k) * 64] = 0.0; }
+                            at(c.prev_meal, i) = 0.0;
+                            hc = 0.0;                           // T1DPatient.reset builds the solver afresh: the first minute probes
+                            failed = false;
+                            stored = s == c.n_steps;
+                        } else if (ra.ep_return) {              // restart_front's accumulators for an env that goes on
+                            const double sum = at(ra.ep_return, i) + reward;
+                            const int len = at(ra.ep_length, i) + 1;
+                            at(ra.ep_return, i) = sum; at(ra.ep_length, i) = len;
+                        }
+                    }
+                }
+            }
+            if (s == c.n_steps) break;
+            if (m == 0) {                                // a step opens: features, layers, the draw, the output function, the pump
+                const int q = s % H, head = q ? H - q : 0;
+                const int start = c.start_minute ? (int)at(c.start_minute, i) : 0;
+                const double prev_meal = at(c.prev_meal, i);
+                const unsigned wave0 = __builtin_amdgcn_readfirstlane(i & ~63u);
+                const unsigned pol = wave0 / c.envs_per_policy;
+                const WPtr w = (WPtr)(c.params + (size_t)pol * (size_t)c.n_params);
+                mlp_features(c, col, buf, head, prev_meal, start + e.t);
+                if (g.feat_trace)
+                    for (int j = 0; j < F; ++j) g.feat_trace[((c.trace_row + s) * F + j) * a.n + i] = buf[j * 64];
+                double y = mlp_layers(c, w, buf, F);
+                double eps = 0.0;
+                if (g.sigma) {                           // wave-uniform
+                    const uint32_t ep = a.episode ? at(a.episode, i) : 0u;
+                    eps = (double)philox_pair(g.explore_seed, (uint64_t)(a.env_offset + i), ep, (uint32_t)e.t).x;
+                    y = fma((double)((WPtr)g.sigma)[pol], eps, y);
+                }
+                if (g.eps_trace) g.eps_trace[(c.trace_row + s) * a.n + i] = eps;
+                const double u = mlp_output(c, y);
+                if (c.act_trace) c.act_trace[(c.trace_row + s) * a.n + i] = u;
+                insulin = dopri5_mlp_pump(a, u);
+                o = StepOut<double>{0.0, 0.0, 0.0, 0.0};
+            }
+            const double meal = meal_lookup(a, i, e);                                         // env.py:50
+            noise = measure_noise<true>(a, i, e, due);
+            const MinuteIn<double> u = eat_minute<0, double>(nop, e.x, meal, insulin, e.planned, e.lq, e.lf, e.eating);
+            d_mg = u.d_mg;
+            o.meal += meal / div; o.ins += insulin / div;                                     // env.py:78-79
+            if (!failed) dopri5_enter(p, e.x, d_mg, insulin, e.lq, e.lf, hc, (double)e.t, r, nf);
+            cold.save(e, o, noise, hc);
+            fresh = false; boundary = false;
+        }
+        if (failed) { boundary = true; continue; }
+        const int rc = dopri5_attempt(p, e.x, d_mg, insulin, e.lq, e.lf, cold.f[Cold::HC * 64], (double)e.t + 1.0, r, nf);
+        failed = rc < 0;
+        boundary = rc != 0;
+    }
+    if (!stored) store_env(a, i, pid, e);
+    at(h_carry, i) = hc;
+    if (nfev) at(nfev, i) = nf;
+    if (failed) atomicOr(a.status, T1D_ST_SOLVER_FAILED);
+    dopri5_mlp_store_windows(a, c, i, col, s);
 }
 
 // t1d_mlp_action: the policy alone, one lane per env -- the action the next step of a roll-out would ask for, from
