@@ -301,6 +301,19 @@ typedef struct t1d_collect {
     void* feat_trace;         /* [rows][F][n] the F = 2 H + 3 features the network was given, in t1d_mlp's order */
 } t1d_collect;
 
+/* t1d_mlp_grad: the rows of a collected batch the network is evaluated on again, and what comes back.  Floating arrays
+ * have the call's dtype. */
+typedef struct t1d_mlp_batch {
+    int64_t n_rows;           /* K >= 1 */
+    const void* feat;         /* [n_rows][F][n]: rows of t1d_collect.feat_trace, F = 2 H + 3 */
+    const void* coef;         /* [n_rows][n] or NULL: dL/dy of every sample */
+    void* y;                  /* [n_rows][n] or NULL: the last layer's output, before noise and output function */
+    void* grad;               /* [n_policies][n_params] or NULL (needs coef), OVERWRITTEN: grad[p][q] = sum over the rows s and
+                                 the envs i of policy p of coef[s][i] * d y[s][i] / d params[p][q] */
+    void* workspace;          /* device scratch for the partial sums; needed with grad */
+    int64_t workspace_bytes;  /* at least t1d_mlp_grad_workspace() */
+} t1d_mlp_batch;
+
 int t1d_abi_version(void);
 const char* t1d_last_error(void);
 
@@ -523,6 +536,33 @@ int t1d_collect_mlp_dopri5(t1d_ctx* ctx, const t1d_batch* b, const t1d_mlp* mlp,
  * policy: action, t1d_step / t1d_step_dopri5, then cgm_hist and ins_hist shifted by one row with batch.cgm / batch.insulin
  * in row 0 and prev_meal = batch.meal.  T1D_E_INVALID: a NULL action, and whatever t1d_rollout_mlp rejects of the policy. */
 int t1d_mlp_action(t1d_ctx* ctx, const t1d_batch* b, const t1d_mlp* mlp, void* action, void* hip_stream);
+
+/* The network of t1d_mlp on recorded features, and the gradient of a scalar loss with respect to its weights: the other half of
+ * a policy-gradient iteration after t1d_collect_mlp / t1d_collect_mlp_dopri5.  No ctx; nothing is allocated, the call only
+ * enqueues work on the stream.  fp64 and fp32.  Of t1d_mlp only history, n_layers, width, hidden_act, n_policies,
+ * envs_per_policy, n_params and params are used; the state arrays, the feature scales, the traces and the output function are
+ * ignored and may be NULL or 0 (noise and output function come after y and stay the host's business, like log_prob).
+ *   y      y[s][i] = the last layer's output for the features feat[s][.][i] under the weights of policy i / envs_per_policy,
+ *          computed by the device code of the roll-outs and collectors (bias first, then one fma per input, ascending, the
+ *          same tanh): with sigma = NULL, out_act = T1D_MLP_IDENTITY, out_scale = 1 and out_bias = 0, y[s] equals
+ *          action_trace[s] of the collect call that produced feat[s], bit for bit.  In general it is the word that call
+ *          added sigma * eps to.
+ *   grad   the vector-Jacobian product above, by back-propagation through the recomputed activations a: the derivative of
+ *          tanh is 1 - a^2, that of relu is (a > 0 ? 1 : 0).  A NaN row (row 0 of a trace buffer) is the caller's to skip.
+ *          Deterministic and portable: no floating-point atomics, and the summation order depends only on (n,
+ *          envs_per_policy, n_rows, dtype, widths) -- not on the CU count, the grid, a context option or timing; two calls
+ *          give identical bits.  The order: a tile is the 64 envs of one 64-env chunk of a policy in one row; the tiles of a
+ *          policy are numbered u = s * C + chunk, C = envs_per_policy / 64.  With T = max(1, ceil(n_policies * C * n_rows /
+ *          2048)), partial k of a policy covers tiles k T .. min((k + 1) T, C * n_rows) - 1 in ascending order; within a tile
+ *          parameter q adds coef-weighted terms of the samples (q + m) mod 64, m = 0 .. 63, each with one fma onto the
+ *          running partial, which starts at 0.  grad[p][q] = ((0 + partial 0) + partial 1) + ... in ascending k.
+ *   workspace  t1d_mlp_grad_workspace(mlp, dtype, n, n_rows) bytes (host only, mlp.params may be NULL; < 0 = invalid
+ *          arguments): n_policies * ceil(C * n_rows / T) * n_params words.  Nothing beyond them is written.
+ * T1D_E_INVALID before anything is launched and before the device is touched: whatever t1d_rollout_mlp rejects of the fields
+ * named above; n != n_policies * envs_per_policy or envs_per_policy % 64 != 0; n_rows < 1; a NULL feat; y and grad both NULL;
+ * grad without coef; grad with a NULL or too small workspace. */
+int64_t t1d_mlp_grad_workspace(const t1d_mlp* mlp, int dtype, int64_t n, int64_t n_rows);
+int t1d_mlp_grad(int hip_device, int dtype, int64_t n, const t1d_mlp* mlp, const t1d_mlp_batch* io, void* hip_stream);
 
 /* RandomScenario.create_scenario (simulation/scenario_gen.py:33-60) for n envs on the device: fills per-env
  * meal tables meal_time int32 [6 (days + 1)][n] (minutes since the episode start, ascending, unused =

@@ -9,7 +9,8 @@ _ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("T1D_LIB_PATH") or os.path.join(_PKG, "libt1d_hip.so")   # override: A/B builds only
 SOURCES = [os.path.join(_PKG, "csrc", "t1d_abi.hip"), os.path.join(_PKG, "csrc", "t1d_kernels.hpp"),
            os.path.join(_PKG, "csrc", "t1d_device.hpp"), os.path.join(_PKG, "csrc", "t1d_dopri5.hpp"),
-           os.path.join(_PKG, "csrc", "t1d_policy.hpp"), os.path.join(_ROOT, "include", "t1d.h")]
+           os.path.join(_PKG, "csrc", "t1d_policy.hpp"), os.path.join(_PKG, "csrc", "t1d_policy_grad.hpp"),
+           os.path.join(_ROOT, "include", "t1d.h")]
 
 T1D_F64, T1D_F32 = 0, 1
 T1D_ST_NORMALS_EXHAUSTED, T1D_ST_NONFINITE, T1D_ST_BAD_INDEX, T1D_ST_STALL = 1, 2, 4, 8
@@ -30,7 +31,8 @@ EXPORTS = ("t1d_abi_version", "t1d_last_error", "t1d_ctx_create", "t1d_ctx_set_o
            "t1d_step", "t1d_rollout_pid", "t1d_philox_normals", "t1d_sync", "t1d_split_tables",
            "t1d_rollout_bb", "t1d_random_meals", "t1d_outcome_stats", "t1d_model_rhs", "t1d_step_dopri5",
            "t1d_rollout_pid_dopri5", "t1d_rollout_bb_dopri5", "t1d_restart_done", "t1d_rollout_mlp",
-           "t1d_collect_mlp", "t1d_rollout_mlp_dopri5", "t1d_mlp_action", "t1d_collect_mlp_dopri5")
+           "t1d_collect_mlp", "t1d_rollout_mlp_dopri5", "t1d_mlp_action", "t1d_collect_mlp_dopri5",
+           "t1d_mlp_grad_workspace", "t1d_mlp_grad")
 
 
 class T1DError(RuntimeError):
@@ -105,6 +107,12 @@ class Collect(C.Structure):
                 ("eps_trace", C.c_void_p), ("feat_trace", C.c_void_p)]
 
 
+class MlpBatch(C.Structure):
+    """struct t1d_mlp_batch (include/t1d.h)"""
+    _fields_ = [("n_rows", C.c_int64), ("feat", C.c_void_p), ("coef", C.c_void_p), ("y", C.c_void_p), ("grad", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 def _stale():
     return not os.path.exists(LIB_PATH) or any(os.path.exists(s) and os.path.getmtime(s) > os.path.getmtime(LIB_PATH)
                                                for s in SOURCES)
@@ -177,6 +185,8 @@ def lib():
     L.t1d_rollout_mlp_dopri5.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), vp, vp, C.c_int, C.c_int, vp]
     L.t1d_collect_mlp_dopri5.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), C.POINTER(Collect), vp, vp, C.c_int, C.c_int, vp]
     L.t1d_mlp_action.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), vp, vp]
+    L.t1d_mlp_grad_workspace.argtypes = [C.POINTER(Mlp), C.c_int, i64, i64]
+    L.t1d_mlp_grad.argtypes = [C.c_int, C.c_int, i64, C.POINTER(Mlp), C.POINTER(MlpBatch), vp]
     L.t1d_restart_done.argtypes = [vp, C.POINTER(Batch), vp, C.POINTER(Restart), vp]
     L.t1d_random_meals.argtypes = [C.c_int, u64, i64, i64, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]
     L.t1d_outcome_stats.argtypes = [C.c_int, C.c_int, i64, i64, vp, C.POINTER(Outcome), vp]
@@ -187,6 +197,7 @@ def lib():
     for name in EXPORTS:
         if name not in ("t1d_last_error",):
             getattr(L, name).restype = C.c_int
+    L.t1d_mlp_grad_workspace.restype = i64
     if L.t1d_abi_version() != ABI_VERSION:
         raise T1DError("libt1d_hip.so ABI version mismatch")
     _lib = L

@@ -640,16 +640,20 @@ class BatchedT1DSimEnv:
         that finished there trace["cgm"][s] is the terminal observation, the new episode's first one shows in
         trace["features"][s + 1] and in env.cgm.  -> policy_state.
 
-        The PPO ratio from a collected batch, with the network evaluated again under autograd (pre() is the network
-        without output function, e.g. an nn.Sequential the controller was made from_torch of):
+        The PPO ratio from a collected batch, with the network evaluated again on the device by the collector's own code
+        (controller.mlp_pre_output: differentiable in the weights, no activations stored; at unchanged weights y_new is
+        y_old bit for bit and the ratio exactly 1):
 
+            from simglucose_amd.controller import mlp_pre_output
             tr = env.new_trace(K, columns=("reward", "done", "eps", "features"), history=pol.history)
             env.collect_mlp(K, pol, sigma=sig, trace=tr, on_done="restart")
             f, eps = tr["features"][1:], tr["eps"][1:]                    # [K, F, n], [K, n]
-            old = MLPController.log_prob(eps, sig)                         # log pi_old(a | s)
-            y_old = pre_old(f.transpose(1, 2)).squeeze(-1)                 # [K, n], no grad
-            y_new = pre_new(f.transpose(1, 2)).squeeze(-1)                 # the net being trained
+            old_params = pol.device_params(env.device, env.dtype)          # [P, n_params], what the collector ran
+            new_params = old_params.clone().requires_grad_(True)           # the weights being trained
+            y_old = mlp_pre_output(old_params, f, pol)                     # [K, n], no grad
             z = y_old + sig * eps                                          # the pre-output sample that was acted on
+            old = MLPController.log_prob((z - y_old) / sig, sig)           # log pi_old(a | s), formed as `new` is
+            y_new = mlp_pre_output(new_params, f, pol)
             new = MLPController.log_prob((z - y_new) / sig_new, sig_new)
             ratio = (new - old).exp()
         """

@@ -175,9 +175,10 @@ class MLPController(Controller):
         cgm_hist[1:] = cgm_hist[:-1].clone(); cgm_hist[0] = cgm
         ins_hist[1:] = ins_hist[:-1].clone(); ins_hist[0] = insulin
 
-    def forward(self, feat, ordered=False):
-        """feat [F, n] -> basal [n], U/min.  With P weight sets env i uses set i // (n // P).  ordered: accumulate bias first,
-        then input by input in ascending order, as the kernel does; otherwise torch.matmul."""
+    def pre_output(self, feat, ordered=False):
+        """feat [F, n] -> y [n]: the last layer's output, before the output function (forward without out_scale g(.) +
+        out_bias) -- the word collect_mlp adds sigma * eps to.  With P weight sets env i uses set i // (n // P).  ordered:
+        accumulate bias first, then input by input in ascending order, as the kernel does; otherwise torch.matmul."""
         P, n = self.n_policies, feat.shape[1]
         if n % P:
             raise ValueError("%d envs do not split into %d weight sets" % (n, P))
@@ -193,9 +194,57 @@ class MLPController(Controller):
                 x = torch.matmul(W, x) + b.unsqueeze(2)
             if k + 1 < len(self.W):
                 x = torch.tanh(x) if self.hidden == "tanh" else torch.relu(x)
-        y = x.reshape(n)
+        return x.reshape(n)
+
+    def forward(self, feat, ordered=False):
+        """feat [F, n] -> basal [n], U/min: out_scale g(pre_output(feat, ordered)) + out_bias."""
+        y = self.pre_output(feat, ordered)
         g = torch.sigmoid(y) if self.output == "logistic" else y
         return self.out_scale * g + self.out_bias
+
+    def grad_reference(self, feat_rows, coef, params=None, info=False):
+        """What t1d_mlp_grad (controller.mlp_pre_output's backward) computes, in plain torch and fp64 on the device of
+        feat_rows: feat_rows [K, F, n], coef [K, n] = dL/dy of every sample -> grad [P, n_params] in the layout of
+        flat_params(), grad[p][q] = sum over the K rows and the envs of policy p of coef * dy / dparams[p][q], by a manual
+        back-propagation (tanh' = 1 - a^2, relu' = a > 0) -- no autograd graph.  params: [P, n_params] to use instead of this
+        controller's weights (taken to fp64 as they are).  info=True: -> (grad, dict) with "scale" [P, n_params], S = sum of
+        |coef * dy / dparam| per parameter, the size a rounding error bound is stated in, and "min_abs_pre", the smallest
+        |pre-activation| of any hidden unit (how far a relu net is from a kink)."""
+        K, F, n = feat_rows.shape
+        P = self.n_policies
+        if F != self.n_features or n % P or tuple(coef.shape) != (K, n):
+            raise ValueError("grad_reference: feat_rows [K, %d, n] and coef [K, n] with n a multiple of %d" % (self.n_features, P))
+        dev, f64 = feat_rows.device, torch.float64
+        if params is None:
+            Ws, bs = [W.to(dev, f64) for W in self.W], [b.to(dev, f64) for b in self.b]
+        else:
+            params = torch.as_tensor(params).detach().to(dev, f64).reshape(P, -1)
+            Ws, bs, n_in, at = [], [], F, 0
+            for w in self.widths:
+                Ws.append(params[:, at:at + w * n_in].reshape(P, w, n_in)); at += w * n_in
+                bs.append(params[:, at:at + w]); at += w
+                n_in = w
+        N = K * (n // P)                                                        # samples of one policy
+        x = feat_rows.detach().to(f64).reshape(K, F, P, n // P).permute(2, 1, 0, 3).reshape(P, F, N)
+        xs, min_pre = [], float("inf")
+        for k, (W, b) in enumerate(zip(Ws, bs)):
+            xs.append(x)
+            x = torch.matmul(W, x) + b.unsqueeze(2)
+            if k + 1 < len(Ws):
+                min_pre = min(min_pre, float(x.abs().min()))
+                x = torch.tanh(x) if self.hidden == "tanh" else torch.relu(x)
+        d = coef.detach().to(f64).reshape(K, P, n // P).permute(1, 0, 2).reshape(P, 1, N)
+        grads, scales = [None] * len(Ws), [None] * len(Ws)
+        for k in range(len(Ws) - 1, -1, -1):
+            grads[k] = torch.cat([torch.matmul(d, xs[k].transpose(1, 2)).reshape(P, -1), d.sum(2)], dim=1)
+            scales[k] = torch.cat([torch.matmul(d.abs(), xs[k].abs().transpose(1, 2)).reshape(P, -1), d.abs().sum(2)], dim=1)
+            if k:
+                a = xs[k]
+                d = torch.matmul(Ws[k].transpose(1, 2), d) * ((1.0 - a * a) if self.hidden == "tanh" else (a > 0).to(f64))
+        grad = torch.cat(grads, dim=1).contiguous()
+        if info:
+            return grad, {"scale": torch.cat(scales, dim=1).contiguous(), "min_abs_pre": min_pre}
+        return grad
 
     @staticmethod
     def log_prob(eps, sigma):

@@ -6,6 +6,7 @@
 #include "t1d_kernels.hpp"
 #include "t1d_dopri5.hpp"
 #include "t1d_policy.hpp"
+#include "t1d_policy_grad.hpp"
 
 #include <climits>
 #include <cmath>
@@ -848,7 +849,8 @@ static MlpArgs<T> make_mlp(const t1d_mlp* m, int n_steps)
 }
 
 // every field of the policy that has a range; -> the rows of a wave's column block in *cols
-static int check_mlp(const char* who, const t1d_batch* b, const t1d_mlp* m, int* cols)
+// state = false (t1d_mlp_grad): the network alone, of n envs -- out_act and the state arrays are not looked at
+static int check_mlp_net(const char* who, int64_t n, const t1d_mlp* m, int* cols, bool state)
 {
     const std::string w = std::string(who) + ": ";
     if (!m) return fail(T1D_E_INVALID, w + "mlp is NULL");
@@ -866,16 +868,18 @@ static int check_mlp(const char* who, const t1d_batch* b, const t1d_mlp* m, int*
     if (m->width[m->n_layers - 1] != 1) return fail(T1D_E_INVALID, w + "the last layer's width must be 1");
     if (m->n_params != count) return fail(T1D_E_INVALID, w + "n_params must be " + std::to_string(count) + " for these widths");
     if (m->hidden_act != T1D_MLP_TANH && m->hidden_act != T1D_MLP_RELU) return fail(T1D_E_INVALID, w + "unknown hidden_act");
-    if (m->out_act != T1D_MLP_IDENTITY && m->out_act != T1D_MLP_LOGISTIC) return fail(T1D_E_INVALID, w + "unknown out_act");
-    if (!m->params || !m->cgm_hist || !m->ins_hist || !m->prev_meal)
-        return fail(T1D_E_INVALID, w + "params / cgm_hist / ins_hist / prev_meal must be set");
+    if (state && m->out_act != T1D_MLP_IDENTITY && m->out_act != T1D_MLP_LOGISTIC) return fail(T1D_E_INVALID, w + "unknown out_act");
+    if (!m->params || (state && (!m->cgm_hist || !m->ins_hist || !m->prev_meal)))
+        return fail(T1D_E_INVALID, w + (state ? "params / cgm_hist / ins_hist / prev_meal must be set" : "params must be set"));
     if (m->n_policies < 1) return fail(T1D_E_INVALID, w + "n_policies < 1");
     if (m->envs_per_policy < 64 || m->envs_per_policy % 64) return fail(T1D_E_INVALID, w + "envs_per_policy must be a multiple of 64");
-    if (m->envs_per_policy > ((int64_t)1 << 28) || m->n_policies > ((int64_t)1 << 28) || b->n != m->n_policies * m->envs_per_policy)
-        return fail(T1D_E_INVALID, w + "batch.n must be n_policies * envs_per_policy");
+    if (m->envs_per_policy > ((int64_t)1 << 28) || m->n_policies > ((int64_t)1 << 28) || n != m->n_policies * m->envs_per_policy)
+        return fail(T1D_E_INVALID, w + (state ? "batch.n must be n_policies * envs_per_policy" : "n must be n_policies * envs_per_policy"));
     *cols = 2 * m->history + widest;
     return T1D_OK;
 }
+
+static int check_mlp(const char* who, const t1d_batch* b, const t1d_mlp* m, int* cols) { return check_mlp_net(who, b->n, m, cols, true); }
 
 // the launch shape of the policy kernels, into the plan and the policy's arguments
 template <typename T>
@@ -1258,6 +1262,101 @@ extern "C" int t1d_outcome_stats(int hip_device, int dtype, int64_t n, int64_t n
     else
         hipLaunchKernelGGL(outcome_kernel<float>, grid_for(n), dim3(kBlock), 0, s, n, n_rows, (const float*)bg_trace, out->counts,
                            (float*)out->pct, out->zone, (float*)out->risk_trace, out->q_lo, out->q_hi, chunk);
+    T1D_HIP(hipGetLastError());
+    return T1D_OK;
+}
+
+// How t1d_mlp_grad cuts the work: a tile is one 64-env chunk of a policy in one row, a policy's tiles are numbered row by
+// row, and one wave takes tiles_per_wave consecutive ones and writes one partial sum.  From the shapes alone (include/t1d.h).
+struct GradPartition { int64_t chunks, tiles, tiles_per_wave, waves_per_policy; };
+static bool grad_partition(const t1d_mlp* m, int64_t n_rows, GradPartition* gp)
+{
+    gp->chunks = m->envs_per_policy / 64;
+    if (n_rows > INT_MAX / gp->chunks) return false;
+    gp->tiles = gp->chunks * n_rows;
+    gp->tiles_per_wave = std::max<int64_t>(1, (m->n_policies * gp->tiles + kGradMaxWaves - 1) / kGradMaxWaves);
+    gp->waves_per_policy = (gp->tiles + gp->tiles_per_wave - 1) / gp->tiles_per_wave;
+    return m->n_policies * gp->waves_per_policy <= INT_MAX;
+}
+
+static int check_mlp_grad(const char* who, int dtype, int64_t n, const t1d_mlp* mlp, int64_t n_rows, GradPartition* gp)
+{
+    const std::string w = std::string(who) + ": ";
+    if (dtype != T1D_F64 && dtype != T1D_F32) return fail(T1D_E_INVALID, w + "bad dtype");
+    if (n < 1 || n > (int64_t)1 << 28) return fail(T1D_E_INVALID, w + "n out of range");
+    if (n_rows < 1) return fail(T1D_E_INVALID, w + "n_rows < 1");
+    int cols = 0;
+    const int rc = check_mlp_net(who, n, mlp, &cols, false);
+    if (rc) return rc;
+    if (!grad_partition(mlp, n_rows, gp)) return fail(T1D_E_INVALID, w + "n_rows is too large");
+    return T1D_OK;
+}
+
+static int64_t grad_workspace_bytes(const t1d_mlp* m, int dtype, const GradPartition& gp)
+{
+    return m->n_policies * gp.waves_per_policy * m->n_params * (int64_t)(dtype == T1D_F64 ? sizeof(double) : sizeof(float));
+}
+
+extern "C" int64_t t1d_mlp_grad_workspace(const t1d_mlp* mlp, int dtype, int64_t n, int64_t n_rows)
+{
+    // the weights themselves are not needed to size the workspace
+    t1d_mlp m;
+    if (!mlp) return fail(T1D_E_INVALID, "t1d_mlp_grad_workspace: mlp is NULL");
+    m = *mlp;
+    if (!m.params) m.params = &m;
+    GradPartition gp;
+    const int rc = check_mlp_grad("t1d_mlp_grad_workspace", dtype, n, &m, n_rows, &gp);
+    if (rc) return rc;
+    return grad_workspace_bytes(&m, dtype, gp);
+}
+
+template <typename T>
+static int launch_mlp_grad(const t1d_mlp* m, int64_t n, const t1d_mlp_batch* io, const GradPartition& gp, hipStream_t s)
+{
+    MlpArgs<T> c = make_mlp<T>(m, 0);
+    GradArgs<T> g;
+    g.feat = (const T*)io->feat; g.coef = (const T*)io->coef; g.y = (T*)io->y; g.partial = io->grad ? (T*)io->workspace : nullptr;
+    g.n = n;
+    g.chunks = (unsigned)gp.chunks; g.tiles = (unsigned)gp.tiles; g.tiles_per_wave = (unsigned)gp.tiles_per_wave;
+    g.waves_per_policy = (unsigned)gp.waves_per_policy; g.n_waves = (unsigned)(m->n_policies * gp.waves_per_policy);
+    int rows = 2 * m->history + 3, deltas = 0;
+    for (int l = 0; l < m->n_layers; ++l) { if (l + 1 < m->n_layers) rows += m->width[l]; deltas += m->width[l]; }
+    g.act_rows = rows;
+    // without grad only the activations are kept
+    const size_t lds = (size_t)(io->grad ? rows + 1 + deltas : rows) * 64 * sizeof(T);
+    if (lds > 65536) {
+        int limit = 0, dev = 0;
+        T1D_HIP(hipGetDevice(&dev));
+        T1D_HIP(hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+        if (lds > (size_t)limit) return fail(T1D_E_INVALID, "t1d_mlp_grad: one wave of this policy does not fit in the device's LDS");
+        T1D_HIP(hipFuncSetAttribute((const void*)mlp_grad_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
+    hipLaunchKernelGGL(mlp_grad_kernel<T>, dim3(g.n_waves), dim3(64), lds, s, c, g);
+    if (io->grad) {
+        const unsigned total = (unsigned)(m->n_policies * m->n_params);
+        hipLaunchKernelGGL(mlp_grad_sum_kernel<T>, dim3((total + 255) / 256), dim3(256), 0, s, (const T*)io->workspace, (T*)io->grad,
+                           g.waves_per_policy, (unsigned)m->n_params, total);
+    }
+    return T1D_OK;
+}
+
+extern "C" int t1d_mlp_grad(int hip_device, int dtype, int64_t n, const t1d_mlp* mlp, const t1d_mlp_batch* io, void* stream)
+{
+    const char* who = "t1d_mlp_grad";
+    if (!io) return fail(T1D_E_INVALID, "t1d_mlp_grad: io is NULL");
+    GradPartition gp;
+    int rc = check_mlp_grad(who, dtype, n, mlp, io->n_rows, &gp);
+    if (rc) return rc;
+    if (!io->feat) return fail(T1D_E_INVALID, "t1d_mlp_grad: feat is NULL");
+    if (!io->y && !io->grad) return fail(T1D_E_INVALID, "t1d_mlp_grad: y and grad are both NULL");
+    if (io->grad && !io->coef) return fail(T1D_E_INVALID, "t1d_mlp_grad: grad needs coef");
+    if (io->grad && (!io->workspace || io->workspace_bytes < grad_workspace_bytes(mlp, dtype, gp)))
+        return fail(T1D_E_INVALID, "t1d_mlp_grad: grad needs a workspace of t1d_mlp_grad_workspace() bytes");
+    if (mlp->n_policies * mlp->n_params > INT_MAX) return fail(T1D_E_INVALID, "t1d_mlp_grad: too many policies");
+    T1D_HIP(hipSetDevice(hip_device));
+    rc = dtype == T1D_F64 ? launch_mlp_grad<double>(mlp, n, io, gp, (hipStream_t)stream)
+                          : launch_mlp_grad<float>(mlp, n, io, gp, (hipStream_t)stream);
+    if (rc) return rc;
     T1D_HIP(hipGetLastError());
     return T1D_OK;
 }

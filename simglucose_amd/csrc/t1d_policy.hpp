@@ -72,7 +72,9 @@ __device__ __forceinline__ void mlp_time_of_day(int m, float& s, float& c) { con
 // The dense layers on the lane's column.  buf: rows of the layer input (row j at buf[j * 64]); w: this wave's weight set,
 // layer after layer, each as row-major W[out][in] followed by b[out].  Accumulation order (include/t1d.h): acc = b[o],
 // then acc = fma(W[o][j], in[j], acc) for j ascending.  -> the last layer's single output, before the output function.
-template <typename T>
+// KEEP (t1d_policy_grad.hpp): a hidden layer's outputs go behind its inputs instead of over them, so that on return the
+// column holds the features and then every hidden layer's activations, in order; the arithmetic is the same.
+template <typename T, bool KEEP = false>
 __device__ __forceinline__ T mlp_layers(const MlpArgs<T>& c, const __attribute__((address_space(4))) T* w, T* buf, int in_w)
 {
     T y = T(0);
@@ -103,6 +105,7 @@ __device__ __forceinline__ T mlp_layers(const MlpArgs<T>& c, const __attribute__
         }
         if (l + 1 == c.n_layers) { y = out[0]; break; }
         // the layer is complete: its outputs replace its inputs, then the activation runs over them in place
+        if constexpr (KEEP) buf += in_w * 64;
 #pragma unroll
         for (int o = 0; o < kMlpMaxWidth; ++o)
             if (o < out_w) buf[o * 64] = out[o];
