@@ -30,6 +30,11 @@
  *                       (simglucose/envs/simglucose_gym_env.py:39-73)
  *   t1d_rollout_pid_dopri5, t1d_rollout_bb_dopri5 <- the two loops with scipy's dopri5 itself (the exact mode)
  *   t1d_rollout_mlp_dopri5, t1d_collect_mlp_dopri5 <- t1d_rollout_mlp and t1d_collect_mlp in the exact mode
+ *   t1d_mlp_features <- the observation a gym trainer keeps for its critic's bootstrap: the network's inputs for the step that
+ *                       would come next (no counterpart in the reference; its gym env hands back one CGM value, env.py:81)
+ *   t1d_mlp_grad     <- the network again on a collected batch, and its weight gradient (what autograd does for a gym trainer)
+ *   t1d_gae          <- the trainer's backward loop over a collected batch: advantages (generalised advantage estimation),
+ *                       value targets and the advantage moments PPO normalises with (no counterpart in the reference)
  *   t1d_random_meals <- RandomScenario.create_scenario  simglucose/simulation/scenario_gen.py:33-60
  *   t1d_restart_done <- the reset() a gym training loop calls when done comes back true (T1DSimEnv.reset + a new
  *                       RandomScenario and start hour, simglucose/envs/simglucose_gym_env.py:58-73), for the finished envs only
@@ -314,6 +319,22 @@ typedef struct t1d_mlp_batch {
     int64_t workspace_bytes;  /* at least t1d_mlp_grad_workspace() */
 } t1d_mlp_batch;
 
+/* t1d_gae: one collected batch of rewards, dones and the critic's values, and what comes back.  Floating arrays have the
+ * call's dtype; done is what t1d_collect.done_trace holds. */
+typedef struct t1d_gae_batch {
+    int64_t n_rows;            /* K >= 1 */
+    int64_t n_policies;        /* >= 1, n % n_policies == 0; only the moments use it */
+    double gamma, lambda;      /* each in [0, 1] */
+    const void* reward;        /* [K][n] */
+    const uint8_t* done;       /* [K][n] or NULL = no episode ends */
+    const void* value;         /* [K][n] or NULL = 0: V of the state each step started from */
+    const void* last_value;    /* [n] or NULL = 0: V of the state after row K-1 (the bootstrap at the cut) */
+    void* adv;                 /* [K][n] or NULL */
+    void* ret;                 /* [K][n] or NULL: adv + value, the critic's regression target */
+    double* moments;           /* [n_policies][2] or NULL: sum of adv and sum of adv^2 over the policy's K * n/n_policies samples, always double */
+    void* workspace; int64_t workspace_bytes;   /* needed with moments */
+} t1d_gae_batch;
+
 int t1d_abi_version(void);
 const char* t1d_last_error(void);
 
@@ -537,6 +558,16 @@ int t1d_collect_mlp_dopri5(t1d_ctx* ctx, const t1d_batch* b, const t1d_mlp* mlp,
  * in row 0 and prev_meal = batch.meal.  T1D_E_INVALID: a NULL action, and whatever t1d_rollout_mlp rejects of the policy. */
 int t1d_mlp_action(t1d_ctx* ctx, const t1d_batch* b, const t1d_mlp* mlp, void* action, void* hip_stream);
 
+/* The features of the step that would come next, one lane per env: feat (device [F][n], F = 2 H + 3, the batch's dtype) = what
+ * the next step of t1d_collect_mlp / t1d_collect_mlp_dopri5 would write to its feat_trace row, bit for bit -- the device's
+ * mlp_features on batch.cgm (CGM[0]), rows 1 .. of mlp.cgm_hist, mlp.ins_hist, mlp.prev_meal, batch.t and mlp.start_minute,
+ * the inputs of t1d_mlp_action, with the device's sinpi / cospi for the time-of-day pair.  After a collect call these are
+ * the features of the state after its last step (for an env that finished there and was restarted: of its new episode's first
+ * state), which the call recorded nowhere: what a critic evaluated by t1d_mlp_grad needs for the bootstrap value at the cut
+ * (t1d_gae_batch.last_value).  It changes nothing: no state is written and no step is taken; the weights are not read.
+ * fp64 and fp32, any integrator, any state layout.  T1D_E_INVALID: a NULL feat, and whatever t1d_mlp_action rejects. */
+int t1d_mlp_features(t1d_ctx* ctx, const t1d_batch* b, const t1d_mlp* mlp, void* feat, void* hip_stream);
+
 /* The network of t1d_mlp on recorded features, and the gradient of a scalar loss with respect to its weights: the other half of
  * a policy-gradient iteration after t1d_collect_mlp / t1d_collect_mlp_dopri5.  No ctx; nothing is allocated, the call only
  * enqueues work on the stream.  fp64 and fp32.  Of t1d_mlp only history, n_layers, width, hidden_act, n_policies,
@@ -563,6 +594,43 @@ int t1d_mlp_action(t1d_ctx* ctx, const t1d_batch* b, const t1d_mlp* mlp, void* a
  * grad without coef; grad with a NULL or too small workspace. */
 int64_t t1d_mlp_grad_workspace(const t1d_mlp* mlp, int dtype, int64_t n, int64_t n_rows);
 int t1d_mlp_grad(int hip_device, int dtype, int64_t n, const t1d_mlp* mlp, const t1d_mlp_batch* io, void* hip_stream);
+
+/* Generalised advantage estimation over a collected batch: the scan from (reward, done, value) to advantages and value targets,
+ * and the per-policy sums advantage normalisation needs -- what stands between t1d_collect_mlp / t1d_collect_mlp_dopri5 and the
+ * loss t1d_mlp_grad differentiates.  No ctx; nothing is allocated, the call only enqueues work on the stream.  fp64 and fp32;
+ * n is any positive number of envs (no multiple of 64 is asked for); policy p owns envs [p E, (p + 1) E), E = n / n_policies.
+ * One lane per env, rows walked from the last to the first.
+ * Arithmetic, part of the contract so that a host can restate it.  With T the call's type, g = (T) gamma and gl = (T) (gamma *
+ * lambda), the product formed in double, for every env and s = K-1 down to 0:
+ *     live   = done == NULL || done[s] == 0
+ *     vn     = live ? (s == K-1 ? last_value : value[s+1]) : 0
+ *     an     = live ? (s == K-1 ? 0 : adv[s+1]) : 0            (the running word, kept in a register: adv may be NULL)
+ *     delta  = fma(g, vn, reward[s]) - value[s]
+ *     adv[s] = fma(gl, an, delta)
+ *     ret[s] = adv[s] + value[s]
+ *   vn and an are SELECTED, never multiplied by zero: a NaN or a stale word in value[s+1] or last_value behind a done does
+ *   not reach row s.  That matters with T1D_COLLECT_RESTART: row s + 1 of a collector's traces belongs to the NEXT episode of
+ *   an env that finished in row s, and so does the critic's value of it.  A NULL value or last_value reads as 0.
+ *   done is a true termination (BG left [70, 350], batch.done): the simulator has no time-limit truncation, so there is no
+ *   second mask for episodes that were cut rather than ended; the cut at the end of the batch is what last_value is for.
+ * moments[p] = (sum of adv, sum of adv^2) over the K E samples of policy p, in double whatever the dtype.  Deterministic and
+ *   portable: no floating-point atomics, and the summation order depends only on (n, n_policies, n_rows, dtype) -- not on the
+ *   CU count, the grid or timing; two calls give identical bits, and a policy's pair depends on its own envs' words alone.
+ *   The order is stated relative to the policy, so a policy's pair does not depend on where its envs sit in the batch (the
+ *   policies' env blocks permuted as whole blocks give the permuted moments).  Every env forms a = ((0 + x[K-1]) + x[K-2]) +
+ *   .. + x[0] and b = fma(x[0], x[0], .. fma(x[K-1], x[K-1], 0)) with x[s] = (double) adv[s].  A tile is the envs 64 c .. min(64
+ *   c + 63, E - 1) of a policy, counted from the policy's first env; partial c adds the a (the b) of the tile's envs in
+ *   ascending order onto 0.  moments[p]: lane l = 0 .. 63 adds the policy's partials l, l + 64, .. in ascending order onto 0;
+ *   then the lane sums are folded: for d = 32, 16, 8, 4, 2, 1: lane l += lane l + d (l < d); the result is lane 0.
+ * workspace: t1d_gae_workspace(dtype, n, io) bytes (host only; < 0 = invalid arguments; of io only n_rows, n_policies, gamma and
+ *   lambda are looked at): 16 bytes for every partial, n_policies * ceil(E / 64) of them.  It does not grow with n_rows.
+ *   Nothing beyond them is written.
+ * T1D_E_INVALID before anything is launched and before the device is touched: a NULL io or reward; adv, ret and moments all
+ * NULL; n_rows < 1 or n < 1; n_policies < 1 or n % n_policies != 0; gamma or lambda outside [0, 1] or NaN; a bad dtype; moments
+ * with a NULL or too small workspace; and beyond the sizes the kernels index: n > 2^31, n_rows * n > 2^40, n_policies > 2^31 - 1.
+ * The workspace needs the alignment of a double, no more. */
+int64_t t1d_gae_workspace(int dtype, int64_t n, const t1d_gae_batch* io);
+int t1d_gae(int hip_device, int dtype, int64_t n, const t1d_gae_batch* io, void* hip_stream);
 
 /* RandomScenario.create_scenario (simulation/scenario_gen.py:33-60) for n envs on the device: fills per-env
  * meal tables meal_time int32 [6 (days + 1)][n] (minutes since the episode start, ascending, unused =

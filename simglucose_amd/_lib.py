@@ -10,6 +10,7 @@ LIB_PATH = os.environ.get("T1D_LIB_PATH") or os.path.join(_PKG, "libt1d_hip.so")
 SOURCES = [os.path.join(_PKG, "csrc", "t1d_abi.hip"), os.path.join(_PKG, "csrc", "t1d_kernels.hpp"),
            os.path.join(_PKG, "csrc", "t1d_device.hpp"), os.path.join(_PKG, "csrc", "t1d_dopri5.hpp"),
            os.path.join(_PKG, "csrc", "t1d_policy.hpp"), os.path.join(_PKG, "csrc", "t1d_policy_grad.hpp"),
+           os.path.join(_PKG, "csrc", "t1d_gae.hpp"),
            os.path.join(_ROOT, "include", "t1d.h")]
 
 T1D_F64, T1D_F32 = 0, 1
@@ -32,7 +33,7 @@ EXPORTS = ("t1d_abi_version", "t1d_last_error", "t1d_ctx_create", "t1d_ctx_set_o
            "t1d_rollout_bb", "t1d_random_meals", "t1d_outcome_stats", "t1d_model_rhs", "t1d_step_dopri5",
            "t1d_rollout_pid_dopri5", "t1d_rollout_bb_dopri5", "t1d_restart_done", "t1d_rollout_mlp",
            "t1d_collect_mlp", "t1d_rollout_mlp_dopri5", "t1d_mlp_action", "t1d_collect_mlp_dopri5",
-           "t1d_mlp_grad_workspace", "t1d_mlp_grad")
+           "t1d_mlp_grad_workspace", "t1d_mlp_grad", "t1d_mlp_features", "t1d_gae_workspace", "t1d_gae")
 
 
 class T1DError(RuntimeError):
@@ -113,6 +114,14 @@ class MlpBatch(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class GaeBatch(C.Structure):
+    """struct t1d_gae_batch (include/t1d.h)"""
+    _fields_ = [("n_rows", C.c_int64), ("n_policies", C.c_int64), ("gamma", C.c_double), ("lam", C.c_double),
+                ("reward", C.c_void_p), ("done", C.c_void_p), ("value", C.c_void_p), ("last_value", C.c_void_p),
+                ("adv", C.c_void_p), ("ret", C.c_void_p), ("moments", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 def _stale():
     return not os.path.exists(LIB_PATH) or any(os.path.exists(s) and os.path.getmtime(s) > os.path.getmtime(LIB_PATH)
                                                for s in SOURCES)
@@ -187,6 +196,9 @@ def lib():
     L.t1d_mlp_action.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), vp, vp]
     L.t1d_mlp_grad_workspace.argtypes = [C.POINTER(Mlp), C.c_int, i64, i64]
     L.t1d_mlp_grad.argtypes = [C.c_int, C.c_int, i64, C.POINTER(Mlp), C.POINTER(MlpBatch), vp]
+    L.t1d_mlp_features.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), vp, vp]
+    L.t1d_gae_workspace.argtypes = [C.c_int, i64, C.POINTER(GaeBatch)]
+    L.t1d_gae.argtypes = [C.c_int, C.c_int, i64, C.POINTER(GaeBatch), vp]
     L.t1d_restart_done.argtypes = [vp, C.POINTER(Batch), vp, C.POINTER(Restart), vp]
     L.t1d_random_meals.argtypes = [C.c_int, u64, i64, i64, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]
     L.t1d_outcome_stats.argtypes = [C.c_int, C.c_int, i64, i64, vp, C.POINTER(Outcome), vp]
@@ -198,6 +210,7 @@ def lib():
         if name not in ("t1d_last_error",):
             getattr(L, name).restype = C.c_int
     L.t1d_mlp_grad_workspace.restype = i64
+    L.t1d_gae_workspace.restype = i64
     if L.t1d_abi_version() != ABI_VERSION:
         raise T1DError("libt1d_hip.so ABI version mismatch")
     _lib = L

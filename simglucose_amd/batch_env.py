@@ -576,6 +576,24 @@ class BatchedT1DSimEnv:
         self._keep = (params, policy_state, out)
         return out
 
+    def policy_features(self, policy, policy_state):
+        """The features [F, n], F = 2 H + 3, that the next step of collect_mlp / collect_mlp_dopri5 would record in its
+        "features" row (t1d_mlp_features, include/t1d.h), bit for bit: the device's own feature code -- its sinpi / cospi
+        for the time-of-day pair -- on the current observation (env.cgm), rows 1 .. of policy_state["cgm_hist"], its
+        ins_hist and prev_meal, the env's clock and start_minute.  Nothing is changed and no step is taken; works in every
+        mode.  After a collect call these are the features of the state after its last step, which no trace row holds:
+        what a critic needs for its bootstrap value at the cut (controller.gae):
+
+            v_last = mlp_pre_output(vparams, env.policy_features(vpol, st)[None], vpol)[0]
+        """
+        p, params = self._mlp_struct("policy_features", policy, policy_state)
+        self._set_trace(p, None, 0)
+        out = torch.empty(2 * int(policy.history) + 3, self.n, dtype=self.dtype, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.t1d_mlp_features(self._ctx, C.byref(self._b), C.byref(p), C.c_void_p(out.data_ptr()), self._stream()))
+        self._keep = (params, policy_state, out)
+        return out
+
     def rollout_mlp_dopri5(self, n_steps, policy, policy_state=None, stats=None, trace=None, max_minutes_per_launch=240):
         """rollout_mlp in the exact mode (t1d_rollout_mlp_dopri5): n_steps closed-loop steps under the in-kernel network with
         scipy's dopri5, every env at its own pace inside a launch -- SimObj.simulate as the reference would run it with that

@@ -7,6 +7,7 @@
 #include "t1d_dopri5.hpp"
 #include "t1d_policy.hpp"
 #include "t1d_policy_grad.hpp"
+#include "t1d_gae.hpp"
 
 #include <climits>
 #include <cmath>
@@ -1029,6 +1030,34 @@ extern "C" int t1d_mlp_action(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp
     return T1D_OK;
 }
 
+// The features alone (mlp_features_kernel, t1d_policy.hpp): the launch shape of launch_mlp_action.
+template <typename T>
+static void launch_mlp_features(const t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, int cols, void* feat, hipStream_t s)
+{
+    MlpArgs<T> ma = make_mlp<T>(mlp, 0);
+    ma.cols = cols;
+    const size_t per_wave = (size_t)cols * 64 * sizeof(T), room = std::min<size_t>((size_t)c->lds_per_block, 65536) - 256;
+    int threads = T1D_POLICY_THREADS;
+    while (threads > 64 && per_wave * (threads / 64) > room) threads /= 2;
+    hipLaunchKernelGGL(mlp_features_kernel<T>, dim3((unsigned)((b->n + threads - 1) / threads)), dim3(threads), per_wave * (threads / 64), s,
+                       make_args<T>(c, b, 1, 1), ma, (T*)feat);
+}
+
+extern "C" int t1d_mlp_features(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, void* feat, void* stream)
+{
+    const char* who = "t1d_mlp_features";
+    int rc = check_batch(who, c, b, false);
+    if (rc) return rc;
+    if (!feat) return fail(T1D_E_INVALID, "t1d_mlp_features: feat is NULL");
+    int cols = 0;
+    rc = check_mlp(who, b, mlp, &cols);
+    if (rc) return rc;
+    if (b->dtype == T1D_F64) launch_mlp_features<double>(c, b, mlp, cols, feat, (hipStream_t)stream);
+    else launch_mlp_features<float>(c, b, mlp, cols, feat, (hipStream_t)stream);
+    T1D_HIP(hipGetLastError());
+    return T1D_OK;
+}
+
 // the six meal windows of RandomScenario.create_scenario (scenario_gen.py:38-45) as the kernels take them
 static MealSlots meal_slots()
 {
@@ -1357,6 +1386,69 @@ extern "C" int t1d_mlp_grad(int hip_device, int dtype, int64_t n, const t1d_mlp*
     rc = dtype == T1D_F64 ? launch_mlp_grad<double>(mlp, n, io, gp, (hipStream_t)stream)
                           : launch_mlp_grad<float>(mlp, n, io, gp, (hipStream_t)stream);
     if (rc) return rc;
+    T1D_HIP(hipGetLastError());
+    return T1D_OK;
+}
+
+// t1d_gae (t1d_gae.hpp): every argument is checked here, before the device is touched.  -> the tiles of one policy (its 64-env
+// pieces counted from its first env: one partial sum each) in *tiles
+static int check_gae(const char* who, int dtype, int64_t n, const t1d_gae_batch* io, int64_t* tiles)
+{
+    const std::string w = std::string(who) + ": ";
+    if (!io) return fail(T1D_E_INVALID, w + "io is NULL");
+    if (dtype != T1D_F64 && dtype != T1D_F32) return fail(T1D_E_INVALID, w + "bad dtype");
+    if (n < 1 || n > (int64_t)1 << 31) return fail(T1D_E_INVALID, w + "n out of range");
+    if (io->n_rows < 1 || io->n_rows > ((int64_t)1 << 40) / n) return fail(T1D_E_INVALID, w + "n_rows out of range");
+    if (io->n_policies < 1 || io->n_policies > INT_MAX || n % io->n_policies)
+        return fail(T1D_E_INVALID, w + "n_policies must be in [1, 2^31 - 1] and divide n");
+    if (!(io->gamma >= 0.0 && io->gamma <= 1.0) || !(io->lambda >= 0.0 && io->lambda <= 1.0))
+        return fail(T1D_E_INVALID, w + "gamma and lambda must be in [0, 1]");
+    *tiles = (n / io->n_policies + 63) / 64;
+    return T1D_OK;
+}
+
+extern "C" int64_t t1d_gae_workspace(int dtype, int64_t n, const t1d_gae_batch* io)
+{
+    int64_t tiles = 0;
+    const int rc = check_gae("t1d_gae_workspace", dtype, n, io, &tiles);
+    if (rc) return rc;
+    return io->n_policies * tiles * 2 * (int64_t)sizeof(double);
+}
+
+template <typename T>
+static void launch_gae(int64_t n, const t1d_gae_batch* io, int64_t tiles, hipStream_t s)
+{
+    GaeArgs<T> a;
+    a.reward = (const T*)io->reward; a.done = io->done; a.value = (const T*)io->value; a.last_value = (const T*)io->last_value;
+    a.adv = (T*)io->adv; a.ret = (T*)io->ret; a.partial = io->moments ? (double*)io->workspace : nullptr;
+    a.n = n; a.n_rows = io->n_rows; a.envs_per_policy = n / io->n_policies; a.tiles = (unsigned)tiles;
+    a.n_waves = (unsigned)(io->moments ? io->n_policies * tiles : (n + 63) / 64);
+    a.g = (T)io->gamma; a.gl = (T)(io->gamma * io->lambda);
+    const dim3 grid((a.n_waves + kGaeBlock / 64 - 1) / (kGaeBlock / 64));
+    // every array given: the streaming form, whose loads and stores the compiler can count
+    const bool full = io->done && io->value && io->adv && io->ret;
+    if (io->moments) {
+        hipLaunchKernelGGL((full ? gae_kernel<T, true, true> : gae_kernel<T, true, false>), grid, dim3(kGaeBlock), 0, s, a);
+        hipLaunchKernelGGL(gae_moments_kernel, dim3((unsigned)io->n_policies), dim3(64), 0, s, (const double*)io->workspace, io->moments,
+                           a.tiles);
+    } else {
+        hipLaunchKernelGGL((full ? gae_kernel<T, false, true> : gae_kernel<T, false, false>), grid, dim3(kGaeBlock), 0, s, a);
+    }
+}
+
+extern "C" int t1d_gae(int hip_device, int dtype, int64_t n, const t1d_gae_batch* io, void* stream)
+{
+    const char* who = "t1d_gae";
+    int64_t tiles = 0;
+    const int rc = check_gae(who, dtype, n, io, &tiles);
+    if (rc) return rc;
+    if (!io->reward) return fail(T1D_E_INVALID, "t1d_gae: reward is NULL");
+    if (!io->adv && !io->ret && !io->moments) return fail(T1D_E_INVALID, "t1d_gae: adv, ret and moments are all NULL");
+    if (io->moments && (!io->workspace || io->workspace_bytes < io->n_policies * tiles * 2 * (int64_t)sizeof(double)))
+        return fail(T1D_E_INVALID, "t1d_gae: moments need a workspace of t1d_gae_workspace() bytes");
+    T1D_HIP(hipSetDevice(hip_device));
+    if (dtype == T1D_F64) launch_gae<double>(n, io, tiles, (hipStream_t)stream);
+    else launch_gae<float>(n, io, tiles, (hipStream_t)stream);
     T1D_HIP(hipGetLastError());
     return T1D_OK;
 }

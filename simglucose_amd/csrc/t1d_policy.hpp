@@ -438,4 +438,27 @@ __global__ __launch_bounds__(T1D_POLICY_THREADS) void mlp_collect_kernel(const K
     }
 }
 
+// t1d_mlp_features: the features alone, one lane per env -- what the next step of a collector would write to its feat_trace
+// row, from the words mlp_action_kernel (t1d_dopri5.hpp) reads: batch.cgm (CGM[0]), rows 1 .. of cgm_hist, ins_hist, prev_meal,
+// batch.t and start_minute.  Reads only; writes feat [F][n].  Dynamic LDS: cols * 64 words for each wave, the lane's column in
+// window order (head 0), as for mlp_action_kernel.
+template <typename T>
+__global__ __launch_bounds__(T1D_POLICY_THREADS) void mlp_features_kernel(const KArgs<T> a, const MlpArgs<T> c, T* feat)
+{
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    __builtin_assume(i < (1u << 28));          // host guarantees n <= 2^28: i * sizeof(T) fits a 32-bit voffset
+    if ((int64_t)i >= a.n) return;
+    T* const col = (T*)t1d_dyn_lds + (threadIdx.x >> 6) * (c.cols * 64) + (threadIdx.x & 63u);
+    const int H = c.history, F = 2 * H + 3;
+    T* const buf = col + 2 * H * 64;
+    col[0] = at(a.cgm, i);
+    for (int k = 1; k < H; ++k) col[k * 64] = at(rowv(c.cgm_hist, a.n, k), i);
+    for (int k = 0; k < H; ++k) col[(H + k) * 64] = at(rowv(c.ins_hist, a.n, k), i);
+    const int start = c.start_minute ? (int)at(c.start_minute, i) : 0;
+    const T prev_meal = at(c.prev_meal, i);
+    const int t = at(a.t, i);
+    mlp_features(c, col, buf, 0, prev_meal, start + t);
+    for (int j = 0; j < F; ++j) at(rowv(feat, a.n, j), i) = buf[j * 64];
+}
+
 } // namespace t1d
