@@ -33,6 +33,7 @@
  *   t1d_mlp_features <- the observation a gym trainer keeps for its critic's bootstrap: the network's inputs for the step that
  *                       would come next (no counterpart in the reference; its gym env hands back one CGM value, env.py:81)
  *   t1d_mlp_grad     <- the network again on a collected batch, and its weight gradient (what autograd does for a gym trainer)
+ *   t1d_mlp_loss     <- the same with the PPO-clip or value loss inside the launch: one forward pass per epoch
  *   t1d_gae          <- the trainer's backward loop over a collected batch: advantages (generalised advantage estimation),
  *                       value targets and the advantage moments PPO normalises with (no counterpart in the reference)
  *   t1d_random_meals <- RandomScenario.create_scenario  simglucose/simulation/scenario_gen.py:33-60
@@ -319,6 +320,33 @@ typedef struct t1d_mlp_batch {
     int64_t workspace_bytes;  /* at least t1d_mlp_grad_workspace() */
 } t1d_mlp_batch;
 
+/* t1d_mlp_loss: t1d_mlp_batch with the loss in place of coef.  Floating arrays have the call's dtype.  The struct shares its
+ * name with the function, so it has no typedef: write `struct t1d_mlp_loss`. */
+enum { T1D_LOSS_PPO_CLIP = 1, T1D_LOSS_VALUE_MSE = 2 };       /* t1d_mlp_loss.kind */
+struct t1d_mlp_loss {
+    int64_t n_rows;           /* K >= 1 */
+    int32_t kind;             /* T1D_LOSS_PPO_CLIP | T1D_LOSS_VALUE_MSE */
+    int32_t reserved;         /* 0 */
+    const void* feat;         /* [n_rows][F][n], as t1d_mlp_batch.feat */
+    /* T1D_LOSS_PPO_CLIP (else ignored) */
+    const void* eps;          /* [n_rows][n] rows of t1d_collect.eps_trace */
+    const void* y_old;        /* [n_rows][n] the collector's y: one y-only call under the collector's weights */
+    const void* adv;          /* [n_rows][n] advantages */
+    const void* sigma_old;    /* [n_policies] device, the call's dtype: t1d_collect.sigma of the collect call, > 0 */
+    const void* sigma;        /* [n_policies] device, the call's dtype: the sigma being trained, > 0 (may be sigma_old) */
+    /* T1D_LOSS_VALUE_MSE (else ignored) */
+    const void* target;       /* [n_rows][n] the critic's regression target (t1d_gae_batch.ret) */
+    double clip;              /* PPO: in (0, 1) */
+    double scale;             /* finite: what every coef is multiplied by, 1 / (n_rows * n) for a mean */
+    /* outputs, each optional, not all NULL */
+    void* y;                  /* [n_rows][n] as t1d_mlp_batch.y */
+    void* coef_out;           /* [n_rows][n] scale * d loss_i / d y of every sample */
+    void* grad;               /* [n_policies][n_params] OVERWRITTEN: t1d_mlp_grad's grad for coef = coef_out */
+    double* stats;            /* [n_policies][4] OVERWRITTEN, always double, unscaled (below) */
+    void* workspace;          /* device scratch for the partial sums; needed with grad or stats */
+    int64_t workspace_bytes;  /* at least t1d_mlp_loss_workspace() */
+};
+
 /* t1d_gae: one collected batch of rewards, dones and the critic's values, and what comes back.  Floating arrays have the
  * call's dtype; done is what t1d_collect.done_trace holds. */
 typedef struct t1d_gae_batch {
@@ -594,6 +622,51 @@ int t1d_mlp_features(t1d_ctx* ctx, const t1d_batch* b, const t1d_mlp* mlp, void*
  * grad without coef; grad with a NULL or too small workspace. */
 int64_t t1d_mlp_grad_workspace(const t1d_mlp* mlp, int dtype, int64_t n, int64_t n_rows);
 int t1d_mlp_grad(int hip_device, int dtype, int64_t n, const t1d_mlp* mlp, const t1d_mlp_batch* io, void* hip_stream);
+
+/* t1d_mlp_grad with the loss inside the launch: the network on recorded features once, the loss of every sample from y in a
+ * register, its derivative as coef, the weight gradient and the per-policy sums a trainer logs -- one forward pass where a
+ * y-only call, a dozen elementwise kernels and a gradient call that evaluates the network again stood.  No ctx; nothing is
+ * allocated, the call only enqueues work on the stream.  fp64 and fp32; t1d_mlp is read as by t1d_mlp_grad.
+ * Arithmetic, part of the contract so that a host can restate it.  T is the call's type, p = i / envs_per_policy the env's
+ * policy, c = (T) clip and k = (T) scale; every operation below is one operation in T unless it says double, products and
+ * quotients are taken left to right; the compiler may contract a product and a sum into one fma where none is written.
+ *   T1D_LOSS_PPO_CLIP, so = sigma_old[p], sg = sigma[p]:
+ *     z      = fma(so, eps, y_old)                          the action the collector took, by its own expression
+ *     e_old  = (z - y_old) / so
+ *     e_new  = (z - y) / sg
+ *     logr   = 0.5 * ((e_old - e_new) * (e_old + e_new)) + (log(so) - log(sg))
+ *     r      = exp(logr)
+ *     active = adv >= 0 ? r <= 1 + c : r >= 1 - c
+ *     loss_i = -min(r * adv, min(max(r, 1 - c), 1 + c) * adv)
+ *     g      = active ? -(r * adv) : 0
+ *     coef   = k * g * e_new / sg
+ *     dsig_i = g * (e_new * e_new - 1) / sg                 d loss_i / d sigma[p]
+ *     stats[p] = (sum loss_i, number of samples not active, sum of expm1(logr) - logr formed in double from (double) logr,
+ *                 sum dsig_i)
+ *   logr is a product of difference and sum so that it is exactly 0 where y == y_old and sg == so bit for bit: under
+ *   unchanged weights r == 1 for every sample, stats[p] = (-sum adv, 0, 0.0, .) and coef = -k * adv * e_new / sg.
+ *   T1D_LOSS_VALUE_MSE:
+ *     d      = y - target
+ *     loss_i = 0.5 * d * d
+ *     coef   = k * d
+ *     stats[p] = (sum loss_i, 0, 0, 0)
+ *   A NaN row (row 0 of a trace buffer) is the caller's to skip.  sigma > 0 is the caller's responsibility: it is device data
+ *   and is not read on the host.
+ * y is t1d_mlp_grad's y and grad is t1d_mlp_grad's grad for coef = coef_out, both bit for bit (the same partition into tiles
+ *   and partials, the same order).  Without grad the back-propagation is skipped; y, coef_out and stats are still written.
+ * stats: every sample's four terms are converted to double and added in double, unscaled.  Deterministic and portable like
+ *   grad, over the same partition: lane l of partial k adds the terms of env 64 chunk + l of its tiles in ascending tile
+ *   order onto 0; the 64 lane sums are folded: for d = 32, 16, 8, 4, 2, 1: lane l += lane l + d (l < d), the result is lane
+ *   0; stats[p][j] = ((0 + partial 0) + partial 1) + ... in ascending k.  A policy's row depends on its own envs alone.
+ * workspace: t1d_mlp_loss_workspace(mlp, dtype, n, n_rows) bytes (host only, mlp.params may be NULL; < 0 = invalid arguments)
+ *   = W rounded up to a multiple of 8, plus 32 bytes for every partial, n_policies * ceil(C * n_rows / T) of them, with W =
+ *   t1d_mlp_grad_workspace() of the same arguments.  Nothing beyond them is written.  It needs the alignment of a double.
+ * T1D_E_INVALID before anything is launched and before the device is touched: whatever t1d_mlp_grad rejects of mlp, dtype, n,
+ * n_rows and feat; a NULL io; a kind that is neither of the two; a NULL eps, y_old, adv, sigma_old or sigma with
+ * T1D_LOSS_PPO_CLIP, a NULL target with T1D_LOSS_VALUE_MSE; with T1D_LOSS_PPO_CLIP a clip outside (0, 1) or NaN; a scale that
+ * is not finite; y, coef_out, grad and stats all NULL; grad or stats with a NULL or too small workspace. */
+int64_t t1d_mlp_loss_workspace(const t1d_mlp* mlp, int dtype, int64_t n, int64_t n_rows);
+int t1d_mlp_loss(int hip_device, int dtype, int64_t n, const t1d_mlp* mlp, const struct t1d_mlp_loss* io, void* hip_stream);
 
 /* Generalised advantage estimation over a collected batch: the scan from (reward, done, value) to advantages and value targets,
  * and the per-policy sums advantage normalisation needs -- what stands between t1d_collect_mlp / t1d_collect_mlp_dopri5 and the

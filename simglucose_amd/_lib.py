@@ -26,6 +26,7 @@ META_EATING = 0x100
 T1D_MLP_TANH, T1D_MLP_RELU = 0, 1
 T1D_MLP_IDENTITY, T1D_MLP_LOGISTIC = 0, 1
 T1D_COLLECT_CONTINUE, T1D_COLLECT_RESTART = 0, 1
+T1D_LOSS_PPO_CLIP, T1D_LOSS_VALUE_MSE = 1, 2
 MLP_MAX_HISTORY, MLP_MAX_LAYERS, MLP_MAX_WIDTH = 12, 4, 32
 
 EXPORTS = ("t1d_abi_version", "t1d_last_error", "t1d_ctx_create", "t1d_ctx_set_option", "t1d_ctx_destroy", "t1d_reset",
@@ -33,7 +34,8 @@ EXPORTS = ("t1d_abi_version", "t1d_last_error", "t1d_ctx_create", "t1d_ctx_set_o
            "t1d_rollout_bb", "t1d_random_meals", "t1d_outcome_stats", "t1d_model_rhs", "t1d_step_dopri5",
            "t1d_rollout_pid_dopri5", "t1d_rollout_bb_dopri5", "t1d_restart_done", "t1d_rollout_mlp",
            "t1d_collect_mlp", "t1d_rollout_mlp_dopri5", "t1d_mlp_action", "t1d_collect_mlp_dopri5",
-           "t1d_mlp_grad_workspace", "t1d_mlp_grad", "t1d_mlp_features", "t1d_gae_workspace", "t1d_gae")
+           "t1d_mlp_grad_workspace", "t1d_mlp_grad", "t1d_mlp_features", "t1d_gae_workspace", "t1d_gae",
+           "t1d_mlp_loss_workspace", "t1d_mlp_loss")
 
 
 class T1DError(RuntimeError):
@@ -111,6 +113,15 @@ class Collect(C.Structure):
 class MlpBatch(C.Structure):
     """struct t1d_mlp_batch (include/t1d.h)"""
     _fields_ = [("n_rows", C.c_int64), ("feat", C.c_void_p), ("coef", C.c_void_p), ("y", C.c_void_p), ("grad", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
+class MlpLoss(C.Structure):
+    """struct t1d_mlp_loss (include/t1d.h)"""
+    _fields_ = [("n_rows", C.c_int64), ("kind", C.c_int32), ("reserved", C.c_int32), ("feat", C.c_void_p),
+                ("eps", C.c_void_p), ("y_old", C.c_void_p), ("adv", C.c_void_p), ("sigma_old", C.c_void_p), ("sigma", C.c_void_p),
+                ("target", C.c_void_p), ("clip", C.c_double), ("scale", C.c_double),
+                ("y", C.c_void_p), ("coef_out", C.c_void_p), ("grad", C.c_void_p), ("stats", C.c_void_p),
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
@@ -196,6 +207,8 @@ def lib():
     L.t1d_mlp_action.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), vp, vp]
     L.t1d_mlp_grad_workspace.argtypes = [C.POINTER(Mlp), C.c_int, i64, i64]
     L.t1d_mlp_grad.argtypes = [C.c_int, C.c_int, i64, C.POINTER(Mlp), C.POINTER(MlpBatch), vp]
+    L.t1d_mlp_loss_workspace.argtypes = [C.POINTER(Mlp), C.c_int, i64, i64]
+    L.t1d_mlp_loss.argtypes = [C.c_int, C.c_int, i64, C.POINTER(Mlp), C.POINTER(MlpLoss), vp]
     L.t1d_mlp_features.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), vp, vp]
     L.t1d_gae_workspace.argtypes = [C.c_int, i64, C.POINTER(GaeBatch)]
     L.t1d_gae.argtypes = [C.c_int, C.c_int, i64, C.POINTER(GaeBatch), vp]
@@ -211,6 +224,7 @@ def lib():
             getattr(L, name).restype = C.c_int
     L.t1d_mlp_grad_workspace.restype = i64
     L.t1d_gae_workspace.restype = i64
+    L.t1d_mlp_loss_workspace.restype = i64
     if L.t1d_abi_version() != ABI_VERSION:
         raise T1DError("libt1d_hip.so ABI version mismatch")
     _lib = L

@@ -1339,6 +1339,25 @@ extern "C" int64_t t1d_mlp_grad_workspace(const t1d_mlp* mlp, int dtype, int64_t
     return grad_workspace_bytes(&m, dtype, gp);
 }
 
+// The LDS of one wave of mlp_grad_kernel (t1d_policy_grad.hpp): act_rows = F + the hidden widths of activations; with grad
+// one row of ones and one delta row per unit of every layer behind them.  Above 64 KiB the kernel's ceiling is raised, and a
+// net that does not fit the device is refused.  Every row a variant of the kernel adds must be counted here.
+static int grad_lds(const char* who, const t1d_mlp* m, bool with_grad, size_t word, const void* kernel, int* act_rows, size_t* lds)
+{
+    int rows = 2 * m->history + 3, deltas = 0;
+    for (int l = 0; l < m->n_layers; ++l) { if (l + 1 < m->n_layers) rows += m->width[l]; deltas += m->width[l]; }
+    *act_rows = rows;
+    *lds = (size_t)(with_grad ? rows + 1 + deltas : rows) * 64 * word;      // without grad only the activations are kept
+    if (*lds > 65536) {
+        int limit = 0, dev = 0;
+        T1D_HIP(hipGetDevice(&dev));
+        T1D_HIP(hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+        if (*lds > (size_t)limit) return fail(T1D_E_INVALID, std::string(who) + ": one wave of this policy does not fit in the device's LDS");
+        T1D_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds));
+    }
+    return T1D_OK;
+}
+
 template <typename T>
 static int launch_mlp_grad(const t1d_mlp* m, int64_t n, const t1d_mlp_batch* io, const GradPartition& gp, hipStream_t s)
 {
@@ -1348,18 +1367,10 @@ static int launch_mlp_grad(const t1d_mlp* m, int64_t n, const t1d_mlp_batch* io,
     g.n = n;
     g.chunks = (unsigned)gp.chunks; g.tiles = (unsigned)gp.tiles; g.tiles_per_wave = (unsigned)gp.tiles_per_wave;
     g.waves_per_policy = (unsigned)gp.waves_per_policy; g.n_waves = (unsigned)(m->n_policies * gp.waves_per_policy);
-    int rows = 2 * m->history + 3, deltas = 0;
-    for (int l = 0; l < m->n_layers; ++l) { if (l + 1 < m->n_layers) rows += m->width[l]; deltas += m->width[l]; }
-    g.act_rows = rows;
-    // without grad only the activations are kept
-    const size_t lds = (size_t)(io->grad ? rows + 1 + deltas : rows) * 64 * sizeof(T);
-    if (lds > 65536) {
-        int limit = 0, dev = 0;
-        T1D_HIP(hipGetDevice(&dev));
-        T1D_HIP(hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
-        if (lds > (size_t)limit) return fail(T1D_E_INVALID, "t1d_mlp_grad: one wave of this policy does not fit in the device's LDS");
-        T1D_HIP(hipFuncSetAttribute((const void*)mlp_grad_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
+    size_t lds = 0;
+    const int rc = grad_lds("t1d_mlp_grad", m, io->grad != nullptr, sizeof(T), (const void*)(void (*)(MlpArgs<T>, GradArgs<T>))mlp_grad_kernel<T>,
+                            &g.act_rows, &lds);
+    if (rc) return rc;
     hipLaunchKernelGGL(mlp_grad_kernel<T>, dim3(g.n_waves), dim3(64), lds, s, c, g);
     if (io->grad) {
         const unsigned total = (unsigned)(m->n_policies * m->n_params);
@@ -1385,6 +1396,99 @@ extern "C" int t1d_mlp_grad(int hip_device, int dtype, int64_t n, const t1d_mlp*
     T1D_HIP(hipSetDevice(hip_device));
     rc = dtype == T1D_F64 ? launch_mlp_grad<double>(mlp, n, io, gp, (hipStream_t)stream)
                           : launch_mlp_grad<float>(mlp, n, io, gp, (hipStream_t)stream);
+    if (rc) return rc;
+    T1D_HIP(hipGetLastError());
+    return T1D_OK;
+}
+
+// t1d_mlp_loss: t1d_mlp_grad's partition and gradient partials, and one partial [4] of doubles per wave behind them
+static int64_t loss_stats_offset(const t1d_mlp* m, int dtype, const GradPartition& gp)
+{
+    return (grad_workspace_bytes(m, dtype, gp) + 7) / 8 * 8;
+}
+
+static int64_t loss_workspace_bytes(const t1d_mlp* m, int dtype, const GradPartition& gp)
+{
+    return loss_stats_offset(m, dtype, gp) + m->n_policies * gp.waves_per_policy * 4 * (int64_t)sizeof(double);
+}
+
+extern "C" int64_t t1d_mlp_loss_workspace(const t1d_mlp* mlp, int dtype, int64_t n, int64_t n_rows)
+{
+    t1d_mlp m;
+    if (!mlp) return fail(T1D_E_INVALID, "t1d_mlp_loss_workspace: mlp is NULL");
+    m = *mlp;
+    if (!m.params) m.params = &m;
+    GradPartition gp;
+    const int rc = check_mlp_grad("t1d_mlp_loss_workspace", dtype, n, &m, n_rows, &gp);
+    if (rc) return rc;
+    return loss_workspace_bytes(&m, dtype, gp);
+}
+
+template <typename T, int KIND>
+static int launch_mlp_loss(int dtype, const t1d_mlp* m, int64_t n, const struct t1d_mlp_loss* io, const GradPartition& gp, hipStream_t s)
+{
+    MlpArgs<T> c = make_mlp<T>(m, 0);
+    GradArgs<T> g;
+    g.feat = (const T*)io->feat; g.coef = nullptr; g.y = (T*)io->y; g.partial = io->grad ? (T*)io->workspace : nullptr;
+    g.n = n;
+    g.chunks = (unsigned)gp.chunks; g.tiles = (unsigned)gp.tiles; g.tiles_per_wave = (unsigned)gp.tiles_per_wave;
+    g.waves_per_policy = (unsigned)gp.waves_per_policy; g.n_waves = (unsigned)(m->n_policies * gp.waves_per_policy);
+    LossArgs<T, KIND> ls;
+    ls.eps = (const T*)io->eps; ls.y_old = (const T*)io->y_old; ls.adv = (const T*)io->adv; ls.target = (const T*)io->target;
+    ls.sigma_old = (const T*)io->sigma_old; ls.sigma = (const T*)io->sigma;
+    ls.coef_out = (T*)io->coef_out;
+    double* const stat_partial = io->stats ? (double*)((char*)io->workspace + loss_stats_offset(m, dtype, gp)) : nullptr;
+    ls.stat_partial = stat_partial;
+    ls.clip = (T)io->clip; ls.scale = (T)io->scale;
+    void (*const fn)(MlpArgs<T>, GradArgs<T>, LossArgs<T, KIND>) = mlp_grad_kernel<T, LossArgs<T, KIND>>;
+    // the statistics live in registers: the rows are t1d_mlp_grad's
+    size_t lds = 0;
+    const int rc = grad_lds("t1d_mlp_loss", m, io->grad != nullptr, sizeof(T), (const void*)fn, &g.act_rows, &lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL(fn, dim3(g.n_waves), dim3(64), lds, s, c, g, ls);
+    if (io->grad) {
+        const unsigned total = (unsigned)(m->n_policies * m->n_params);
+        hipLaunchKernelGGL(mlp_grad_sum_kernel<T>, dim3((total + 255) / 256), dim3(256), 0, s, (const T*)io->workspace, (T*)io->grad,
+                           g.waves_per_policy, (unsigned)m->n_params, total);
+    }
+    if (io->stats) {
+        const unsigned total = (unsigned)(4 * m->n_policies);
+        hipLaunchKernelGGL(mlp_loss_stats_kernel, dim3((total + 63) / 64), dim3(64), 0, s, (const double*)stat_partial, io->stats,
+                           g.waves_per_policy, total);
+    }
+    return T1D_OK;
+}
+
+extern "C" int t1d_mlp_loss(int hip_device, int dtype, int64_t n, const t1d_mlp* mlp, const struct t1d_mlp_loss* io, void* stream)
+{
+    const char* who = "t1d_mlp_loss";
+    if (!io) return fail(T1D_E_INVALID, "t1d_mlp_loss: io is NULL");
+    GradPartition gp;
+    int rc = check_mlp_grad(who, dtype, n, mlp, io->n_rows, &gp);
+    if (rc) return rc;
+    if (!io->feat) return fail(T1D_E_INVALID, "t1d_mlp_loss: feat is NULL");
+    if (io->kind == T1D_LOSS_PPO_CLIP) {
+        if (!io->eps || !io->y_old || !io->adv || !io->sigma_old || !io->sigma)
+            return fail(T1D_E_INVALID, "t1d_mlp_loss: T1D_LOSS_PPO_CLIP needs eps, y_old, adv, sigma_old and sigma");
+        if (!(io->clip > 0.0 && io->clip < 1.0)) return fail(T1D_E_INVALID, "t1d_mlp_loss: clip must be in (0, 1)");
+    } else if (io->kind == T1D_LOSS_VALUE_MSE) {
+        if (!io->target) return fail(T1D_E_INVALID, "t1d_mlp_loss: T1D_LOSS_VALUE_MSE needs target");
+    } else {
+        return fail(T1D_E_INVALID, "t1d_mlp_loss: unknown kind");
+    }
+    if (!std::isfinite(io->scale)) return fail(T1D_E_INVALID, "t1d_mlp_loss: scale must be finite");
+    if (!io->y && !io->coef_out && !io->grad && !io->stats) return fail(T1D_E_INVALID, "t1d_mlp_loss: y, coef_out, grad and stats are all NULL");
+    if ((io->grad || io->stats) && (!io->workspace || io->workspace_bytes < loss_workspace_bytes(mlp, dtype, gp)))
+        return fail(T1D_E_INVALID, "t1d_mlp_loss: grad and stats need a workspace of t1d_mlp_loss_workspace() bytes");
+    if (mlp->n_policies * mlp->n_params > INT_MAX) return fail(T1D_E_INVALID, "t1d_mlp_loss: too many policies");
+    T1D_HIP(hipSetDevice(hip_device));
+    const bool ppo = io->kind == T1D_LOSS_PPO_CLIP;
+    if (dtype == T1D_F64)
+        rc = ppo ? launch_mlp_loss<double, T1D_LOSS_PPO_CLIP>(dtype, mlp, n, io, gp, (hipStream_t)stream)
+                 : launch_mlp_loss<double, T1D_LOSS_VALUE_MSE>(dtype, mlp, n, io, gp, (hipStream_t)stream);
+    else
+        rc = ppo ? launch_mlp_loss<float, T1D_LOSS_PPO_CLIP>(dtype, mlp, n, io, gp, (hipStream_t)stream)
+                 : launch_mlp_loss<float, T1D_LOSS_VALUE_MSE>(dtype, mlp, n, io, gp, (hipStream_t)stream);
     if (rc) return rc;
     T1D_HIP(hipGetLastError());
     return T1D_OK;

@@ -24,6 +24,18 @@
 //                        The accumulators carry on across the wave's tiles, then go to the workspace as one partial
 //                        [n_params] (vector stores).
 //   mlp_grad_sum_kernel  grad[p][q] = the partials of policy p added in wave order.
+//   with LossArgs        t1d_mlp_loss: mlp_grad_kernel<T, LossArgs<T, KIND>>, the same kernel with a third argument and the loss
+//                        between the forward pass and the deltas (the template's trailing pack is empty for t1d_mlp_grad,
+//                        whose two instances are compiled from the text they always were).
+//                        coef is not read: every lane forms it from y and the loss's inputs of its sample (loss_ppo_clip /
+//                        loss_value_mse, the arithmetic of include/t1d.h) and writes it to the last layer's delta row, so
+//                        the network is evaluated once and y and coef make no round trip through memory.  Everything from
+//                        there on is the code above in its order: grad is what mlp_grad_kernel gives for the stored coef.
+//                        The four statistics of a sample are added, in double, to four per-lane sums over the wave's
+//                        tiles; behind the tile loop the 64 lane sums are folded 32, 16, .. 1 lanes down and lane 0 stores
+//                        one partial [4] per wave behind the gradient partials.  With partial == NULL the deltas and phase
+//                        B are skipped; y, coef_out and the statistics are still formed.
+//   mlp_loss_stats_kernel  stats[p][k] = the partials of policy p added in wave order.
 // Nothing here is atomic and nothing depends on the grid the hardware happens to run: two calls give the same bits.
 #pragma once
 #include "t1d_policy.hpp"
@@ -41,6 +53,63 @@ template <typename T> struct GradArgs {
     unsigned tiles_per_wave, waves_per_policy, n_waves;
     int act_rows;                         // A: F + the hidden widths
 };
+
+// t1d_mlp_loss: what the loss of a sample is formed from.  The scalars are the call's doubles converted once on the host.
+template <typename T, int KIND> struct LossArgs {   // KIND: T1D_LOSS_PPO_CLIP | T1D_LOSS_VALUE_MSE
+    const T* eps; const T* y_old; const T* adv; const T* target;
+    const T* sigma_old; const T* sigma;   // [n_policies]
+    T* coef_out;                          // [K][n] or null
+    double* stat_partial;                 // [n_waves][4] or null
+    T clip, scale;
+};
+
+// the kind of mlp_grad_kernel's trailing pack: 0 for the empty one (coef is read from memory), and its one member
+template <typename... LS> struct LossKind { static constexpr int value = 0; };
+template <typename T, int KIND> struct LossKind<LossArgs<T, KIND>> { static constexpr int value = KIND; };
+template <typename A> __device__ __forceinline__ const A& loss_first(const A& a) { return a; }
+
+// a wave-uniform word a lane computed, moved to scalar registers so that it costs no vector register in the tile loop
+__device__ __forceinline__ float loss_uniform(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); }
+__device__ __forceinline__ double loss_uniform(double v)
+{
+    const long long b = __double_as_longlong(v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b >> 32));
+    return __longlong_as_double((long long)((unsigned long long)hi << 32 | lo));
+}
+__device__ __forceinline__ float loss_exp(float x) { return expf(x); }
+__device__ __forceinline__ double loss_exp(double x) { return exp(x); }
+__device__ __forceinline__ float loss_log(float x) { return logf(x); }
+__device__ __forceinline__ double loss_log(double x) { return log(x); }
+
+// T1D_LOSS_PPO_CLIP of include/t1d.h for one sample: -> coef; st[0..3] += (loss, not active, expm1(logr) - logr, dsig).
+// dlog = log(sigma_old) - log(sigma).  e_old - e_new is exactly 0 where y == y_old and sg == so bit for bit (the two
+// quotients are then the same operation on the same words), so logr is 0 and r is 1 there however the rest is contracted.
+template <typename T>
+__device__ __forceinline__ T loss_ppo_clip(T y, T eps, T y_old, T adv, T so, T sg, T dlog, T clip, T scale, double (&st)[4])
+{
+    const T z = fma(so, eps, y_old);
+    const T e_old = (z - y_old) / so, e_new = (z - y) / sg;
+    const T logr = T(0.5) * ((e_old - e_new) * (e_old + e_new)) + dlog;
+    const T r = loss_exp(logr);
+    const T lo = T(1) - clip, hi = T(1) + clip;
+    const bool active = adv >= T(0) ? r <= hi : r >= lo;
+    const T ra = r * adv;
+    const T loss = -fmin(ra, fmin(fmax(r, lo), hi) * adv);
+    const T gg = active ? -ra : T(0);
+    const T dsig = gg * (e_new * e_new - T(1)) / sg;
+    const double lr = (double)logr;
+    st[0] += (double)loss; st[1] += active ? 0.0 : 1.0; st[2] += expm1(lr) - lr; st[3] += (double)dsig;
+    return scale * gg * e_new / sg;
+}
+
+// T1D_LOSS_VALUE_MSE
+template <typename T>
+__device__ __forceinline__ T loss_value_mse(T y, T target, T scale, double (&st)[4])
+{
+    const T d = y - target;
+    st[0] += (double)(T(0.5) * d * d);
+    return scale * d;
+}
 
 // all lanes of the wave have made their LDS writes visible to each other, and the compiler moves no access across
 __device__ __forceinline__ void grad_wave_sync()
@@ -70,10 +139,13 @@ __device__ __forceinline__ unsigned grad_rows_of(const MlpArgs<T>& c, int act_ro
     return res;                           // q beyond n_params: rows 0 and 0, read and never stored
 }
 
-// Dynamic LDS: (act_rows + 1 + the sum of all widths) * 64 words.  Grid: n_waves workgroups of 64 threads.
-template <typename T>
-__global__ __launch_bounds__(64) void mlp_grad_kernel(const MlpArgs<T> c, const GradArgs<T> g)
+// Dynamic LDS: (act_rows + 1 + the sum of all widths) * 64 words.  Grid: n_waves workgroups of 64 threads.  LS: nothing
+// (t1d_mlp_grad: coef is read from g.coef) or one LossArgs<T, KIND> (t1d_mlp_loss: coef comes from the loss, g.coef is not
+// looked at).
+template <typename T, typename... LS>
+__global__ __launch_bounds__(64) void mlp_grad_kernel(const MlpArgs<T> c, const GradArgs<T> g, const LS... lp)
 {
+    constexpr int KIND = LossKind<LS...>::value;
     typedef const __attribute__((address_space(4))) T* WPtr;
     const unsigned lane = threadIdx.x;
     const unsigned wave = blockIdx.x;
@@ -103,6 +175,14 @@ __global__ __launch_bounds__(64) void mlp_grad_kernel(const MlpArgs<T> c, const 
         const int out_w = (int)((c.widths >> (8 * l)) & 0xffu);
         w_last += out_w * (in_w + 1); x_last += in_w; d_last += out_w; in_w = out_w;
     }
+    // the loss: the policy's two sigmas and the difference of their logarithms, one per wave; the lane's four sums
+    double st[4] = {0.0, 0.0, 0.0, 0.0};
+    T so = T(1), sg = T(1), dlog = T(0);
+    if constexpr (KIND == T1D_LOSS_PPO_CLIP) {
+        const auto& ls = loss_first(lp...);
+        so = (T)((WPtr)ls.sigma_old)[pol]; sg = (T)((WPtr)ls.sigma)[pol];
+        dlog = loss_uniform(loss_log(so) - loss_log(sg));
+    }
 
 #pragma unroll 1
     for (unsigned u = t0; u < t1; ++u) {
@@ -110,12 +190,26 @@ __global__ __launch_bounds__(64) void mlp_grad_kernel(const MlpArgs<T> c, const 
         const int64_t i = (int64_t)pol * c.envs_per_policy + (int64_t)chunk * 64 + lane;
         const T* const f = g.feat + (int64_t)row * F * g.n + i;
         for (int j = 0; j < F; ++j) col[j * 64] = f[(int64_t)j * g.n];
+        T in0 = T(0), in1 = T(0), in2 = T(0);                   // the sample's loss inputs, asked for ahead of the layers
+        if constexpr (KIND == T1D_LOSS_PPO_CLIP) {
+            const auto& ls = loss_first(lp...);
+            in0 = ls.eps[(int64_t)row * g.n + i]; in1 = ls.y_old[(int64_t)row * g.n + i]; in2 = ls.adv[(int64_t)row * g.n + i];
+        }
+        if constexpr (KIND == T1D_LOSS_VALUE_MSE) in0 = loss_first(lp...).target[(int64_t)row * g.n + i];
         const T y = mlp_layers<T, true>(c, w, col, F);
         if (g.y) g.y[(int64_t)row * g.n + i] = y;
+        T coef = T(0);
+        if constexpr (KIND != 0) {
+            const auto& ls = loss_first(lp...);
+            if constexpr (KIND == T1D_LOSS_PPO_CLIP) coef = loss_ppo_clip(y, in0, in1, in2, so, sg, dlog, ls.clip, ls.scale, st);
+            else coef = loss_value_mse(y, in0, ls.scale, st);
+            if (ls.coef_out) ls.coef_out[(int64_t)row * g.n + i] = coef;
+        }
         if (!with_grad) continue;
 
         // ---- phase A, backwards: delta of layer l's outputs -> delta of layer l - 1's outputs (= layer l's inputs)
-        col[d_last * 64] = g.coef[(int64_t)row * g.n + i];
+        if constexpr (KIND == 0) coef = g.coef[(int64_t)row * g.n + i];
+        col[d_last * 64] = coef;
         int woff = w_last, xoff = x_last, doff = d_last;
 #pragma unroll 1
         for (int l = L - 1; l >= 1; --l) {
@@ -173,6 +267,23 @@ __global__ __launch_bounds__(64) void mlp_grad_kernel(const MlpArgs<T> c, const 
             if (k < n_slots && q < (unsigned)c.n_params) out[q] = acc[k];
         }
     }
+    if constexpr (KIND != 0) {
+        const auto& ls = loss_first(lp...);
+        if (ls.stat_partial) {                                   // kernel argument: wave-uniform
+            // lane l += lane l + d for l < d, as gae_moments_kernel folds: a shuffle goes through the LDS crossbar without
+            // taking LDS space, which a y-only call of a small net does not have.  Lanes >= d add words that are no
+            // longer part of the sum (or their own); they never feed lane 0, and only lane 0 is stored.
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+#pragma unroll
+                for (int d = 32; d >= 1; d >>= 1) st[k] += __shfl_down(st[k], d, 64);
+            }
+            if (lane == 0) {
+                double* const out = ls.stat_partial + 4 * (size_t)wave;
+                out[0] = st[0]; out[1] = st[1]; out[2] = st[2]; out[3] = st[3];
+            }
+        }
+    }
 }
 
 // grad[p][q] = partial[p][0][q] + partial[p][1][q] + ... in that order; one lane per parameter
@@ -186,6 +297,18 @@ __global__ __launch_bounds__(256) void mlp_grad_sum_kernel(const T* partial, T* 
     T sum = T(0);
     for (unsigned k = 0; k < waves_per_policy; ++k) sum += src[(size_t)k * n_params];
     grad[e] = sum;
+}
+
+// stats[p][k] = partial[p][0][k] + partial[p][1][k] + ... in that order; one lane per word
+__global__ __launch_bounds__(64) void mlp_loss_stats_kernel(const double* partial, double* stats, unsigned waves_per_policy, unsigned total)
+{
+    const unsigned e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= total) return;
+    const unsigned p = e >> 2, k = e & 3u;
+    const double* src = partial + 4 * (size_t)p * waves_per_policy + k;
+    double sum = 0.0;
+    for (unsigned j = 0; j < waves_per_policy; ++j) sum += src[4 * (size_t)j];
+    stats[e] = sum;
 }
 
 } // namespace t1d
