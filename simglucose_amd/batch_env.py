@@ -568,11 +568,15 @@ class BatchedT1DSimEnv:
             u = env.policy_action(pol, st); env.step(u, 0 * u)
             pol.shift(st["cgm_hist"], st["ins_hist"], env.cgm, env.insulin); st["prev_meal"] = env.meal.clone()
         """
-        p, params = self._mlp_struct("policy_action", policy, policy_state)
+        return self._policy_alone("policy_action", self._L.t1d_mlp_action, policy, policy_state, (self.n,))
+
+    def _policy_alone(self, who, fn, policy, policy_state, shape):
+        """policy_action / policy_features: fn (t1d_mlp_action, t1d_mlp_features) on the state as it is -> its output"""
+        p, params = self._mlp_struct(who, policy, policy_state)
         self._set_trace(p, None, 0)
-        out = torch.empty(self.n, dtype=self.dtype, device=self.device)
+        out = torch.empty(*shape, dtype=self.dtype, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(self._L.t1d_mlp_action(self._ctx, C.byref(self._b), C.byref(p), C.c_void_p(out.data_ptr()), self._stream()))
+            _lib.check(fn(self._ctx, C.byref(self._b), C.byref(p), C.c_void_p(out.data_ptr()), self._stream()))
         self._keep = (params, policy_state, out)
         return out
 
@@ -586,13 +590,8 @@ class BatchedT1DSimEnv:
 
             v_last = mlp_pre_output(vparams, env.policy_features(vpol, st)[None], vpol)[0]
         """
-        p, params = self._mlp_struct("policy_features", policy, policy_state)
-        self._set_trace(p, None, 0)
-        out = torch.empty(2 * int(policy.history) + 3, self.n, dtype=self.dtype, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.t1d_mlp_features(self._ctx, C.byref(self._b), C.byref(p), C.c_void_p(out.data_ptr()), self._stream()))
-        self._keep = (params, policy_state, out)
-        return out
+        return self._policy_alone("policy_features", self._L.t1d_mlp_features, policy, policy_state,
+                                  (2 * int(policy.history) + 3, self.n))
 
     def rollout_mlp_dopri5(self, n_steps, policy, policy_state=None, stats=None, trace=None, max_minutes_per_launch=240):
         """rollout_mlp in the exact mode (t1d_rollout_mlp_dopri5): n_steps closed-loop steps under the in-kernel network with
@@ -705,16 +704,10 @@ class BatchedT1DSimEnv:
             raise ValueError("n_steps must be at least 1")
         if on_done not in ("continue", "restart"):
             raise ValueError("on_done must be 'continue' or 'restart'")
-        npol = int(policy.n_policies)
-        if self.n % npol or (self.n // npol) % 64:
-            raise ValueError("%s: %d envs do not split into %d policies of a multiple of 64 envs each" % (who, self.n, npol))
         if policy_state is None:
             policy_state = self.new_policy_state(policy)
-        H = int(policy.history)
-        for k, shape in (("cgm_hist", (H, self.n)), ("ins_hist", (H, self.n)), ("prev_meal", (self.n,))):
-            t = policy_state.get(k)
-            if t is None or tuple(t.shape) != shape or t.dtype != self.dtype or t.device != self.device or not t.is_contiguous():
-                raise ValueError("policy_state['%s'] must be a contiguous %s tensor of the env's dtype on its device" % (k, shape))
+        p, params = self._mlp_struct(who, policy, policy_state, stats)
+        npol = int(policy.n_policies)
         g = _lib.Collect()
         g.explore_seed = (self.seed ^ 0x5851F42D4C957F2D if explore_seed is None else int(explore_seed)) & 0xFFFFFFFFFFFFFFFF
         if sigma is not None:
@@ -727,19 +720,9 @@ class BatchedT1DSimEnv:
                 raise _lib.T1DError("%s(on_done='restart') draws every episode on the device: not available with host normals" % who)
             r = self._restart_struct(int(days), terminal_obs, episode_stats or {}, reset_outputs, who)
             g.restart = C.pointer(r)
+            p.start_minute = r.start_minute          # _restart_struct creates the array for an env that had none
             self._b.x0_override = None
-        params = policy.device_params(self.device, self.dtype)
-        p = _lib.Mlp()
-        policy.fill_struct(p)
-        p.n_policies, p.envs_per_policy, p.n_params = npol, self.n // npol, params.shape[1]
-        p.params = params.data_ptr()
-        for k in ("cgm_hist", "ins_hist", "prev_meal"):
-            setattr(p, k, policy_state[k].data_ptr())
-        p.start_minute = self.start_minute.data_ptr() if self.start_minute is not None else None
-        stats = stats or {}
-        for k in ("sum_risk", "min_bg", "max_bg", "n_low", "n_high"):
-            setattr(p, k, stats[k].data_ptr() if k in stats else None)
-        F = 2 * H + 3
+        F = 2 * int(policy.history) + 3
         for k, f, dt, shape in (("reward", "reward_trace", self.dtype, (self.n,)), ("done", "done_trace", torch.uint8, (self.n,)),
                                 ("eps", "eps_trace", self.dtype, (self.n,)), ("features", "feat_trace", self.dtype, (F, self.n))):
             t = trace.get(k) if trace else None

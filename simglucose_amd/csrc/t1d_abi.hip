@@ -1,7 +1,12 @@
-// t1d_abi.hip -- host side of the C ABI of libt1d_hip.so (gfx950 only; see include/t1d.h): context and tables,
-// argument checks, kernel selection and launches.  A step or a roll-out is planned by plan_call (which kernel instance,
-// grid, block, dynamic LDS) and launched by launch_plan.  The kernels are in t1d_kernels.hpp, the per-lane arithmetic in
-// t1d_device.hpp.  This is the one translation unit of the library.
+// t1d_abi.hip -- host side of the C ABI of libt1d_hip.so (gfx950 only; see include/t1d.h): context and tables, argument
+// checks, kernel selection and launches.  A step or a roll-out is planned by plan_call (which kernel instance, grid,
+// block, dynamic LDS) and launched by launch_plan.  The kernels that run the policy network (t1d_policy.hpp,
+// t1d_dopri5.hpp) get their workgroup and dynamic LDS from launch_shape, through one line of constants per family
+// (shape_mlp, shape_mlp_dopri5, shape_mlp_alone); the gradient kernel's LDS is counted by grad_wave_lds.  All of these
+// are pure functions, checked on the CPU by tests/dispatch_plan_driver.cpp.  Each argument struct of a kernel has one
+// builder (make_*), each group of entry-point checks one function (check_*); by_dtype and by_variant pick the template
+// instance.  The kernels are in t1d_kernels.hpp, the per-lane arithmetic in t1d_device.hpp.  This is the one
+// translation unit of the library.
 #include "../../include/t1d.h"
 #include "t1d_kernels.hpp"
 #include "t1d_dopri5.hpp"
@@ -15,6 +20,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 // =============================================================================================
@@ -467,15 +473,18 @@ static KArgs<T> make_args(const t1d_ctx* c, const t1d_batch* b, int minutes, int
 
 static inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
 
+// f(T()) with T the word of dtype: for the entry points whose two arms would differ in double / float alone
+template <typename F>
+static auto by_dtype(int dtype, F&& f) { return dtype == T1D_F64 ? f(double()) : f(float()); }
+
 extern "C" int t1d_reset(t1d_ctx* c, const t1d_batch* b, const uint8_t* mask, int random_init_bg, void* stream)
 {
     int rc = check_batch("t1d_reset", c, b, false);
     if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (b->dtype == T1D_F64)
-        hipLaunchKernelGGL(reset_kernel<double>, grid_for(b->n), dim3(kBlock), 0, s, make_args<double>(c, b, 1, 1), mask, random_init_bg);
-    else
-        hipLaunchKernelGGL(reset_kernel<float>, grid_for(b->n), dim3(kBlock), 0, s, make_args<float>(c, b, 1, 1), mask, random_init_bg);
+    by_dtype(b->dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(reset_kernel<T>, grid_for(b->n), dim3(kBlock), 0, (hipStream_t)stream, make_args<T>(c, b, 1, 1), mask, random_init_bg);
+    });
     T1D_HIP(hipGetLastError());
     return T1D_OK;
 }
@@ -656,27 +665,29 @@ static int launch(t1d_ctx* c, const t1d_batch* b, const Plan& p, int minutes, in
     return T1D_OK;
 }
 
-// the generic kernels by variant; the split variant with per-minute step sizes is 7 in fp64, 6 in fp32
+// the generic kernels by variant: f(std::integral_constant<int, VARIANT>()) for the VARIANT of a plan; the split
+// variant with per-minute step sizes is 7 in fp64, 6 in fp32
+template <typename T, typename F>
+static auto by_variant(int variant, F&& f)
+{
+    switch (variant) {
+    case 0: return f(std::integral_constant<int, 0>());
+    case 3: return f(std::integral_constant<int, 3>());
+    case 4: return f(std::integral_constant<int, 4>());
+    default: return f(std::integral_constant<int, sizeof(T) == 8 ? 7 : 6>());
+    }
+}
+
 template <typename T, bool REFILL>
 static KernelFn<T> step_fn(int variant)
 {
-    switch (variant) {
-    case 0: return step_kernel<0, T, REFILL>;
-    case 3: return step_kernel<3, T, REFILL>;
-    case 4: return step_kernel<4, T, REFILL>;
-    default: return step_kernel<sizeof(T) == 8 ? 7 : 6, T, REFILL>;
-    }
+    return by_variant<T>(variant, [](auto v) -> KernelFn<T> { return step_kernel<decltype(v)::value, T, REFILL>; });
 }
 
 template <typename T>
 static KernelFn<T, PidArgs<T>> rollout_fn(int variant)
 {
-    switch (variant) {
-    case 0: return rollout_pid_kernel<0, T>;
-    case 3: return rollout_pid_kernel<3, T>;
-    case 4: return rollout_pid_kernel<4, T>;
-    default: return rollout_pid_kernel<sizeof(T) == 8 ? 7 : 6, T>;
-    }
+    return by_variant<T>(variant, [](auto v) -> KernelFn<T, PidArgs<T>> { return rollout_pid_kernel<decltype(v)::value, T>; });
 }
 
 template <typename T, int STRIDE>
@@ -724,16 +735,28 @@ extern "C" int t1d_step(t1d_ctx* c, const t1d_batch* b, int minutes, int n_sub, 
     return T1D_OK;
 }
 
+// What every exact-mode call asks of its arguments, checked before any device work.  rollout: n_steps closed-loop
+// steps, whose actions are the controller's and whose meals the meal table's; else one step with the batch's actions
+// (t1d_step_dopri5).
+static int check_dopri5(const char* who, const t1d_ctx* c, const t1d_batch* b, const double* h_carry, int n_steps, int minutes,
+                        bool rollout = true)
+{
+    const std::string w(who);
+    if (!c) return fail(T1D_E_INVALID, w + ": ctx is NULL");
+    if (!b) return fail(T1D_E_INVALID, w + ": batch is NULL");
+    if (!h_carry) return fail(T1D_E_INVALID, w + ": h_carry is NULL");
+    if (b->dtype != T1D_F64) return fail(T1D_E_INVALID, w + ": fp64 batches only");
+    if (rollout && n_steps < 1) return fail(T1D_E_INVALID, w + ": n_steps < 1");
+    if (minutes < 1 || minutes > 100000) return fail(T1D_E_INVALID, w + ": minutes out of range");
+    if (rollout && b->cho) return fail(T1D_E_INVALID, w + ": dense cho is not supported, use the meal table");
+    return check_batch(who, c, b, !rollout);
+}
+
 // The exact mode (t1d_dopri5.hpp): one lane per env on the grid of the generic kernel, whatever the layout; no plan, no
 // refill ahead (the noise-block refill runs inline).
 extern "C" int t1d_step_dopri5(t1d_ctx* c, const t1d_batch* b, double* h_carry, int32_t* nfev, int minutes, void* stream)
 {
-    if (!c) return fail(T1D_E_INVALID, "t1d_step_dopri5: ctx is NULL");
-    if (!b) return fail(T1D_E_INVALID, "t1d_step_dopri5: batch is NULL");
-    if (!h_carry) return fail(T1D_E_INVALID, "t1d_step_dopri5: h_carry is NULL");
-    if (b->dtype != T1D_F64) return fail(T1D_E_INVALID, "t1d_step_dopri5: fp64 batches only");
-    if (minutes < 1 || minutes > 100000) return fail(T1D_E_INVALID, "t1d_step_dopri5: minutes out of range");
-    const int rc = check_batch("t1d_step_dopri5", c, b, true);
+    const int rc = check_dopri5("t1d_step_dopri5", c, b, h_carry, /* n_steps */ 1, minutes, /* rollout */ false);
     if (rc) return rc;
     hipLaunchKernelGGL(dopri5_step_kernel, grid_for(b->n), dim3(kBlock), 0, (hipStream_t)stream, make_args<double>(c, b, minutes, 1),
                        (const double*)c->d_raw64, h_carry, nfev);
@@ -783,14 +806,22 @@ static int run_rollout(t1d_ctx* c, const t1d_batch* b, const Plan& p, const PidA
     return T1D_OK;
 }
 
+// the batch and the step count of a fixed-step closed-loop call: the controller acts, the meals are the meal table's
+static int check_closed_loop(const char* who, const t1d_ctx* c, const t1d_batch* b, int n_steps)
+{
+    const int rc = check_batch(who, c, b, false);
+    if (rc) return rc;
+    if (b->cho) return fail(T1D_E_INVALID, std::string(who) + ": dense cho is not supported, use the meal table");
+    if (n_steps < 1) return fail(T1D_E_INVALID, std::string(who) + ": n_steps < 1");
+    return T1D_OK;
+}
+
 // a closed-loop roll-out under the PID controller pid or the basal-bolus controller bb (the other one NULL)
 static int launch_rollout(const char* who, t1d_ctx* c, const t1d_batch* b, const t1d_pid* pid, const t1d_bb* bb, int n_steps,
                           int minutes, int n_sub, void* stream)
 {
-    int rc = check_batch(who, c, b, false);
+    int rc = check_closed_loop(who, c, b, n_steps);
     if (rc) return rc;
-    if (b->cho) return fail(T1D_E_INVALID, std::string(who) + ": dense cho is not supported, use the meal table");
-    if (n_steps < 1) return fail(T1D_E_INVALID, std::string(who) + ": n_steps < 1");
     Plan p;
     rc = plan_and_tables(who, c, b, minutes, n_sub, true, &p);
     if (rc) return rc;
@@ -821,12 +852,7 @@ extern "C" int t1d_rollout_bb(t1d_ctx* c, const t1d_batch* b, const t1d_bb* bb, 
 template <typename T>
 static KernelFn<T, MlpArgs<T>> mlp_rollout_fn(int variant)
 {
-    switch (variant) {
-    case 0: return mlp_rollout_kernel<0, T>;
-    case 3: return mlp_rollout_kernel<3, T>;
-    case 4: return mlp_rollout_kernel<4, T>;
-    default: return mlp_rollout_kernel<sizeof(T) == 8 ? 7 : 6, T>;
-    }
+    return by_variant<T>(variant, [](auto v) -> KernelFn<T, MlpArgs<T>> { return mlp_rollout_kernel<decltype(v)::value, T>; });
 }
 
 template <typename T>
@@ -882,23 +908,56 @@ static int check_mlp_net(const char* who, int64_t n, const t1d_mlp* m, int* cols
 
 static int check_mlp(const char* who, const t1d_batch* b, const t1d_mlp* m, int* cols) { return check_mlp_net(who, b->n, m, cols, true); }
 
-// the launch shape of the policy kernels, into the plan and the policy's arguments
+// The launch shape of the kernels that run the policy: every wave of a workgroup has per_wave bytes of dynamic LDS of
+// its own, behind front bytes they share (rounded up to 16) and beside fixed bytes of static LDS.  The workgroup is the
+// largest, from `largest` threads down by halves to one wave, whose LDS stays within the ceiling.  A pure function,
+// like plan_call; each family below brings its constants and its refusal.  Checked on the CPU by
+// tests/dispatch_plan_driver.cpp.
+struct Shape { unsigned threads = 0, grid = 0; size_t front = 0, lds = 0; };   // lds: dynamic bytes; front: where the waves' begin
+
+static bool launch_shape(int64_t n, size_t fixed, size_t front, size_t per_wave, unsigned largest, size_t ceiling, Shape* sh)
+{
+    sh->front = (front + 15) & ~(size_t)15;
+    sh->threads = largest;
+    while (sh->threads > 64 && fixed + sh->front + per_wave * (sh->threads / 64) > ceiling) sh->threads /= 2;
+    sh->grid = (unsigned)((n + sh->threads - 1) / sh->threads);
+    sh->lds = sh->front + per_wave * (sh->threads / 64);
+    return fixed + sh->lds <= ceiling;      // false: not even one wave fits
+}
+
+// the fixed-step kernels' (t1d_rollout_mlp, t1d_collect_mlp), into the plan and the policy's arguments.  Dynamic LDS:
+// the propagator table as the plan sized it, then the columns of every wave (the LDS-parameter variants hold theirs in
+// static LDS)
 template <typename T>
 static int shape_mlp(const char* who, const t1d_ctx* c, const t1d_batch* b, int cols, Plan& p, MlpArgs<T>& ma)
 {
-    // dynamic LDS: the propagator table as the plan sized it, then the columns of every wave; the workgroup is the
-    // largest whose columns fit beside the tables (the LDS-parameter variants hold theirs in static LDS)
-    ma.lds_off = (int)((p.lds + 15) & ~(size_t)15);
-    ma.cols = cols;
     const size_t fixed = (p.variant == 0 || p.variant == 7 ? (size_t)DP_COUNT * kMaxPatients * sizeof(T) : 0) + 256;   // static LDS
-    const size_t per_wave = (size_t)cols * 64 * sizeof(T);
-    int threads = T1D_POLICY_THREADS;
-    while (threads > 64 && fixed + ma.lds_off + per_wave * (threads / 64) > (size_t)c->lds_per_block) threads /= 2;
-    if (fixed + ma.lds_off + per_wave * (threads / 64) > (size_t)c->lds_per_block)
+    Shape sh;
+    if (!launch_shape(b->n, fixed, p.lds, (size_t)cols * 64 * sizeof(T), T1D_POLICY_THREADS, (size_t)c->lds_per_block, &sh))
         return fail(T1D_E_INVALID, std::string(who) + ": the integrator's tables leave no room in LDS for one wave of this policy");
-    p.lds = ma.lds_off + per_wave * (threads / 64);
-    p.block = threads; p.grid = (unsigned)((b->n + threads - 1) / threads);
+    ma.lds_off = (int)sh.front; ma.cols = cols;
+    p.lds = sh.lds; p.block = sh.threads; p.grid = sh.grid;
     return T1D_OK;
+}
+
+// the exact mode's (dopri5_mlp_rollout_kernel, dopri5_mlp_collect_kernel): for every wave RollCold's words and the
+// policy's columns; the workgroup is the most waves (4, 2 or 1) whose pieces fit beside the raw patient rows
+static int shape_mlp_dopri5(const char* who, const t1d_ctx* c, int64_t n, int cols, Shape* sh)
+{
+    const size_t fixed = (size_t)kRawPars * kMaxPatients * sizeof(double) + 256;           // static LDS
+    if (!launch_shape(n, fixed, 0, (size_t)kRollColdWaveBytes + (size_t)cols * 64 * sizeof(double), kBlock, (size_t)c->lds_per_block, sh))
+        return fail(T1D_E_INVALID, std::string(who) + ": the patient rows leave no room in LDS for one wave of this policy");
+    return T1D_OK;
+}
+
+// the policy's alone (mlp_action_kernel, mlp_features_kernel): the columns of every wave, within the 64 KiB any kernel
+// may have without asking; one wave of the widest policy is 28 KiB, so there is nothing to refuse
+template <typename T>
+static Shape shape_mlp_alone(const t1d_ctx* c, int64_t n, int cols)
+{
+    Shape sh;
+    (void)launch_shape(n, 0, 0, (size_t)cols * 64 * sizeof(T), T1D_POLICY_THREADS, std::min<size_t>((size_t)c->lds_per_block, 65536) - 256, &sh);
+    return sh;
 }
 
 template <typename T>
@@ -913,10 +972,8 @@ static int run_rollout_mlp(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* m, Pla
 extern "C" int t1d_rollout_mlp(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, int n_steps, int minutes,
                                int n_sub, void* stream)
 {
-    int rc = check_batch("t1d_rollout_mlp", c, b, false);
+    int rc = check_closed_loop("t1d_rollout_mlp", c, b, n_steps);
     if (rc) return rc;
-    if (b->cho) return fail(T1D_E_INVALID, "t1d_rollout_mlp: dense cho is not supported, use the meal table");
-    if (n_steps < 1) return fail(T1D_E_INVALID, "t1d_rollout_mlp: n_steps < 1");
     int cols = 0;
     rc = check_mlp("t1d_rollout_mlp", b, mlp, &cols);
     if (rc) return rc;
@@ -933,24 +990,11 @@ extern "C" int t1d_rollout_mlp(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* ml
 }
 
 // The exact mode's roll-outs (t1d_dopri5.hpp): all n_steps in one launch of dopri5_rollout_kernel on the grid of
-// dopri5_step_kernel, every lane at its own pace; no plan, no refill ahead.  Every argument is checked before any device work.
-static int check_rollout_dopri5(const char* who, const t1d_ctx* c, const t1d_batch* b, const double* h_carry, int n_steps, int minutes)
-{
-    const std::string w(who);
-    if (!c) return fail(T1D_E_INVALID, w + ": ctx is NULL");
-    if (!b) return fail(T1D_E_INVALID, w + ": batch is NULL");
-    if (!h_carry) return fail(T1D_E_INVALID, w + ": h_carry is NULL");
-    if (b->dtype != T1D_F64) return fail(T1D_E_INVALID, w + ": fp64 batches only");
-    if (n_steps < 1) return fail(T1D_E_INVALID, w + ": n_steps < 1");
-    if (minutes < 1 || minutes > 100000) return fail(T1D_E_INVALID, w + ": minutes out of range");
-    if (b->cho) return fail(T1D_E_INVALID, w + ": dense cho is not supported, use the meal table");
-    return check_batch(who, c, b, false);
-}
-
+// dopri5_step_kernel, every lane at its own pace; no plan, no refill ahead.
 static int launch_rollout_dopri5(const char* who, t1d_ctx* c, const t1d_batch* b, const t1d_pid* pid, const t1d_bb* bb,
                                  double* h_carry, int32_t* nfev, int n_steps, int minutes, void* stream)
 {
-    const int rc = check_rollout_dopri5(who, c, b, h_carry, n_steps, minutes);
+    const int rc = check_dopri5(who, c, b, h_carry, n_steps, minutes);
     if (rc) return rc;
     hipLaunchKernelGGL(dopri5_rollout_kernel, grid_for(b->n), dim3(kBlock), 0, (hipStream_t)stream, make_args<double>(c, b, minutes, 1),
                        pid ? make_pid<double>(pid, n_steps) : make_bb<double>(bb, n_steps), (const double*)c->d_raw64, h_carry, nfev);
@@ -973,89 +1017,65 @@ extern "C" int t1d_rollout_bb_dopri5(t1d_ctx* c, const t1d_batch* b, const t1d_b
     return launch_rollout_dopri5("t1d_rollout_bb_dopri5", c, b, nullptr, bb, h_carry, nfev, n_steps, minutes, stream);
 }
 
-// The exact mode's roll-out under the policy of t1d_mlp (dopri5_mlp_rollout_kernel, t1d_dopri5.hpp).  Dynamic LDS: for every
-// wave RollCold's words and the policy's columns; the workgroup is the most waves (4, 2 or 1) whose pieces fit beside the raw
-// patient rows.
+// one launch of an exact-mode policy kernel in the shape of shape_mlp_dopri5; rest: what the kernel takes behind KArgs
+template <typename... X, typename... A>
+static int launch_mlp_dopri5(const char* who, t1d_ctx* c, const t1d_batch* b, int cols, int minutes, void* stream,
+                             KernelFn<double, X...> kernel, A... rest)
+{
+    Shape sh;
+    const int rc = shape_mlp_dopri5(who, c, b->n, cols, &sh);
+    if (rc) return rc;
+    T1D_HIP(allow_lds(c, (const void*)kernel, sh.lds));
+    hipLaunchKernelGGL(kernel, dim3(sh.grid), dim3(sh.threads), sh.lds, (hipStream_t)stream, make_args<double>(c, b, minutes, 1), rest...);
+    T1D_HIP(hipGetLastError());
+    return T1D_OK;
+}
+
+// The exact mode's roll-out under the policy of t1d_mlp (dopri5_mlp_rollout_kernel, t1d_dopri5.hpp).
 extern "C" int t1d_rollout_mlp_dopri5(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, double* h_carry, int32_t* nfev,
                                       int n_steps, int minutes, void* stream)
 {
     const char* who = "t1d_rollout_mlp_dopri5";
-    int rc = check_rollout_dopri5(who, c, b, h_carry, n_steps, minutes);
+    int rc = check_dopri5(who, c, b, h_carry, n_steps, minutes);
     if (rc) return rc;
     int cols = 0;
     rc = check_mlp(who, b, mlp, &cols);
     if (rc) return rc;
     MlpArgs<double> ma = make_mlp<double>(mlp, n_steps);
     ma.cols = cols;
-    const size_t fixed = (size_t)kRawPars * kMaxPatients * sizeof(double) + 256;           // static LDS
-    const size_t per_wave = (size_t)kRollColdWaveBytes + (size_t)cols * 64 * sizeof(double);
-    int threads = kBlock;
-    while (threads > 64 && fixed + per_wave * (threads / 64) > (size_t)c->lds_per_block) threads /= 2;
-    if (fixed + per_wave * (threads / 64) > (size_t)c->lds_per_block)
-        return fail(T1D_E_INVALID, std::string(who) + ": the patient rows leave no room in LDS for one wave of this policy");
-    const size_t dyn = per_wave * (threads / 64);
-    T1D_HIP(allow_lds(c, (const void*)dopri5_mlp_rollout_kernel, dyn));
-    hipLaunchKernelGGL(dopri5_mlp_rollout_kernel, dim3((unsigned)((b->n + threads - 1) / threads)), dim3(threads), dyn, (hipStream_t)stream,
-                       make_args<double>(c, b, minutes, 1), ma, (const double*)c->d_raw64, h_carry, nfev);
-    T1D_HIP(hipGetLastError());
-    return T1D_OK;
+    return launch_mlp_dopri5(who, c, b, cols, minutes, stream, dopri5_mlp_rollout_kernel, ma, (const double*)c->d_raw64, h_carry, nfev);
 }
 
-// The policy alone (mlp_action_kernel, t1d_dopri5.hpp): dynamic LDS is the columns of every wave, within the 64 KiB any
-// kernel may have without asking.
-template <typename T>
-static void launch_mlp_action(const t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, int cols, void* action, hipStream_t s)
+// The policy alone (mlp_action_kernel, t1d_dopri5.hpp) or its features alone (mlp_features_kernel, t1d_policy.hpp), of
+// the state as it is: nothing is stepped.  what: the name of the output in the messages.
+template <typename K>
+static int launch_mlp_alone(const char* who, const char* what, t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, void* out, void* stream, K kernel)
 {
-    MlpArgs<T> ma = make_mlp<T>(mlp, 0);
-    ma.cols = cols;
-    const size_t per_wave = (size_t)cols * 64 * sizeof(T), room = std::min<size_t>((size_t)c->lds_per_block, 65536) - 256;
-    int threads = T1D_POLICY_THREADS;
-    while (threads > 64 && per_wave * (threads / 64) > room) threads /= 2;
-    hipLaunchKernelGGL(mlp_action_kernel<T>, dim3((unsigned)((b->n + threads - 1) / threads)), dim3(threads), per_wave * (threads / 64), s,
-                       make_args<T>(c, b, 1, 1), ma, (T*)action);
+    int rc = check_batch(who, c, b, false);
+    if (rc) return rc;
+    if (!out) return fail(T1D_E_INVALID, std::string(who) + ": " + what + " is NULL");
+    int cols = 0;
+    rc = check_mlp(who, b, mlp, &cols);
+    if (rc) return rc;
+    by_dtype(b->dtype, [&](auto t) {
+        using T = decltype(t);
+        MlpArgs<T> ma = make_mlp<T>(mlp, 0);
+        ma.cols = cols;
+        const Shape sh = shape_mlp_alone<T>(c, b->n, cols);
+        hipLaunchKernelGGL(kernel(t), dim3(sh.grid), dim3(sh.threads), sh.lds, (hipStream_t)stream, make_args<T>(c, b, 1, 1), ma, (T*)out);
+    });
+    T1D_HIP(hipGetLastError());
+    return T1D_OK;
 }
 
 extern "C" int t1d_mlp_action(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, void* action, void* stream)
 {
-    const char* who = "t1d_mlp_action";
-    int rc = check_batch(who, c, b, false);
-    if (rc) return rc;
-    if (!action) return fail(T1D_E_INVALID, "t1d_mlp_action: action is NULL");
-    int cols = 0;
-    rc = check_mlp(who, b, mlp, &cols);
-    if (rc) return rc;
-    if (b->dtype == T1D_F64) launch_mlp_action<double>(c, b, mlp, cols, action, (hipStream_t)stream);
-    else launch_mlp_action<float>(c, b, mlp, cols, action, (hipStream_t)stream);
-    T1D_HIP(hipGetLastError());
-    return T1D_OK;
-}
-
-// The features alone (mlp_features_kernel, t1d_policy.hpp): the launch shape of launch_mlp_action.
-template <typename T>
-static void launch_mlp_features(const t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, int cols, void* feat, hipStream_t s)
-{
-    MlpArgs<T> ma = make_mlp<T>(mlp, 0);
-    ma.cols = cols;
-    const size_t per_wave = (size_t)cols * 64 * sizeof(T), room = std::min<size_t>((size_t)c->lds_per_block, 65536) - 256;
-    int threads = T1D_POLICY_THREADS;
-    while (threads > 64 && per_wave * (threads / 64) > room) threads /= 2;
-    hipLaunchKernelGGL(mlp_features_kernel<T>, dim3((unsigned)((b->n + threads - 1) / threads)), dim3(threads), per_wave * (threads / 64), s,
-                       make_args<T>(c, b, 1, 1), ma, (T*)feat);
+    return launch_mlp_alone("t1d_mlp_action", "action", c, b, mlp, action, stream, [](auto t) { return mlp_action_kernel<decltype(t)>; });
 }
 
 extern "C" int t1d_mlp_features(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, void* feat, void* stream)
 {
-    const char* who = "t1d_mlp_features";
-    int rc = check_batch(who, c, b, false);
-    if (rc) return rc;
-    if (!feat) return fail(T1D_E_INVALID, "t1d_mlp_features: feat is NULL");
-    int cols = 0;
-    rc = check_mlp(who, b, mlp, &cols);
-    if (rc) return rc;
-    if (b->dtype == T1D_F64) launch_mlp_features<double>(c, b, mlp, cols, feat, (hipStream_t)stream);
-    else launch_mlp_features<float>(c, b, mlp, cols, feat, (hipStream_t)stream);
-    T1D_HIP(hipGetLastError());
-    return T1D_OK;
+    return launch_mlp_alone("t1d_mlp_features", "feat", c, b, mlp, feat, stream, [](auto t) { return mlp_features_kernel<decltype(t)>; });
 }
 
 // the six meal windows of RandomScenario.create_scenario (scenario_gen.py:38-45) as the kernels take them
@@ -1131,22 +1151,27 @@ extern "C" int t1d_restart_done(t1d_ctx* c, const t1d_batch* b, const uint8_t* m
     if (r->h_carry && b->dtype != T1D_F64) return fail(T1D_E_INVALID, "t1d_restart_done: h_carry belongs to fp64 batches");
     rc = check_batch("t1d_restart_done", c, b, false);
     if (rc) return rc;
-    if (b->dtype == T1D_F64) launch_restart<double>(c, b, mask, r, (hipStream_t)stream);
-    else launch_restart<float>(c, b, mask, r, (hipStream_t)stream);
+    by_dtype(b->dtype, [&](auto t) { launch_restart<decltype(t)>(c, b, mask, r, (hipStream_t)stream); });
     T1D_HIP(hipGetLastError());
     return T1D_OK;
 }
 
 // ---- t1d_collect_mlp (t1d_policy.hpp) ---------------------------------------------------------------------------------
+template <typename T> using CollectFn = KernelFn<T, MlpArgs<T>, CollectArgs<T>, RestartArgs<T>>;
 template <typename T>
-static KernelFn<T, MlpArgs<T>, CollectArgs<T>, RestartArgs<T>> mlp_collect_fn(int variant)
+static CollectFn<T> mlp_collect_fn(int variant)
 {
-    switch (variant) {
-    case 0: return mlp_collect_kernel<0, T>;
-    case 3: return mlp_collect_kernel<3, T>;
-    case 4: return mlp_collect_kernel<4, T>;
-    default: return mlp_collect_kernel<sizeof(T) == 8 ? 7 : 6, T>;
-    }
+    return by_variant<T>(variant, [](auto v) -> CollectFn<T> { return mlp_collect_kernel<decltype(v)::value, T>; });
+}
+
+template <typename T>
+static CollectArgs<T> make_collect(const t1d_ctx* c, const t1d_collect* g)
+{
+    CollectArgs<T> ga;
+    ga.explore_seed = g->explore_seed; ga.sigma = (const T*)g->sigma; ga.on_done = g->on_done;
+    ga.reward_trace = (T*)g->reward_trace; ga.done_trace = g->done_trace; ga.eps_trace = (T*)g->eps_trace; ga.feat_trace = (T*)g->feat_trace;
+    ga.slots = c->d_slots;
+    return ga;
 }
 
 template <typename T>
@@ -1156,16 +1181,13 @@ static int run_collect_mlp(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* m, con
     MlpArgs<T> ma = make_mlp<T>(m, n_steps);
     const int rc = shape_mlp<T>("t1d_collect_mlp", c, b, cols, p, ma);
     if (rc) return rc;
-    CollectArgs<T> ga;
-    ga.explore_seed = g->explore_seed; ga.sigma = (const T*)g->sigma; ga.on_done = g->on_done;
-    ga.reward_trace = (T*)g->reward_trace; ga.done_trace = g->done_trace; ga.eps_trace = (T*)g->eps_trace; ga.feat_trace = (T*)g->feat_trace;
-    ga.slots = c->d_slots;
     const RestartArgs<T> ra = g->on_done == T1D_COLLECT_RESTART ? make_restart<T>(g->restart) : RestartArgs<T>{};
-    return launch(c, b, p, minutes, n_sub, s, mlp_collect_fn<T>(p.variant), ma, ga, ra);
+    return launch(c, b, p, minutes, n_sub, s, mlp_collect_fn<T>(p.variant), ma, make_collect<T>(c, g), ra);
 }
 
-// what a t1d_collect must be, for both collectors; needs no device.  h_carry: the exact mode's array (NULL: fixed-step)
-static int check_collect(const char* who, const t1d_batch* b, const t1d_collect* g, const double* h_carry)
+// what a t1d_collect must be, for both collectors, and the policy beside it (checked by check_mlp; NULL is left to
+// that); needs no device.  h_carry: the exact mode's array (NULL: fixed-step)
+static int check_collect(const char* who, const t1d_batch* b, const t1d_mlp* m, const t1d_collect* g, const double* h_carry)
 {
     const std::string w = std::string(who) + ": ";
     if (!g) return fail(T1D_E_INVALID, w + "collect is NULL");
@@ -1180,6 +1202,10 @@ static int check_collect(const char* who, const t1d_batch* b, const t1d_collect*
             return fail(T1D_E_INVALID, w + "restart.h_carry must be NULL (the exact mode's collector is t1d_collect_mlp_dopri5)");
         if (h_carry && g->restart->h_carry && g->restart->h_carry != h_carry)
             return fail(T1D_E_INVALID, w + "restart.h_carry must be NULL or the call's h_carry");
+        // a restarted env's time-of-day features follow its new start: the array the restart writes is the one the
+        // policy reads
+        if (m && m->start_minute && m->start_minute != g->restart->start_minute)
+            return fail(T1D_E_INVALID, w + "mlp.start_minute must be restart.start_minute (or NULL)");
     }
     return T1D_OK;
 }
@@ -1188,18 +1214,13 @@ extern "C" int t1d_collect_mlp(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* ml
                                int n_sub, void* stream)
 {
     const char* who = "t1d_collect_mlp";
-    int rc = check_collect(who, b, g, nullptr);
+    int rc = check_collect(who, b, mlp, g, nullptr);
     if (rc) return rc;
-    rc = check_batch(who, c, b, false);
+    rc = check_closed_loop(who, c, b, n_steps);
     if (rc) return rc;
-    if (b->cho) return fail(T1D_E_INVALID, "t1d_collect_mlp: dense cho is not supported, use the meal table");
-    if (n_steps < 1) return fail(T1D_E_INVALID, "t1d_collect_mlp: n_steps < 1");
     int cols = 0;
     rc = check_mlp(who, b, mlp, &cols);
     if (rc) return rc;
-    // a restarted env's time-of-day features follow its new start: the array the restart writes is the one the policy reads
-    if (g->on_done == T1D_COLLECT_RESTART && mlp->start_minute && mlp->start_minute != g->restart->start_minute)
-        return fail(T1D_E_INVALID, "t1d_collect_mlp: mlp.start_minute must be restart.start_minute (or NULL)");
     Plan p;
     rc = plan_and_tables(who, c, b, minutes, n_sub, true, &p, true);
     if (rc) return rc;
@@ -1212,42 +1233,24 @@ extern "C" int t1d_collect_mlp(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* ml
 }
 
 // The exact mode's collector (dopri5_mlp_collect_kernel, t1d_dopri5.hpp): the checks of t1d_rollout_mlp_dopri5 and of
-// t1d_collect_mlp, then one launch with the LDS pieces and the workgroup of t1d_rollout_mlp_dopri5.
+// t1d_collect_mlp, then one launch in the shape of t1d_rollout_mlp_dopri5.
 extern "C" int t1d_collect_mlp_dopri5(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_collect* g, double* h_carry,
                                       int32_t* nfev, int n_steps, int minutes, void* stream)
 {
     const char* who = "t1d_collect_mlp_dopri5";
-    int rc = check_rollout_dopri5(who, c, b, h_carry, n_steps, minutes);
+    int rc = check_dopri5(who, c, b, h_carry, n_steps, minutes);
     if (rc) return rc;
-    rc = check_collect(who, b, g, h_carry);
+    rc = check_collect(who, b, mlp, g, h_carry);
     if (rc) return rc;
     int cols = 0;
     rc = check_mlp(who, b, mlp, &cols);
     if (rc) return rc;
-    // a restarted env's time-of-day features follow its new start: the array the restart writes is the one the policy reads
-    if (g->on_done == T1D_COLLECT_RESTART && mlp->start_minute && mlp->start_minute != g->restart->start_minute)
-        return fail(T1D_E_INVALID, std::string(who) + ": mlp.start_minute must be restart.start_minute (or NULL)");
     MlpArgs<double> ma = make_mlp<double>(mlp, n_steps);
     ma.cols = cols;
-    CollectArgs<double> ga;
-    ga.explore_seed = g->explore_seed; ga.sigma = (const double*)g->sigma; ga.on_done = g->on_done;
-    ga.reward_trace = (double*)g->reward_trace; ga.done_trace = g->done_trace; ga.eps_trace = (double*)g->eps_trace;
-    ga.feat_trace = (double*)g->feat_trace;
-    ga.slots = c->d_slots;
     RestartArgs<double> ra = g->on_done == T1D_COLLECT_RESTART ? make_restart<double>(g->restart) : RestartArgs<double>{};
     if (g->on_done == T1D_COLLECT_RESTART) ra.h_carry = h_carry;      // the env's predicted step is part of what restarts
-    const size_t fixed = (size_t)kRawPars * kMaxPatients * sizeof(double) + 256;           // static LDS
-    const size_t per_wave = (size_t)kRollColdWaveBytes + (size_t)cols * 64 * sizeof(double);
-    int threads = kBlock;
-    while (threads > 64 && fixed + per_wave * (threads / 64) > (size_t)c->lds_per_block) threads /= 2;
-    if (fixed + per_wave * (threads / 64) > (size_t)c->lds_per_block)
-        return fail(T1D_E_INVALID, std::string(who) + ": the patient rows leave no room in LDS for one wave of this policy");
-    const size_t dyn = per_wave * (threads / 64);
-    T1D_HIP(allow_lds(c, (const void*)dopri5_mlp_collect_kernel, dyn));
-    hipLaunchKernelGGL(dopri5_mlp_collect_kernel, dim3((unsigned)((b->n + threads - 1) / threads)), dim3(threads), dyn, (hipStream_t)stream,
-                       make_args<double>(c, b, minutes, 1), ma, ga, ra, (const double*)c->d_raw64, h_carry, nfev);
-    T1D_HIP(hipGetLastError());
-    return T1D_OK;
+    return launch_mlp_dopri5(who, c, b, cols, minutes, stream, dopri5_mlp_collect_kernel, ma, make_collect<double>(c, g), ra,
+                             (const double*)c->d_raw64, h_carry, nfev);
 }
 
 extern "C" int t1d_random_meals(int hip_device, uint64_t seed, int64_t env_offset, int64_t n, int dtype, int days,
@@ -1262,13 +1265,11 @@ extern "C" int t1d_random_meals(int hip_device, uint64_t seed, int64_t env_offse
         return fail(T1D_E_INVALID, "t1d_random_meals: start minute of day must be in [0, 1440)");
     T1D_HIP(hipSetDevice(hip_device));
     const MealSlots ms = meal_slots();
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == T1D_F64)
-        hipLaunchKernelGGL(random_meals_kernel<double>, grid_for(n), dim3(kBlock), 0, s, seed, env_offset, n, days,
-                           start_minute_of_day, start_scalar, meal_time, (double*)meal_amt, ms);
-    else
-        hipLaunchKernelGGL(random_meals_kernel<float>, grid_for(n), dim3(kBlock), 0, s, seed, env_offset, n, days,
-                           start_minute_of_day, start_scalar, meal_time, (float*)meal_amt, ms);
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(random_meals_kernel<T>, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, seed, env_offset, n, days,
+                           start_minute_of_day, start_scalar, meal_time, (T*)meal_amt, ms);
+    });
     T1D_HIP(hipGetLastError());
     return T1D_OK;
 }
@@ -1283,14 +1284,12 @@ extern "C" int t1d_outcome_stats(int hip_device, int dtype, int64_t n, int64_t n
     if ((out->pct || out->zone) && !(out->q_lo >= 0.0 && out->q_lo <= 100.0 && out->q_hi >= 0.0 && out->q_hi <= 100.0))
         return fail(T1D_E_INVALID, "t1d_outcome_stats: percentiles must be in [0, 100]");
     T1D_HIP(hipSetDevice(hip_device));
-    hipStream_t s = (hipStream_t)stream;
     const int chunk = out->chunk > 0 ? out->chunk : 60;
-    if (dtype == T1D_F64)
-        hipLaunchKernelGGL(outcome_kernel<double>, grid_for(n), dim3(kBlock), 0, s, n, n_rows, (const double*)bg_trace, out->counts,
-                           (double*)out->pct, out->zone, (double*)out->risk_trace, out->q_lo, out->q_hi, chunk);
-    else
-        hipLaunchKernelGGL(outcome_kernel<float>, grid_for(n), dim3(kBlock), 0, s, n, n_rows, (const float*)bg_trace, out->counts,
-                           (float*)out->pct, out->zone, (float*)out->risk_trace, out->q_lo, out->q_hi, chunk);
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(outcome_kernel<T>, grid_for(n), dim3(kBlock), 0, (hipStream_t)stream, n, n_rows, (const T*)bg_trace, out->counts,
+                           (T*)out->pct, out->zone, (T*)out->risk_trace, out->q_lo, out->q_hi, chunk);
+    });
     T1D_HIP(hipGetLastError());
     return T1D_OK;
 }
@@ -1326,52 +1325,82 @@ static int64_t grad_workspace_bytes(const t1d_mlp* m, int dtype, const GradParti
     return m->n_policies * gp.waves_per_policy * m->n_params * (int64_t)(dtype == T1D_F64 ? sizeof(double) : sizeof(float));
 }
 
-extern "C" int64_t t1d_mlp_grad_workspace(const t1d_mlp* mlp, int dtype, int64_t n, int64_t n_rows)
+// t1d_mlp_loss: t1d_mlp_grad's partition and gradient partials, and one partial [4] of doubles per wave behind them
+static int64_t loss_stats_offset(const t1d_mlp* m, int dtype, const GradPartition& gp)
 {
-    // the weights themselves are not needed to size the workspace
-    t1d_mlp m;
-    if (!mlp) return fail(T1D_E_INVALID, "t1d_mlp_grad_workspace: mlp is NULL");
-    m = *mlp;
-    if (!m.params) m.params = &m;
-    GradPartition gp;
-    const int rc = check_mlp_grad("t1d_mlp_grad_workspace", dtype, n, &m, n_rows, &gp);
-    if (rc) return rc;
-    return grad_workspace_bytes(&m, dtype, gp);
+    return (grad_workspace_bytes(m, dtype, gp) + 7) / 8 * 8;
 }
 
-// The LDS of one wave of mlp_grad_kernel (t1d_policy_grad.hpp): act_rows = F + the hidden widths of activations; with grad
-// one row of ones and one delta row per unit of every layer behind them.  Above 64 KiB the kernel's ceiling is raised, and a
-// net that does not fit the device is refused.  Every row a variant of the kernel adds must be counted here.
-static int grad_lds(const char* who, const t1d_mlp* m, bool with_grad, size_t word, const void* kernel, int* act_rows, size_t* lds)
+static int64_t loss_workspace_bytes(const t1d_mlp* m, int dtype, const GradPartition& gp)
+{
+    return loss_stats_offset(m, dtype, gp) + m->n_policies * gp.waves_per_policy * 4 * (int64_t)sizeof(double);
+}
+
+// the workspace of a call of these shapes; the weights themselves are not needed to size it
+static int64_t mlp_workspace(const char* who, const t1d_mlp* mlp, int dtype, int64_t n, int64_t n_rows,
+                             int64_t (*bytes)(const t1d_mlp*, int, const GradPartition&))
+{
+    if (!mlp) return fail(T1D_E_INVALID, std::string(who) + ": mlp is NULL");
+    t1d_mlp m = *mlp;
+    if (!m.params) m.params = &m;
+    GradPartition gp;
+    const int rc = check_mlp_grad(who, dtype, n, &m, n_rows, &gp);
+    if (rc) return rc;
+    return bytes(&m, dtype, gp);
+}
+
+extern "C" int64_t t1d_mlp_grad_workspace(const t1d_mlp* mlp, int dtype, int64_t n, int64_t n_rows)
+{
+    return mlp_workspace("t1d_mlp_grad_workspace", mlp, dtype, n, n_rows, grad_workspace_bytes);
+}
+
+extern "C" int64_t t1d_mlp_loss_workspace(const t1d_mlp* mlp, int dtype, int64_t n, int64_t n_rows)
+{
+    return mlp_workspace("t1d_mlp_loss_workspace", mlp, dtype, n, n_rows, loss_workspace_bytes);
+}
+
+// The LDS of one wave of mlp_grad_kernel (t1d_policy_grad.hpp): act_rows = F + the hidden widths of activations; with
+// grad one row of ones and one delta row per unit of every layer behind them.  Every row a variant of the kernel adds
+// must be counted here.  From the policy alone: checked on the CPU by tests/dispatch_plan_driver.cpp.
+static size_t grad_wave_lds(const t1d_mlp* m, bool with_grad, size_t word, int* act_rows)
 {
     int rows = 2 * m->history + 3, deltas = 0;
     for (int l = 0; l < m->n_layers; ++l) { if (l + 1 < m->n_layers) rows += m->width[l]; deltas += m->width[l]; }
     *act_rows = rows;
-    *lds = (size_t)(with_grad ? rows + 1 + deltas : rows) * 64 * word;      // without grad only the activations are kept
-    if (*lds > 65536) {
+    return (size_t)(with_grad ? rows + 1 + deltas : rows) * 64 * word;      // without grad only the activations are kept
+}
+
+// Above 64 KiB the kernel's ceiling is raised, and a net that does not fit the device is refused.
+static int grad_lds(const char* who, const void* kernel, size_t lds)
+{
+    if (lds > 65536) {
         int limit = 0, dev = 0;
         T1D_HIP(hipGetDevice(&dev));
         T1D_HIP(hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
-        if (*lds > (size_t)limit) return fail(T1D_E_INVALID, std::string(who) + ": one wave of this policy does not fit in the device's LDS");
-        T1D_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds));
+        if (lds > (size_t)limit) return fail(T1D_E_INVALID, std::string(who) + ": one wave of this policy does not fit in the device's LDS");
+        T1D_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
     return T1D_OK;
 }
 
-template <typename T>
-static int launch_mlp_grad(const t1d_mlp* m, int64_t n, const t1d_mlp_batch* io, const GradPartition& gp, hipStream_t s)
+// mlp_grad_kernel<T, LS...> with one wave per partial sum of the partition, then the sum of the partials.  io: a
+// t1d_mlp_batch or a t1d_mlp_loss (feat, y, grad, workspace); ls: the LossArgs of t1d_mlp_loss, nothing for
+// t1d_mlp_grad.
+template <typename T, typename IO, typename... LS>
+static int launch_grad(const char* who, const t1d_mlp* m, int64_t n, const IO* io, const void* coef, const GradPartition& gp, hipStream_t s,
+                       LS... ls)
 {
     MlpArgs<T> c = make_mlp<T>(m, 0);
     GradArgs<T> g;
-    g.feat = (const T*)io->feat; g.coef = (const T*)io->coef; g.y = (T*)io->y; g.partial = io->grad ? (T*)io->workspace : nullptr;
+    g.feat = (const T*)io->feat; g.coef = (const T*)coef; g.y = (T*)io->y; g.partial = io->grad ? (T*)io->workspace : nullptr;
     g.n = n;
     g.chunks = (unsigned)gp.chunks; g.tiles = (unsigned)gp.tiles; g.tiles_per_wave = (unsigned)gp.tiles_per_wave;
     g.waves_per_policy = (unsigned)gp.waves_per_policy; g.n_waves = (unsigned)(m->n_policies * gp.waves_per_policy);
-    size_t lds = 0;
-    const int rc = grad_lds("t1d_mlp_grad", m, io->grad != nullptr, sizeof(T), (const void*)(void (*)(MlpArgs<T>, GradArgs<T>))mlp_grad_kernel<T>,
-                            &g.act_rows, &lds);
+    void (*const fn)(MlpArgs<T>, GradArgs<T>, LS...) = mlp_grad_kernel<T, LS...>;
+    const size_t lds = grad_wave_lds(m, io->grad != nullptr, sizeof(T), &g.act_rows);
+    const int rc = grad_lds(who, (const void*)fn, lds);
     if (rc) return rc;
-    hipLaunchKernelGGL(mlp_grad_kernel<T>, dim3(g.n_waves), dim3(64), lds, s, c, g);
+    hipLaunchKernelGGL(fn, dim3(g.n_waves), dim3(64), lds, s, c, g, ls...);
     if (io->grad) {
         const unsigned total = (unsigned)(m->n_policies * m->n_params);
         hipLaunchKernelGGL(mlp_grad_sum_kernel<T>, dim3((total + 255) / 256), dim3(256), 0, s, (const T*)io->workspace, (T*)io->grad,
@@ -1394,67 +1423,28 @@ extern "C" int t1d_mlp_grad(int hip_device, int dtype, int64_t n, const t1d_mlp*
         return fail(T1D_E_INVALID, "t1d_mlp_grad: grad needs a workspace of t1d_mlp_grad_workspace() bytes");
     if (mlp->n_policies * mlp->n_params > INT_MAX) return fail(T1D_E_INVALID, "t1d_mlp_grad: too many policies");
     T1D_HIP(hipSetDevice(hip_device));
-    rc = dtype == T1D_F64 ? launch_mlp_grad<double>(mlp, n, io, gp, (hipStream_t)stream)
-                          : launch_mlp_grad<float>(mlp, n, io, gp, (hipStream_t)stream);
+    rc = by_dtype(dtype, [&](auto t) { return launch_grad<decltype(t)>(who, mlp, n, io, io->coef, gp, (hipStream_t)stream); });
     if (rc) return rc;
     T1D_HIP(hipGetLastError());
     return T1D_OK;
 }
 
-// t1d_mlp_loss: t1d_mlp_grad's partition and gradient partials, and one partial [4] of doubles per wave behind them
-static int64_t loss_stats_offset(const t1d_mlp* m, int dtype, const GradPartition& gp)
-{
-    return (grad_workspace_bytes(m, dtype, gp) + 7) / 8 * 8;
-}
-
-static int64_t loss_workspace_bytes(const t1d_mlp* m, int dtype, const GradPartition& gp)
-{
-    return loss_stats_offset(m, dtype, gp) + m->n_policies * gp.waves_per_policy * 4 * (int64_t)sizeof(double);
-}
-
-extern "C" int64_t t1d_mlp_loss_workspace(const t1d_mlp* mlp, int dtype, int64_t n, int64_t n_rows)
-{
-    t1d_mlp m;
-    if (!mlp) return fail(T1D_E_INVALID, "t1d_mlp_loss_workspace: mlp is NULL");
-    m = *mlp;
-    if (!m.params) m.params = &m;
-    GradPartition gp;
-    const int rc = check_mlp_grad("t1d_mlp_loss_workspace", dtype, n, &m, n_rows, &gp);
-    if (rc) return rc;
-    return loss_workspace_bytes(&m, dtype, gp);
-}
-
+// t1d_mlp_loss: the statistics live in registers, so the launch is t1d_mlp_grad's with the LossArgs behind it
 template <typename T, int KIND>
 static int launch_mlp_loss(int dtype, const t1d_mlp* m, int64_t n, const struct t1d_mlp_loss* io, const GradPartition& gp, hipStream_t s)
 {
-    MlpArgs<T> c = make_mlp<T>(m, 0);
-    GradArgs<T> g;
-    g.feat = (const T*)io->feat; g.coef = nullptr; g.y = (T*)io->y; g.partial = io->grad ? (T*)io->workspace : nullptr;
-    g.n = n;
-    g.chunks = (unsigned)gp.chunks; g.tiles = (unsigned)gp.tiles; g.tiles_per_wave = (unsigned)gp.tiles_per_wave;
-    g.waves_per_policy = (unsigned)gp.waves_per_policy; g.n_waves = (unsigned)(m->n_policies * gp.waves_per_policy);
     LossArgs<T, KIND> ls;
     ls.eps = (const T*)io->eps; ls.y_old = (const T*)io->y_old; ls.adv = (const T*)io->adv; ls.target = (const T*)io->target;
     ls.sigma_old = (const T*)io->sigma_old; ls.sigma = (const T*)io->sigma;
     ls.coef_out = (T*)io->coef_out;
-    double* const stat_partial = io->stats ? (double*)((char*)io->workspace + loss_stats_offset(m, dtype, gp)) : nullptr;
-    ls.stat_partial = stat_partial;
+    ls.stat_partial = io->stats ? (double*)((char*)io->workspace + loss_stats_offset(m, dtype, gp)) : nullptr;
     ls.clip = (T)io->clip; ls.scale = (T)io->scale;
-    void (*const fn)(MlpArgs<T>, GradArgs<T>, LossArgs<T, KIND>) = mlp_grad_kernel<T, LossArgs<T, KIND>>;
-    // the statistics live in registers: the rows are t1d_mlp_grad's
-    size_t lds = 0;
-    const int rc = grad_lds("t1d_mlp_loss", m, io->grad != nullptr, sizeof(T), (const void*)fn, &g.act_rows, &lds);
+    const int rc = launch_grad<T>("t1d_mlp_loss", m, n, io, nullptr, gp, s, ls);
     if (rc) return rc;
-    hipLaunchKernelGGL(fn, dim3(g.n_waves), dim3(64), lds, s, c, g, ls);
-    if (io->grad) {
-        const unsigned total = (unsigned)(m->n_policies * m->n_params);
-        hipLaunchKernelGGL(mlp_grad_sum_kernel<T>, dim3((total + 255) / 256), dim3(256), 0, s, (const T*)io->workspace, (T*)io->grad,
-                           g.waves_per_policy, (unsigned)m->n_params, total);
-    }
     if (io->stats) {
         const unsigned total = (unsigned)(4 * m->n_policies);
-        hipLaunchKernelGGL(mlp_loss_stats_kernel, dim3((total + 63) / 64), dim3(64), 0, s, (const double*)stat_partial, io->stats,
-                           g.waves_per_policy, total);
+        hipLaunchKernelGGL(mlp_loss_stats_kernel, dim3((total + 63) / 64), dim3(64), 0, s, (const double*)ls.stat_partial, io->stats,
+                           (unsigned)gp.waves_per_policy, total);
     }
     return T1D_OK;
 }
@@ -1551,8 +1541,7 @@ extern "C" int t1d_gae(int hip_device, int dtype, int64_t n, const t1d_gae_batch
     if (io->moments && (!io->workspace || io->workspace_bytes < io->n_policies * tiles * 2 * (int64_t)sizeof(double)))
         return fail(T1D_E_INVALID, "t1d_gae: moments need a workspace of t1d_gae_workspace() bytes");
     T1D_HIP(hipSetDevice(hip_device));
-    if (dtype == T1D_F64) launch_gae<double>(n, io, tiles, (hipStream_t)stream);
-    else launch_gae<float>(n, io, tiles, (hipStream_t)stream);
+    by_dtype(dtype, [&](auto t) { launch_gae<decltype(t)>(n, io, tiles, (hipStream_t)stream); });
     T1D_HIP(hipGetLastError());
     return T1D_OK;
 }

@@ -1,7 +1,9 @@
 // The kernel plan of t1d_step and of the roll-outs (plan_call in t1d_abi.hip) for hand-made contexts and batches, checked
 // against a table of expected rows: template instance, refill ahead, grid, block, dynamic LDS and the record capacity of
-// stepn_kernel.  No HIP call: the batch pointers are computed addresses that are never dereferenced.  Built and run by
-// test_dispatch_plan.py; prints one line per row and exits non-zero on any mismatch.
+// stepn_kernel.  Behind them the launch shapes of the kernels that run the policy (shape_mlp after plan_call, shape_mlp_dopri5,
+// shape_mlp_alone) and the LDS of one wave of mlp_grad_kernel (grad_wave_lds), against this file's own arithmetic.  No HIP
+// call: the batch pointers are computed addresses that are never dereferenced.  Built and run by test_dispatch_plan.py;
+// prints one line per row and exits non-zero on any mismatch.
 #include "../simglucose_amd/csrc/t1d_abi.hip"
 
 #include <cstdint>
@@ -83,14 +85,27 @@ static std::string expect(const Call& k, const std::string& kernel, bool refill,
 
 static int g_failed = 0, g_rows = 0;
 
-static void row(const char* name, const Call& k, const std::string& want, bool show_tables = false)
+static void report(const char* name, const std::string& got, const std::string& want)
 {
-    t1d_ctx c;
+    const bool ok = got == want;
+    printf("%s %-56s %s\n", ok ? "ok  " : "FAIL", name, got.c_str());
+    if (!ok) { printf("     %-56s %s\n", "expected", want.c_str()); ++g_failed; }
+    ++g_rows;
+}
+
+static void make_ctx(const Call& k, t1d_ctx& c)
+{
     c.np = k.np; c.np_pad = (k.np + 1) & ~1; c.n_cu = 256; c.lds_per_block = k.lds_per_block;
     std::memset(c.sensor, 0, sizeof(c.sensor));
     c.sensor[5] = k.sample_time;
     for (auto& o : k.opts)
         if (t1d_ctx_set_option(&c, o.first, o.second)) { printf("bad option %s\n", o.first); ++g_failed; }
+}
+
+static void row(const char* name, const Call& k, const std::string& want, bool show_tables = false)
+{
+    t1d_ctx c;
+    make_ctx(k, c);
     t1d_batch b = make_batch(k.dtype, k.n, k.packed);
     b.flags = k.flags;
     if (k.extra) b.lbgi = (char*)b.x + 100;
@@ -98,10 +113,162 @@ static void row(const char* name, const Call& k, const std::string& want, bool s
     const int rc = plan_call(k.rollout ? "t1d_rollout_pid" : "t1d_step", &c, &b, k.minutes, k.n_sub, k.rollout, &p);
     std::string got = rc ? "error " + std::to_string(rc) + " " + t1d_last_error() : describe(p);
     if (show_tables) got += p.tables ? " tables" : " no tables";
-    const bool ok = got == want;
-    printf("%s %-56s %s\n", ok ? "ok  " : "FAIL", name, got.c_str());
-    if (!ok) { printf("     %-56s %s\n", "expected", want.c_str()); ++g_failed; }
-    ++g_rows;
+    report(name, got, want);
+}
+
+// ---- the kernels that run the policy ----------------------------------------------------------------------------------
+// the two policies of the rows: H = 4 with widths (16, 16, 1) and H = 12 with widths (32, 32, 32, 1)
+struct Net { const char* name; int history, n_layers, width[4]; };
+static const Net kNets[2] = {{"H 4 (16, 16, 1)", 4, 3, {16, 16, 1, 0}}, {"H 12 (32, 32, 32, 1)", 12, 4, {32, 32, 32, 1}}};
+
+// the rows of a wave's column block: 2 H for the windows, then the wider of the features and the widest hidden layer
+static int cols_of(const Net& p)
+{
+    int widest = 2 * p.history + 3;
+    for (int l = 0; l + 1 < p.n_layers; ++l) widest = std::max(widest, p.width[l]);
+    return 2 * p.history + widest;
+}
+
+// the t1d_mlp of p for one policy of n envs, as check_mlp takes it; the pointers are never dereferenced
+static t1d_mlp make_net(const Net& p, int64_t n)
+{
+    t1d_mlp m;
+    std::memset(&m, 0, sizeof(m));
+    m.history = p.history; m.n_layers = p.n_layers;
+    int in_w = 2 * p.history + 3;
+    for (int l = 0; l < p.n_layers; ++l) { m.width[l] = p.width[l]; m.n_params += p.width[l] * (in_w + 1); in_w = p.width[l]; }
+    m.hidden_act = T1D_MLP_TANH; m.out_act = T1D_MLP_LOGISTIC;
+    m.n_policies = 1; m.envs_per_policy = n;
+    m.params = m.cgm_hist = m.ins_hist = m.prev_meal = (void*)(uintptr_t)0x100000000ull;
+    return m;
+}
+
+// The expected shape: the most waves of 4, 2 and 1 whose pieces fit under the ceiling beside the fixed bytes and the front
+// bytes (rounded up to 16), or the refusal.  seen[]: which outcomes a family has shown -- 4, 2, 1 waves, refused.
+static std::string want_shape(int64_t n, size_t fixed, size_t front, size_t per_wave, size_t ceiling, const std::string& refusal, bool seen[4])
+{
+    const size_t off = (front + 15) / 16 * 16;
+    for (int k = 0; k < 3; ++k) {
+        const int waves = 4 >> k;
+        if (fixed + off + per_wave * waves > ceiling) continue;
+        seen[k] = true;
+        char r[200];
+        snprintf(r, sizeof(r), "threads %d grid %lld lds %zu off %zu", 64 * waves, (long long)((n + 64 * waves - 1) / (64 * waves)), off + per_wave * waves, off);
+        return r;
+    }
+    seen[3] = true;
+    return "error " + std::to_string(T1D_E_INVALID) + " " + refusal;
+}
+
+static std::string shape_text(unsigned threads, unsigned grid, size_t lds, size_t off)
+{
+    char r[200];
+    snprintf(r, sizeof(r), "threads %u grid %u lds %zu off %zu", threads, grid, lds, off);
+    return r;
+}
+
+static void all_seen(const char* family, const bool seen[4], int n_outcomes)
+{
+    static const char* what[4] = {"four waves", "two waves", "one wave", "the refusal"};
+    for (int k = 0; k < n_outcomes; ++k) report((std::string(family) + " shows " + what[k]).c_str(), seen[k] ? "yes" : "no", "yes");
+}
+
+// t1d_rollout_mlp, t1d_collect_mlp: plan_call for a roll-out in one launch, then shape_mlp.  variant: what the plan must
+// choose; the static parameter table goes with variants 0 and 7, the propagator table in front with the split variants
+template <typename T>
+static void mlp_row(const char* name, const Call& k, const Net& net, int variant, bool seen[4])
+{
+    t1d_ctx c;
+    make_ctx(k, c);
+    t1d_batch b = make_batch(k.dtype, k.n, false);
+    const t1d_mlp m = make_net(net, k.n);
+    int cols = 0;
+    Plan p;
+    MlpArgs<T> ma = make_mlp<T>(&m, 1);
+    int rc = check_mlp("t1d_rollout_mlp", &b, &m, &cols);
+    if (!rc && cols != cols_of(net)) { report(name, "cols " + std::to_string(cols), "cols " + std::to_string(cols_of(net))); return; }
+    if (!rc) rc = plan_call("t1d_rollout_mlp", &c, &b, k.minutes, k.n_sub, true, &p, true);
+    if (!rc) rc = shape_mlp<T>("t1d_rollout_mlp", &c, &b, cols, p, ma);
+    const std::string got = "variant " + std::to_string(p.variant) + " " +
+        (rc ? "error " + std::to_string(rc) + " " + t1d_last_error() : shape_text(p.block, p.grid, p.lds, (size_t)ma.lds_off));
+    const size_t fixed = (variant == 0 || variant == 7 ? (size_t)DP_COUNT * 64 * sizeof(T) : 0) + 256;
+    const size_t front = variant == 0 || variant == 3 ? 0 : lds_generic(k);
+    report(name, got, "variant " + std::to_string(variant) + " " +
+           want_shape(k.n, fixed, front, (size_t)cols_of(net) * 64 * sizeof(T), (size_t)k.lds_per_block,
+                      "t1d_rollout_mlp: the integrator's tables leave no room in LDS for one wave of this policy", seen));
+}
+
+static void policy_rows()
+{
+    bool seen_mlp[4] = {}, seen_exact[4] = {}, seen_alone[4] = {};
+    for (int dt : {T1D_F64, T1D_F32})
+        for (const Net& net : kNets)
+            for (int big = 0; big < 2; ++big)
+                for (int lds : {kLds160, 65536})
+                    for (int opt = 0; opt < 3; ++opt)
+                        for (int64_t n : {(int64_t)192, (int64_t)65536}) {
+                            if (opt && n != 192) continue;
+                            const bool f64 = dt == T1D_F64;
+                            Call k; k.dtype = dt; k.n = n; k.sample_time = 3; k.minutes = 3; k.lds_per_block = lds;
+                            k.np = big ? 64 : 30; k.n_sub = big ? 8 : 4;
+                            if (opt == 1) k.opts = {{"math", 0}};
+                            if (opt == 2) k.opts = {{"integrator", 0}};
+                            // 64 patients x n_sub 8 beside the parameter table in 64 KiB: the plan falls back to RK4
+                            const bool rk4 = opt == 2 || (big && lds == 65536);
+                            const int variant = opt == 1 ? 0 : rk4 ? 3 : f64 ? 7 : 6;
+                            const std::string name = std::string(f64 ? "fp64 " : "fp32 ") + "mlp " + net.name + ", " + std::to_string(k.np) + " x " +
+                                std::to_string(k.n_sub) + ", " + std::to_string(lds / 1024) + " KiB" + (opt == 1 ? ", math 0" : opt == 2 ? ", integrator 0" : "") +
+                                ", n " + std::to_string(n);
+                            if (f64) mlp_row<double>(name.c_str(), k, net, variant, seen_mlp); else mlp_row<float>(name.c_str(), k, net, variant, seen_mlp);
+                        }
+    all_seen("t1d_rollout_mlp", seen_mlp, 4);
+
+    // the exact mode: the raw patient rows (32 columns of 64 doubles) and 256 bytes fixed; per wave RollCold's 13 doubles and
+    // 3 ints per lane and the columns.  32 KiB is no gfx950's: the row of the refusal
+    for (const Net& net : kNets)
+        for (int lds : {kLds160, 65536, 32768}) {
+            t1d_ctx c;
+            c.lds_per_block = lds;
+            Shape sh;
+            const int64_t n = 65536 + 64;
+            const int rc = shape_mlp_dopri5("t1d_rollout_mlp_dopri5", &c, n, cols_of(net), &sh);
+            const std::string name = std::string("exact mode mlp ") + net.name + ", " + std::to_string(lds / 1024) + " KiB";
+            report(name.c_str(), rc ? "error " + std::to_string(rc) + " " + t1d_last_error() : shape_text(sh.threads, sh.grid, sh.lds, sh.front),
+                   want_shape(n, (size_t)32 * 64 * 8 + 256, 0, (size_t)(13 * 8 + 3 * 4) * 64 + (size_t)cols_of(net) * 64 * 8, (size_t)lds,
+                              "t1d_rollout_mlp_dopri5: the patient rows leave no room in LDS for one wave of this policy", seen_exact));
+        }
+    all_seen("t1d_rollout_mlp_dopri5", seen_exact, 4);
+
+    // the policy alone: nothing fixed, the ceiling 64 KiB less 256 bytes whatever the device has; never refused
+    for (int dt : {T1D_F64, T1D_F32})
+        for (const Net& net : kNets) {
+            const bool f64 = dt == T1D_F64;
+            t1d_ctx c;
+            c.lds_per_block = kLds160;
+            const int64_t n = 192;
+            const Shape sh = f64 ? shape_mlp_alone<double>(&c, n, cols_of(net)) : shape_mlp_alone<float>(&c, n, cols_of(net));
+            const std::string name = std::string(f64 ? "fp64 " : "fp32 ") + "t1d_mlp_action " + net.name;
+            report(name.c_str(), shape_text(sh.threads, sh.grid, sh.lds, sh.front),
+                   want_shape(n, 0, 0, (size_t)cols_of(net) * 64 * (f64 ? 8 : 4), 65280, "never", seen_alone));
+        }
+    all_seen("t1d_mlp_action", seen_alone, 2);
+
+    // one wave of mlp_grad_kernel: the features and every hidden unit's activation; with grad a row of ones and a delta
+    // per unit of every layer
+    for (int dt : {T1D_F64, T1D_F32})
+        for (const Net& net : kNets)
+            for (bool grad : {false, true}) {
+                const size_t word = dt == T1D_F64 ? 8 : 4;
+                int act = 2 * net.history + 3, units = 0;
+                for (int l = 0; l < net.n_layers; ++l) { units += net.width[l]; if (l + 1 < net.n_layers) act += net.width[l]; }
+                const size_t want = (size_t)(grad ? act + 1 + units : act) * 64 * word;
+                const t1d_mlp m = make_net(net, 64);
+                int act_rows = 0;
+                const size_t lds = grad_wave_lds(&m, grad, word, &act_rows);
+                const std::string name = std::string(word == 8 ? "fp64 " : "fp32 ") + "mlp_grad_kernel " + net.name + (grad ? ", grad" : ", forward");
+                report(name.c_str(), "act_rows " + std::to_string(act_rows) + " lds " + std::to_string(lds) + (lds > 65536 ? " above 64 KiB" : ""),
+                       "act_rows " + std::to_string(act) + " lds " + std::to_string(want) + (want > 65536 ? " above 64 KiB" : ""));
+            }
 }
 
 int main()
@@ -175,6 +342,7 @@ int main()
                                                                 : " t1d_step: split tables exceed the LDS of a workgroup (n_patients x n_sub too large); use integrator 0 or -1") + " tables", true);
         }
     }
+    policy_rows();
     printf("%d rows, %d failed\n", g_rows, g_failed);
     return g_failed ? 1 : 0;
 }

@@ -15,4 +15,4 @@ def test_dispatch_plan_matches_table(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     print(r.stdout)
     assert r.returncode == 0, r.stdout + r.stderr
-    assert r.stdout.strip().splitlines()[-1] == "70 rows, 0 failed"
+    assert r.stdout.strip().splitlines()[-1] == "162 rows, 0 failed"

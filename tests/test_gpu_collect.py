@@ -201,6 +201,34 @@ def test_restart_is_the_loop_of_existing_entry_points_bit_for_bit(dtype_name):
     assert high_lo + high_hi > 0
 
 
+def test_first_restart_call_on_an_env_without_start_minute_reads_the_array_it_creates():
+    """collect_mlp(on_done="restart") on an env that never had a start_minute creates the array the restarts write; the policy
+    of that same call must read it, not a constant 0: the features are those of an env that was given the zeros beforehand."""
+    torch = _torch()
+    from simglucose_amd.batch_env import BatchedT1DSimEnv
+    n, K = 128, 400
+    pol = _constant_policy(0.05)                                  # episodes end low, as in the test above
+    envs, traces = [], []
+    for given in (False, True):
+        e = BatchedT1DSimEnv(patient=["child#001", "adult#001"] * (n // 2), sensor="Dexcom", pump="Insulet", dtype=torch.float64,
+                             n_sub=4, seed=3, noise="philox", random_init_bg=True)
+        e.reset()
+        assert e.start_minute is None
+        if given:
+            e.start_minute = torch.zeros(n, dtype=torch.int32, device=e.device)
+        tr = e.new_trace(K, columns=("done", "features"), history=pol.history)
+        e.collect_mlp(K, pol, trace=tr, on_done="restart", days=DAYS)
+        assert e.sync() == 0
+        envs.append(e); traces.append(tr)
+    A, B = envs
+    restarted = traces[1]["done"][1:].bool().any(0)
+    print("\nrestarted envs %d of %d, of them with a new start minute %d" % (int(restarted.sum()), n, int((B.start_minute != 0).sum())))
+    assert int((restarted & (B.start_minute != 0)).sum()) >= 1     # else the comparison passes on nothing
+    assert torch.equal(A.start_minute, B.start_minute)
+    _same_dicts(traces[0], traces[1], ("done", "features"))
+    _same_env(A, B)
+
+
 # ---------------------------------------------------------------------------------------------------------- 3
 def _draw_of_pair(m):
     """the draw index of t1d_philox_normals whose value is philox_pair(.., pair = m).x"""
