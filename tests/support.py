@@ -1,0 +1,309 @@
+"""What the test files share: constants, bit-for-bit comparisons, the random policies, the env builders and the collectors'
+reference loops.  Imported by bare name (`import support`), as test_gpu_step_trim.py imports test_gpu_parity.  Importing it
+touches no device; only the env builders and gpu_torch() ask for one."""
+import csv
+import functools
+import math
+import os
+import re
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+ST = 3                                   # Dexcom's sample time, minutes
+START = 360                              # episodes start at 06:00, so that breakfast and lunch fall inside 160 steps
+DAYS = 2
+STATE = ("state", "istate", "ar_e", "cgm", "bg", "reward", "done", "lbgi", "hbgi", "risk", "meal", "insulin")
+STATE_EXACT = STATE + ("h_carry",)
+GYM_STATE = STATE + ("meal_time", "meal_amt", "start_minute", "cgm0")
+STATS = ("sum_risk", "min_bg", "max_bg", "n_low", "n_high")
+POLICY_STATE = ("cgm_hist", "ins_hist", "prev_meal")
+MLP_TRACE = ("bg", "cgm", "cho", "insulin", "action")
+EPISODE_STATS = ("ep_return", "ep_length", "last_return", "last_length")
+
+
+def gpu_torch():
+    import torch
+    assert torch.cuda.is_available()
+    return torch
+
+
+# ------------------------------------------------------------------------------------------------ comparisons
+def bits(t):
+    """the words of a tensor as integers: equal bit patterns compare equal, also the NaN rows new_trace leaves unwritten"""
+    import torch
+    t = t.contiguous()
+    return t.view({8: torch.int64, 4: torch.int32, 1: torch.uint8}[t.element_size()]) if t.is_floating_point() else t
+
+
+def _equal(a, b, by):
+    """by="bits": the same words (equal NaNs pass, +0.0 against -0.0 fails); by="value": torch.equal (any NaN fails)"""
+    import torch
+    assert by in ("bits", "value"), by
+    return torch.equal(bits(a), bits(b)) if by == "bits" else torch.equal(a, b)
+
+
+def same_env(a, b, keys=STATE, sl=slice(None), by="bits"):
+    """the attributes `keys` of env a, its envs `sl`, are those of env b"""
+    for k in keys:
+        assert _equal(getattr(a, k)[..., sl], getattr(b, k), by), k
+
+
+def same_dicts(a, b, keys, sl=slice(None), by="bits"):
+    for k in keys:
+        assert _equal(a[k][..., sl], b[k], by), k
+
+
+# ------------------------------------------------------------------------------------------------ policies
+def random_policy(history=4, widths=(16, 16, 1), n_policies=1, seed=0, hidden="tanh", output="logistic", gain=1.0, bias_gain=None,
+                  **kw):
+    """layer by layer from one generator: weights gain N(0, 1) / sqrt(fan-in), biases bias_gain 0.1 N(0, 1) (None: as gain)"""
+    import torch
+    from simglucose_amd.controller.mlp_ctrller import MLPController
+    bias_gain = gain if bias_gain is None else bias_gain
+    g = torch.Generator().manual_seed(seed)
+    layers, n_in = [], 2 * history + 3
+    for w in widths:
+        layers.append((gain * torch.randn(n_policies, w, n_in, generator=g, dtype=torch.float64) / math.sqrt(n_in),
+                       bias_gain * 0.1 * torch.randn(n_policies, w, generator=g, dtype=torch.float64)))
+        n_in = w
+    # the logistic output spans [0, 0.06] U/min, about four times a basal rate and far below the pump's 0.5 U/min
+    kw.setdefault("out_scale", 0.06)
+    return MLPController(layers, history=history, hidden=hidden, output=output, **kw)
+
+
+# for t1d_mlp_grad and t1d_mlp_loss: y itself is the output, and the biases do not follow `gain`
+identity_policy = functools.partial(random_policy, output="identity", bias_gain=1.0, out_scale=1.0, out_bias=0.0)
+
+
+def constant_policy(basal, history=4):
+    """a one-layer net with zero weights and identity output: `basal` U/min whatever it sees"""
+    import torch
+    from simglucose_amd.controller.mlp_ctrller import MLPController
+    return MLPController([(torch.zeros(1, 2 * history + 3, dtype=torch.float64), torch.zeros(1, dtype=torch.float64))],
+                         history=history, output="identity", out_scale=1.0, out_bias=basal)
+
+
+def hypo_leaning_policies(P, seed=11, **kw):
+    """small random weights around a constant 0.05 U/min: episodes end low"""
+    kw.setdefault("history", 4); kw.setdefault("widths", (8, 1))
+    return random_policy(n_policies=P, seed=seed, output="identity", gain=0.02, out_scale=1.0, out_bias=0.05, **kw)
+
+
+def mlp_struct(widths=(8, 8, 1), history=4, n_policies=2, envs_per_policy=64, params=0x1000):
+    """a host-side t1d_mlp for the argument checks: the network's fields set, `params` an address nothing reads"""
+    from simglucose_amd import _lib
+    from simglucose_amd.controller.mlp_ctrller import MLPController
+    p = _lib.Mlp()
+    p.history, p.n_layers = history, len(widths)
+    for k in range(4):
+        p.width[k] = widths[k] if k < len(widths) else 0
+    p.hidden_act = 0
+    p.n_policies, p.envs_per_policy = n_policies, envs_per_policy
+    p.n_params = MLPController.count_params(history, widths)
+    p.params = params
+    return p
+
+
+# ------------------------------------------------------------------------------------------------ accumulators
+def stats(e):
+    torch = gpu_torch()
+    z = lambda dt=e.dtype: torch.zeros(e.n, dtype=dt, device=e.device)
+    return {"sum_risk": z(), "min_bg": z() + 1000.0, "max_bg": z(), "n_low": z(torch.int32), "n_high": z(torch.int32)}
+
+
+def episode_stats(e):
+    torch = gpu_torch()
+    z = lambda dt=e.dtype: torch.zeros(e.n, dtype=dt, device=e.device)
+    return {"ep_return": z(), "ep_length": z(torch.int32), "last_return": z(), "last_length": z(torch.int32)}
+
+
+# ------------------------------------------------------------------------------------------------ envs
+def plain_env(**kw):
+    """BatchedT1DSimEnv(**kw) on a machine that has a GPU; plain_env(integrator="dopri5", ...) is the exact mode"""
+    gpu_torch()
+    from simglucose_amd.batch_env import BatchedT1DSimEnv
+    return BatchedT1DSimEnv(**kw)
+
+
+def meal_day_env(n, dtype, env_offset=0, seed=5, meals=True, start=None, **kw):
+    """all 30 patients, a random-meal day from START (or from `start`: int32 [n] minute of day per env), reset"""
+    torch = gpu_torch()
+    from simglucose_amd.batch_env import BatchedT1DSimEnv
+    from simglucose_amd.scenario_batch import random_meal_tables
+    pid = (np.arange(n) + env_offset) % 30
+    e = BatchedT1DSimEnv(patient=pid, sensor="Dexcom", dtype=dtype, seed=seed, env_offset=env_offset, **kw)
+    e.start_minute = torch.full((n,), START, dtype=torch.int32, device=e.device) if start is None else \
+        torch.as_tensor(start, dtype=torch.int32).to(e.device).contiguous()
+    if meals:
+        e.set_meals(*random_meal_tables(n, days=1, start_minute_of_day=e.start_minute, seed=seed, dtype=dtype, env_offset=env_offset))
+    e.reset()
+    return e
+
+
+def gym_env(n, dtype=None, seed=3, env_offset=0, exact=False):
+    """child#001 / adult#001 alternating, random initial glucose, Philox noise, every env in episode 0 of the device's own
+    episode stream (started through restart_done); dtype None: fp64.  n_sub = 4 and integrator = None are the constructor's
+    defaults, and the exact mode ignores n_sub."""
+    torch = gpu_torch()
+    from simglucose_amd.batch_env import BatchedT1DSimEnv
+    e = BatchedT1DSimEnv(patient=["child#001", "adult#001"] * (n // 2), sensor="Dexcom", pump="Insulet", dtype=dtype or torch.float64,
+                         n_sub=4, seed=seed, env_offset=env_offset, noise="philox", random_init_bg=True,
+                         integrator="dopri5" if exact else None)
+    e.restart_done(mask=torch.ones(n, dtype=torch.uint8, device=e.device), days=DAYS, reset_outputs=True)
+    return e
+
+
+def exact_inputs(n, K, seed=3):
+    """per-env inputs that do not depend on the env's index in a batch: patient row, host normals, a meal table"""
+    rs = np.random.RandomState(seed)
+    pid = np.arange(n) % 30
+    z = rs.randn(1 + 10 * (2 + K * ST // 150), n)
+    mt = np.sort(rs.choice(np.arange(2, max(8, K * ST - 2)), size=(n, 4)), axis=1).T.copy()      # [4][n], ascending
+    for j in range(1, 4):                                            # at most one entry per minute
+        mt[j] = np.maximum(mt[j], mt[j - 1] + 1)
+    ma = rs.uniform(15.0, 90.0, size=(4, n))
+    return pid, z, mt.astype(np.int64), ma
+
+
+def host_noise_env(pid, z, mt, ma, cols=None, exact=True, start=START, **kw):
+    """Dexcom, host normals and explicit meal tables (exact_inputs), the columns `cols` of them; start=None: no start_minute"""
+    torch = gpu_torch()
+    from simglucose_amd.batch_env import BatchedT1DSimEnv
+    if cols is not None:
+        pid, z, mt, ma = pid[cols], z[:, cols], mt[:, cols], ma[:, cols]
+    e = BatchedT1DSimEnv(patient=pid, sensor="Dexcom", noise="host", normals=z, integrator="dopri5" if exact else None, **kw)
+    e.set_meals(torch.as_tensor(mt), torch.as_tensor(ma))
+    if start is not None:
+        e.start_minute = torch.full((e.n,), start, dtype=torch.int32, device=e.device)
+    e.reset()
+    return e
+
+
+def basal_of(pid):
+    from simglucose_amd import params
+    _, tab = params.patient_table()
+    return tab[pid, params.P_COL["u2ss"]] * tab[pid, params.P_COL["BW"]] / 6000.0
+
+
+def dense_cho(mt, ma, sample, minutes):
+    """the meal tables of the envs `sample` as grams per minute [minutes, len(sample)], for the oracle"""
+    t_s, a_s = mt[:, sample].cpu().numpy().astype(np.int64), ma[:, sample].double().cpu().numpy()
+    cho = np.zeros((minutes, len(sample)))
+    for j in range(len(sample)):
+        for tt, aa in zip(t_s[:, j], a_s[:, j]):
+            if 0 <= tt < minutes:
+                cho[tt, j] = aa
+    return cho
+
+
+# ------------------------------------------------------------------------------------------------ files
+def golden_hist(name):
+    """a history CSV of tests/golden -> ({column: values, NaN where empty}, the Time column)"""
+    with open(os.path.join(GOLDEN, name), newline="") as f:
+        rows = list(csv.DictReader(f))
+    return {k: np.array([float(r[k]) if r[k] else np.nan for r in rows]) for k in rows[0] if k != "Time"}, \
+        [r["Time"] for r in rows]
+
+
+def header_fields(name):
+    """the fields of `typedef struct name` in include/t1d.h -> [(field, C type, is a pointer, array length)]"""
+    src = open(os.path.join(ROOT, "include", "t1d.h")).read()
+    body = src[src.index("typedef struct %s {" % name):src.index("} %s;" % name)]
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S).replace("typedef struct %s {" % name, "")
+    out = []
+    for stmt in body.split(";"):
+        stmt = stmt.strip()
+        if not stmt:
+            continue
+        ctype = re.match(r"(const\s+)?(\w+)", stmt).group(2)
+        for part in stmt.split(","):
+            m = re.search(r"([A-Za-z_0-9]+)(\[(\d+)\])?\s*$", part.strip())
+            out.append((m.group(1), ctype, "*" in stmt, int(m.group(3) or 1)))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ the collectors' references
+# One body for collect_mlp and collect_mlp_dopri5: `exact` picks the entry points.  The right-hand-side counts (nfev) ride
+# along; a fixed-step env has none and its sums stay 0.
+TRACES = MLP_TRACE + ("reward", "done", "eps", "features")
+
+
+def loop_of_entry_points(e, pol, K, acc, tr, term, es, exact=False):
+    """what a trainer does without the collector: per step rollout_mlp(1) or rollout_mlp_dopri5(1), restart_done, the torch
+    reset of the policy state -> policy state, low endings, high endings, summed nfev"""
+    torch = gpu_torch()
+    rollout = e.rollout_mlp_dopri5 if exact else e.rollout_mlp
+    st = e.new_policy_state(pol)
+    low = high = 0
+    zero = torch.zeros((), dtype=e.dtype, device=e.device)
+    nf = torch.zeros(e.n, dtype=torch.int64, device=e.device)
+    for _ in range(K):
+        row = tr["row"]
+        rollout(1, pol, policy_state=st, stats=acc, trace=tr)
+        nf += e.nfev if exact else 0
+        done = e.done.bool()
+        tr["reward"][row] = e.reward; tr["done"][row] = e.done
+        low = low + (done & (e.bg < 70)).sum(); high = high + (done & (e.bg > 350)).sum()
+        e.restart_done(days=DAYS, terminal_obs=term, episode_stats=es)
+        st["cgm_hist"].copy_(torch.where(done, e.cgm, st["cgm_hist"]))           # new_policy_state for the envs that restarted
+        st["ins_hist"].copy_(torch.where(done, zero, st["ins_hist"]))
+        st["prev_meal"].copy_(torch.where(done, zero, st["prev_meal"]))
+    assert e.sync() == 0
+    return st, int(low), int(high), nf
+
+
+def restart_pair(pol, cuts, dtype=None, exact=False, seed=3, **kw):
+    """A: the collector in launches of `cuts` steps; B: the loop of existing entry points; equal bit for bit
+    -> what happened in B: restarts per env, low endings, high endings"""
+    torch = gpu_torch()
+    n, K = 256, sum(cuts)
+    cols = MLP_TRACE + ("reward", "done", "eps")
+    A, B = gym_env(n, dtype, seed, exact=exact), gym_env(n, dtype, seed, exact=exact)
+    collect = A.collect_mlp_dopri5 if exact else A.collect_mlp
+    z = lambda: torch.zeros(n, dtype=A.dtype, device=A.device)
+    sa, ta, terma, esa = stats(A), A.new_trace(K, columns=cols), z(), episode_stats(A)
+    sb, tb, termb, esb = stats(B), B.new_trace(K, columns=cols[:7]), z(), episode_stats(B)
+    sta = None
+    nfa = torch.zeros(n, dtype=torch.int64, device=A.device)
+    for k in cuts:
+        sta = collect(k, pol, policy_state=sta, stats=sa, trace=ta, on_done="restart", days=DAYS, terminal_obs=terma,
+                      episode_stats=esa, **kw)
+        nfa += A.nfev if exact else 0
+    assert A.sync() == 0
+    stb, low, high, nfb = loop_of_entry_points(B, pol, K, sb, tb, termb, esb, exact)
+    same_env(B, A, keys=(STATE_EXACT if exact else STATE) + ("meal_time", "meal_amt", "start_minute", "episode", "cgm0"))
+    same_dicts(stb, sta, POLICY_STATE)
+    same_dicts(sb, sa, STATS)
+    same_dicts(esb, esa, EPISODE_STATS)
+    assert torch.equal(bits(termb), bits(terma))
+    same_dicts(tb, ta, cols[:7])
+    assert torch.equal(nfb, nfa)
+    assert bool((ta["eps"][1:] == 0).all())
+    assert A._clock is None
+    return (B.episode - 1).cpu().numpy(), low, high
+
+
+def noisy_run(e, pol, sigma, warm, chunks, explore_seed=99, exact=False, **kw2):
+    """`warm` steps in one launch (far enough for episodes to end in what follows), then the traced chunks (**kw2 to them)
+    -> policy state, accumulators, episode statistics with terminal_obs and the summed nfev, trace"""
+    torch = gpu_torch()
+    collect = e.collect_mlp_dopri5 if exact else e.collect_mlp
+    acc, es, term = stats(e), episode_stats(e), torch.zeros(e.n, dtype=e.dtype, device=e.device)
+    kw = dict(sigma=sigma, explore_seed=explore_seed, stats=acc, on_done="restart", days=DAYS, terminal_obs=term, episode_stats=es)
+    st = collect(warm, pol, **kw)
+    tr = e.new_trace(sum(chunks), columns=TRACES, history=pol.history)
+    nf = torch.zeros(e.n, dtype=torch.int64, device=e.device)
+    for ch in chunks:
+        collect(ch, pol, policy_state=st, trace=tr, **kw, **kw2)
+        nf += e.nfev if exact else 0
+    assert e.sync() == 0
+    es["terminal_obs"] = term
+    es["nfev"] = nf
+    return st, acc, es, tr
+
+
+def draw_of_pair(m):
+    """the draw index of t1d_philox_normals whose value is philox_pair(.., pair = m).x"""
+    return np.where(m >= 3, 1 + 10 * ((m - 3) // 5) + 2 * ((m - 3) % 5), 0)

@@ -8,23 +8,9 @@ import re
 import pytest
 import torch
 
+from support import header_fields as _header_fields
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _header_fields(name):
-    src = open(os.path.join(ROOT, "include", "t1d.h")).read()
-    body = src[src.index("typedef struct %s {" % name):src.index("} %s;" % name)]
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S).replace("typedef struct %s {" % name, "")
-    out = []
-    for stmt in body.split(";"):
-        stmt = stmt.strip()
-        if not stmt:
-            continue
-        ctype = re.match(r"(const\s+)?(\w+)", stmt).group(2)
-        for part in stmt.split(","):
-            m = re.search(r"([A-Za-z_0-9]+)(\[(\d+)\])?\s*$", part.strip())
-            out.append((m.group(1), ctype, "*" in stmt, int(m.group(3) or 1)))
-    return out
 
 
 def test_collect_struct_layout_matches_header():

@@ -4,9 +4,10 @@ and the Python start-hour formula, composed on the host."""
 import numpy as np
 import pytest
 
+from support import DAYS
+
 pytestmark = pytest.mark.gpu
 
-DAYS = 2
 OUT8 = ("reward", "done", "bg", "lbgi", "hbgi", "risk", "meal", "insulin")
 
 

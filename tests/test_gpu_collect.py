@@ -2,106 +2,21 @@
 for bit to rollout_mlp (no noise, no episode ends) and to the per-step loop of rollout_mlp(1), restart_done and the torch
 reset of the policy state (episodes that end); the exploration draws replayed through t1d_philox_normals; the action and the
 recorded features against the host's forward pass; cut and shard invariance with noise and restarts on; the argument checks.
-The helpers are those of test_gpu_policy.py and test_gpu_autoreset.py, copied."""
+The envs of test_gpu_policy.py (_mk) and of the device's own episode stream (_mk_gym), the policies, the comparisons and the
+reference loops shared with test_gpu_collect_dopri5.py come from support.py."""
 import ctypes as C
 import math
 
 import numpy as np
 import pytest
 
+from support import (DAYS, EPISODE_STATS, GYM_STATE, POLICY_STATE, ST, STATS, TRACES, bits as _bits, constant_policy as _constant_policy,
+                     draw_of_pair as _draw_of_pair, episode_stats as _episode_stats, gpu_torch as _torch, gym_env as _mk_gym,
+                     hypo_leaning_policies as _hypo_leaning_policies, meal_day_env as _mk, noisy_run as _noisy_run,
+                     random_policy as _policy, restart_pair as _restart_pair, same_dicts as _same_dicts, same_env as _same_env,
+                     stats as _stats)
+
 pytestmark = pytest.mark.gpu
-ST = 3                                   # Dexcom
-START = 360
-DAYS = 2
-STATE = ("state", "istate", "ar_e", "cgm", "bg", "reward", "done", "lbgi", "hbgi", "risk", "meal", "insulin")
-STATS = ("sum_risk", "min_bg", "max_bg", "n_low", "n_high")
-POLICY_STATE = ("cgm_hist", "ins_hist", "prev_meal")
-TRACES = ("bg", "cgm", "cho", "insulin", "action", "reward", "done", "eps", "features")
-EPISODE_STATS = ("ep_return", "ep_length", "last_return", "last_length")
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-def _mk(n, dtype, env_offset=0, seed=5, meals=True, start=None, **kw):
-    """all 30 patients, random-meal day from START (or per-env start minutes), reset: the envs of test_gpu_policy.py"""
-    torch = _torch()
-    from simglucose_amd.batch_env import BatchedT1DSimEnv
-    from simglucose_amd.scenario_batch import random_meal_tables
-    pid = (np.arange(n) + env_offset) % 30
-    e = BatchedT1DSimEnv(patient=pid, sensor="Dexcom", dtype=dtype, seed=seed, env_offset=env_offset, **kw)
-    e.start_minute = torch.full((n,), START, dtype=torch.int32, device=e.device) if start is None else \
-        torch.as_tensor(start, dtype=torch.int32).to(e.device).contiguous()
-    if meals:
-        e.set_meals(*random_meal_tables(n, days=1, start_minute_of_day=e.start_minute, seed=seed, dtype=dtype, env_offset=env_offset))
-    e.reset()
-    return e
-
-
-def _mk_gym(n, dtype, seed=3, env_offset=0):
-    """child#001 / adult#001 alternating, random initial glucose, Philox noise, every env in episode 0 of the device's own
-    episode stream: the envs of test_gpu_autoreset.py"""
-    torch = _torch()
-    from simglucose_amd.batch_env import BatchedT1DSimEnv
-    e = BatchedT1DSimEnv(patient=["child#001", "adult#001"] * (n // 2), sensor="Dexcom", pump="Insulet", dtype=dtype, n_sub=4,
-                         seed=seed, env_offset=env_offset, noise="philox", random_init_bg=True)
-    e.restart_done(mask=torch.ones(n, dtype=torch.uint8, device=e.device), days=DAYS, reset_outputs=True)
-    return e
-
-
-def _stats(e):
-    torch = _torch()
-    z = lambda dt=e.dtype: torch.zeros(e.n, dtype=dt, device=e.device)
-    return {"sum_risk": z(), "min_bg": z() + 1000.0, "max_bg": z(), "n_low": z(torch.int32), "n_high": z(torch.int32)}
-
-
-def _episode_stats(e):
-    torch = _torch()
-    z = lambda dt=e.dtype: torch.zeros(e.n, dtype=dt, device=e.device)
-    return {"ep_return": z(), "ep_length": z(torch.int32), "last_return": z(), "last_length": z(torch.int32)}
-
-
-def _policy(history=4, widths=(16, 16, 1), n_policies=1, seed=0, hidden="tanh", output="logistic", gain=1.0, **kw):
-    torch = _torch()
-    from simglucose_amd.controller.mlp_ctrller import MLPController
-    g = torch.Generator().manual_seed(seed)
-    layers, n_in = [], 2 * history + 3
-    for w in widths:
-        layers.append((gain * torch.randn(n_policies, w, n_in, generator=g, dtype=torch.float64) / math.sqrt(n_in),
-                       gain * 0.1 * torch.randn(n_policies, w, generator=g, dtype=torch.float64)))
-        n_in = w
-    kw.setdefault("out_scale", 0.06)
-    return MLPController(layers, history=history, hidden=hidden, output=output, **kw)
-
-
-def _constant_policy(basal, history=4):
-    """a one-layer net with zero weights and identity output: `basal` U/min whatever it sees"""
-    torch = _torch()
-    from simglucose_amd.controller.mlp_ctrller import MLPController
-    return MLPController([(torch.zeros(1, 2 * history + 3, dtype=torch.float64), torch.zeros(1, dtype=torch.float64))],
-                         history=history, output="identity", out_scale=1.0, out_bias=basal)
-
-
-def _bits(t):
-    """the words of a tensor as integers: equal bit patterns compare equal, also the NaN rows new_trace leaves unwritten"""
-    torch = _torch()
-    t = t.contiguous()
-    return t.view({8: torch.int64, 4: torch.int32, 1: torch.uint8}[t.element_size()]) if t.is_floating_point() else t
-
-
-def _same_env(a, b, sl=slice(None), keys=STATE):
-    torch = _torch()
-    for k in keys:
-        assert torch.equal(_bits(getattr(a, k)[..., sl]), _bits(getattr(b, k))), k
-
-
-def _same_dicts(a, b, keys, sl=slice(None)):
-    torch = _torch()
-    for k in keys:
-        assert torch.equal(_bits(a[k][..., sl]), _bits(b[k])), k
 
 
 # ---------------------------------------------------------------------------------------------------------- 1
@@ -138,60 +53,14 @@ def test_without_noise_and_episode_ends_it_is_rollout_mlp_bit_for_bit(dtype_name
 
 
 # ---------------------------------------------------------------------------------------------------------- 2
-def _loop_of_entry_points(e, pol, K, stats, tr, term, es):
-    """what a trainer does without collect_mlp: per step rollout_mlp(1), restart_done, the torch reset of the policy state"""
-    torch = _torch()
-    st = e.new_policy_state(pol)
-    low = high = 0
-    zero = torch.zeros((), dtype=e.dtype, device=e.device)
-    for _ in range(K):
-        row = tr["row"]
-        e.rollout_mlp(1, pol, policy_state=st, stats=stats, trace=tr)
-        done = e.done.bool()
-        tr["reward"][row] = e.reward; tr["done"][row] = e.done
-        low = low + (done & (e.bg < 70)).sum(); high = high + (done & (e.bg > 350)).sum()
-        e.restart_done(days=DAYS, terminal_obs=term, episode_stats=es)
-        st["cgm_hist"].copy_(torch.where(done, e.cgm, st["cgm_hist"]))           # new_policy_state for the envs that restarted
-        st["ins_hist"].copy_(torch.where(done, zero, st["ins_hist"]))
-        st["prev_meal"].copy_(torch.where(done, zero, st["prev_meal"]))
-    assert e.sync() == 0
-    return st, int(low), int(high)
-
-
-def _restart_pair(dtype, basal, cuts):
-    torch = _torch()
-    n, K = 256, sum(cuts)
-    pol = _constant_policy(basal)
-    cols = ("bg", "cgm", "cho", "insulin", "action", "reward", "done", "eps")
-    A, B = _mk_gym(n, dtype), _mk_gym(n, dtype)
-    z = lambda: torch.zeros(n, dtype=dtype, device=A.device)
-    sa, ta, terma, esa = _stats(A), A.new_trace(K, columns=cols), z(), _episode_stats(A)
-    sb, tb, termb, esb = _stats(B), B.new_trace(K, columns=cols[:5] + ("reward", "done")), z(), _episode_stats(B)
-    sta = None
-    for k in cuts:
-        sta = A.collect_mlp(k, pol, policy_state=sta, stats=sa, trace=ta, on_done="restart", days=DAYS, terminal_obs=terma,
-                            episode_stats=esa)
-    assert A.sync() == 0
-    stb, low, high = _loop_of_entry_points(B, pol, K, sb, tb, termb, esb)
-    _same_env(B, A, keys=STATE + ("meal_time", "meal_amt", "start_minute", "episode", "cgm0"))
-    _same_dicts(stb, sta, POLICY_STATE)
-    _same_dicts(sb, sa, STATS)
-    _same_dicts(esb, esa, EPISODE_STATS)
-    assert torch.equal(_bits(termb), _bits(terma))
-    _same_dicts(tb, ta, cols[:7])
-    assert bool((ta["eps"][1:] == 0).all())
-    assert A._clock is None
-    return (B.episode - 1).cpu().numpy(), low, high
-
-
 @pytest.mark.parametrize("dtype_name", ["float64", "float32"])
 def test_restart_is_the_loop_of_existing_entry_points_bit_for_bit(dtype_name):
     """400 Dexcom steps under a constant 0.05 U/min (episodes end low) in launches of 150 and 250 steps, and 400 steps without
     insulin (episodes end high)."""
     torch = _torch()
     dtype = getattr(torch, dtype_name)
-    restarts_lo, low_lo, high_lo = _restart_pair(dtype, 0.05, (150, 250))
-    restarts_hi, low_hi, high_hi = _restart_pair(dtype, 0.0, (400,))
+    restarts_lo, low_lo, high_lo = _restart_pair(_constant_policy(0.05), (150, 250), dtype)
+    restarts_hi, low_hi, high_hi = _restart_pair(_constant_policy(0.0), (400,), dtype)
     print("\n[%s] restarted envs %d / %d of 256, max restarts per env %d / %d, endings < 70: %d / %d, > 350: %d / %d"
           % (dtype_name, (restarts_lo > 0).sum(), (restarts_hi > 0).sum(), restarts_lo.max(), restarts_hi.max(), low_lo, low_hi,
              high_lo, high_hi))
@@ -230,11 +99,6 @@ def test_first_restart_call_on_an_env_without_start_minute_reads_the_array_it_cr
 
 
 # ---------------------------------------------------------------------------------------------------------- 3
-def _draw_of_pair(m):
-    """the draw index of t1d_philox_normals whose value is philox_pair(.., pair = m).x"""
-    return np.where(m >= 3, 1 + 10 * ((m - 3) // 5) + 2 * ((m - 3) % 5), 0)
-
-
 @pytest.mark.parametrize("dtype_name", ["float64", "float32"])
 def test_exploration_draws_are_keyed_by_env_episode_and_clock(dtype_name):
     torch = _torch()
@@ -333,27 +197,6 @@ def test_action_and_features_are_what_the_contract_says(dtype_name, shape):
 
 
 # ---------------------------------------------------------------------------------------------------------- 5
-def _noisy_run(e, pol, sigma, warm, chunks, explore_seed=99):
-    """`warm` steps in one launch (far enough for episodes to end in what follows), then the traced chunks"""
-    stats, es, term = _stats(e), _episode_stats(e), _torch().zeros(e.n, dtype=e.dtype, device=e.device)
-    kw = dict(sigma=sigma, explore_seed=explore_seed, stats=stats, on_done="restart", days=DAYS, terminal_obs=term, episode_stats=es)
-    st = e.collect_mlp(warm, pol, **kw)
-    tr = e.new_trace(sum(chunks), columns=TRACES, history=pol.history)
-    for ch in chunks:
-        e.collect_mlp(ch, pol, policy_state=st, trace=tr, **kw)
-    assert e.sync() == 0
-    es["terminal_obs"] = term
-    return st, stats, es, tr
-
-
-def _hypo_leaning_policies(P, seed=11):
-    """small random weights around a constant 0.05 U/min"""
-    return _policy(history=4, widths=(8, 1), n_policies=P, seed=seed, output="identity", gain=0.02, out_scale=1.0, out_bias=0.05)
-
-
-GYM_STATE = STATE + ("meal_time", "meal_amt", "start_minute", "cgm0")
-
-
 def test_cuts_change_nothing_with_noise_and_restarts_on():
     torch = _torch()
     pol = _hypo_leaning_policies(1)
@@ -387,7 +230,7 @@ def test_shards_are_slices_of_the_big_batch_with_noise_and_restarts_on():
         e = _mk_gym(b - a, torch.float64, env_offset=a)
         s2, stats2, es2, tr2 = _noisy_run(e, sub, sigma[pa:pb], 150, (40,))
         sl = slice(a, b)
-        _same_env(big, e, sl, keys=GYM_STATE)
+        _same_env(big, e, GYM_STATE, sl)
         _same_dicts(st, s2, POLICY_STATE, sl)
         _same_dicts(stats, stats2, STATS, sl)
         _same_dicts(es, es2, EPISODE_STATS + ("terminal_obs",), sl)

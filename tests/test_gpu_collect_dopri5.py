@@ -3,142 +3,28 @@ csrc/t1d_dopri5.hpp): pinned bit for bit to rollout_mlp_dopri5 (no noise, no epi
 rollout_mlp_dopri5(1), restart_done and the torch reset of the policy state (episodes that end, lanes of a wave in different
 steps and episodes); the draws replayed through t1d_philox_normals; the noisy step teacher-forced through step(); the top of
 the policy's range; cut, shard and neighbour invariance; the argument checks; a solver that gives up.
-fp64, Dexcom.  The helpers are those of test_gpu_collect.py and test_gpu_policy_dopri5.py, copied."""
+fp64, Dexcom.  The gym envs, policies, comparisons and reference loops are those of test_gpu_collect.py with exact=True, the
+host-noise envs those of test_gpu_policy_dopri5.py: all from support.py."""
 import ctypes as C
+import functools
 import math
 
 import numpy as np
 import pytest
 
+import support
+from support import (DAYS, EPISODE_STATS, MLP_TRACE, POLICY_STATE, ST, STATS, TRACES, bits as _bits,
+                     constant_policy as _constant_policy, draw_of_pair as _draw_of_pair, episode_stats as _episode_stats,
+                     exact_inputs as _inputs, gpu_torch as _torch, host_noise_env as _env,
+                     hypo_leaning_policies as _hypo_leaning_policies, random_policy as _policy, same_dicts as _same_dicts,
+                     same_env as _same_env, stats as _stats)
+
 pytestmark = pytest.mark.gpu
-ST = 3                                   # Dexcom
-START = 360
-DAYS = 2
-STATE = ("state", "istate", "ar_e", "cgm", "bg", "reward", "done", "lbgi", "hbgi", "risk", "meal", "insulin", "h_carry")
-GYM_STATE = STATE + ("meal_time", "meal_amt", "start_minute", "cgm0")
-STATS = ("sum_risk", "min_bg", "max_bg", "n_low", "n_high")
-POLICY_STATE = ("cgm_hist", "ins_hist", "prev_meal")
-MLP_TRACE = ("bg", "cgm", "cho", "insulin", "action")
-TRACES = MLP_TRACE + ("reward", "done", "eps", "features")
-EPISODE_STATS = ("ep_return", "ep_length", "last_return", "last_length")
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-def _inputs(n, K, seed=3):
-    """test_gpu_policy_dopri5.py: patient row, host normals, a meal table per env"""
-    rs = np.random.RandomState(seed)
-    pid = np.arange(n) % 30
-    z = rs.randn(1 + 10 * (2 + K * ST // 150), n)
-    mt = np.sort(rs.choice(np.arange(2, max(8, K * ST - 2)), size=(n, 4)), axis=1).T.copy()
-    for j in range(1, 4):
-        mt[j] = np.maximum(mt[j], mt[j - 1] + 1)
-    ma = rs.uniform(15.0, 90.0, size=(4, n))
-    return pid, z, mt.astype(np.int64), ma
-
-
-def _env(pid, z, mt, ma):
-    torch = _torch()
-    from simglucose_amd.batch_env import BatchedT1DSimEnv
-    e = BatchedT1DSimEnv(patient=pid, sensor="Dexcom", noise="host", normals=z, integrator="dopri5")
-    e.set_meals(torch.as_tensor(mt), torch.as_tensor(ma))
-    e.start_minute = torch.full((e.n,), START, dtype=torch.int32, device=e.device)
-    e.reset()
-    return e
-
-
-def _mk_gym(n, seed=3, env_offset=0, exact=True, dtype=None):
-    """test_gpu_collect.py::_mk_gym: child#001 / adult#001 alternating, random initial glucose, Philox noise, every env
-    started through restart_done"""
-    torch = _torch()
-    from simglucose_amd.batch_env import BatchedT1DSimEnv
-    e = BatchedT1DSimEnv(patient=["child#001", "adult#001"] * (n // 2), sensor="Dexcom", pump="Insulet", dtype=dtype or torch.float64,
-                         n_sub=4, seed=seed, env_offset=env_offset, noise="philox", random_init_bg=True,
-                         integrator="dopri5" if exact else None)
-    e.restart_done(mask=torch.ones(n, dtype=torch.uint8, device=e.device), days=DAYS, reset_outputs=True)
-    return e
-
-
-def _stats(e):
-    torch = _torch()
-    z = lambda dt=e.dtype: torch.zeros(e.n, dtype=dt, device=e.device)
-    return {"sum_risk": z(), "min_bg": z() + 1000.0, "max_bg": z(), "n_low": z(torch.int32), "n_high": z(torch.int32)}
-
-
-def _episode_stats(e):
-    torch = _torch()
-    z = lambda dt=e.dtype: torch.zeros(e.n, dtype=dt, device=e.device)
-    return {"ep_return": z(), "ep_length": z(torch.int32), "last_return": z(), "last_length": z(torch.int32)}
-
-
-def _policy(history=4, widths=(16, 16, 1), n_policies=1, seed=0, hidden="tanh", output="logistic", gain=1.0, **kw):
-    torch = _torch()
-    from simglucose_amd.controller.mlp_ctrller import MLPController
-    g = torch.Generator().manual_seed(seed)
-    layers, n_in = [], 2 * history + 3
-    for w in widths:
-        layers.append((gain * torch.randn(n_policies, w, n_in, generator=g, dtype=torch.float64) / math.sqrt(n_in),
-                       gain * 0.1 * torch.randn(n_policies, w, generator=g, dtype=torch.float64)))
-        n_in = w
-    kw.setdefault("out_scale", 0.06)
-    return MLPController(layers, history=history, hidden=hidden, output=output, **kw)
-
-
-def _constant_policy(basal, history=4):
-    torch = _torch()
-    from simglucose_amd.controller.mlp_ctrller import MLPController
-    return MLPController([(torch.zeros(1, 2 * history + 3, dtype=torch.float64), torch.zeros(1, dtype=torch.float64))],
-                         history=history, output="identity", out_scale=1.0, out_bias=basal)
-
-
-def _hypo_leaning_policies(P, seed=11, **kw):
-    """small random weights around a constant 0.05 U/min"""
-    kw.setdefault("history", 4); kw.setdefault("widths", (8, 1))
-    return _policy(n_policies=P, seed=seed, output="identity", gain=0.02, out_scale=1.0, out_bias=0.05, **kw)
-
-
-def _bits(t):
-    torch = _torch()
-    t = t.contiguous()
-    return t.view({8: torch.int64, 4: torch.int32, 1: torch.uint8}[t.element_size()]) if t.is_floating_point() else t
-
-
-def _same_env(a, b, sl=slice(None), keys=STATE):
-    torch = _torch()
-    for k in keys:
-        assert torch.equal(_bits(getattr(a, k)[..., sl]), _bits(getattr(b, k))), k
-
-
-def _same_dicts(a, b, keys, sl=slice(None)):
-    torch = _torch()
-    for k in keys:
-        assert torch.equal(_bits(a[k][..., sl]), _bits(b[k])), k
-
-
-def _loop_of_entry_points(e, pol, K, stats, tr, term, es):
-    """the reference: per step rollout_mlp_dopri5(1), restart_done with h_carry, the torch reset of the policy state"""
-    torch = _torch()
-    st = e.new_policy_state(pol)
-    low = high = 0
-    zero = torch.zeros((), dtype=e.dtype, device=e.device)
-    nf = torch.zeros(e.n, dtype=torch.int64, device=e.device)
-    for _ in range(K):
-        row = tr["row"]
-        e.rollout_mlp_dopri5(1, pol, policy_state=st, stats=stats, trace=tr)
-        nf += e.nfev
-        done = e.done.bool()
-        tr["reward"][row] = e.reward; tr["done"][row] = e.done
-        low = low + (done & (e.bg < 70)).sum(); high = high + (done & (e.bg > 350)).sum()
-        e.restart_done(days=DAYS, terminal_obs=term, episode_stats=es)
-        st["cgm_hist"].copy_(torch.where(done, e.cgm, st["cgm_hist"]))
-        st["ins_hist"].copy_(torch.where(done, zero, st["ins_hist"]))
-        st["prev_meal"].copy_(torch.where(done, zero, st["prev_meal"]))
-    assert e.sync() == 0
-    return st, nf, int(low), int(high)
+STATE = support.STATE_EXACT
+GYM_STATE = support.GYM_STATE + ("h_carry",)
+_mk_gym = functools.partial(support.gym_env, exact=True)              # fp64 unless told otherwise
+_restart_pair = functools.partial(support.restart_pair, exact=True)
+_noisy_run = functools.partial(support.noisy_run, exact=True)
 
 
 # ---------------------------------------------------------------------------------------------------------- 1
@@ -160,7 +46,7 @@ def test_without_noise_and_episode_ends_it_is_rollout_mlp_dopri5_bit_for_bit():
     assert b.collect_mlp_dopri5(K - 20, pol, policy_state=sb2, stats=sb, trace=tb, sigma=None, on_done="continue") is sb2
     nfb += b.nfev
     assert b.sync() == 0
-    _same_env(a, b)
+    _same_env(a, b, STATE)
     _same_dicts(st, sb2, POLICY_STATE)
     _same_dicts(sa, sb, STATS)
     _same_dicts(ta, tb, MLP_TRACE)
@@ -173,40 +59,11 @@ def test_without_noise_and_episode_ends_it_is_rollout_mlp_dopri5_bit_for_bit():
         assert torch.equal(_bits(tb["reward"][s]), _bits(c.reward)), s
         assert torch.equal(tb["done"][s], c.done), s
     assert c.sync() == 0
-    _same_env(a, c)
+    _same_env(a, c, STATE)
     assert float(tb["reward"][1:].abs().max()) > 0
 
 
 # ---------------------------------------------------------------------------------------------------------- 2
-def _restart_pair(pol, cuts, seed=3, **kw):
-    """A: collect_mlp_dopri5 in launches of `cuts` steps; B: the loop of existing entry points -> restarts per env, endings"""
-    torch = _torch()
-    n, K = 256, sum(cuts)
-    cols = MLP_TRACE + ("reward", "done", "eps")
-    A, B = _mk_gym(n, seed=seed), _mk_gym(n, seed=seed)
-    z = lambda: torch.zeros(n, dtype=torch.float64, device=A.device)
-    sa, ta, terma, esa = _stats(A), A.new_trace(K, columns=cols), z(), _episode_stats(A)
-    sb, tb, termb, esb = _stats(B), B.new_trace(K, columns=cols[:7]), z(), _episode_stats(B)
-    sta = None
-    nfa = torch.zeros(n, dtype=torch.int64, device=A.device)
-    for k in cuts:
-        sta = A.collect_mlp_dopri5(k, pol, policy_state=sta, stats=sa, trace=ta, on_done="restart", days=DAYS, terminal_obs=terma,
-                                   episode_stats=esa, **kw)
-        nfa += A.nfev
-    assert A.sync() == 0
-    stb, nfb, low, high = _loop_of_entry_points(B, pol, K, sb, tb, termb, esb)
-    _same_env(B, A, keys=GYM_STATE + ("episode",))
-    _same_dicts(stb, sta, POLICY_STATE)
-    _same_dicts(sb, sa, STATS)
-    _same_dicts(esb, esa, EPISODE_STATS)
-    assert torch.equal(_bits(termb), _bits(terma))
-    _same_dicts(tb, ta, cols[:7])
-    assert torch.equal(nfb, nfa)
-    assert bool((ta["eps"][1:] == 0).all())
-    assert A._clock is None
-    return (B.episode - 1).cpu().numpy(), low, high
-
-
 def test_restart_is_the_loop_of_existing_entry_points_bit_for_bit():
     """400 Dexcom steps under a constant 0.05 U/min (episodes end low) in launches of 150 and 250 steps, and 400 steps without
     insulin (episodes end high), each launch cut again at 240 simulated minutes."""
@@ -221,11 +78,6 @@ def test_restart_is_the_loop_of_existing_entry_points_bit_for_bit():
 
 
 # ---------------------------------------------------------------------------------------------------------- 3
-def _draw_of_pair(m):
-    """the draw index of t1d_philox_normals whose value is philox_pair(.., pair = m).x"""
-    return np.where(m >= 3, 1 + 10 * ((m - 3) // 5) + 2 * ((m - 3) % 5), 0)
-
-
 def test_exploration_draws_are_keyed_by_env_episode_and_clock():
     torch = _torch()
     n, K, warm, explore_seed = 256, 40, 150, 0x1234ABCD5678
@@ -339,21 +191,6 @@ def test_top_of_the_range():
 
 
 # ---------------------------------------------------------------------------------------------------------- 6
-def _noisy_run(e, pol, sigma, warm, chunks, explore_seed=99, **kw2):
-    stats, es, term = _stats(e), _episode_stats(e), _torch().zeros(e.n, dtype=e.dtype, device=e.device)
-    kw = dict(sigma=sigma, explore_seed=explore_seed, stats=stats, on_done="restart", days=DAYS, terminal_obs=term, episode_stats=es)
-    st = e.collect_mlp_dopri5(warm, pol, **kw)
-    tr = e.new_trace(sum(chunks), columns=TRACES, history=pol.history)
-    nf = _torch().zeros(e.n, dtype=_torch().int64, device=e.device)
-    for ch in chunks:
-        e.collect_mlp_dopri5(ch, pol, policy_state=st, trace=tr, **kw, **kw2)
-        nf += e.nfev
-    assert e.sync() == 0
-    es["terminal_obs"] = term
-    es["nfev"] = nf
-    return st, stats, es, tr
-
-
 def test_cuts_shards_and_neighbours_change_nothing_with_noise_and_restarts_on():
     torch = _torch()
     from simglucose_amd.controller.mlp_ctrller import MLPController
@@ -380,7 +217,7 @@ def test_cuts_shards_and_neighbours_change_nothing_with_noise_and_restarts_on():
         e = _mk_gym(b - a, env_offset=a)
         s2, stats2, es2, tr2 = _noisy_run(e, sub, sigma[pa:pb], 150, (K,))
         sl = slice(a, b)
-        _same_env(e0, e, sl, keys=GYM_STATE + ("episode",))
+        _same_env(e0, e, GYM_STATE + ("episode",), sl)
         _same_dicts(st0, s2, POLICY_STATE, sl)
         _same_dicts(stats0, stats2, STATS, sl)
         _same_dicts(es0, es2, more, sl)

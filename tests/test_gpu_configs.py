@@ -10,30 +10,9 @@ Tolerances:
 import numpy as np
 import pytest
 
+from support import basal_of as _basal, dense_cho as _dense_cho, plain_env as _mk
+
 pytestmark = pytest.mark.gpu
-
-
-def _mk(**kw):
-    import torch
-    from simglucose_amd.batch_env import BatchedT1DSimEnv
-    assert torch.cuda.is_available()
-    return BatchedT1DSimEnv(**kw)
-
-
-def _basal(pid):
-    from simglucose_amd import params
-    _, tab = params.patient_table()
-    return tab[pid, params.P_COL["u2ss"]] * tab[pid, params.P_COL["BW"]] / 6000.0
-
-
-def _dense_cho(mt, ma, sample, minutes):
-    t_s, a_s = mt[:, sample].cpu().numpy().astype(np.int64), ma[:, sample].double().cpu().numpy()
-    cho = np.zeros((minutes, len(sample)))
-    for j in range(len(sample)):
-        for tt, aa in zip(t_s[:, j], a_s[:, j]):
-            if 0 <= tt < minutes:
-                cho[tt, j] = aa
-    return cho
 
 
 def test_config3_61440_envs_fp32_24h_sampled_envs_match_fp64_oracle():

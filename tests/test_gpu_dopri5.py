@@ -1,29 +1,19 @@
 """The exact mode on the GPU: t1d_step_dopri5 (scipy's dopri5 as the reference drives it) against the reference's golden
 vectors and the oracle's restatement of the same driver (oracle/t1d_oracle.c, t1d_o_dopri5_minute), from one env to
 262 144, through every layer of the Python surface."""
-import csv
+import functools
 import os
 from datetime import datetime, timedelta
 
 import numpy as np
 import pytest
 
+import support
+from support import GOLDEN, basal_of as _basal, golden_hist as _hist
+
 pytestmark = pytest.mark.gpu
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+_mk = functools.partial(support.plain_env, integrator="dopri5")
 INSULET_EXACT = np.array([0.0, 1e9, 1e-9, 0.0, 1e9, 1e-9])      # a pump that (almost) passes the action through
-
-
-def _mk(**kw):
-    import torch
-    from simglucose_amd.batch_env import BatchedT1DSimEnv
-    assert torch.cuda.is_available()
-    return BatchedT1DSimEnv(integrator="dopri5", **kw)
-
-
-def _basal(pid):
-    from simglucose_amd import params
-    _, tab = params.patient_table()
-    return tab[pid, params.P_COL["u2ss"]] * tab[pid, params.P_COL["BW"]] / 6000.0
 
 
 @pytest.mark.parametrize("sensor", ["Dexcom", "Navigator", "GuardianRT"])
@@ -132,13 +122,6 @@ def test_1024_replicas_of_one_patient_are_bitwise_equal(golden):
     assert env.sync() == 0
     assert bool((env.x == env.x[:, :1]).all()) and bool((env.h_carry == env.h_carry[0]).all())
     assert worst <= 2e-5, worst
-
-
-def _hist(name):
-    with open(os.path.join(GOLDEN, name), newline="") as f:
-        rows = list(csv.DictReader(f))
-    return {k: np.array([float(r[k]) if r[k] else np.nan for r in rows]) for k in rows[0] if k != "Time"}, \
-        [r["Time"] for r in rows]
 
 
 def test_reference_regression_test_on_the_gpu_surface():

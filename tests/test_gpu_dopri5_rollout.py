@@ -1,46 +1,23 @@
 """Closed-loop roll-outs in the exact mode on the GPU (rollout_pid_dopri5 / rollout_bb_dopri5: dopri5_rollout_kernel, every
 lane at its own pace inside a launch): bit for bit the step() loop with the controller evaluated operation by operation,
-independent of the other envs of the batch, and the reference's own closed-loop files."""
+independent of the other envs of the batch, and the reference's own closed-loop files.  Inputs and envs come from
+support.py; comparisons are by value (torch.equal): a NaN anywhere fails them.  _step_loop and _rollout stay here: they
+evaluate a PID or basal-bolus controller in torch, those of test_gpu_policy_dopri5.py a network through policy_action."""
+import functools
 import os
 from datetime import datetime
 
 import numpy as np
 import pytest
 
+import support
+from support import GOLDEN, ST, dense_cho as _dense_cho, exact_inputs as _inputs
+
 pytestmark = pytest.mark.gpu
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-ST = 3                       # Dexcom
+_mk = functools.partial(support.plain_env, integrator="dopri5")
+_env = functools.partial(support.host_noise_env, start=None)         # no start_minute: these controllers take no time of day
 STATE = ("x", "t", "cgm", "bg", "reward", "last_cgm", "prev_risk", "planned", "h_carry")
 MILD = (1.5e-4, 4e-7, 5e-4)
-
-
-def _mk(**kw):
-    import torch
-    from simglucose_amd.batch_env import BatchedT1DSimEnv
-    assert torch.cuda.is_available()
-    return BatchedT1DSimEnv(integrator="dopri5", **kw)
-
-
-def _inputs(n, K, seed=3):
-    """per-env inputs that do not depend on the env's index in a batch: patient row, host normals, a meal table"""
-    rs = np.random.RandomState(seed)
-    pid = np.arange(n) % 30
-    z = rs.randn(1 + 10 * (2 + K * ST // 150), n)
-    mt = np.sort(rs.choice(np.arange(2, max(8, K * ST - 2)), size=(n, 4)), axis=1).T.copy()      # [4][n], ascending
-    for j in range(1, 4):                                            # at most one entry per minute
-        mt[j] = np.maximum(mt[j], mt[j - 1] + 1)
-    ma = rs.uniform(15.0, 90.0, size=(4, n))
-    return pid, z, mt.astype(np.int64), ma
-
-
-def _env(pid, z, mt, ma, cols=None, **kw):
-    import torch
-    if cols is not None:
-        pid, z, mt, ma = pid[cols], z[:, cols], mt[:, cols], ma[:, cols]
-    e = _mk(patient=pid, sensor="Dexcom", noise="host", normals=z, **kw)
-    e.set_meals(torch.as_tensor(mt), torch.as_tensor(ma))
-    e.reset()
-    return e
 
 
 def _step_loop(e, kind, K, gains=MILD, target=140.0):
@@ -92,12 +69,6 @@ def _rollout(e, kind, chunks, gains=MILD, stats=None, **kw):
     return state, tr, nf
 
 
-def _same(a, b, keys=STATE):
-    import torch
-    for k in keys:
-        assert torch.equal(getattr(a, k), getattr(b, k)), k
-
-
 @pytest.mark.parametrize("kind", ["bb", "pid"])
 def test_rollout_equals_step_loop_bit_for_bit(kind):
     """Independence from the neighbours: in A the 64 envs of a wave are in the same minute in every launch, in B each lane is
@@ -108,7 +79,7 @@ def test_rollout_equals_step_loop_bit_for_bit(kind):
     ea, eb, ec = _env(*inp), _env(*inp), _env(*inp)
     sa, rows, nfa = _step_loop(ea, kind, K)
     sb_, tr, nfb = _rollout(eb, kind, (1, 9, 70, 80))
-    _same(ea, eb)
+    support.same_env(ea, eb, STATE, by="value")
     for k in sa:
         assert torch.equal(sa[k], sb_[k]), k
     for k in rows:
@@ -121,7 +92,7 @@ def test_rollout_equals_step_loop_bit_for_bit(kind):
     sc, trc, nfc = _rollout(ec, kind, (K,), max_minutes_per_launch=10 ** 6)
     ed = _env(*inp)
     sd, trd, nfd = _rollout(ed, kind, (K,), max_minutes_per_launch=30)
-    _same(ec, ed); _same(ec, eb)
+    support.same_env(ec, ed, STATE, by="value"); support.same_env(ec, eb, STATE, by="value")
     for k in sc:
         assert torch.equal(sc[k], sd[k]) and torch.equal(sc[k], sb_[k]), k
     for k in ("bg", "cgm", "cho", "insulin"):
@@ -192,16 +163,6 @@ def test_reference_closed_loop_files(golden, case):
     print(case, worst)
     for col in ref.columns:
         assert worst[col] <= {"CHO": 1e-12, "insulin": 1e-9}.get(col, 1e-6), (col, worst)
-
-
-def _dense_cho(mt, ma, sample, minutes):
-    t_s, a_s = mt[:, sample].cpu().numpy().astype(np.int64), ma[:, sample].cpu().numpy()
-    cho = np.zeros((minutes, len(sample)))
-    for j in range(len(sample)):
-        for tt, aa in zip(t_s[:, j], a_s[:, j]):
-            if 0 <= tt < minutes:
-                cho[tt, j] = aa
-    return cho
 
 
 @pytest.mark.parametrize("n,n_sample,edge", [(1 << 18, 300, 130), (1 << 20, 200, 70)])

@@ -3,20 +3,9 @@ the in-kernel PID roll-out, fp32, checkpointing and size-independent properties 
 import numpy as np
 import pytest
 
+from support import basal_of as _basal, plain_env as _mk
+
 pytestmark = pytest.mark.gpu
-
-
-def _mk(**kw):
-    import torch
-    from simglucose_amd.batch_env import BatchedT1DSimEnv
-    assert torch.cuda.is_available()
-    return BatchedT1DSimEnv(**kw)
-
-
-def _basal(pid):
-    from simglucose_amd import params
-    _, tab = params.patient_table()
-    return tab[pid, params.P_COL["u2ss"]] * tab[pid, params.P_COL["BW"]] / 6000.0
 
 
 @pytest.mark.parametrize("sensor", ["Dexcom", "Navigator"])

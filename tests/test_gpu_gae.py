@@ -7,18 +7,14 @@ import math
 
 import pytest
 
+from support import bits as _bits, gpu_torch as _torch
+
 pytestmark = pytest.mark.gpu
 SHAPES = [(64, 1), (100, 1), (100, 4), (192, 3), (300, 1)]        # a full wave; a partial one; policies that straddle a wave;
 #                                                                   policies on wave boundaries; more than one 256-thread block
 ROWS = [1, 2, 5, 33]                                               # fewer rows than a group of 8, and groups with a short first one
 GAMMA_LAMBDA = [(0.99, 0.95), (1.0, 1.0), (0.9, 0.0), (0.0, 0.5)]
 DTYPES = ["float64", "float32"]
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
 
 
 _cache = {}
@@ -41,11 +37,6 @@ def _inputs(n, K, dtype_name):
             assert int(d[row].max()) == 1 and int(d[row].min()) == 0
         _cache[key] = tuple(t.cuda().contiguous() for t in (r, d, v, vl))
     return _cache[key]
-
-
-def _bits(t):
-    torch = _torch()
-    return t.contiguous().view({8: torch.int64, 4: torch.int32}[t.element_size()])
 
 
 def _rows_left(K, like):

@@ -1,22 +1,14 @@
 """GPU tests of the drop-in Python surface: the reference's own tests, re-expressed on this package
 (tests/test_sim_engine.py::test_results_consistency, test_seed.py, test_reset.py, test_reward_fun.py,
 test_gym.py of the reference)."""
-import csv
-import os
 from datetime import datetime, timedelta
 
 import numpy as np
 import pytest
 
+from support import golden_hist as _hist
+
 pytestmark = pytest.mark.gpu
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def _hist(name):
-    with open(os.path.join(GOLDEN, name), newline="") as f:
-        rows = list(csv.DictReader(f))
-    return {k: np.array([float(r[k]) if r[k] else np.nan for r in rows]) for k in rows[0] if k != "Time"}, \
-        [r["Time"] for r in rows]
 
 
 def test_results_consistency_with_upstream_golden_file():

@@ -1,17 +1,17 @@
 """Closed-loop roll-outs under the in-kernel MLP policy on the GPU (BatchedT1DSimEnv.rollout_mlp -> t1d_rollout_mlp,
 csrc/t1d_policy.hpp): pinned to rollout_pid bit for bit, against the step() loop with the policy in torch, cut / shard /
-multi-policy invariance, the meaning of every feature, and the argument checks."""
+multi-policy invariance, the meaning of every feature, and the argument checks.  The envs (_mk: all 30 patients, a
+random-meal day from 06:00), the random policies and the comparisons come from support.py."""
 import ctypes as C
 import math
 
 import numpy as np
 import pytest
 
+from support import (ST, STATE, STATS, bits as _bits, gpu_torch as _torch, meal_day_env as _mk, random_policy as _policy,
+                     same_dicts as _same_dicts, same_env as _same_env, stats as _stats)
+
 pytestmark = pytest.mark.gpu
-ST = 3                                   # Dexcom
-START = 360                              # episodes start at 06:00, so that breakfast and lunch fall inside 160 steps
-STATE = ("state", "istate", "ar_e", "cgm", "bg", "reward", "done", "lbgi", "hbgi", "risk", "meal", "insulin")
-STATS = ("sum_risk", "min_bg", "max_bg", "n_low", "n_high")
 # fp32 tolerance of test_against_host_loop: the issue leaves it open.  Summation order is the only legitimate difference
 # between the kernel and the host loop, so the yardstick is how far the host loop's own two evaluation orders (torch.matmul
 # and bias-first ascending accumulation) drift apart on this workload: FP32_ORDER_DRIFT is the 99.5th percentile over the
@@ -23,47 +23,6 @@ FP32_ORDER_DRIFT = None                  # mg/dL
 FP32_DRIFT_FACTOR = 4.0
 
 
-def _torch():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-def _mk(n, dtype, env_offset=0, seed=5, meals=True, start=None, **kw):
-    """start: int32 [n] minute of day at which each env's episode starts (None: START for all)"""
-    torch = _torch()
-    from simglucose_amd.batch_env import BatchedT1DSimEnv
-    from simglucose_amd.scenario_batch import random_meal_tables
-    pid = (np.arange(n) + env_offset) % 30
-    e = BatchedT1DSimEnv(patient=pid, sensor="Dexcom", dtype=dtype, seed=seed, env_offset=env_offset, **kw)
-    e.start_minute = torch.full((n,), START, dtype=torch.int32, device=e.device) if start is None else \
-        torch.as_tensor(start, dtype=torch.int32).to(e.device).contiguous()
-    if meals:
-        e.set_meals(*random_meal_tables(n, days=1, start_minute_of_day=e.start_minute, seed=seed, dtype=dtype, env_offset=env_offset))
-    e.reset()
-    return e
-
-
-def _stats(e):
-    torch = _torch()
-    z = lambda dt=e.dtype: torch.zeros(e.n, dtype=dt, device=e.device)
-    st = {"sum_risk": z(), "min_bg": z() + 1000.0, "max_bg": z(), "n_low": z(torch.int32), "n_high": z(torch.int32)}
-    return st
-
-
-def _policy(history=4, widths=(16, 16, 1), n_policies=1, seed=0, hidden="tanh", output="logistic", **kw):
-    torch = _torch()
-    from simglucose_amd.controller.mlp_ctrller import MLPController
-    g = torch.Generator().manual_seed(seed)
-    layers, n_in = [], 2 * history + 3
-    for w in widths:
-        layers.append((torch.randn(n_policies, w, n_in, generator=g, dtype=torch.float64) / math.sqrt(n_in),
-                       0.1 * torch.randn(n_policies, w, generator=g, dtype=torch.float64)))
-        n_in = w
-    kw.setdefault("out_scale", 0.06)     # the logistic output spans [0, 0.06] U/min, about four times a basal rate
-    return MLPController(layers, history=history, hidden=hidden, output=output, **kw)
-
-
 def _rollout(e, pol, chunks, columns=("bg", "cgm", "cho", "insulin", "action")):
     tr = e.new_trace(sum(chunks), columns=columns)
     stats, state = _stats(e), None
@@ -71,25 +30,6 @@ def _rollout(e, pol, chunks, columns=("bg", "cgm", "cho", "insulin", "action")):
         state = e.rollout_mlp(ch, pol, policy_state=state, stats=stats, trace=tr)
     assert e.sync() == 0
     return state, stats, tr
-
-
-def _bits(t):
-    """the words of a tensor as integers: equal bit patterns compare equal, also the NaN rows new_trace leaves unwritten"""
-    torch = _torch()
-    t = t.contiguous()
-    return t.view({8: torch.int64, 4: torch.int32, 1: torch.uint8}[t.element_size()]) if t.is_floating_point() else t
-
-
-def _same_env(a, b, sl=slice(None)):
-    torch = _torch()
-    for k in STATE:
-        assert torch.equal(_bits(getattr(a, k)[..., sl]), _bits(getattr(b, k))), k
-
-
-def _same_dicts(a, b, keys, sl=slice(None)):
-    torch = _torch()
-    for k in keys:
-        assert torch.equal(_bits(a[k][..., sl]), _bits(b[k])), k
 
 
 # ---------------------------------------------------------------------------------------------------------- 1
@@ -209,7 +149,7 @@ def test_shards_equal_slices_of_the_big_batch():
         e = _mk(b - a, torch.float64, env_offset=a)
         s2, stats2, tr2 = _rollout(e, sub, (K,))
         sl = slice(a, b)
-        _same_env(big, e, sl)
+        _same_env(big, e, sl=sl)
         _same_dicts(st, s2, ("cgm_hist", "ins_hist", "prev_meal"), sl)
         _same_dicts(stats, stats2, STATS, sl)
         _same_dicts(tr, tr2, ("bg", "cgm", "cho", "insulin", "action"), sl)
@@ -245,7 +185,7 @@ def test_many_policies():
         e = mk(epp)
         s2, stats2, tr2 = _rollout(e, one, (K,))
         sl = slice(k * epp, (k + 1) * epp)
-        _same_env(big, e, sl)
+        _same_env(big, e, sl=sl)
         _same_dicts(st, s2, ("cgm_hist", "ins_hist", "prev_meal"), sl)
         _same_dicts(stats, stats2, STATS, sl)
         _same_dicts(tr, tr2, ("bg", "cgm", "cho", "insulin", "action"), sl)

@@ -3,63 +3,21 @@ t1d_rollout_mlp_dopri5, csrc/t1d_dopri5.hpp) and the policy alone (policy_action
 loop driven by policy_action, independent of the other envs of the batch, pinned to rollout_pid_dopri5 and to the oracle's
 DOPRI5 on the recorded actions, the top of the policy's range, the argument checks and a solver failure.
 
-All cases: Dexcom (3-minute steps), host normals and explicit meal tables."""
+All cases: Dexcom (3-minute steps), host normals and explicit meal tables (support.exact_inputs, support.host_noise_env).
+Comparisons are by value (torch.equal): a NaN anywhere fails them.  _step_loop and _rollout stay here: those of
+test_gpu_dopri5_rollout.py evaluate a PID or basal-bolus controller in torch, these a network through policy_action."""
 import ctypes as C
-import math
+import functools
 
 import numpy as np
 import pytest
 
+import support
+from support import MLP_TRACE as TRACE, POLICY_STATE, ST, exact_inputs as _inputs, gpu_torch as _torch, host_noise_env as _env
+
 pytestmark = pytest.mark.gpu
-ST = 3                       # Dexcom
-START = 360                  # the time-of-day features: every episode starts at 06:00
+_policy = functools.partial(support.random_policy, widths=(16, 1))       # this file's own default: one hidden layer
 STATE = ("x", "t", "cgm", "bg", "reward", "last_cgm", "prev_risk", "planned", "h_carry")      # test_gpu_dopri5_rollout.py::STATE
-POLICY_STATE = ("cgm_hist", "ins_hist", "prev_meal")
-TRACE = ("bg", "cgm", "cho", "insulin", "action")
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-def _inputs(n, K, seed=3):
-    """per-env inputs that do not depend on the env's index in a batch: patient row, host normals, a meal table"""
-    rs = np.random.RandomState(seed)
-    pid = np.arange(n) % 30
-    z = rs.randn(1 + 10 * (2 + K * ST // 150), n)
-    mt = np.sort(rs.choice(np.arange(2, max(8, K * ST - 2)), size=(n, 4)), axis=1).T.copy()      # [4][n], ascending
-    for j in range(1, 4):                                            # at most one entry per minute
-        mt[j] = np.maximum(mt[j], mt[j - 1] + 1)
-    ma = rs.uniform(15.0, 90.0, size=(4, n))
-    return pid, z, mt.astype(np.int64), ma
-
-
-def _env(pid, z, mt, ma, cols=None, exact=True, **kw):
-    torch = _torch()
-    from simglucose_amd.batch_env import BatchedT1DSimEnv
-    if cols is not None:
-        pid, z, mt, ma = pid[cols], z[:, cols], mt[:, cols], ma[:, cols]
-    e = BatchedT1DSimEnv(patient=pid, sensor="Dexcom", noise="host", normals=z, integrator="dopri5" if exact else None, **kw)
-    e.set_meals(torch.as_tensor(mt), torch.as_tensor(ma))
-    e.start_minute = torch.full((e.n,), START, dtype=torch.int32, device=e.device)
-    e.reset()
-    return e
-
-
-def _policy(history=4, widths=(16, 1), n_policies=1, seed=0, hidden="tanh", output="logistic", **kw):
-    torch = _torch()
-    from simglucose_amd.controller.mlp_ctrller import MLPController
-    g = torch.Generator().manual_seed(seed)
-    layers, n_in = [], 2 * history + 3
-    for w in widths:
-        layers.append((torch.randn(n_policies, w, n_in, generator=g, dtype=torch.float64) / math.sqrt(n_in),
-                       0.1 * torch.randn(n_policies, w, generator=g, dtype=torch.float64)))
-        n_in = w
-    # the logistic output spans [0, 0.06] U/min, about four times a basal rate and far below the pump's 0.5 U/min
-    kw.setdefault("out_scale", 0.06)
-    return MLPController(layers, history=history, hidden=hidden, output=output, **kw)
 
 
 def _step_loop(e, pol, K):
@@ -92,18 +50,6 @@ def _rollout(e, pol, chunks, **kw):
     return st, tr, nf
 
 
-def _same(a, b, keys=STATE, sl=slice(None)):
-    torch = _torch()
-    for k in keys:
-        assert torch.equal(getattr(a, k)[..., sl], getattr(b, k)), k
-
-
-def _same_dicts(a, b, keys, sl=slice(None)):
-    torch = _torch()
-    for k in keys:
-        assert torch.equal(a[k][..., sl], b[k]), k
-
-
 def _meals_and_moving_actions(rows):
     assert bool((rows["cho"] > 0).any())
     assert float(rows["action"].std(dim=0).max()) > 0            # the action trace is not constant
@@ -124,8 +70,8 @@ def test_rollout_equals_step_loop_bit_for_bit():
     for chunks, kw in (((1, 9, 50), {}), ((K,), {"max_minutes_per_launch": 10 ** 6}), ((K,), {"max_minutes_per_launch": 30})):
         e = _env(*inp)
         st, tr, nf = _rollout(e, pol, chunks, **kw)
-        _same(ea, e)
-        _same_dicts(sa, st, POLICY_STATE)
+        support.same_env(ea, e, STATE, by="value")
+        support.same_dicts(sa, st, POLICY_STATE, by="value")
         for k in TRACE:
             assert torch.equal(rows[k], tr[k][1:]), (k, chunks, kw)
         assert torch.equal(nfa, nf)
@@ -177,8 +123,8 @@ def test_the_same_envs_in_different_company():
     sb, trb, nfb = _rollout(big, pol, (K,))
     ss, trs, nfs = _rollout(small, one, (K,))
     sl = slice(0, 64)
-    _same(big, small, sl=sl)
-    _same_dicts(sb, ss, POLICY_STATE, sl)
+    support.same_env(big, small, STATE, sl, by="value")
+    support.same_dicts(sb, ss, POLICY_STATE, sl, by="value")
     for k in TRACE:
         assert torch.equal(trb[k][1:, sl], trs[k][1:]), k
     assert torch.equal(nfb[sl], nfs)
@@ -206,7 +152,7 @@ def test_one_weight_on_cgm0_is_rollout_pid_dopri5_bit_for_bit():
     nfa += a.nfev
     _, tb, nfb = _rollout(b, pol, (15, K - 15))
     assert a.sync() == 0 and b.sync() == 0
-    _same(a, b)
+    support.same_env(a, b, STATE, by="value")
     for k in ("bg", "cgm", "cho", "insulin"):
         assert torch.equal(ta[k][1:], tb[k][1:]), k              # row 0: what reset() recorded (NaN for cho and insulin)
     assert torch.equal(nfa, nfb)
@@ -272,8 +218,8 @@ def test_top_of_the_range():
     ea, eb = _env(*inp), _env(*inp)
     sa, rows, nfa = _step_loop(ea, pol, K)
     sb, tr, nfb = _rollout(eb, pol, (5, 7))
-    _same(ea, eb)
-    _same_dicts(sa, sb, POLICY_STATE)
+    support.same_env(ea, eb, STATE, by="value")
+    support.same_dicts(sa, sb, POLICY_STATE, by="value")
     for k in TRACE:
         assert torch.equal(rows[k], tr[k][1:]), k
     assert torch.equal(nfa, nfb)

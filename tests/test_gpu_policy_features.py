@@ -2,73 +2,18 @@
 come next, pinned bit for bit to the row the next collect call records -- on a fresh state, after episodes ended and
 restarted inside a launch, and in the exact mode; against the host restatement MLPController.features; the rejections; and
 one whole actor-critic iteration (collect, critic, bootstrap, gae, PPO loss, backward) whose gradients repeat bit for bit.
-The helpers are those of test_gpu_collect.py, copied."""
+The envs, policies and the bit comparison are those of test_gpu_collect.py, from support.py."""
 import ctypes as C
-import math
 
 import pytest
 
+import support
+from support import (DAYS, POLICY_STATE, bits as _bits, gpu_torch as _torch, gym_env as _mk_gym,
+                     hypo_leaning_policies as _hypo_leaning_policies, meal_day_env as _mk, random_policy as _policy)
+
 pytestmark = pytest.mark.gpu
 N = 128
-DAYS = 2
-STATE = ("state", "istate", "ar_e", "cgm", "bg", "reward", "done", "lbgi", "hbgi", "risk", "meal", "insulin", "meal_time",
-         "meal_amt", "start_minute", "episode")
-POLICY_STATE = ("cgm_hist", "ins_hist", "prev_meal")
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available()
-    return torch
-
-
-def _mk_gym(n, dtype, seed=3, exact=False):
-    """child#001 / adult#001 alternating, random initial glucose, Philox noise, every env in episode 0 of the device's own
-    episode stream: the envs of test_gpu_collect.py"""
-    torch = _torch()
-    from simglucose_amd.batch_env import BatchedT1DSimEnv
-    kw = dict(integrator="dopri5") if exact else dict(n_sub=4)
-    e = BatchedT1DSimEnv(patient=["child#001", "adult#001"] * (n // 2), sensor="Dexcom", pump="Insulet", dtype=dtype,
-                         seed=seed, noise="philox", random_init_bg=True, **kw)
-    e.restart_done(mask=torch.ones(n, dtype=torch.uint8, device=e.device), days=DAYS, reset_outputs=True)
-    return e
-
-
-def _mk(n, dtype, seed=5):
-    """all 30 patients, a random-meal day from 06:00, reset: the envs of test_gpu_policy.py"""
-    torch = _torch()
-    import numpy as np
-    from simglucose_amd.batch_env import BatchedT1DSimEnv
-    from simglucose_amd.scenario_batch import random_meal_tables
-    e = BatchedT1DSimEnv(patient=np.arange(n) % 30, sensor="Dexcom", dtype=dtype, seed=seed)
-    e.start_minute = torch.full((n,), 360, dtype=torch.int32, device=e.device)
-    e.set_meals(*random_meal_tables(n, days=1, start_minute_of_day=e.start_minute, seed=seed, dtype=dtype))
-    e.reset()
-    return e
-
-
-def _policy(history=4, widths=(16, 16, 1), n_policies=1, seed=0, hidden="tanh", output="logistic", gain=1.0, **kw):
-    torch = _torch()
-    from simglucose_amd.controller.mlp_ctrller import MLPController
-    g = torch.Generator().manual_seed(seed)
-    layers, n_in = [], 2 * history + 3
-    for w in widths:
-        layers.append((gain * torch.randn(n_policies, w, n_in, generator=g, dtype=torch.float64) / math.sqrt(n_in),
-                       gain * 0.1 * torch.randn(n_policies, w, generator=g, dtype=torch.float64)))
-        n_in = w
-    kw.setdefault("out_scale", 0.06)
-    return MLPController(layers, history=history, hidden=hidden, output=output, **kw)
-
-
-def _hypo_leaning_policy(history, seed=11):
-    """small random weights around a constant 0.05 U/min: episodes end low (test_gpu_collect.py)"""
-    return _policy(history=history, widths=(8, 1), seed=seed, output="identity", gain=0.02, out_scale=1.0, out_bias=0.05)
-
-
-def _bits(t):
-    torch = _torch()
-    t = t.contiguous()
-    return t.view({8: torch.int64, 4: torch.int32, 1: torch.uint8}[t.element_size()]) if t.is_floating_point() else t
+STATE = support.STATE + ("meal_time", "meal_amt", "start_minute", "episode")
 
 
 def _snapshot(e, st):
@@ -118,7 +63,7 @@ def test_after_restarts_inside_a_launch(H, dtype_name):
     starts a new episode: its start_minute, clock and windows are the new episode's."""
     torch = _torch()
     e = _mk_gym(N, getattr(torch, dtype_name))
-    pol = _hypo_leaning_policy(H)
+    pol = _hypo_leaning_policies(1, history=H)
     kw = dict(sigma=0.3, explore_seed=99, on_done="restart", days=DAYS)
     st = e.collect_mlp(150, pol, **kw)
     ep0, start0 = e.episode.clone(), e.start_minute.clone()
@@ -138,7 +83,7 @@ def test_after_restarts_inside_a_launch(H, dtype_name):
 def test_exact_mode():
     torch = _torch()
     e = _mk_gym(N, torch.float64, exact=True)
-    pol = _hypo_leaning_policy(4)
+    pol = _hypo_leaning_policies(1, history=4)
     kw = dict(sigma=0.3, explore_seed=99, on_done="restart", days=DAYS)
     st = e.new_policy_state(pol)
     f = e.policy_features(pol, st)
@@ -217,7 +162,7 @@ def _iteration():
     from simglucose_amd.controller.mlp_ctrller import MLPController
     K, sig, clip = 8, 0.3, 0.2
     e = _mk_gym(N, torch.float64)
-    pol = _hypo_leaning_policy(4)
+    pol = _hypo_leaning_policies(1, history=4)
     vpol = _policy(history=4, widths=(8, 1), seed=5, output="identity", out_scale=1.0)
     st = e.collect_mlp(150, pol, sigma=sig, explore_seed=7, on_done="restart", days=DAYS)
     tr = e.new_trace(K, columns=("reward", "done", "eps", "features"), history=pol.history)

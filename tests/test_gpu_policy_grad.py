@@ -4,28 +4,12 @@ Largest measured |grad - grad_reference| / S on an MI355X over the cases of test
 test prints it): fp64 2.76e-14 where the bound 8 (N + 200) u is 3.48e-13, fp32 2.29e-07 where it is 1.87e-04
 (profiles/policy/README.md)."""
 import ctypes as C
-import math
 
 import pytest
 
+from support import gpu_torch as _torch, identity_policy as _policy
+
 pytestmark = pytest.mark.gpu
-
-
-def _torch():
-    import torch
-    return torch
-
-
-def _policy(history, widths, P, hidden, seed, gain=1.0):
-    torch = _torch()
-    from simglucose_amd.controller.mlp_ctrller import MLPController
-    g = torch.Generator().manual_seed(seed)
-    layers, n_in = [], 2 * history + 3
-    for w in widths:
-        layers.append((gain * torch.randn(P, w, n_in, generator=g, dtype=torch.float64) / math.sqrt(n_in),
-                       0.1 * torch.randn(P, w, generator=g, dtype=torch.float64)))
-        n_in = w
-    return MLPController(layers, history=history, hidden=hidden, output="identity", out_scale=1.0, out_bias=0.0)
 
 
 def _inputs(pol, K, n, dtype, seed):
@@ -58,7 +42,7 @@ def test_y_is_the_collectors_word(history, widths, hidden, f64, exact):
     from simglucose_amd.controller import mlp_pre_output
     dtype = torch.float64 if f64 else torch.float32
     n, P, K = 128, 2, 5
-    pol = _policy(history, widths, P, hidden, seed=5, gain=0.3)
+    pol = _policy(history, widths, P, hidden=hidden, seed=5, gain=0.3)
     env = BatchedT1DSimEnv(patient=["child#001", "adult#001"] * (n // 2), sensor="Dexcom", dtype=dtype, seed=3,
                            integrator="dopri5" if exact else None)
     env.reset()
@@ -92,7 +76,7 @@ def test_gradient_against_the_reference(history, widths, n, K, hidden, f64):
     torch = _torch()
     P = 2
     dtype = torch.float64 if f64 else torch.float32
-    pol = _policy(history, widths, P, hidden, seed=7)
+    pol = _policy(history, widths, P, hidden=hidden, seed=7)
     params, feat, coef = _inputs(pol, K, n, dtype, seed=11)
     ref, info = pol.grad_reference(feat, coef, params=params, info=True)
     if hidden == "relu" and len(widths) > 1:
@@ -114,7 +98,7 @@ def test_relu_seed_keeps_clear_of_the_kink_on_the_cpu():
     for history, widths, n, K in GRAD_CASES:
         if len(widths) == 1:
             continue
-        pol = _policy(history, widths, 2, "relu", seed=7)
+        pol = _policy(history, widths, 2, hidden="relu", seed=7)
         g = torch.Generator().manual_seed(11)
         feat = torch.rand(K, pol.n_features, n, generator=g, dtype=torch.float64) * 4 - 2
         coef = torch.randn(K, n, generator=g, dtype=torch.float64)
@@ -125,7 +109,7 @@ def test_relu_seed_keeps_clear_of_the_kink_on_the_cpu():
 def test_determinism_and_independence():
     torch = _torch()
     from simglucose_amd.controller import mlp_pre_output
-    pol = _policy(4, (8, 8, 1), 2, "tanh", seed=9)
+    pol = _policy(4, (8, 8, 1), 2, hidden="tanh", seed=9)
     n, K = 256, 5
     params, feat, coef = _inputs(pol, K, n, torch.float64, seed=13)
     g1, y1 = _grad(pol, params, feat, coef, y=True)
@@ -149,7 +133,7 @@ def test_autograd_plumbing():
     torch = _torch()
     from simglucose_amd.controller import mlp_pre_output
     from simglucose_amd.controller.mlp_ctrller import MLPController
-    pol = _policy(4, (8, 8, 1), 2, "tanh", seed=15)
+    pol = _policy(4, (8, 8, 1), 2, hidden="tanh", seed=15)
     n, K = 128, 3
     old_params, feat, adv = _inputs(pol, K, n, torch.float64, seed=17)
     g = torch.Generator().manual_seed(19)
@@ -204,7 +188,7 @@ def test_buffers():
     torch = _torch()
     from simglucose_amd import _lib
     from simglucose_amd.controller.mlp_grad import mlp_grad_call, _struct
-    pol = _policy(4, (8, 8, 1), 2, "tanh", seed=21)
+    pol = _policy(4, (8, 8, 1), 2, hidden="tanh", seed=21)
     n, K = 256, 5
     params, feat, coef = _inputs(pol, K, n, torch.float64, seed=23)
     both, y_both = _grad(pol, params, feat, coef, y=True)

@@ -8,6 +8,7 @@ import ctypes as C
 
 import pytest
 
+from support import gpu_torch as _torch
 from test_policy_loss_host import CLIP, LOSS_CASES, recipe
 
 pytestmark = pytest.mark.gpu
@@ -19,11 +20,6 @@ COEF_RTOL = {True: 4 * 4.53e-14, False: 4 * 1.20e-05}
 LOSS_RTOL = {True: 4 * 2.32e-16, False: 4 * 4.85e-08}
 DSIG_RTOL = {True: 4 * 2.14e-16, False: 4 * 1.14e-07}
 KL_RTOL = {True: 4 * 1.97e-15, False: 4 * 3.47e-07}      # sum of expm1(logr) - logr, formed in double from the call's logr
-
-
-def _torch():
-    import torch
-    return torch
 
 
 def _dev(c):

@@ -1,28 +1,13 @@
 """CPU suite: t1d_mlp_grad without a GPU -- the exports, the struct mirror, the workspace size, every argument check
 (validation comes before any HIP call), and the host restatements MLPController.pre_output / grad_reference."""
 import ctypes as C
-import os
-import re
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import header_fields, mlp_struct as _mlp
+
 U = 2.0 ** -53
-
-
-def _mlp(L, widths=(8, 8, 1), history=4, n_policies=2, envs_per_policy=64, params=0x1000):
-    from simglucose_amd import _lib
-    from simglucose_amd.controller.mlp_ctrller import MLPController
-    p = _lib.Mlp()
-    p.history, p.n_layers = history, len(widths)
-    for k in range(4):
-        p.width[k] = widths[k] if k < len(widths) else 0
-    p.hidden_act = 0
-    p.n_policies, p.envs_per_policy = n_policies, envs_per_policy
-    p.n_params = MLPController.count_params(history, widths)
-    p.params = params
-    return p
 
 
 def test_symbols_are_exported():
@@ -34,15 +19,7 @@ def test_symbols_are_exported():
 
 def test_mlp_batch_struct_layout_matches_header():
     from simglucose_amd import _lib
-    src = open(os.path.join(ROOT, "include", "t1d.h")).read()
-    body = src[src.index("typedef struct t1d_mlp_batch {"):src.index("} t1d_mlp_batch;")]
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for stmt in body.replace("typedef struct t1d_mlp_batch {", "").split(";"):
-        for part in stmt.split(","):
-            m = re.findall(r"([A-Za-z_0-9]+)\s*$", part.strip())
-            if m and part.strip():
-                fields.append(m[0])
+    fields = [f[0] for f in header_fields("t1d_mlp_batch")]
     assert fields == [f[0] for f in _lib.MlpBatch._fields_]
     assert C.sizeof(_lib.MlpBatch) == 8 * len(fields)
 
@@ -50,7 +27,7 @@ def test_mlp_batch_struct_layout_matches_header():
 def test_workspace_size():
     from simglucose_amd import _lib
     L = _lib.lib()
-    p = _mlp(L)
+    p = _mlp()
     # 2 policies x 1 chunk x 3 rows: one partial per tile
     assert L.t1d_mlp_grad_workspace(C.byref(p), _lib.T1D_F64, 128, 3) == 2 * 3 * p.n_params * 8
     assert L.t1d_mlp_grad_workspace(C.byref(p), _lib.T1D_F32, 128, 3) == 2 * 3 * p.n_params * 4
@@ -59,7 +36,7 @@ def test_workspace_size():
     # many tiles: about 2048 partials in all, whatever the number of rows
     big = L.t1d_mlp_grad_workspace(C.byref(p), _lib.T1D_F64, 128, 100000)
     assert 0 < big <= 2 * 1025 * p.n_params * 8
-    bad = _mlp(L, widths=(33, 1))
+    bad = _mlp(widths=(33, 1))
     assert L.t1d_mlp_grad_workspace(C.byref(bad), _lib.T1D_F64, 128, 3) < 0
     assert L.t1d_mlp_grad_workspace(C.byref(p), _lib.T1D_F64, 128, 0) < 0
     assert L.t1d_mlp_grad_workspace(C.byref(p), 7, 128, 3) < 0
@@ -80,26 +57,26 @@ def test_every_invalid_argument_is_rejected_without_a_gpu():
     def call(p, b, n=128, dtype=F64):
         return L.t1d_mlp_grad(0, dtype, n, C.byref(p) if p is not None else None, C.byref(b) if b is not None else None, None)
 
-    ok = _mlp(L)
+    ok = _mlp()
     # what t1d_rollout_mlp rejects of the network's fields
-    assert call(_mlp(L, history=0), io()) == -1 and b"history" in L.t1d_last_error()
-    assert call(_mlp(L, history=13), io()) == -1
-    assert call(_mlp(L, widths=(33, 1)), io()) == -1 and b"width" in L.t1d_last_error()
-    assert call(_mlp(L, widths=(8, 2)), io()) == -1 and b"last layer" in L.t1d_last_error()
-    p = _mlp(L); p.n_layers = 5
+    assert call(_mlp(history=0), io()) == -1 and b"history" in L.t1d_last_error()
+    assert call(_mlp(history=13), io()) == -1
+    assert call(_mlp(widths=(33, 1)), io()) == -1 and b"width" in L.t1d_last_error()
+    assert call(_mlp(widths=(8, 2)), io()) == -1 and b"last layer" in L.t1d_last_error()
+    p = _mlp(); p.n_layers = 5
     assert call(p, io()) == -1
-    p = _mlp(L); p.n_params += 1
+    p = _mlp(); p.n_params += 1
     assert call(p, io()) == -1 and b"n_params" in L.t1d_last_error()
-    p = _mlp(L); p.hidden_act = 2
+    p = _mlp(); p.hidden_act = 2
     assert call(p, io()) == -1 and b"hidden_act" in L.t1d_last_error()
-    assert call(_mlp(L, params=None), io()) == -1 and b"params" in L.t1d_last_error()
-    assert call(_mlp(L, n_policies=0), io()) == -1
+    assert call(_mlp(params=None), io()) == -1 and b"params" in L.t1d_last_error()
+    assert call(_mlp(n_policies=0), io()) == -1
     assert call(None, io()) == -1
     assert call(ok, None) == -1
     assert call(ok, io(), dtype=5) == -1
     # n and the split into policies
     assert call(ok, io(), n=192) == -1 and b"n_policies * envs_per_policy" in L.t1d_last_error()
-    assert call(_mlp(L, envs_per_policy=96), io(), n=192) == -1 and b"multiple of 64" in L.t1d_last_error()
+    assert call(_mlp(envs_per_policy=96), io(), n=192) == -1 and b"multiple of 64" in L.t1d_last_error()
     # the batch
     assert call(ok, io(n_rows=0)) == -1 and b"n_rows" in L.t1d_last_error()
     assert call(ok, io(feat=None)) == -1 and b"feat" in L.t1d_last_error()
@@ -110,7 +87,7 @@ def test_every_invalid_argument_is_rejected_without_a_gpu():
     assert call(ok, io(workspace_bytes=need - 1)) == -1 and b"workspace" in L.t1d_last_error()
     # the ignored fields may be anything: out_act, scales and state pointers are not looked at (a valid call would go on to
     # the device, so this is only checked through the workspace size)
-    p = _mlp(L); p.out_act = 9
+    p = _mlp(); p.out_act = 9
     assert L.t1d_mlp_grad_workspace(C.byref(p), F64, 128, 3) == need
 
 

@@ -1,15 +1,12 @@
 """CPU suite: the host form of the in-kernel policy (controller/mlp_ctrller.py) and the ctypes mirror of t1d_mlp."""
 import ctypes as C
 import math
-import os
-import re
 
 import pytest
 import torch
 
 from simglucose_amd.controller.mlp_ctrller import MLPController
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import header_fields as _header_fields
 
 
 def _net(history=3, widths=(8, 5, 1), act=torch.nn.Tanh, sigmoid=True, seed=0):
@@ -128,22 +125,6 @@ def test_argument_checks_raise():
         two.forward(torch.zeros(11, 3, dtype=torch.float64))
     with pytest.raises(ValueError):
         two.policy(None, 0, False)
-
-
-def _header_fields(name):
-    src = open(os.path.join(ROOT, "include", "t1d.h")).read()
-    body = src[src.index("typedef struct %s {" % name):src.index("} %s;" % name)]
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S).replace("typedef struct %s {" % name, "")
-    out = []
-    for stmt in body.split(";"):
-        stmt = stmt.strip()
-        if not stmt:
-            continue
-        ctype = re.match(r"(const\s+)?(\w+)", stmt).group(2)
-        for part in stmt.split(","):
-            m = re.search(r"([A-Za-z_0-9]+)(\[(\d+)\])?\s*$", part.strip())
-            out.append((m.group(1), ctype, "*" in stmt, int(m.group(3) or 1)))
-    return out
 
 
 def test_mlp_struct_matches_header():

@@ -3,12 +3,13 @@
 input recipe of the GPU suite (tests/test_gpu_policy_loss.py imports it from here)."""
 import ctypes as C
 import functools
-import math
 import os
 import re
 
 import pytest
 import torch
+
+from support import identity_policy as _policy, mlp_struct as _mlp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLIP = 0.2
@@ -23,17 +24,6 @@ LOSS_CASES = [
 
 
 # ------------------------------------------------------------------------------------------------ the GPU suite's inputs
-def _policy(history, widths, P, hidden, seed, gain=1.0):
-    from simglucose_amd.controller.mlp_ctrller import MLPController
-    g = torch.Generator().manual_seed(seed)
-    layers, n_in = [], 2 * history + 3
-    for w in widths:
-        layers.append((gain * torch.randn(P, w, n_in, generator=g, dtype=torch.float64) / math.sqrt(n_in),
-                       0.1 * torch.randn(P, w, generator=g, dtype=torch.float64)))
-        n_in = w
-    return MLPController(layers, history=history, hidden=hidden, output="identity", out_scale=1.0, out_bias=0.0)
-
-
 def host_y(pol, params, feat):
     """y [K, n] in fp64 on the CPU under params [P, n_params]: MLPController.pre_output(ordered=True), the kernel's order, on
     all K rows at once (the envs regrouped so that policy p still owns one contiguous block)"""
@@ -55,7 +45,7 @@ def recipe(history, widths, n, K, P, hidden, f64):
     from simglucose_amd.controller.policy_loss import ppo_clip_loss_reference
     dtype = torch.float64 if f64 else torch.float32
     rd = lambda t: t.to(dtype).double()
-    pol = _policy(history, widths, P, hidden, seed=7)
+    pol = _policy(history, widths, P, hidden=hidden, seed=7)
     g = torch.Generator().manual_seed(11)
     feat = rd(torch.rand(K, pol.n_features, n, generator=g, dtype=torch.float64) * 4 - 2)
     eps = rd(torch.randn(K, n, generator=g, dtype=torch.float64))
@@ -82,20 +72,6 @@ def recipe(history, widths, n, K, P, hidden, f64):
 
 
 # ------------------------------------------------------------------------------------------------ 1: exports, struct
-def _mlp(widths=(8, 8, 1), history=4, n_policies=2, envs_per_policy=64, params=0x1000):
-    from simglucose_amd import _lib
-    from simglucose_amd.controller.mlp_ctrller import MLPController
-    p = _lib.Mlp()
-    p.history, p.n_layers = history, len(widths)
-    for k in range(4):
-        p.width[k] = widths[k] if k < len(widths) else 0
-    p.hidden_act = 0
-    p.n_policies, p.envs_per_policy = n_policies, envs_per_policy
-    p.n_params = MLPController.count_params(history, widths)
-    p.params = params
-    return p
-
-
 def test_symbols_are_exported():
     from simglucose_amd import _lib
     L = _lib.lib()
@@ -216,7 +192,7 @@ def test_every_invalid_argument_is_rejected_without_a_gpu():
 def test_python_argument_checks_raise_value_error():
     """what can be refused before the device is needed: tensors on the CPU are refused like mlp_pre_output refuses them"""
     from simglucose_amd.controller import ppo_clip_loss, value_loss
-    pol = _policy(4, (8, 8, 1), 2, "tanh", seed=1)
+    pol = _policy(4, (8, 8, 1), 2, hidden="tanh", seed=1)
     feat = torch.zeros(3, pol.n_features, 128, dtype=torch.float64)
     a = torch.zeros(3, 128, dtype=torch.float64)
     with pytest.raises(ValueError, match="ppo_clip_loss"):
