@@ -34,6 +34,7 @@
  *                       would come next (no counterpart in the reference; its gym env hands back one CGM value, env.py:81)
  *   t1d_mlp_grad     <- the network again on a collected batch, and its weight gradient (what autograd does for a gym trainer)
  *   t1d_mlp_loss     <- the same with the PPO-clip or value loss inside the launch: one forward pass per epoch
+ *   t1d_mlp_grad_tiles, t1d_mlp_loss_tiles  <- either on a minibatch: a list of 64-env tiles of the batch, read in place
  *   t1d_gae          <- the trainer's backward loop over a collected batch: advantages (generalised advantage estimation),
  *                       value targets and the advantage moments PPO normalises with (no counterpart in the reference)
  *   t1d_random_meals <- RandomScenario.create_scenario  simglucose/simulation/scenario_gen.py:33-60
@@ -346,6 +347,15 @@ struct t1d_mlp_loss {
     void* workspace;          /* device scratch for the partial sums; needed with grad or stats */
     int64_t workspace_bytes;  /* at least t1d_mlp_loss_workspace() */
 };
+
+/* t1d_mlp_grad_tiles / t1d_mlp_loss_tiles: the minibatch of a call, as a list of tiles per policy.  A tile is the 64 envs of
+ * one 64-env chunk of one policy in one row, numbered u = row * C + chunk, C = envs_per_policy / 64 (the unit t1d_mlp_grad's
+ * summation order is stated in). */
+typedef struct t1d_tile_list {
+    int64_t n_tiles;          /* M >= 1: list positions per policy */
+    const int32_t* tiles;     /* device, [n_policies][M]: tile ids u = row * C + chunk of that policy; an id < 0 or >= C *
+                                 n_rows is skipped */
+} t1d_tile_list;
 
 /* t1d_gae: one collected batch of rewards, dones and the critic's values, and what comes back.  Floating arrays have the
  * call's dtype; done is what t1d_collect.done_trace holds. */
@@ -667,6 +677,43 @@ int t1d_mlp_grad(int hip_device, int dtype, int64_t n, const t1d_mlp* mlp, const
  * is not finite; y, coef_out, grad and stats all NULL; grad or stats with a NULL or too small workspace. */
 int64_t t1d_mlp_loss_workspace(const t1d_mlp* mlp, int dtype, int64_t n, int64_t n_rows);
 int t1d_mlp_loss(int hip_device, int dtype, int64_t n, const t1d_mlp* mlp, const struct t1d_mlp_loss* io, void* hip_stream);
+
+/* t1d_mlp_grad and t1d_mlp_loss on a minibatch: the same call on the tiles a list names, read and written in place -- the
+ * gradient step of a PPO epoch on a random part of the batch without a gathered copy of it.  No ctx; nothing is allocated, the
+ * call only enqueues work on the stream.  fp64 and fp32; mlp and io are read as by the plain call, and nothing is added to
+ * either struct.
+ * Same arrays: feat, eps, y_old, adv, target, coef, y and coef_out keep their full [n_rows][...][n] layout and addressing; only
+ *   the listed tiles are visited.  Position j of policy p's row names tile u = tiles[p][j]: row u / C, envs p * envs_per_policy
+ *   + 64 * (u % C) .. + 63.  y and coef_out are written at the listed tiles' own positions; every other word of them is left
+ *   untouched.
+ * Duplicates: the list may name a tile twice (sampling with replacement); the tile then counts twice in grad and stats, and its
+ *   words of y and coef_out are written twice with the same values.
+ * Skipped ids: an id < 0 or >= C * n_rows is skipped: nothing is read or written for it and it adds nothing to any sum.  The
+ *   ids are device data that the host cannot check, so the bound check is made on the device and is part of the contract, not
+ *   a debug aid; -1 serves as padding.  A list of skipped ids alone gives grad = 0 and stats = 0.
+ * Order: t1d_mlp_grad's rule with list positions in place of tile numbers.  With T = max(1, ceil(n_policies * M / 2048)),
+ *   partial k of a policy covers positions k T .. min((k + 1) T, M) - 1 in ascending order; inside a tile the order is that of
+ *   the plain call; grad[p][q] and stats[p][j] = ((0 + partial 0) + partial 1) + ... in ascending k.  Deterministic and portable
+ *   as the plain calls are: the order depends only on (n_policies, M, dtype, widths) and the list.
+ * Two identities follow, both bit for bit:
+ *   - with the identity list 0 .. C * n_rows - 1 for every policy, every output equals the plain call's;
+ *   - for any list without skipped ids, grad, stats and the visited words of y / coef_out equal those of a plain call on the
+ *     gathered batch: n' = 64 * n_policies, envs_per_policy' = 64, n_rows' = M, row j of policy p holding tile tiles[p][j] of
+ *     every array (the same scale, sigma and weights).
+ * scale stays the caller's, e.g. 1 / (64 * M * n_policies) for a mean over the listed samples.
+ * workspace: t1d_mlp_grad_tiles_workspace(mlp, dtype, n, n_tiles) bytes = n_policies * ceil(M / T) * n_params words;
+ *   t1d_mlp_loss_tiles_workspace(mlp, dtype, n, n_tiles) = that rounded up to a multiple of 8, plus 32 bytes for every partial,
+ *   n_policies * ceil(M / T) of them (host only, mlp.params may be NULL; < 0 = invalid arguments, n_tiles < 1 among them).
+ *   Neither depends on n_rows.  Nothing beyond them is written.
+ * T1D_E_INVALID before anything is launched and before the device is touched: everything the plain call rejects; a NULL list,
+ * a NULL tiles, n_tiles < 1; n_policies * n_tiles > 2^31 - 1; grad (or stats) with a workspace smaller than the
+ * _tiles_workspace() of the call. */
+int64_t t1d_mlp_grad_tiles_workspace(const t1d_mlp* mlp, int dtype, int64_t n, int64_t n_tiles);
+int t1d_mlp_grad_tiles(int hip_device, int dtype, int64_t n, const t1d_mlp* mlp, const t1d_mlp_batch* io, const t1d_tile_list* list,
+                       void* hip_stream);
+int64_t t1d_mlp_loss_tiles_workspace(const t1d_mlp* mlp, int dtype, int64_t n, int64_t n_tiles);
+int t1d_mlp_loss_tiles(int hip_device, int dtype, int64_t n, const t1d_mlp* mlp, const struct t1d_mlp_loss* io,
+                       const t1d_tile_list* list, void* hip_stream);
 
 /* Generalised advantage estimation over a collected batch: the scan from (reward, done, value) to advantages and value targets,
  * and the per-policy sums advantage normalisation needs -- what stands between t1d_collect_mlp / t1d_collect_mlp_dopri5 and the

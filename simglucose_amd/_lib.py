@@ -35,7 +35,8 @@ EXPORTS = ("t1d_abi_version", "t1d_last_error", "t1d_ctx_create", "t1d_ctx_set_o
            "t1d_rollout_pid_dopri5", "t1d_rollout_bb_dopri5", "t1d_restart_done", "t1d_rollout_mlp",
            "t1d_collect_mlp", "t1d_rollout_mlp_dopri5", "t1d_mlp_action", "t1d_collect_mlp_dopri5",
            "t1d_mlp_grad_workspace", "t1d_mlp_grad", "t1d_mlp_features", "t1d_gae_workspace", "t1d_gae",
-           "t1d_mlp_loss_workspace", "t1d_mlp_loss")
+           "t1d_mlp_loss_workspace", "t1d_mlp_loss", "t1d_mlp_grad_tiles_workspace", "t1d_mlp_grad_tiles",
+           "t1d_mlp_loss_tiles_workspace", "t1d_mlp_loss_tiles")
 
 
 class T1DError(RuntimeError):
@@ -125,6 +126,11 @@ class MlpLoss(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class TileList(C.Structure):
+    """struct t1d_tile_list (include/t1d.h)"""
+    _fields_ = [("n_tiles", C.c_int64), ("tiles", C.c_void_p)]
+
+
 class GaeBatch(C.Structure):
     """struct t1d_gae_batch (include/t1d.h)"""
     _fields_ = [("n_rows", C.c_int64), ("n_policies", C.c_int64), ("gamma", C.c_double), ("lam", C.c_double),
@@ -209,6 +215,10 @@ def lib():
     L.t1d_mlp_grad.argtypes = [C.c_int, C.c_int, i64, C.POINTER(Mlp), C.POINTER(MlpBatch), vp]
     L.t1d_mlp_loss_workspace.argtypes = [C.POINTER(Mlp), C.c_int, i64, i64]
     L.t1d_mlp_loss.argtypes = [C.c_int, C.c_int, i64, C.POINTER(Mlp), C.POINTER(MlpLoss), vp]
+    L.t1d_mlp_grad_tiles_workspace.argtypes = [C.POINTER(Mlp), C.c_int, i64, i64]
+    L.t1d_mlp_grad_tiles.argtypes = [C.c_int, C.c_int, i64, C.POINTER(Mlp), C.POINTER(MlpBatch), C.POINTER(TileList), vp]
+    L.t1d_mlp_loss_tiles_workspace.argtypes = [C.POINTER(Mlp), C.c_int, i64, i64]
+    L.t1d_mlp_loss_tiles.argtypes = [C.c_int, C.c_int, i64, C.POINTER(Mlp), C.POINTER(MlpLoss), C.POINTER(TileList), vp]
     L.t1d_mlp_features.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), vp, vp]
     L.t1d_gae_workspace.argtypes = [C.c_int, i64, C.POINTER(GaeBatch)]
     L.t1d_gae.argtypes = [C.c_int, C.c_int, i64, C.POINTER(GaeBatch), vp]
@@ -225,6 +235,8 @@ def lib():
     L.t1d_mlp_grad_workspace.restype = i64
     L.t1d_gae_workspace.restype = i64
     L.t1d_mlp_loss_workspace.restype = i64
+    L.t1d_mlp_grad_tiles_workspace.restype = i64
+    L.t1d_mlp_loss_tiles_workspace.restype = i64
     if L.t1d_abi_version() != ABI_VERSION:
         raise T1DError("libt1d_hip.so ABI version mismatch")
     _lib = L

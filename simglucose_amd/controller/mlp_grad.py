@@ -39,14 +39,39 @@ def _check(params, features, policy):
         raise ValueError("mlp_pre_output: %d envs do not split into %d policies of a multiple of 64 envs each" % (n, policy.n_policies))
 
 
-def mlp_grad_call(policy, params, features, coef=None, y=None, grad=None, workspace=None):
+def check_tiles(who, tiles, features, P):
+    """the `tiles` of a listed call -> the int32 [P, M] tensor itself ([M] is taken as [1, M] when P == 1)"""
+    if not isinstance(tiles, torch.Tensor) or tiles.dtype != torch.int32:
+        raise ValueError("%s: tiles must be an int32 tensor" % who)
+    if tiles.dim() == 1 and P == 1:
+        tiles = tiles.unsqueeze(0)
+    if tiles.dim() != 2 or tiles.shape[0] != P or tiles.shape[1] < 1:
+        raise ValueError("%s: tiles must be [%d, M >= 1]" % (who, P))
+    if not tiles.is_contiguous():
+        raise ValueError("%s: tiles must be contiguous" % who)
+    if tiles.device.type != "cuda" or tiles.device != getattr(features, "device", None):
+        raise ValueError("%s: tiles must be on the features' device, a GPU" % who)
+    return tiles
+
+
+def tile_list(tiles):
+    """the t1d_tile_list of a checked [P, M] tensor"""
+    tl = _lib.TileList()
+    tl.n_tiles, tl.tiles = tiles.shape[1], tiles.data_ptr()
+    return tl
+
+
+def mlp_grad_call(policy, params, features, coef=None, y=None, grad=None, workspace=None, tiles=None):
     """One t1d_mlp_grad call on the current stream of the features' device.  y [K, n] and / or grad [P, n_params] are
     written where given; grad needs coef [K, n].  workspace: a tensor of at least t1d_mlp_grad_workspace bytes (default:
-    the cached one of this shape)."""
+    the cached one of this shape).  tiles (int32 [P, M] on the device, or [M] with P == 1): t1d_mlp_grad_tiles on the
+    listed 64-env tiles u = row * C + chunk of every policy instead; y is then written at those tiles alone."""
     L = _lib.lib()
     K, _, n = features.shape
     p = _struct(policy, params, n)
     dt = _T1D_DTYPE[features.dtype]
+    if tiles is not None:
+        tiles = check_tiles("mlp_grad_call", tiles, features, params.shape[0])
     io = _lib.MlpBatch()
     io.n_rows, io.feat = K, features.data_ptr()
     io.coef = coef.data_ptr() if coef is not None else None
@@ -54,7 +79,8 @@ def mlp_grad_call(policy, params, features, coef=None, y=None, grad=None, worksp
     if grad is not None:
         io.grad = grad.data_ptr()
         if workspace is None:
-            need = L.t1d_mlp_grad_workspace(C.byref(p), dt, n, K)
+            need = L.t1d_mlp_grad_workspace(C.byref(p), dt, n, K) if tiles is None else \
+                L.t1d_mlp_grad_tiles_workspace(C.byref(p), dt, n, tiles.shape[1])
             if need < 0:
                 _lib.check(int(need))
             key = (str(features.device), features.dtype, need)
@@ -64,7 +90,10 @@ def mlp_grad_call(policy, params, features, coef=None, y=None, grad=None, worksp
         io.workspace, io.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
     with torch.cuda.device(features.device):
         stream = C.c_void_p(torch.cuda.current_stream(features.device).cuda_stream)
-        _lib.check(L.t1d_mlp_grad(features.device.index, dt, n, C.byref(p), C.byref(io), stream))
+        if tiles is None:
+            _lib.check(L.t1d_mlp_grad(features.device.index, dt, n, C.byref(p), C.byref(io), stream))
+        else:
+            _lib.check(L.t1d_mlp_grad_tiles(features.device.index, dt, n, C.byref(p), C.byref(io), C.byref(tile_list(tiles)), stream))
 
 
 class _PreOutput(torch.autograd.Function):

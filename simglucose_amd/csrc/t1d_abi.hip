@@ -1296,27 +1296,45 @@ extern "C" int t1d_outcome_stats(int hip_device, int dtype, int64_t n, int64_t n
 
 // How t1d_mlp_grad cuts the work: a tile is one 64-env chunk of a policy in one row, a policy's tiles are numbered row by
 // row, and one wave takes tiles_per_wave consecutive ones and writes one partial sum.  From the shapes alone (include/t1d.h).
-struct GradPartition { int64_t chunks, tiles, tiles_per_wave, waves_per_policy; };
-static bool grad_partition(const t1d_mlp* m, int64_t n_rows, GradPartition* gp)
+// The listed calls (t1d_mlp_grad_tiles, t1d_mlp_loss_tiles) cut the n_tiles positions of a policy's list row by the same rule:
+// positions is what the waves walk, tiles for a plain call (n_tiles = 0).
+struct GradPartition { int64_t chunks, tiles, tiles_per_wave, waves_per_policy, positions; };
+static bool grad_partition(const t1d_mlp* m, int64_t n_rows, GradPartition* gp, int64_t n_tiles = 0)
 {
     gp->chunks = m->envs_per_policy / 64;
     if (n_rows > INT_MAX / gp->chunks) return false;
     gp->tiles = gp->chunks * n_rows;
-    gp->tiles_per_wave = std::max<int64_t>(1, (m->n_policies * gp->tiles + kGradMaxWaves - 1) / kGradMaxWaves);
-    gp->waves_per_policy = (gp->tiles + gp->tiles_per_wave - 1) / gp->tiles_per_wave;
+    if (n_tiles > INT_MAX / m->n_policies) return false;
+    gp->positions = n_tiles ? n_tiles : gp->tiles;
+    gp->tiles_per_wave = std::max<int64_t>(1, (m->n_policies * gp->positions + kGradMaxWaves - 1) / kGradMaxWaves);
+    gp->waves_per_policy = (gp->positions + gp->tiles_per_wave - 1) / gp->tiles_per_wave;
     return m->n_policies * gp->waves_per_policy <= INT_MAX;
 }
 
-static int check_mlp_grad(const char* who, int dtype, int64_t n, const t1d_mlp* mlp, int64_t n_rows, GradPartition* gp)
+// n_tiles: NULL for a plain call, else the n_tiles of a listed one
+static int check_mlp_grad(const char* who, int dtype, int64_t n, const t1d_mlp* mlp, int64_t n_rows, GradPartition* gp,
+                          const int64_t* n_tiles = nullptr)
 {
     const std::string w = std::string(who) + ": ";
     if (dtype != T1D_F64 && dtype != T1D_F32) return fail(T1D_E_INVALID, w + "bad dtype");
     if (n < 1 || n > (int64_t)1 << 28) return fail(T1D_E_INVALID, w + "n out of range");
     if (n_rows < 1) return fail(T1D_E_INVALID, w + "n_rows < 1");
+    if (n_tiles && *n_tiles < 1) return fail(T1D_E_INVALID, w + "n_tiles < 1");
     int cols = 0;
     const int rc = check_mlp_net(who, n, mlp, &cols, false);
     if (rc) return rc;
     if (!grad_partition(mlp, n_rows, gp)) return fail(T1D_E_INVALID, w + "n_rows is too large");
+    if (n_tiles && !grad_partition(mlp, n_rows, gp, *n_tiles)) return fail(T1D_E_INVALID, w + "n_policies * n_tiles is too large");
+    return T1D_OK;
+}
+
+// the list of a listed call
+static int check_tile_list(const char* who, const t1d_tile_list* list)
+{
+    const std::string w = std::string(who) + ": ";
+    if (!list) return fail(T1D_E_INVALID, w + "the tile list is NULL");
+    if (!list->tiles) return fail(T1D_E_INVALID, w + "tiles is NULL");
+    if (list->n_tiles < 1) return fail(T1D_E_INVALID, w + "n_tiles < 1");
     return T1D_OK;
 }
 
@@ -1338,13 +1356,13 @@ static int64_t loss_workspace_bytes(const t1d_mlp* m, int dtype, const GradParti
 
 // the workspace of a call of these shapes; the weights themselves are not needed to size it
 static int64_t mlp_workspace(const char* who, const t1d_mlp* mlp, int dtype, int64_t n, int64_t n_rows,
-                             int64_t (*bytes)(const t1d_mlp*, int, const GradPartition&))
+                             int64_t (*bytes)(const t1d_mlp*, int, const GradPartition&), const int64_t* n_tiles = nullptr)
 {
     if (!mlp) return fail(T1D_E_INVALID, std::string(who) + ": mlp is NULL");
     t1d_mlp m = *mlp;
     if (!m.params) m.params = &m;
     GradPartition gp;
-    const int rc = check_mlp_grad(who, dtype, n, &m, n_rows, &gp);
+    const int rc = check_mlp_grad(who, dtype, n, &m, n_rows, &gp, n_tiles);
     if (rc) return rc;
     return bytes(&m, dtype, gp);
 }
@@ -1357,6 +1375,17 @@ extern "C" int64_t t1d_mlp_grad_workspace(const t1d_mlp* mlp, int dtype, int64_t
 extern "C" int64_t t1d_mlp_loss_workspace(const t1d_mlp* mlp, int dtype, int64_t n, int64_t n_rows)
 {
     return mlp_workspace("t1d_mlp_loss_workspace", mlp, dtype, n, n_rows, loss_workspace_bytes);
+}
+
+// the listed calls: the partition depends on n_tiles alone, so the size does not ask for n_rows
+extern "C" int64_t t1d_mlp_grad_tiles_workspace(const t1d_mlp* mlp, int dtype, int64_t n, int64_t n_tiles)
+{
+    return mlp_workspace("t1d_mlp_grad_tiles_workspace", mlp, dtype, n, 1, grad_workspace_bytes, &n_tiles);
+}
+
+extern "C" int64_t t1d_mlp_loss_tiles_workspace(const t1d_mlp* mlp, int dtype, int64_t n, int64_t n_tiles)
+{
+    return mlp_workspace("t1d_mlp_loss_tiles_workspace", mlp, dtype, n, 1, loss_workspace_bytes, &n_tiles);
 }
 
 // The LDS of one wave of mlp_grad_kernel (t1d_policy_grad.hpp): act_rows = F + the hidden widths of activations; with
@@ -1385,7 +1414,7 @@ static int grad_lds(const char* who, const void* kernel, size_t lds)
 
 // mlp_grad_kernel<T, LS...> with one wave per partial sum of the partition, then the sum of the partials.  io: a
 // t1d_mlp_batch or a t1d_mlp_loss (feat, y, grad, workspace); ls: the LossArgs of t1d_mlp_loss, nothing for
-// t1d_mlp_grad.
+// t1d_mlp_grad; behind either the TileArgs of a listed call, whose waves walk gp.positions list positions.
 template <typename T, typename IO, typename... LS>
 static int launch_grad(const char* who, const t1d_mlp* m, int64_t n, const IO* io, const void* coef, const GradPartition& gp, hipStream_t s,
                        LS... ls)
@@ -1394,7 +1423,7 @@ static int launch_grad(const char* who, const t1d_mlp* m, int64_t n, const IO* i
     GradArgs<T> g;
     g.feat = (const T*)io->feat; g.coef = (const T*)coef; g.y = (T*)io->y; g.partial = io->grad ? (T*)io->workspace : nullptr;
     g.n = n;
-    g.chunks = (unsigned)gp.chunks; g.tiles = (unsigned)gp.tiles; g.tiles_per_wave = (unsigned)gp.tiles_per_wave;
+    g.chunks = (unsigned)gp.chunks; g.tiles = (unsigned)gp.positions; g.tiles_per_wave = (unsigned)gp.tiles_per_wave;
     g.waves_per_policy = (unsigned)gp.waves_per_policy; g.n_waves = (unsigned)(m->n_policies * gp.waves_per_policy);
     void (*const fn)(MlpArgs<T>, GradArgs<T>, LS...) = mlp_grad_kernel<T, LS...>;
     const size_t lds = grad_wave_lds(m, io->grad != nullptr, sizeof(T), &g.act_rows);
@@ -1409,29 +1438,50 @@ static int launch_grad(const char* who, const t1d_mlp* m, int64_t n, const IO* i
     return T1D_OK;
 }
 
-extern "C" int t1d_mlp_grad(int hip_device, int dtype, int64_t n, const t1d_mlp* mlp, const t1d_mlp_batch* io, void* stream)
+// t1d_mlp_grad (list == NULL) and t1d_mlp_grad_tiles
+static int mlp_grad_entry(const char* who, int hip_device, int dtype, int64_t n, const t1d_mlp* mlp, const t1d_mlp_batch* io,
+                          const t1d_tile_list* list, bool listed, void* stream)
 {
-    const char* who = "t1d_mlp_grad";
-    if (!io) return fail(T1D_E_INVALID, "t1d_mlp_grad: io is NULL");
-    GradPartition gp;
-    int rc = check_mlp_grad(who, dtype, n, mlp, io->n_rows, &gp);
+    const std::string w = std::string(who) + ": ";
+    if (!io) return fail(T1D_E_INVALID, w + "io is NULL");
+    int rc = listed ? check_tile_list(who, list) : T1D_OK;
     if (rc) return rc;
-    if (!io->feat) return fail(T1D_E_INVALID, "t1d_mlp_grad: feat is NULL");
-    if (!io->y && !io->grad) return fail(T1D_E_INVALID, "t1d_mlp_grad: y and grad are both NULL");
-    if (io->grad && !io->coef) return fail(T1D_E_INVALID, "t1d_mlp_grad: grad needs coef");
+    GradPartition gp;
+    rc = check_mlp_grad(who, dtype, n, mlp, io->n_rows, &gp, listed ? &list->n_tiles : nullptr);
+    if (rc) return rc;
+    if (!io->feat) return fail(T1D_E_INVALID, w + "feat is NULL");
+    if (!io->y && !io->grad) return fail(T1D_E_INVALID, w + "y and grad are both NULL");
+    if (io->grad && !io->coef) return fail(T1D_E_INVALID, w + "grad needs coef");
     if (io->grad && (!io->workspace || io->workspace_bytes < grad_workspace_bytes(mlp, dtype, gp)))
-        return fail(T1D_E_INVALID, "t1d_mlp_grad: grad needs a workspace of t1d_mlp_grad_workspace() bytes");
-    if (mlp->n_policies * mlp->n_params > INT_MAX) return fail(T1D_E_INVALID, "t1d_mlp_grad: too many policies");
+        return fail(T1D_E_INVALID, w + "grad needs a workspace of " + who + "_workspace() bytes");
+    if (mlp->n_policies * mlp->n_params > INT_MAX) return fail(T1D_E_INVALID, w + "too many policies");
     T1D_HIP(hipSetDevice(hip_device));
-    rc = by_dtype(dtype, [&](auto t) { return launch_grad<decltype(t)>(who, mlp, n, io, io->coef, gp, (hipStream_t)stream); });
+    rc = by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        if (!listed) return launch_grad<T>(who, mlp, n, io, io->coef, gp, (hipStream_t)stream);
+        return launch_grad<T>(who, mlp, n, io, io->coef, gp, (hipStream_t)stream, TileArgs{list->tiles, (unsigned)gp.tiles});
+    });
     if (rc) return rc;
     T1D_HIP(hipGetLastError());
     return T1D_OK;
 }
 
-// t1d_mlp_loss: the statistics live in registers, so the launch is t1d_mlp_grad's with the LossArgs behind it
+extern "C" int t1d_mlp_grad(int hip_device, int dtype, int64_t n, const t1d_mlp* mlp, const t1d_mlp_batch* io, void* stream)
+{
+    return mlp_grad_entry("t1d_mlp_grad", hip_device, dtype, n, mlp, io, nullptr, false, stream);
+}
+
+extern "C" int t1d_mlp_grad_tiles(int hip_device, int dtype, int64_t n, const t1d_mlp* mlp, const t1d_mlp_batch* io,
+                                  const t1d_tile_list* list, void* stream)
+{
+    return mlp_grad_entry("t1d_mlp_grad_tiles", hip_device, dtype, n, mlp, io, list, true, stream);
+}
+
+// t1d_mlp_loss: the statistics live in registers, so the launch is t1d_mlp_grad's with the LossArgs behind it (and the
+// TileArgs of t1d_mlp_loss_tiles behind those)
 template <typename T, int KIND>
-static int launch_mlp_loss(int dtype, const t1d_mlp* m, int64_t n, const struct t1d_mlp_loss* io, const GradPartition& gp, hipStream_t s)
+static int launch_mlp_loss(const char* who, int dtype, const t1d_mlp* m, int64_t n, const struct t1d_mlp_loss* io, const GradPartition& gp,
+                           const t1d_tile_list* list, hipStream_t s)
 {
     LossArgs<T, KIND> ls;
     ls.eps = (const T*)io->eps; ls.y_old = (const T*)io->y_old; ls.adv = (const T*)io->adv; ls.target = (const T*)io->target;
@@ -1439,7 +1489,8 @@ static int launch_mlp_loss(int dtype, const t1d_mlp* m, int64_t n, const struct 
     ls.coef_out = (T*)io->coef_out;
     ls.stat_partial = io->stats ? (double*)((char*)io->workspace + loss_stats_offset(m, dtype, gp)) : nullptr;
     ls.clip = (T)io->clip; ls.scale = (T)io->scale;
-    const int rc = launch_grad<T>("t1d_mlp_loss", m, n, io, nullptr, gp, s, ls);
+    const int rc = list ? launch_grad<T>(who, m, n, io, nullptr, gp, s, ls, TileArgs{list->tiles, (unsigned)gp.tiles})
+                        : launch_grad<T>(who, m, n, io, nullptr, gp, s, ls);
     if (rc) return rc;
     if (io->stats) {
         const unsigned total = (unsigned)(4 * m->n_policies);
@@ -1449,39 +1500,55 @@ static int launch_mlp_loss(int dtype, const t1d_mlp* m, int64_t n, const struct 
     return T1D_OK;
 }
 
-extern "C" int t1d_mlp_loss(int hip_device, int dtype, int64_t n, const t1d_mlp* mlp, const struct t1d_mlp_loss* io, void* stream)
+// t1d_mlp_loss (list == NULL) and t1d_mlp_loss_tiles
+static int mlp_loss_entry(const char* who, int hip_device, int dtype, int64_t n, const t1d_mlp* mlp, const struct t1d_mlp_loss* io,
+                          const t1d_tile_list* list, bool listed, void* stream)
 {
-    const char* who = "t1d_mlp_loss";
-    if (!io) return fail(T1D_E_INVALID, "t1d_mlp_loss: io is NULL");
-    GradPartition gp;
-    int rc = check_mlp_grad(who, dtype, n, mlp, io->n_rows, &gp);
+    const std::string w = std::string(who) + ": ";
+    if (!io) return fail(T1D_E_INVALID, w + "io is NULL");
+    int rc = listed ? check_tile_list(who, list) : T1D_OK;
     if (rc) return rc;
-    if (!io->feat) return fail(T1D_E_INVALID, "t1d_mlp_loss: feat is NULL");
+    GradPartition gp;
+    rc = check_mlp_grad(who, dtype, n, mlp, io->n_rows, &gp, listed ? &list->n_tiles : nullptr);
+    if (rc) return rc;
+    if (!io->feat) return fail(T1D_E_INVALID, w + "feat is NULL");
     if (io->kind == T1D_LOSS_PPO_CLIP) {
         if (!io->eps || !io->y_old || !io->adv || !io->sigma_old || !io->sigma)
-            return fail(T1D_E_INVALID, "t1d_mlp_loss: T1D_LOSS_PPO_CLIP needs eps, y_old, adv, sigma_old and sigma");
-        if (!(io->clip > 0.0 && io->clip < 1.0)) return fail(T1D_E_INVALID, "t1d_mlp_loss: clip must be in (0, 1)");
+            return fail(T1D_E_INVALID, w + "T1D_LOSS_PPO_CLIP needs eps, y_old, adv, sigma_old and sigma");
+        if (!(io->clip > 0.0 && io->clip < 1.0)) return fail(T1D_E_INVALID, w + "clip must be in (0, 1)");
     } else if (io->kind == T1D_LOSS_VALUE_MSE) {
-        if (!io->target) return fail(T1D_E_INVALID, "t1d_mlp_loss: T1D_LOSS_VALUE_MSE needs target");
+        if (!io->target) return fail(T1D_E_INVALID, w + "T1D_LOSS_VALUE_MSE needs target");
     } else {
-        return fail(T1D_E_INVALID, "t1d_mlp_loss: unknown kind");
+        return fail(T1D_E_INVALID, w + "unknown kind");
     }
-    if (!std::isfinite(io->scale)) return fail(T1D_E_INVALID, "t1d_mlp_loss: scale must be finite");
-    if (!io->y && !io->coef_out && !io->grad && !io->stats) return fail(T1D_E_INVALID, "t1d_mlp_loss: y, coef_out, grad and stats are all NULL");
+    if (!std::isfinite(io->scale)) return fail(T1D_E_INVALID, w + "scale must be finite");
+    if (!io->y && !io->coef_out && !io->grad && !io->stats) return fail(T1D_E_INVALID, w + "y, coef_out, grad and stats are all NULL");
     if ((io->grad || io->stats) && (!io->workspace || io->workspace_bytes < loss_workspace_bytes(mlp, dtype, gp)))
-        return fail(T1D_E_INVALID, "t1d_mlp_loss: grad and stats need a workspace of t1d_mlp_loss_workspace() bytes");
-    if (mlp->n_policies * mlp->n_params > INT_MAX) return fail(T1D_E_INVALID, "t1d_mlp_loss: too many policies");
+        return fail(T1D_E_INVALID, w + "grad and stats need a workspace of " + who + "_workspace() bytes");
+    if (mlp->n_policies * mlp->n_params > INT_MAX) return fail(T1D_E_INVALID, w + "too many policies");
     T1D_HIP(hipSetDevice(hip_device));
     const bool ppo = io->kind == T1D_LOSS_PPO_CLIP;
+    const t1d_tile_list* const tl = listed ? list : nullptr;
     if (dtype == T1D_F64)
-        rc = ppo ? launch_mlp_loss<double, T1D_LOSS_PPO_CLIP>(dtype, mlp, n, io, gp, (hipStream_t)stream)
-                 : launch_mlp_loss<double, T1D_LOSS_VALUE_MSE>(dtype, mlp, n, io, gp, (hipStream_t)stream);
+        rc = ppo ? launch_mlp_loss<double, T1D_LOSS_PPO_CLIP>(who, dtype, mlp, n, io, gp, tl, (hipStream_t)stream)
+                 : launch_mlp_loss<double, T1D_LOSS_VALUE_MSE>(who, dtype, mlp, n, io, gp, tl, (hipStream_t)stream);
     else
-        rc = ppo ? launch_mlp_loss<float, T1D_LOSS_PPO_CLIP>(dtype, mlp, n, io, gp, (hipStream_t)stream)
-                 : launch_mlp_loss<float, T1D_LOSS_VALUE_MSE>(dtype, mlp, n, io, gp, (hipStream_t)stream);
+        rc = ppo ? launch_mlp_loss<float, T1D_LOSS_PPO_CLIP>(who, dtype, mlp, n, io, gp, tl, (hipStream_t)stream)
+                 : launch_mlp_loss<float, T1D_LOSS_VALUE_MSE>(who, dtype, mlp, n, io, gp, tl, (hipStream_t)stream);
     if (rc) return rc;
     T1D_HIP(hipGetLastError());
     return T1D_OK;
+}
+
+extern "C" int t1d_mlp_loss(int hip_device, int dtype, int64_t n, const t1d_mlp* mlp, const struct t1d_mlp_loss* io, void* stream)
+{
+    return mlp_loss_entry("t1d_mlp_loss", hip_device, dtype, n, mlp, io, nullptr, false, stream);
+}
+
+extern "C" int t1d_mlp_loss_tiles(int hip_device, int dtype, int64_t n, const t1d_mlp* mlp, const struct t1d_mlp_loss* io,
+                                  const t1d_tile_list* list, void* stream)
+{
+    return mlp_loss_entry("t1d_mlp_loss_tiles", hip_device, dtype, n, mlp, io, list, true, stream);
 }
 
 // t1d_gae (t1d_gae.hpp): every argument is checked here, before the device is touched.  -> the tiles of one policy (its 64-env

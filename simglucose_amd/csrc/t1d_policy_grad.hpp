@@ -36,6 +36,14 @@
 //                        one partial [4] per wave behind the gradient partials.  With partial == NULL the deltas and phase
 //                        B are skipped; y, coef_out and the statistics are still formed.
 //   mlp_loss_stats_kernel  stats[p][k] = the partials of policy p added in wave order.
+//   with TileArgs        t1d_mlp_grad_tiles / t1d_mlp_loss_tiles: a TileArgs as the pack's last member, and the waves walk the
+//                        positions of the policy's row of a tile list instead of the tile numbers: position pos names tile
+//                        u = ids[pol][pos], read through the scalar data cache like the weights, so it is wave-uniform; an id
+//                        outside [0, tiles of a policy) is stepped over by one uniform branch around the whole tile body.
+//                        Everything inside a tile is the code above on the arrays' own addresses, and the partition is the
+//                        one above with positions for tiles, so the identity list gives the plain call's bits and any list
+//                        those of a plain call on the gathered tiles.  The instances without TileArgs are compiled from the
+//                        text they always were.
 // Nothing here is atomic and nothing depends on the grid the hardware happens to run: two calls give the same bits.
 #pragma once
 #include "t1d_policy.hpp"
@@ -49,7 +57,7 @@ template <typename T> struct GradArgs {
     const T* feat; const T* coef; T* y; T* partial;
     int64_t n;
     unsigned chunks;                      // 64-env chunks of one policy
-    unsigned tiles;                       // chunks * n_rows: tiles of one policy
+    unsigned tiles;                       // chunks * n_rows: tiles of one policy (with TileArgs: the positions of its list row)
     unsigned tiles_per_wave, waves_per_policy, n_waves;
     int act_rows;                         // A: F + the hidden widths
 };
@@ -63,10 +71,22 @@ template <typename T, int KIND> struct LossArgs {   // KIND: T1D_LOSS_PPO_CLIP |
     T clip, scale;
 };
 
-// the kind of mlp_grad_kernel's trailing pack: 0 for the empty one (coef is read from memory), and its one member
+// t1d_mlp_grad_tiles / t1d_mlp_loss_tiles: the list the waves walk.  GradArgs.tiles is then the positions of one policy.
+struct TileArgs {
+    const int32_t* ids;                   // [n_policies][GradArgs.tiles]
+    unsigned limit;                       // chunks * n_rows: an id is a tile of the policy when (unsigned)id < limit
+};
+
+// the kind of mlp_grad_kernel's trailing pack: 0 without a LossArgs (coef is read from memory), else that of its first member
 template <typename... LS> struct LossKind { static constexpr int value = 0; };
-template <typename T, int KIND> struct LossKind<LossArgs<T, KIND>> { static constexpr int value = KIND; };
-template <typename A> __device__ __forceinline__ const A& loss_first(const A& a) { return a; }
+template <typename T, int KIND, typename... R> struct LossKind<LossArgs<T, KIND>, R...> { static constexpr int value = KIND; };
+template <typename A, typename... R> __device__ __forceinline__ const A& loss_first(const A& a, const R&...) { return a; }
+// the pack's TileArgs, which is its last member, or none
+template <typename... LS> struct HasTiles { static constexpr bool value = false; };
+template <typename A, typename... R> struct HasTiles<A, R...> { static constexpr bool value = HasTiles<R...>::value; };
+template <> struct HasTiles<TileArgs> { static constexpr bool value = true; };
+__device__ __forceinline__ const TileArgs& tiles_last(const TileArgs& a) { return a; }
+template <typename A, typename... R> __device__ __forceinline__ const TileArgs& tiles_last(const A&, const R&... r) { return tiles_last(r...); }
 
 // a wave-uniform word a lane computed, moved to scalar registers so that it costs no vector register in the tile loop
 __device__ __forceinline__ float loss_uniform(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); }
@@ -141,11 +161,12 @@ __device__ __forceinline__ unsigned grad_rows_of(const MlpArgs<T>& c, int act_ro
 
 // Dynamic LDS: (act_rows + 1 + the sum of all widths) * 64 words.  Grid: n_waves workgroups of 64 threads.  LS: nothing
 // (t1d_mlp_grad: coef is read from g.coef) or one LossArgs<T, KIND> (t1d_mlp_loss: coef comes from the loss, g.coef is not
-// looked at).
+// looked at), and behind either a TileArgs for the listed calls.
 template <typename T, typename... LS>
 __global__ __launch_bounds__(64) void mlp_grad_kernel(const MlpArgs<T> c, const GradArgs<T> g, const LS... lp)
 {
     constexpr int KIND = LossKind<LS...>::value;
+    constexpr bool LISTED = HasTiles<LS...>::value;
     typedef const __attribute__((address_space(4))) T* WPtr;
     const unsigned lane = threadIdx.x;
     const unsigned wave = blockIdx.x;
@@ -185,7 +206,14 @@ __global__ __launch_bounds__(64) void mlp_grad_kernel(const MlpArgs<T> c, const 
     }
 
 #pragma unroll 1
-    for (unsigned u = t0; u < t1; ++u) {
+    for (unsigned pos = t0; pos < t1; ++pos) {
+        unsigned u = pos;
+        if constexpr (LISTED) {
+            const TileArgs& tl = tiles_last(lp...);
+            typedef const __attribute__((address_space(4))) int32_t* IPtr;
+            u = (unsigned)((IPtr)tl.ids)[(size_t)pol * g.tiles + pos];           // wave-uniform: a scalar load
+            if (u >= tl.limit) continue;                                         // id < 0 or beyond the policy's tiles: skipped
+        }
         const unsigned row = u / g.chunks, chunk = u - row * g.chunks;
         const int64_t i = (int64_t)pol * c.envs_per_policy + (int64_t)chunk * 64 + lane;
         const T* const f = g.feat + (int64_t)row * F * g.n + i;

@@ -1,7 +1,8 @@
 #!/bin/bash
 # Compile the library with -Rpass-analysis=kernel-resource-usage and print one line per kernel matching $1 (regex on the
 # demangled name): VGPRs, AGPRs, scratch bytes per lane, occupancy.  mlp_grad also lists the loss-carrying instances of
-# t1d_mlp_loss (mlp_grad_kernel<T, LossArgs<T, kind>>) and mlp_loss their sum kernel.  Extra hipcc flags after the pattern.
+# t1d_mlp_loss (mlp_grad_kernel<T, LossArgs<T, kind>>) and the listed ones (.., TileArgs>), mlp_loss their sum kernel.  Extra
+# hipcc flags after the pattern.
 pat="${1:-.}"; shift
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fno-slp-vectorize -std=c++17 -shared -fPIC -Rpass-analysis=kernel-resource-usage "$@" \
     -o /tmp/libt1d_res.so "$(dirname "$0")/../simglucose_amd/csrc/t1d_abi.hip" 2>&1 |
