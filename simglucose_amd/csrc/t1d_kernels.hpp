@@ -313,8 +313,12 @@ __device__ __forceinline__ T noise_sample(const KArgs<T>& a, unsigned i, int s, 
             for (int k = 0; k < 4; ++k) at(row(a.pts, n, 22 + k), i) = cur[k];
         }
     }
-    const T B = T(tau - 15 * m) * T(1.0 / 15.0), A = T(1) - B;
-    return A * cur[0] + B * cur[1] + T(37.5) * ((A * A * A - A) * cur[2] + (B * B * B - B) * cur[3]);
+    // Every product that feeds a sum is an explicit fma.  Left to the compiler, the instantiations of this function (step
+    // kernels, roll-outs, reset) contracted the sum differently, and step() and rollout_mlp disagreed in the last bit of the
+    // CGM at every sample time that puts a sample off a knot.
+    const T B = T(tau - 15 * m) * T(1.0 / 15.0), A = fma(-T(tau - 15 * m), T(1.0 / 15.0), T(1));
+    const T ca = fma(A * A, A, -A), cb = fma(B * B, B, -B);
+    return fma(A, cur[0], fma(B, cur[1], T(37.5) * fma(ca, cur[2], cb * cur[3])));
 }
 
 // CGMSensor.measure (cgm.py:26-36) split in two so that the memory latency of the noise block hides

@@ -142,15 +142,15 @@ def meal_day_env(n, dtype, env_offset=0, seed=5, meals=True, start=None, **kw):
     return e
 
 
-def gym_env(n, dtype=None, seed=3, env_offset=0, exact=False):
+def gym_env(n, dtype=None, seed=3, env_offset=0, exact=False, sensor_row=None):
     """child#001 / adult#001 alternating, random initial glucose, Philox noise, every env in episode 0 of the device's own
     episode stream (started through restart_done); dtype None: fp64.  n_sub = 4 and integrator = None are the constructor's
-    defaults, and the exact mode ignores n_sub."""
+    defaults, and the exact mode ignores n_sub.  sensor_row: a custom row in place of Dexcom's."""
     torch = gpu_torch()
     from simglucose_amd.batch_env import BatchedT1DSimEnv
     e = BatchedT1DSimEnv(patient=["child#001", "adult#001"] * (n // 2), sensor="Dexcom", pump="Insulet", dtype=dtype or torch.float64,
                          n_sub=4, seed=seed, env_offset=env_offset, noise="philox", random_init_bg=True,
-                         integrator="dopri5" if exact else None)
+                         integrator="dopri5" if exact else None, sensor_row=sensor_row)
     e.restart_done(mask=torch.ones(n, dtype=torch.uint8, device=e.device), days=DAYS, reset_outputs=True)
     return e
 
@@ -254,13 +254,13 @@ def loop_of_entry_points(e, pol, K, acc, tr, term, es, exact=False):
     return st, int(low), int(high), nf
 
 
-def restart_pair(pol, cuts, dtype=None, exact=False, seed=3, **kw):
+def restart_pair(pol, cuts, dtype=None, exact=False, seed=3, sensor_row=None, **kw):
     """A: the collector in launches of `cuts` steps; B: the loop of existing entry points; equal bit for bit
     -> what happened in B: restarts per env, low endings, high endings"""
     torch = gpu_torch()
     n, K = 256, sum(cuts)
     cols = MLP_TRACE + ("reward", "done", "eps")
-    A, B = gym_env(n, dtype, seed, exact=exact), gym_env(n, dtype, seed, exact=exact)
+    A, B = (gym_env(n, dtype, seed, exact=exact, sensor_row=sensor_row) for _ in range(2))
     collect = A.collect_mlp_dopri5 if exact else A.collect_mlp
     z = lambda: torch.zeros(n, dtype=A.dtype, device=A.device)
     sa, ta, terma, esa = stats(A), A.new_trace(K, columns=cols), z(), episode_stats(A)
@@ -307,3 +307,129 @@ def noisy_run(e, pol, sigma, warm, chunks, explore_seed=99, exact=False, **kw2):
 def draw_of_pair(m):
     """the draw index of t1d_philox_normals whose value is philox_pair(.., pair = m).x"""
     return np.where(m >= 3, 1 + 10 * ((m - 3) // 5) + 2 * ((m - 3) % 5), 0)
+
+
+# ------------------------------------------------------------------------------------------------ the sensor grid
+# Custom sample times (test_sensor_grid_host.py, test_gpu_sensor_grid.py): the Dexcom row with another sample_time, 150 envs
+# (two full 64-env chunks and a partial one), host normals, one 60 g meal in every third env, an action that moves with the
+# step.  Importing and building the inputs touches no device.
+GRID_N = 150
+GRID_STS = (2, 4, 7, 10, 15, 20, 30, 50, 100, 150)           # the sample times the device runs
+GRID_STS_HOST = GRID_STS + (60, 75)                          # ... and the oracle alone
+GRID_OUT = ("cgm", "bg", "reward", "risk", "done")
+
+
+def grid_sensor_row(st):
+    """the Dexcom row with column 5 (sample_time) replaced"""
+    from simglucose_amd import params
+    row = np.array(params.sensor_row("Dexcom"), dtype=np.float64)
+    row[5] = st
+    return row
+
+
+@functools.lru_cache(maxsize=None)
+def grid_inputs(st, n=GRID_N, seed=17, feed=3):
+    """-> dict: row, pid, S = samples per noise block, K steps (the reset's two samples and K steps open a third block),
+    z = host normals [1 + 10 ceil((K + 2) / S), n], mt / ma = the meal table [1, n] (60 g at the first minute of step 1 in
+    every `feed`-th env), cho = the same meals per minute [K st, n], basal [n]"""
+    from simglucose_amd import _lib
+    S = 150 // st
+    K = max(5, 2 * S + 1)
+    pid = np.arange(n) % 30
+    z = np.random.RandomState(seed).randn(1 + 10 * math.ceil((K + 2) / S), n)
+    fed = np.arange(n) % feed == 0
+    mt = np.where(fed, st, _lib.MEAL_UNUSED).astype(np.int64)[None, :]
+    ma = np.where(fed, 60.0, 0.0)[None, :]
+    cho = np.zeros((K * st, n))
+    cho[st, fed] = 60.0
+    return dict(st=st, row=grid_sensor_row(st), n=n, pid=pid, S=S, K=K, z=z, mt=mt, ma=ma, cho=cho, basal=basal_of(pid))
+
+
+def grid_action(inp, k):
+    return inp["basal"] * (0.5 + 0.5 * (k % 3))
+
+
+def grid_oracle_run(st, integrator="split_adaptive", z=None, n=GRID_N, feed=3):
+    """the oracle over the grid's inputs (z: other normals, e.g. the device's Philox draws) -> dict: GRID_OUT as arrays
+    [K + 1, n] (row 0 = after reset; reward and risk of row 0 as reset leaves them), x [13, n], t, last_cgm, level_count"""
+    from oracle import t1d_oracle as O
+    inp = grid_inputs(st, n, feed=feed)
+    orc = O.OracleEnv(inp["pid"], normals=inp["z"] if z is None else z, integrator=integrator, n_sub=4,
+                      sensor_row_override=inp["row"])
+    rows = [orc.reset()]
+    for k in range(inp["K"]):
+        rows.append(orc.step(grid_action(inp, k), None, inp["cho"][k * st:(k + 1) * st]))
+    out = {key: np.stack([r[key] for r in rows]) for key in GRID_OUT}
+    out.update(x=orc.x.copy(), t=orc.t.copy(), last_cgm=orc.last_cgm.copy(), level_count=orc.level_count.copy())
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def grid_oracle(st, integrator="split_adaptive"):
+    """grid_oracle_run on the grid's own normals, computed once per sample time and integrator; treat as read-only"""
+    return grid_oracle_run(st, integrator)
+
+
+def uneven_cuts(st, total):
+    """launch lengths that are not the sample time: (1, 2, st + 1, 2 st, 1, st - 1, 3 st + 2) repeated and cut off at
+    `total` - st, then one launch of st minutes.  The last launch is a whole step because prev_risk is the risk index of the
+    last launch's mean CGM: it compares with a run in steps of st minutes only where the two last launches span the same
+    minutes (at st = 7 the plain cut-off would end on a launch of one minute)."""
+    pattern, cuts, k = (1, 2, st + 1, 2 * st, 1, st - 1, 3 * st + 2), [], 0
+    while sum(cuts) < total - st:
+        cuts.append(min(pattern[k % len(pattern)], total - st - sum(cuts)))
+        k += 1
+    return cuts + [st]
+
+
+def whole_pair_launch(st, cuts):
+    """the first launch of 2 st minutes in `cuts` that starts on a step boundary -> (its index, the index of the first of
+    the two steps of st minutes it spans), None if there is none"""
+    t0 = 0
+    for j, m in enumerate(cuts):
+        if m == 2 * st and t0 % st == 0:
+            return j, t0 // st
+        t0 += m
+    return None
+
+
+def grid_env(st, n=GRID_N, options=(), z=None, meals=True, feed=3, **kw):
+    """the device env of the grid: custom sensor row, host normals (noise="philox" in kw: none), the meal table, `options`
+    as (name, value) pairs set before reset(), reset"""
+    torch = gpu_torch()
+    from simglucose_amd.batch_env import BatchedT1DSimEnv
+    inp = grid_inputs(st, n, feed=feed)
+    if kw.get("noise", "host") == "host":
+        kw.update(noise="host", normals=inp["z"] if z is None else z)
+    kw.setdefault("n_sub", 4)
+    e = BatchedT1DSimEnv(patient=inp["pid"], sensor="Dexcom", sensor_row=inp["row"], **kw)
+    for name, value in options:
+        e.set_option(name, value)
+    if meals:
+        e.set_meals(torch.as_tensor(inp["mt"]), torch.as_tensor(inp["ma"]))
+    e.reset()
+    return e
+
+
+def grid_level2_lanes(st, n, feed=1):
+    """per step of the grid's oracle run: how many envs spend at least one minute at level 2 of the step-size rule.  The
+    patient's minutes do not depend on the sensor noise, and action and meal depend on the env through its patient and on
+    whether it is fed alone: one single-env oracle per (patient, fed) says it for every env -> int array [K]"""
+    from oracle import t1d_oracle as O
+    inp = grid_inputs(st, n, feed=feed)
+    K, count = inp["K"], np.zeros(inp["K"], dtype=np.int64)
+    seen = {}
+    for i in range(n):
+        key = (int(inp["pid"][i]), bool(inp["cho"][st, i] > 0))
+        if key not in seen:
+            orc = O.OracleEnv(inp["pid"][i:i + 1], normals=inp["z"][:, i:i + 1], integrator="split_adaptive", n_sub=4,
+                              sensor_row_override=inp["row"])
+            orc.reset()
+            flags = np.zeros(K, dtype=bool)
+            for k in range(K):
+                before = int(orc.level_count[2])
+                orc.step(grid_action(inp, k)[i:i + 1], None, inp["cho"][k * st:(k + 1) * st, i:i + 1])
+                flags[k] = int(orc.level_count[2]) > before
+            seen[key] = flags
+        count += seen[key]
+    return count
