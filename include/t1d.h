@@ -75,10 +75,22 @@ enum {
     T1D_E_STATUS = -4        /* t1d_sync: a kernel raised a status bit (see T1D_ST_*) */
 };
 
-/* bits of the device status word returned through t1d_sync */
+/* bits of the device status word returned through t1d_sync.  The word is cleared by the t1d_sync that reads it: a second
+ * t1d_sync right after returns 0, and a bit tells of the launches since the last read.
+ * T1D_ST_NONFINITE is raised by every launch that leaves a non-finite word (NaN, +-Inf) in some env's stored x[12], the
+ * subcutaneous glucose that BG and the sensor read: by the launch in which a NaN action, or a non-finite word elsewhere in
+ * the state, reaches x[12], and by every later launch for as long as it stays there.  Such an env is NOT visible in the
+ * outputs: the sensor's clamp to its range turns a NaN sample into the range's lower end, so `cgm` reads sensor min, and
+ * `done` = BG < 70 || BG > 350 is 0 for a NaN BG, so the env never ends and is never restarted (t1d_restart_done,
+ * on_done = restart).  The bit is the only signal: a trainer that does not read t1d_sync sees an ordinary deep low.  In the
+ * exact mode the solver gives up on such an env (T1D_ST_SOLVER_FAILED) and the env keeps its last accepted state, so a
+ * non-finite word outside x[12] stays where it is and raises T1D_ST_SOLVER_FAILED alone.  The other envs are unaffected.
+ * T1D_ST_NORMALS_EXHAUSTED is raised by the launch (t1d_reset included) that builds a 150-minute noise block for which
+ * the rows are missing, not by the launches that go on using that block.  The block takes its ten rows in five pairs and
+ * a pair counts as missing unless both of its rows exist: the draws of such a pair are zero as a whole. */
 enum {
     T1D_ST_NORMALS_EXHAUSTED = 1,   /* host-normals mode ran past n_normals rows; zeros were used */
-    T1D_ST_NONFINITE = 2,           /* some env's state became NaN/Inf */
+    T1D_ST_NONFINITE = 2,           /* some env's stored x[12] is NaN/Inf after the launch (above) */
     T1D_ST_BAD_INDEX = 4,           /* t1d_model_rhs: a patient index outside the context's table (row 0 was used) */
     T1D_ST_STALL = 8,               /* a wave of a persistent kernel gave up waiting for its workgroup (never, by design): results invalid */
     T1D_ST_SOLVER_FAILED = 16       /* t1d_step_dopri5: some env's solver gave up (step budget or step underflow; the reference raises

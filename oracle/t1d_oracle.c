@@ -446,8 +446,8 @@ double t1d_o_pump(double amount, double inc, double lo, double hi)
     double v = amount * 6000.0;          /* :24 / :33 */
     v = rint(v / inc) * inc;             /* :25-26 / :34-35 */
     v = v / 6000.0;                      /* :27 / :36 */
-    v = (v < hi) ? v : hi;               /* min(v, max)  :28 / :37 */
-    v = (v > lo) ? v : lo;               /* max(v, min)  :29 / :38 */
+    v = (hi < v) ? hi : v;               /* min(v, max)  :28 / :37, Python's operand order: a NaN amount stays NaN */
+    v = (lo > v) ? lo : v;               /* max(v, min)  :29 / :38 */
     return v;
 }
 

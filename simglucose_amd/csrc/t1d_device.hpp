@@ -718,14 +718,20 @@ __device__ __forceinline__ MinuteIn<T> eat_minute(P& p, const T (&x)[13], T meal
 
 // InsulinPump.basal/.bolus (pump.py:23-39); rint = round-half-to-even = np.round.  IEEE divisions
 // on purpose: the quantiser must land on the same increment as the reference at exact ties.
+// The clamps are Python's min(v, hi) and max(v, lo) in the reference's operand order (:28-29, :37-38): v is handed on
+// unless the limit compares beyond it, so a NaN amount stays NaN (the step then raises T1D_ST_NONFINITE) where the
+// mirrored selects would turn it into the pump's maximum; +Inf -> hi and -Inf -> lo.  The fp64 fdiv corrects its
+// quotient by the residual a - b q, which is Inf - Inf for an infinite amount: where the quotient comes back NaN the
+// dividend is handed on in its place (+-Inf for the clamps, a NaN as it is), which no finite amount reaches.
 template <typename T>
 __device__ __forceinline__ T pump_quantise(T amount, T inc, T lo, T hi)
 {
     T v = amount * T(6000);
     v = t_rint(v / inc) * inc;          // IEEE division: decides which increment an exact tie rounds to
-    v = fdiv(v, T(6000));               // <= 1 ulp: scaling back to U/min decides nothing
-    v = v < hi ? v : hi;
-    v = v > lo ? v : lo;
+    const T q = fdiv(v, T(6000));       // <= 1 ulp: scaling back to U/min decides nothing
+    v = q != q ? v : q;
+    v = hi < v ? hi : v;
+    v = lo > v ? lo : v;
     return v;
 }
 

@@ -61,7 +61,7 @@ __device__ __forceinline__ T mlp_logistic(T v)
 {
     const T lim = sizeof(T) == 8 ? T(700) : T(80);
     const T E = exp_core(t_max(t_min(-v, lim), -lim));
-    return v != v ? v : fdiv(T(1), T(1) + E);                // a NaN stays a NaN (the step then raises T1D_ST_NONFINITE)
+    return v != v ? v : fdiv(T(1), T(1) + E);                // a NaN stays a NaN (pump_quantise hands it on: the step raises T1D_ST_NONFINITE)
 }
 
 // sin and cos of 2 pi m / 1440 for the minute of day m in [0, 1440): sinpi / cospi of m / 720 -- their argument

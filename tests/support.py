@@ -55,6 +55,17 @@ def same_dicts(a, b, keys, sl=slice(None), by="bits"):
         assert _equal(a[k][..., sl], b[k], by), k
 
 
+def same_env_at(a, b, keys, idx, by="bits", what=""):
+    """the attributes `keys` of env a (or the entries of dict a) are those of b in the envs `idx` (a tensor of indices
+    into the last dimension)"""
+    get = (lambda o, k: o[k]) if isinstance(a, dict) else getattr
+    for k in keys:
+        ta, tb = get(a, k), get(b, k)
+        if ta is None and tb is None:
+            continue
+        assert _equal(ta.index_select(-1, idx), tb.index_select(-1, idx), by), (what, k)
+
+
 # ------------------------------------------------------------------------------------------------ policies
 def random_policy(history=4, widths=(16, 16, 1), n_policies=1, seed=0, hidden="tanh", output="logistic", gain=1.0, bias_gain=None,
                   **kw):
@@ -142,7 +153,7 @@ def meal_day_env(n, dtype, env_offset=0, seed=5, meals=True, start=None, **kw):
     return e
 
 
-def gym_env(n, dtype=None, seed=3, env_offset=0, exact=False, sensor_row=None):
+def gym_env(n, dtype=None, seed=3, env_offset=0, exact=False, sensor_row=None, use_pump=True):
     """child#001 / adult#001 alternating, random initial glucose, Philox noise, every env in episode 0 of the device's own
     episode stream (started through restart_done); dtype None: fp64.  n_sub = 4 and integrator = None are the constructor's
     defaults, and the exact mode ignores n_sub.  sensor_row: a custom row in place of Dexcom's."""
@@ -150,7 +161,7 @@ def gym_env(n, dtype=None, seed=3, env_offset=0, exact=False, sensor_row=None):
     from simglucose_amd.batch_env import BatchedT1DSimEnv
     e = BatchedT1DSimEnv(patient=["child#001", "adult#001"] * (n // 2), sensor="Dexcom", pump="Insulet", dtype=dtype or torch.float64,
                          n_sub=4, seed=seed, env_offset=env_offset, noise="philox", random_init_bg=True,
-                         integrator="dopri5" if exact else None, sensor_row=sensor_row)
+                         integrator="dopri5" if exact else None, sensor_row=sensor_row, use_pump=use_pump)
     e.restart_done(mask=torch.ones(n, dtype=torch.uint8, device=e.device), days=DAYS, reset_outputs=True)
     return e
 
@@ -433,3 +444,113 @@ def grid_level2_lanes(st, n, feed=1):
             seen[key] = flags
         count += seen[key]
     return count
+
+
+# ------------------------------------------------------------------------------------------------ status word, non-finite data
+# test_status_host.py, test_gpu_status.py: 150 envs (two full 64-env chunks and a partial one), all 30 patients, host normals,
+# 70 g at the first minute of step `meal_step` in every `feed`-th env, grid_action's moving basal.  Two steps, then one state
+# word of three lanes is made non-finite, then three more steps.  Importing and building the inputs touches no device.
+STATUS_N = 150
+STATUS_PRE, STATUS_POST = 2, 3
+POISONS = {"x12_nan": (12, float("nan")), "x0_nan": (0, float("nan")), "x5_nan": (5, float("nan")), "x12_inf": (12, float("inf"))}
+STATUS_SCHEMES = {False: "split_adaptive", True: "dopri"}       # exact mode? -> the oracle's integrator
+
+
+@functools.lru_cache(maxsize=None)
+def status_inputs(sensor="Navigator", n=STATUS_N, feed=3, meal_step=1, seed=23):
+    """-> dict: st, pid, z = host normals [31, n], mt / ma = the meal table [1, n], cho = the same meal per minute [K st, n],
+    basal [n], vmin / vmax = the sensor's range, K = STATUS_PRE + STATUS_POST"""
+    from simglucose_amd import _lib, params
+    row = np.array(params.sensor_row(sensor), dtype=np.float64)
+    st, K = int(row[5]), STATUS_PRE + STATUS_POST
+    pid = np.arange(n) % 30
+    fed = np.arange(n) % feed == 0
+    cho = np.zeros((K * st, n))
+    cho[meal_step * st, fed] = 70.0
+    return dict(sensor=sensor, st=st, n=n, K=K, pid=pid, z=np.random.RandomState(seed).randn(31, n), fed=fed,
+                mt=np.where(fed, meal_step * st, _lib.MEAL_UNUSED).astype(np.int64)[None, :], ma=np.where(fed, 70.0, 0.0)[None, :], cho=cho,
+                basal=basal_of(pid), vmin=float(row[6]), vmax=float(row[7]))
+
+
+def status_oracle_env(inp, integrator, cols=None):
+    from oracle import t1d_oracle as O
+    cols = slice(None) if cols is None else cols
+    return O.OracleEnv(inp["pid"][cols], sensor=inp["sensor"], normals=inp["z"][:, cols], integrator=integrator, n_sub=4)
+
+
+def oracle_step(orc, basal, bolus, cho):
+    """OracleEnv.step that reports a solver that gave up instead of raising: the C side has written the state (an env whose
+    solver gives up keeps its last accepted one) and every output by then -> (outputs, gave up?)"""
+    try:
+        return orc.step(basal, bolus, cho), False
+    except RuntimeError:
+        return {k: v.copy() for k, v in orc.out.items()}, True
+
+
+@functools.lru_cache(maxsize=None)
+def status_lanes(sensor="Navigator", n=STATUS_N, feed=3, meal_step=1):
+    """the three lanes that get the non-finite word: one in chunk 0, one in the partial chunk, and the first env of chunk 1
+    (failing that, of the rest) that the oracle's step-size rule puts at level 2 in the first minute after the STATUS_PRE
+    steps.  Found as grid_level2_lanes finds them: the patient's minutes depend on the env through its patient and on whether
+    it is fed alone, and not on the sensor, so one single-env oracle per (patient, fed) with a one-minute sensor says it."""
+    from oracle import t1d_oracle as O
+    inp = status_inputs(sensor, n, feed, meal_step)
+    st, t0 = inp["st"], STATUS_PRE * inp["st"]
+    first, last = 5, n - 9
+    seen = {}
+    for i in list(range(64, min(n, 128))) + list(range(0, 64)) + list(range(128, n)):
+        key = (int(inp["pid"][i]), bool(inp["fed"][i]))
+        if key not in seen:
+            orc = O.OracleEnv(inp["pid"][i:i + 1], sensor="Navigator", normals=inp["z"][:, i:i + 1], integrator="split_adaptive", n_sub=4)
+            assert orc.sample_time == 1
+            orc.reset()
+            for m in range(t0):
+                orc.step(grid_action(inp, m // st)[i:i + 1], None, inp["cho"][m:m + 1, i:i + 1])
+            before = int(orc.level_count[2])
+            orc.step(grid_action(inp, STATUS_PRE)[i:i + 1], None, inp["cho"][t0:t0 + 1, i:i + 1])
+            seen[key] = int(orc.level_count[2]) > before
+        if seen[key] and i not in (first, last):
+            return (first, last, i)
+    raise AssertionError("no lane at level 2 in the minute after the first %d steps" % STATUS_PRE)
+
+
+@functools.lru_cache(maxsize=None)
+def status_oracle(sensor="Navigator", exact=False, poison=None, n=STATUS_N, feed=3, meal_step=1):
+    """The oracle over the status inputs (exact: its DOPRI5, else the default scheme); poison: a key of POISONS written into
+    status_lanes after STATUS_PRE steps, None: the clean run.  Computed once per argument set; treat as read-only.
+    -> dict: lanes; per step after the poison, arrays [STATUS_POST, n]: x12_bad (stored x[12] not finite), bg_bad, done,
+    last_cgm, gave_up (bool [STATUS_POST]); x = the final state"""
+    inp = status_inputs(sensor, n, feed, meal_step)
+    st = inp["st"]
+    lanes = status_lanes(sensor, n, feed, meal_step)
+    orc = status_oracle_env(inp, STATUS_SCHEMES[exact])
+    orc.reset()
+    rows = {k: [] for k in ("x12_bad", "bg_bad", "done", "last_cgm", "gave_up", "bg", "insulin")}
+    for k in range(inp["K"]):
+        if k == STATUS_PRE and poison is not None:
+            word, value = POISONS[poison]
+            orc.x[word, list(lanes)] = value
+        r, gave_up = oracle_step(orc, grid_action(inp, k), None, inp["cho"][k * st:(k + 1) * st])
+        assert k >= STATUS_PRE or not gave_up
+        if k >= STATUS_PRE:
+            rows["x12_bad"].append(~np.isfinite(orc.x[12])); rows["bg_bad"].append(~np.isfinite(r["bg"]))
+            rows["done"].append(r["done"].copy()); rows["last_cgm"].append(orc.last_cgm.copy()); rows["gave_up"].append(gave_up)
+            rows["bg"].append(r["bg"]); rows["insulin"].append(r["insulin"])
+    out = {k: np.stack(v) for k, v in rows.items()}
+    out.update(lanes=lanes, x=orc.x.copy())
+    return out
+
+
+def status_env(sensor="Navigator", n=STATUS_N, feed=3, options=(), dtype=None, exact=False, z=None, meal_step=1, **kw):
+    """the device env of the status inputs: host normals (z: others), the meal table, `options` as (name, value) pairs
+    set before reset(), reset"""
+    torch = gpu_torch()
+    from simglucose_amd.batch_env import BatchedT1DSimEnv
+    inp = status_inputs(sensor, n, feed, meal_step)
+    e = BatchedT1DSimEnv(patient=inp["pid"], sensor=sensor, noise="host", normals=inp["z"] if z is None else z, n_sub=4,
+                         dtype=dtype or torch.float64, integrator="dopri5" if exact else None, **kw)
+    for name, value in options:
+        e.set_option(name, value)
+    e.set_meals(torch.as_tensor(inp["mt"]), torch.as_tensor(inp["ma"]))
+    e.reset()
+    return e
