@@ -525,6 +525,44 @@ int t1d_rollout_mlp(t1d_ctx* ctx, const t1d_batch* batch, const t1d_mlp* mlp, in
 int t1d_collect_mlp(t1d_ctx* ctx, const t1d_batch* batch, const t1d_mlp* mlp, const t1d_collect* collect, int n_steps,
                     int minutes, int n_sub, void* stream);
 
+/* t1d_rollout_pid / t1d_rollout_bb with what t1d_collect_mlp adds: trajectories collected while a classical controller drives
+ * the envs -- the data a network is fitted to before it explores (behaviour cloning), and the return and length of the
+ * controller under the collectors' episode rules.  n_steps steps in ONE launch, the env state in registers, the two feature
+ * windows and the features in LDS (4 H + 3 words per lane).  fp64 and fp32, any state layout, the fixed-step integrators as
+ * configured on the context, meals from the meal tables.
+ * Controller: the struct's gains or constants, its state (integ / prev, prev_meal), its accumulators, its four traces and its
+ *   trace_row mean what they mean in t1d_rollout_pid / t1d_rollout_bb, and the action of a step is the word that entry point
+ *   computes from the same observation and state.
+ * Features: of feat (a t1d_mlp) only history, cgm_mean, cgm_scale, ins_scale, cho_scale, cgm_hist, ins_hist, prev_meal,
+ *   start_minute (NULL = 0) and action_trace are read.  The widths, n_layers, params, the output function, n_policies /
+ *   envs_per_policy, its accumulators, its other traces and its trace_row are ignored and may be 0 / NULL; batch.n need not be
+ *   a multiple of 64.  Before each step the F = 2 H + 3 features of t1d_mlp are formed by the collectors' own device code --
+ *   the words t1d_mlp_features would return at that moment, bit for bit -- and written to collect->feat_trace; the windows and
+ *   prev_meal are maintained as in t1d_collect_mlp.
+ * Action trace: feat->action_trace[trace_row + s] = basal + bolus of step s, one addition in the batch's dtype, before the
+ *   pump; trace_row is the controller's, as for every row of this call.  With the features of the same row it is the
+ *   regression sample for a network with identity output.
+ * Per step: reward_trace and done_trace as in t1d_collect_mlp.  collect->sigma and collect->eps_trace must be NULL (there is
+ *   no exploration noise); explore_seed is ignored.
+ * on_done = T1D_COLLECT_RESTART: as in t1d_collect_mlp -- a finished env goes through what t1d_restart_done does to it, its
+ *   feature windows become those of a fresh reset, and its controller state becomes what PIDController.reset /
+ *   BBController.reset leave: integ = prev = 0, bb.prev_meal = 0.  The ep_return .. last_length accumulators advance as
+ *   documented there.
+ * Equivalence: after the call the batch, the env state, the controller state, the feature windows, the accumulators, the
+ *   restart outputs and every trace row are what n_steps x (t1d_mlp_features; t1d_rollout_pid(1) or t1d_rollout_bb(1) through
+ *   the generic roll-out kernel, "rollout_launches" = 0; the shift of the windows with prev_meal = batch.meal;
+ *   t1d_restart_done; the reset of the windows and of the controller state of the envs that were done) leave, bit for bit,
+ *   wherever the call is cut.  With T1D_COLLECT_CONTINUE the env and the controller end where t1d_rollout_pid(n_steps) /
+ *   t1d_rollout_bb(n_steps) leave them.
+ * T1D_E_INVALID before anything is launched, nothing changed: whatever t1d_rollout_pid / t1d_rollout_bb rejects; whatever
+ *   t1d_collect_mlp rejects of collect and of the fields of feat that are read (history outside [1, 12], a NULL cgm_hist /
+ *   ins_hist / prev_meal, with T1D_COLLECT_RESTART a start_minute that is neither NULL nor restart->start_minute); a non-NULL
+ *   sigma or eps_trace; a non-NULL restart->h_carry (these two calls run the fixed-step integrators only). */
+int t1d_collect_pid(t1d_ctx* ctx, const t1d_batch* batch, const t1d_pid* pid, const t1d_mlp* feat, const t1d_collect* collect,
+                    int n_steps, int minutes, int n_sub, void* hip_stream);
+int t1d_collect_bb(t1d_ctx* ctx, const t1d_batch* batch, const t1d_bb* bb, const t1d_mlp* feat, const t1d_collect* collect,
+                   int n_steps, int minutes, int n_sub, void* hip_stream);
+
 /* SimObj.simulate (sim_engine.py:29-39) with PIDController.policy (pid_ctrller.py:17-36) and the integrator of
  * t1d_step_dopri5, scipy's dopri5 as the reference drives it (t1dpatient.py:110-113,276): t1d_rollout_pid (controller,
  * b->cgm on entry, accumulators, traces, the last step's reward) in the exact mode.  All n_steps steps of `minutes` minutes

@@ -36,7 +36,7 @@ EXPORTS = ("t1d_abi_version", "t1d_last_error", "t1d_ctx_create", "t1d_ctx_set_o
            "t1d_collect_mlp", "t1d_rollout_mlp_dopri5", "t1d_mlp_action", "t1d_collect_mlp_dopri5",
            "t1d_mlp_grad_workspace", "t1d_mlp_grad", "t1d_mlp_features", "t1d_gae_workspace", "t1d_gae",
            "t1d_mlp_loss_workspace", "t1d_mlp_loss", "t1d_mlp_grad_tiles_workspace", "t1d_mlp_grad_tiles",
-           "t1d_mlp_loss_tiles_workspace", "t1d_mlp_loss_tiles")
+           "t1d_mlp_loss_tiles_workspace", "t1d_mlp_loss_tiles", "t1d_collect_pid", "t1d_collect_bb")
 
 
 class T1DError(RuntimeError):
@@ -206,6 +206,8 @@ def lib():
     L.t1d_rollout_bb.argtypes = [vp, C.POINTER(Batch), C.POINTER(Bb), C.c_int, C.c_int, C.c_int, vp]
     L.t1d_rollout_mlp.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), C.c_int, C.c_int, C.c_int, vp]
     L.t1d_collect_mlp.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), C.POINTER(Collect), C.c_int, C.c_int, C.c_int, vp]
+    L.t1d_collect_pid.argtypes = [vp, C.POINTER(Batch), C.POINTER(Pid), C.POINTER(Mlp), C.POINTER(Collect), C.c_int, C.c_int, C.c_int, vp]
+    L.t1d_collect_bb.argtypes = [vp, C.POINTER(Batch), C.POINTER(Bb), C.POINTER(Mlp), C.POINTER(Collect), C.c_int, C.c_int, C.c_int, vp]
     L.t1d_rollout_pid_dopri5.argtypes = [vp, C.POINTER(Batch), C.POINTER(Pid), vp, vp, C.c_int, C.c_int, vp]
     L.t1d_rollout_bb_dopri5.argtypes = [vp, C.POINTER(Batch), C.POINTER(Bb), vp, vp, C.c_int, C.c_int, vp]
     L.t1d_rollout_mlp_dopri5.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), vp, vp, C.c_int, C.c_int, vp]

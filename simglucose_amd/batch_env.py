@@ -452,9 +452,10 @@ class BatchedT1DSimEnv:
 
     def _no_dopri5_rollout(self):
         if self.integrator == "dopri5":
-            raise _lib.T1DError("rollout_pid / rollout_bb / rollout_mlp / collect_mlp run the fixed-step kernels, which have no DOPRI5 "
-                                "path: an env with integrator='dopri5' takes rollout_pid_dopri5 / rollout_bb_dopri5 / "
-                                "rollout_mlp_dopri5 / collect_mlp_dopri5")
+            raise _lib.T1DError("rollout_pid / rollout_bb / rollout_mlp / collect_mlp / collect_pid / collect_bb run the fixed-step "
+                                "kernels, which have no DOPRI5 path: an env with integrator='dopri5' takes rollout_pid_dopri5 / "
+                                "rollout_bb_dopri5 / rollout_mlp_dopri5 / collect_mlp_dopri5 (collect_pid and collect_bb have no "
+                                "exact-mode form)")
 
     def rollout_pid(self, n_steps, P, I, D, target=140.0, pid_state=None, stats=None, trace=None):
         """n_steps closed-loop PID steps in one launch (PIDController.policy + env.step per step).
@@ -731,6 +732,120 @@ class BatchedT1DSimEnv:
                     raise ValueError("trace['%s'] must be contiguous [rows >= row + n_steps, %s] of %s" % (k, ", ".join(map(str, shape)), dt))
                 setattr(g, f, t.data_ptr())
         return policy_state, p, g, (params, policy_state, sigma, r, terminal_obs, episode_stats, trace)
+
+    def _collect_ctrl(self, who, fn, ctl, n_steps, features, policy_state, stats, trace, on_done, days, terminal_obs,
+                      episode_stats, reset_outputs, keep):
+        """collect_pid / collect_bb: fn (t1d_collect_pid, t1d_collect_bb) with the controller's struct ctl -> policy_state"""
+        self._no_dopri5_rollout()
+        n_steps = int(n_steps)
+        if n_steps < 1:
+            raise ValueError("n_steps must be at least 1")
+        if on_done not in ("continue", "restart"):
+            raise ValueError("on_done must be 'continue' or 'restart'")
+        if features is None:
+            raise ValueError("%s: features= takes the MLPController whose history and scales form the features" % who)
+        if trace and trace.get("eps") is not None:
+            raise ValueError("%s: a controller draws no exploration noise, there is no 'eps' column" % who)
+        if policy_state is None:
+            policy_state = self.new_policy_state(features)
+        H = int(features.history)
+        for k, shape in (("cgm_hist", (H, self.n)), ("ins_hist", (H, self.n)), ("prev_meal", (self.n,))):
+            t = policy_state.get(k)
+            if t is None or tuple(t.shape) != shape or t.dtype != self.dtype or t.device != self.device or not t.is_contiguous():
+                raise ValueError("policy_state['%s'] must be a contiguous %s tensor of the env's dtype on its device" % (k, shape))
+        f = _lib.Mlp()                          # history, the feature scales, the windows and action_trace: nothing else is read
+        f.history = H
+        f.cgm_mean, f.cgm_scale, f.ins_scale, f.cho_scale = features.cgm_mean, features.cgm_scale, features.ins_scale, features.cho_scale
+        for k in ("cgm_hist", "ins_hist", "prev_meal"):
+            setattr(f, k, policy_state[k].data_ptr())
+        f.start_minute = self.start_minute.data_ptr() if self.start_minute is not None else None
+        stats = stats or {}
+        for k in ("sum_risk", "min_bg", "max_bg", "n_low", "n_high"):
+            setattr(ctl, k, stats[k].data_ptr() if k in stats else None)
+        g = _lib.Collect()
+        g.on_done, g.reserved = (_lib.T1D_COLLECT_RESTART if on_done == "restart" else _lib.T1D_COLLECT_CONTINUE), 0
+        r = None
+        if on_done == "restart":
+            if self.noise == "host" or self.normals is not None:
+                raise _lib.T1DError("%s(on_done='restart') draws every episode on the device: not available with host normals" % who)
+            r = self._restart_struct(int(days), terminal_obs, episode_stats or {}, reset_outputs, who)
+            r.h_carry = None
+            g.restart = C.pointer(r)
+            f.start_minute = r.start_minute          # _restart_struct creates the array for an env that had none
+            self._b.x0_override = None
+        row = int(trace.get("row", 0)) if trace else 0
+        F = 2 * H + 3
+        for k, tgt, fld, dt, shape in (("reward", g, "reward_trace", self.dtype, (self.n,)), ("done", g, "done_trace", torch.uint8, (self.n,)),
+                                       ("features", g, "feat_trace", self.dtype, (F, self.n)), ("action", f, "action_trace", self.dtype, (self.n,))):
+            t = trace.get(k) if trace else None
+            if t is not None:
+                if t.dtype != dt or tuple(t.shape[1:]) != shape or t.shape[0] < row + n_steps or not t.is_contiguous():
+                    raise ValueError("trace['%s'] must be contiguous [rows >= row + n_steps, %s] of %s" % (k, ", ".join(map(str, shape)), dt))
+                setattr(tgt, fld, t.data_ptr())
+        self._set_trace(ctl, trace, n_steps)          # bg, cgm, cho, insulin and the row every column of this call starts at
+        self._b.cho = None
+        self._b.flags = self._flags0
+        clock, self._clock = self._clock, None
+        ep0 = self.episode.clone() if (on_done == "restart" and self._hist is not None) else None
+        with torch.cuda.device(self.device):
+            _lib.check(fn(self._ctx, C.byref(self._b), C.byref(ctl), C.byref(f), C.byref(g), n_steps,
+                          self.minutes_per_step, self.n_sub, self._stream()))
+        if clock is not None and on_done != "restart":         # restarted envs no longer share the clock
+            self._clock = clock + n_steps * self.minutes_per_step
+        self._keep = (keep, policy_state, r, terminal_obs, episode_stats, stats, trace)
+        self._hist_after_rollout()
+        if ep0 is not None:                                     # CGM_hist of an env whose last step ended its episode = [sample #0]
+            self._hist_restart((self.episode != ep0) & (self.t == 0))
+        return policy_state
+
+    def collect_pid(self, n_steps, P, I, D, target=140.0, features=None, pid_state=None, policy_state=None, stats=None, trace=None,
+                    on_done="continue", days=2, terminal_obs=None, episode_stats=None, reset_outputs=False):
+        """rollout_pid with what collect_mlp adds, in one launch (t1d_collect_pid, include/t1d.h): the PID controller drives
+        the envs while every step records the features a network would have been given and the insulin the controller
+        asked for -- the data a policy is fitted to before it explores -- and the reward and done of every step, with
+        episodes that end (on_done="restart") under collect_mlp's rules.
+        features: an MLPController; only its history and feature scales are used (no network runs, and n need not be a
+        multiple of 64).  policy_state: the feature windows, dict(cgm_hist, ins_hist, prev_meal) as new_policy_state(features)
+        makes it (created if None: call right after reset()).  pid_state, stats as in rollout_pid; on_done, days,
+        terminal_obs, episode_stats, reset_outputs as in collect_mlp.  A restarted env's integ and prev become 0.
+        trace: new_trace's bg, cgm, cho, insulin, action, reward, done, features; "action" is basal + bolus of the step,
+        before the pump -- with "features" of the same row the regression sample for a network with identity output.
+        The result is that of a loop of policy_features(), rollout_pid(1) with rollout_launches = 0, the shift of the
+        windows, restart_done() and the torch reset of both states, bit for bit.  Measured on an MI355X (collect_bb, fp64
+        Dexcom, 32 steps, profiles/collect): at 64 Ki envs one launch is 2.2 - 3.3 times faster than that loop; at 1 Mi envs
+        it wins by 20 % under the stock basal-bolus constants (0.27 % of the envs finish per step) and LOSES by 12 % where
+        1 % finish per step, like collect_mlp.  -> (pid_state, policy_state)"""
+        if pid_state is None:
+            pid_state = {"integ": torch.zeros(self.n, dtype=self.dtype, device=self.device),
+                         "prev": torch.zeros(self.n, dtype=self.dtype, device=self.device)}
+        p = _lib.Pid()
+        p.P, p.I, p.D, p.target = float(P), float(I), float(D), float(target)
+        p.integ, p.prev = pid_state["integ"].data_ptr(), pid_state["prev"].data_ptr()
+        policy_state = self._collect_ctrl("collect_pid", self._L.t1d_collect_pid, p, n_steps, features, policy_state, stats, trace,
+                                          on_done, days, terminal_obs, episode_stats, reset_outputs, pid_state)
+        return pid_state, policy_state
+
+    def collect_bb(self, n_steps, target=140.0, features=None, bb_state=None, policy_state=None, stats=None, trace=None,
+                   on_done="continue", days=2, terminal_obs=None, episode_stats=None, reset_outputs=False):
+        """rollout_bb with what collect_mlp adds, in one launch (t1d_collect_bb, include/t1d.h): the basal-bolus controller
+        drives the envs; everything else as collect_pid.  bb_state as in rollout_bb (created from bb_constants() if None);
+        a restarted env's bb_state["prev_meal"] becomes 0.  The warm start of a policy:
+
+            tr = env.new_trace(K, columns=("action", "features"), history=pol.history)
+            env.collect_bb(K, features=pol, trace=tr, on_done="restart")
+            loss = value_loss(params, tr["features"][1:], pol, target=tr["action"][1:])
+
+        -> (bb_state, policy_state)"""
+        if bb_state is None:
+            bb_state = self.bb_constants()
+            bb_state["prev_meal"] = torch.zeros(self.n, dtype=self.dtype, device=self.device)
+        p = _lib.Bb()
+        p.target = float(target)
+        for k in ("basal", "cr", "cf", "prev_meal"):
+            setattr(p, k, bb_state[k].data_ptr())
+        policy_state = self._collect_ctrl("collect_bb", self._L.t1d_collect_bb, p, n_steps, features, policy_state, stats, trace,
+                                          on_done, days, terminal_obs, episode_stats, reset_outputs, bb_state)
+        return bb_state, policy_state
 
     def collect_mlp_dopri5(self, n_steps, policy, sigma=None, explore_seed=None, policy_state=None, stats=None, trace=None,
                            on_done="continue", days=2, terminal_obs=None, episode_stats=None, reset_outputs=False,

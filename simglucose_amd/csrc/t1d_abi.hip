@@ -1232,6 +1232,83 @@ extern "C" int t1d_collect_mlp(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* ml
     return T1D_OK;
 }
 
+// ---- t1d_collect_pid / t1d_collect_bb (ctrl_collect_kernel, t1d_policy.hpp) ----------------------------------------------
+template <typename T> using CtrlCollectFn = KernelFn<T, PidArgs<T>, MlpArgs<T>, CollectArgs<T>, RestartArgs<T>>;
+template <typename T>
+static CtrlCollectFn<T> ctrl_collect_fn(int variant)
+{
+    return by_variant<T>(variant, [](auto v) -> CtrlCollectFn<T> { return ctrl_collect_kernel<decltype(v)::value, T>; });
+}
+
+// the t1d_mlp of a controller's collector with nothing but the fields that are read: history, the four feature scales, the
+// two windows, prev_meal, start_minute and action_trace.  No network (n_layers = 0), no accumulators, no other trace.
+static t1d_mlp features_only(const t1d_mlp* m)
+{
+    t1d_mlp f = {};
+    f.history = m->history;
+    f.cgm_mean = m->cgm_mean; f.cgm_scale = m->cgm_scale; f.ins_scale = m->ins_scale; f.cho_scale = m->cho_scale;
+    f.cgm_hist = m->cgm_hist; f.ins_hist = m->ins_hist; f.prev_meal = m->prev_meal; f.start_minute = m->start_minute;
+    f.action_trace = m->action_trace;
+    return f;
+}
+
+template <typename T>
+static int run_collect_ctrl(const char* who, t1d_ctx* c, const t1d_batch* b, const PidArgs<T>& pa, const t1d_mlp* feat, const t1d_collect* g,
+                            Plan p, int minutes, int n_sub, hipStream_t s)
+{
+    const t1d_mlp fm = features_only(feat);
+    MlpArgs<T> fa = make_mlp<T>(&fm, pa.n_steps);
+    // a wave's columns: the two windows and the F = 2 H + 3 features, no activations
+    const int rc = shape_mlp<T>(who, c, b, 4 * fm.history + 3, p, fa);
+    if (rc) return rc;
+    const RestartArgs<T> ra = g->on_done == T1D_COLLECT_RESTART ? make_restart<T>(g->restart) : RestartArgs<T>{};
+    return launch(c, b, p, minutes, n_sub, s, ctrl_collect_fn<T>(p.variant), pa, fa, make_collect<T>(c, g), ra);
+}
+
+// a collector under the PID controller pid or the basal-bolus controller bb (the other one NULL).  What needs no device is
+// checked first, so that a bad call is refused on any machine.
+static int launch_collect_ctrl(const char* who, t1d_ctx* c, const t1d_batch* b, const t1d_pid* pid, const t1d_bb* bb, const t1d_mlp* feat,
+                               const t1d_collect* g, int n_steps, int minutes, int n_sub, void* stream)
+{
+    const std::string w = std::string(who) + ": ";
+    if (!feat) return fail(T1D_E_INVALID, w + "feat is NULL");
+    if (feat->history < 1 || feat->history > kMlpMaxHistory) return fail(T1D_E_INVALID, w + "history must be in [1, 12]");
+    if (!feat->cgm_hist || !feat->ins_hist || !feat->prev_meal) return fail(T1D_E_INVALID, w + "cgm_hist / ins_hist / prev_meal must be set");
+    int rc = check_collect(who, b, feat, g, nullptr);
+    if (rc) return rc;
+    if (g->sigma || g->eps_trace) return fail(T1D_E_INVALID, w + "sigma and eps_trace must be NULL (a controller has no exploration noise)");
+    if (n_steps < 1) return fail(T1D_E_INVALID, w + "n_steps < 1");
+    if (b && b->cho) return fail(T1D_E_INVALID, w + "dense cho is not supported, use the meal table");
+    if (minutes < 1 || minutes > 100000) return fail(T1D_E_INVALID, w + "minutes out of range");
+    if (n_sub < 1 || n_sub > 4096) return fail(T1D_E_INVALID, w + "n_sub out of range");
+    rc = check_closed_loop(who, c, b, n_steps);
+    if (rc) return rc;
+    Plan p;
+    rc = plan_and_tables(who, c, b, minutes, n_sub, true, &p, true);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (p.f64) rc = run_collect_ctrl<double>(who, c, b, pid ? make_pid<double>(pid, n_steps) : make_bb<double>(bb, n_steps), feat, g, p, minutes, n_sub, s);
+    else rc = run_collect_ctrl<float>(who, c, b, pid ? make_pid<float>(pid, n_steps) : make_bb<float>(bb, n_steps), feat, g, p, minutes, n_sub, s);
+    if (rc) return rc;
+    T1D_HIP(hipGetLastError());
+    return T1D_OK;
+}
+
+extern "C" int t1d_collect_pid(t1d_ctx* c, const t1d_batch* b, const t1d_pid* pid, const t1d_mlp* feat, const t1d_collect* g,
+                               int n_steps, int minutes, int n_sub, void* stream)
+{
+    if (!pid || !pid->integ || !pid->prev) return fail(T1D_E_INVALID, "t1d_collect_pid: pid state is NULL");
+    return launch_collect_ctrl("t1d_collect_pid", c, b, pid, nullptr, feat, g, n_steps, minutes, n_sub, stream);
+}
+
+extern "C" int t1d_collect_bb(t1d_ctx* c, const t1d_batch* b, const t1d_bb* bb, const t1d_mlp* feat, const t1d_collect* g,
+                              int n_steps, int minutes, int n_sub, void* stream)
+{
+    if (!bb || !bb->basal || !bb->cr || !bb->cf || !bb->prev_meal)
+        return fail(T1D_E_INVALID, "t1d_collect_bb: basal / cr / cf / prev_meal must be set");
+    return launch_collect_ctrl("t1d_collect_bb", c, b, nullptr, bb, feat, g, n_steps, minutes, n_sub, stream);
+}
+
 // The exact mode's collector (dopri5_mlp_collect_kernel, t1d_dopri5.hpp): the checks of t1d_rollout_mlp_dopri5 and of
 // t1d_collect_mlp, then one launch in the shape of t1d_rollout_mlp_dopri5.
 extern "C" int t1d_collect_mlp_dopri5(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_collect* g, double* h_carry,

@@ -438,6 +438,175 @@ __global__ __launch_bounds__(T1D_POLICY_THREADS) void mlp_collect_kernel(const K
     }
 }
 
+// ---- t1d_collect_pid / t1d_collect_bb: trajectories under the two hand-written controllers ---------------------------------
+//   ctrl_collect_kernel  mlp_collect_kernel with the controller of rollout_pid_kernel in the place of the network: the env state
+//                        in registers, the two windows and the feature buffer in the lane's LDS column (4 H + 3 words per lane:
+//                        there are no activation columns), no weights and no draw.  Every step forms the features a network
+//                        would have been given (mlp_features, written to feat_trace) and records what the controller asked for
+//                        (basal + bolus, to the policy's action_trace): the two halves of a behaviour-cloning sample.  Reward,
+//                        done, the restart of a finished env and the episode accumulators are mlp_collect_body's; a restarted
+//                        env's controller state becomes what PIDController.reset / BBController.reset leave.
+//   the controller       ctrl_policy below: rollout_body's expressions (t1d_kernels.hpp) under the same run-time `kind`, so that
+//                        the action of a step is the word rollout_pid_kernel computes from the same observation and state.
+//                        rollout_body leaves the PID's contraction into fused multiply-adds to the compiler, which forms
+//                        u = fma(I, integ, P (obs - target)) + D (obs - prev) / st and integ = fma(obs - target, st, integ) in
+//                        all eight instances of rollout_pid_kernel; left to itself here it formed fma(P, obs - target, I integ)
+//                        in an fp32 instance, another word.  So ctrl_policy writes the two fused multiply-adds out.  Calling
+//                        it from rollout_body as well moved instructions in three of that kernel's fp32 instances, so
+//                        rollout_body keeps its text: change one, check the other (tests/test_gpu_collect_ctrl.py does).
+//   traces               every row index is the controller's trace_row (PidArgs); the policy's own trace_row is not read.
+template <typename T>
+__device__ __forceinline__ void ctrl_policy(const PidArgs<T>& c, bool bb, T st, T obs, T bb_basal, T bb_cr, T bb_cf, T prev_meal,
+                                            T& integ, T& prev, T& u, T& bolus)
+{
+    bolus = T(0);
+    if (bb) {
+        // BBController._bb_policy (basal_bolus_ctrller.py:64-79)
+        u = bb_basal;
+        if (prev_meal > T(0)) {
+            const T corr = obs > T(150) ? (obs - c.target) / bb_cf : T(0);
+            bolus = ((prev_meal * st) / bb_cr + corr) / st;
+        }
+    } else {
+        // PIDController.policy (pid_ctrller.py:17-36): P (obs - target) + I integ + D (obs - prev) / st, integ += (obs - target) st
+        u = fma(c.I, integ, c.P * (obs - c.target)) + c.D * (obs - prev) / st;
+        prev = obs;
+        integ = fma(obs - c.target, st, integ);
+    }
+}
+
+template <int VARIANT, typename T, typename P, typename PR = NoProp>
+__device__ __forceinline__ void ctrl_collect_body(const KArgs<T>& a, const PidArgs<T>& c, const MlpArgs<T>& f, const CollectArgs<T>& g,
+                                                  const RestartArgs<T>& r, P& p, unsigned i, uint32_t pid, Env<T>& e, T* col, PR pr = PR())
+{
+    constexpr int MATH = VariantMath<VARIANT>::value;
+    const int H = f.history, F = 2 * H + 3;
+    T* const buf = col + 2 * H * 64;
+    T obs = at(a.cgm, i);
+    col[0] = obs;                                               // CGM[0] is the observation the step starts from
+    for (int k = 1; k < H; ++k) col[k * 64] = at(rowv(f.cgm_hist, a.n, k), i);
+    for (int k = 0; k < H; ++k) col[(H + k) * 64] = at(rowv(f.ins_hist, a.n, k), i);
+    int head = 0;
+    T feat_meal = at(f.prev_meal, i);                           // the policy's prev_meal: its own array, the same word after a step
+    int start = f.start_minute ? (int)at(f.start_minute, i) : 0;
+    const bool bb = c.kind == 1;
+    T integ = T(0), prev = T(0), bb_basal = T(0), bb_cr = T(1), bb_cf = T(1), prev_meal = T(0);
+    if (bb) { bb_basal = at(c.bb_basal, i); bb_cr = at(c.bb_cr, i); bb_cf = at(c.bb_cf, i); prev_meal = at(c.bb_prev_meal, i); }
+    else { integ = at(c.integ, i); prev = at(c.prev, i); }
+    T sum_risk = c.sum_risk ? at(c.sum_risk, i) : T(0);
+    T min_bg = c.min_bg ? at(c.min_bg, i) : T(0), max_bg = c.max_bg ? at(c.max_bg, i) : T(0);
+    int n_low = c.n_low ? at(c.n_low, i) : 0, n_high = c.n_high ? at(c.n_high, i) : 0;
+    const T st = T(a.sen.st);
+    StepOut<T> o{T(0), T(0), T(0), T(0)};
+    T rp = e.prev_risk;                         // risk of the observation the last step started from
+    bool fresh = false;                         // the last step ended the episode: outputs and state are in memory already
+#pragma unroll 1
+    for (int s = 0; s < c.n_steps; ++s) {
+        const int64_t trow = (c.trace_row + s) * a.n + i;
+        mlp_features(f, col, buf, head, feat_meal, start + e.t);
+        if (g.feat_trace)
+            for (int j = 0; j < F; ++j) g.feat_trace[((c.trace_row + s) * F + j) * a.n + i] = buf[j * 64];
+        T u, bolus;
+        ctrl_policy(c, bb, st, obs, bb_basal, bb_cr, bb_cf, prev_meal, integ, prev, u, bolus);
+        if (f.act_trace) f.act_trace[trow] = u + bolus;         // what the controller asked for, before the pump
+        rp = e.prev_risk;
+        o = step_body<MATH, T, P, true, PR, VariantInfo<VARIANT>::tiered>(a, p, i, e, u, bolus, true, pr);
+        // the step's reward and done, as write_outputs forms them
+        T rl, rh, rc;
+        risk_index1<MATH>(o.cgm, rl, rh, rc);
+        e.prev_risk = rc;
+        const T reward = rp - rc;
+        const bool fin = o.bg < T(70) || o.bg > T(350);
+        obs = o.cgm;
+        prev_meal = o.meal;
+        feat_meal = o.meal;
+        head = head == 0 ? H - 1 : head - 1;                    // the oldest row becomes the newest
+        col[head * 64] = o.cgm; col[(H + head) * 64] = o.ins;
+        if (c.bg_trace) c.bg_trace[trow] = o.bg;
+        if (c.cgm_trace) c.cgm_trace[trow] = o.cgm;
+        if (c.cho_trace) c.cho_trace[trow] = o.meal;
+        if (c.ins_trace) c.ins_trace[trow] = o.ins;
+        if (g.reward_trace) g.reward_trace[trow] = reward;
+        if (g.done_trace) g.done_trace[trow] = fin ? 1 : 0;
+        if (c.sum_risk) { T l, h, q; risk_index1<MATH>(o.bg, l, h, q); sum_risk += q; }
+        min_bg = o.bg < min_bg ? o.bg : min_bg;
+        max_bg = o.bg > max_bg ? o.bg : max_bg;
+        n_low += o.bg < T(70); n_high += o.bg > T(180);
+        fresh = false;
+        if (g.on_done) {
+            if (fin) {
+                // the finished step goes to memory as the end of a launch leaves it; the restart works on those words
+                write_outputs<MATH>(a, i, e, o, rp);
+                store_env(a, i, pid, e);
+                collect_restart<T>(a, r, g.slots, i);
+                load_env(a, i, at(a.meta, i), e);
+                obs = at(a.cgm, i);                             // the new episode's first observation
+                for (int k = 0; k < H; ++k) { col[k * 64] = obs; col[(H + k) * 64] = T(0); }
+                feat_meal = T(0);
+                integ = T(0); prev = T(0); prev_meal = T(0);    // PIDController.reset, BBController.reset
+                if (f.start_minute) start = (int)at(f.start_minute, i);
+                fresh = true;
+            } else if (r.ep_return) {                           // restart_front's accumulators for an env that goes on
+                const T sum = at(r.ep_return, i) + reward;
+                const int len = at(r.ep_length, i) + 1;
+                at(r.ep_return, i) = sum; at(r.ep_length, i) = len;
+            }
+        }
+    }
+    if (!fresh) {
+        write_outputs<MATH>(a, i, e, o, rp);
+        store_env(a, i, pid, e);
+    }
+    for (int k = 0, q = head; k < H; ++k) {                     // the windows back in window order
+        at(rowv(f.cgm_hist, a.n, k), i) = col[q * 64];
+        at(rowv(f.ins_hist, a.n, k), i) = col[(H + q) * 64];
+        q = q + 1 == H ? 0 : q + 1;
+    }
+    at(f.prev_meal, i) = feat_meal;
+    if (bb) at(c.bb_prev_meal, i) = prev_meal;
+    else { at(c.integ, i) = integ; at(c.prev, i) = prev; }
+    if (c.sum_risk) at(c.sum_risk, i) = sum_risk;
+    if (c.min_bg) at(c.min_bg, i) = min_bg;
+    if (c.max_bg) at(c.max_bg, i) = max_bg;
+    if (c.n_low) at(c.n_low, i) = n_low;
+    if (c.n_high) at(c.n_high, i) = n_high;
+}
+
+// Launch shape, LDS and VARIANT as for mlp_rollout_kernel, with cols = 4 H + 3.  Any n: no lane looks at another.
+template <int VARIANT, typename T>
+__global__ __launch_bounds__(T1D_POLICY_THREADS) void ctrl_collect_kernel(const KArgs<T> a, const PidArgs<T> c, const MlpArgs<T> f,
+                                                                          const CollectArgs<T> g, const RestartArgs<T> r)
+{
+    using VI = VariantInfo<VARIANT>;
+    constexpr int kParRows = VI::split ? DP_COUNT : DP_RK4_COUNT;
+    __shared__ T lds[VI::lds_pars ? kParRows * kMaxPatients : 1];
+    if (VI::lds_pars) stage_pars(a, lds, kParRows);
+    if (VI::split) stage_prop(a, (T*)t1d_dyn_lds);
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    __builtin_assume(i < (1u << 28));          // host guarantees n <= 2^28: i * sizeof(T) fits a 32-bit voffset
+    if ((int64_t)i >= a.n) return;
+    T* const col = (T*)(t1d_dyn_lds + f.lds_off) + (threadIdx.x >> 6) * (f.cols * 64) + (threadIdx.x & 63u);
+    const uint32_t meta = at(a.meta, i);
+    const uint32_t pid = T1D_META_PID(meta);
+    Env<T> e;
+    load_env(a, i, meta, e);
+    if constexpr (VARIANT == 4 || VARIANT == 6) {
+        ParsReg<T> p;
+        p.load(a.dpar, (int)pid);
+        ctrl_collect_body<VARIANT>(a, c, f, g, r, p, i, pid, e, col, PropLds<T>{(const T*)t1d_dyn_lds, a.np_pad, (int)pid});
+    } else if constexpr (VARIANT == 7) {
+        ParsLds<T> p{lds, (int)pid};
+        ctrl_collect_body<VARIANT>(a, c, f, g, r, p, i, pid, e, col, PropLds<T>{(const T*)t1d_dyn_lds, a.np_pad, (int)pid});
+    } else if constexpr (VARIANT == 3) {
+        ParsReg<T> p;
+        p.load(a.dpar, (int)pid);
+        ctrl_collect_body<VARIANT>(a, c, f, g, r, p, i, pid, e, col);
+    } else {
+        ParsLds<T> p{lds, (int)pid};
+        ctrl_collect_body<VARIANT>(a, c, f, g, r, p, i, pid, e, col);
+    }
+}
+
 // t1d_mlp_features: the features alone, one lane per env -- what the next step of a collector would write to its feat_trace
 // row, from the words mlp_action_kernel (t1d_dopri5.hpp) reads: batch.cgm (CGM[0]), rows 1 .. of cgm_hist, ins_hist, prev_meal,
 // batch.t and start_minute.  Reads only; writes feat [F][n].  Dynamic LDS: cols * 64 words for each wave, the lane's column in

@@ -1,0 +1,139 @@
+"""Cost of collecting K steps of trajectories while the basal-bolus controller drives the envs, fp64 Dexcom, child#001 /
+adult#001 with random initial glucose (the envs of tools/collect_bench.py), every trace column, two workloads:
+  stock    bb_constants() for every env: almost no episode ends
+  hot      the upper half of the envs at basal = 0.05 U/min (the workload of tests/test_gpu_collect_ctrl.py): their episodes end
+           low all the time
+and two legs:
+  collect  collect_bb(K, on_done="restart") with bg, cgm, cho, insulin, action, reward, done, features: one launch
+  loop     the entry points that did the same before it (include/t1d.h, t1d_collect_bb): K x (policy_features, rollout_bb(1)
+           through the generic roll-out kernel, the window shift, restart_done, the torch reset of windows and prev_meal,
+           keeping reward, done and features); the loop has no action column, the roll-out records none
+Every leg: fresh env, `warm_steps` steps so that the batch is mixed, one warm-up pass, then K steps between two device
+synchronisations (host clock), `reps` times, legs alternated; the median is reported.  `finish_rate` is the share of env-steps of
+the timed window that ended an episode.  One JSON line per (workload, batch size); --out writes them as a list.
+
+    python tools/ctrl_collect_bench.py --out profiles/collect/ctrl_collect_bench.json
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+DAYS = 2
+COLUMNS = ("bg", "cgm", "cho", "insulin", "action", "reward", "done", "features")
+
+
+def make_features(history=4):
+    """only history and the feature scales matter to collect_bb; policy_features (the loop) asks for a complete network"""
+    import torch
+    from simglucose_amd.controller.mlp_ctrller import MLPController
+    return MLPController([(torch.zeros(1, 2 * history + 3, dtype=torch.float64), torch.zeros(1, dtype=torch.float64))], history=history)
+
+
+def make_env(n, seed):
+    import torch
+    from simglucose_amd.batch_env import BatchedT1DSimEnv
+    e = BatchedT1DSimEnv(patient=["child#001", "adult#001"] * (n // 2), sensor="Dexcom", dtype=torch.float64, seed=seed,
+                         random_init_bg=True)
+    e.set_option("rollout_launches", 0)
+    e.restart_done(mask=torch.ones(n, dtype=torch.uint8, device=e.device), days=DAYS, reset_outputs=True)
+    return e
+
+
+def run_leg(leg, workload, n, pol, K, warm_steps, hot_basal, seed):
+    import torch
+    e = make_env(n, seed)
+    bb = e.bb_constants()
+    if workload == "hot":
+        bb["basal"][n // 2:] = hot_basal
+    bb["prev_meal"] = torch.zeros(n, dtype=e.dtype, device=e.device)
+    state = e.new_policy_state(pol)
+    if warm_steps:
+        e.collect_bb(warm_steps, features=pol, bb_state=bb, policy_state=state, on_done="restart", days=DAYS)
+    zero = torch.zeros((), dtype=e.dtype, device=e.device)
+    finished = torch.zeros((), dtype=torch.int64, device=e.device)
+
+    def go():
+        nonlocal finished
+        if leg == "collect":
+            tr = e.new_trace(K, columns=COLUMNS, history=pol.history)
+            e.collect_bb(K, features=pol, bb_state=bb, policy_state=state, trace=tr, on_done="restart", days=DAYS)
+            finished = tr["done"][1:].sum()
+        else:
+            tr = e.new_trace(K, columns=COLUMNS[:4])
+            rew, don, feat = [], [], []
+            for _ in range(K):
+                feat.append(e.policy_features(pol, state))
+                e.rollout_bb(1, bb_state=bb, trace=tr)
+                pol.shift(state["cgm_hist"], state["ins_hist"], e.cgm, e.insulin)
+                state["prev_meal"].copy_(e.meal)
+                done = e.done.bool()
+                rew.append(e.reward.clone()); don.append(e.done.clone())
+                e.restart_done(days=DAYS)
+                state["cgm_hist"].copy_(torch.where(done, e.cgm, state["cgm_hist"]))
+                state["ins_hist"].copy_(torch.where(done, zero, state["ins_hist"]))
+                state["prev_meal"].copy_(torch.where(done, zero, state["prev_meal"]))
+                bb["prev_meal"].copy_(torch.where(done, zero, bb["prev_meal"]))
+            tr["reward"], tr["done"], tr["features"] = torch.stack(rew), torch.stack(don), torch.stack(feat)
+            finished = tr["done"].sum()
+    go()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    go()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    status = e.sync(raise_on_status=False)
+    rate = float(finished) / (K * n)
+    e.close()
+    del e
+    torch.cuda.empty_cache()
+    return {"ms": 1e3 * dt, "status": status, "finish_rate": rate}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, nargs="+", default=[1 << 16, 1 << 20])
+    ap.add_argument("--workloads", nargs="+", default=["stock", "hot"], choices=["stock", "hot"])
+    ap.add_argument("--legs", nargs="+", default=["collect", "loop"], choices=["collect", "loop"])
+    ap.add_argument("--steps", type=int, default=32)
+    ap.add_argument("--warm-steps", type=int, default=160, help="steps before the timed window, so that episodes end inside it")
+    ap.add_argument("--hot-basal", type=float, default=0.05, help="U/min of the upper half of the envs on the hot workload")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--seed", type=int, default=3)
+    ap.add_argument("--label", default=None)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("ctrl_collect_bench.py measures on the GPU: none found")
+    pol = make_features()
+    results = []
+    for workload in args.workloads:
+        for n in args.n:
+            runs = {leg: [] for leg in args.legs}
+            for _ in range(args.reps):
+                for leg in args.legs:
+                    runs[leg].append(run_leg(leg, workload, n, pol, args.steps, args.warm_steps, args.hot_basal, args.seed))
+            res = {"controller": "bb", "workload": workload, "hot_basal": args.hot_basal if workload == "hot" else None, "n_envs": n,
+                   "dtype": "float64", "steps": args.steps, "warm_steps": args.warm_steps, "sensor": "Dexcom", "label": args.label,
+                   "device": torch.cuda.get_device_name(0), "legs": {}}
+            for leg, rr in runs.items():
+                ms = sorted(r["ms"] for r in rr)
+                res["legs"][leg] = {"ms_median": ms[len(ms) // 2], "ms_runs": [r["ms"] for r in rr],
+                                    "status": max(r["status"] for r in rr), "finish_rate": rr[-1]["finish_rate"]}
+            med = {leg: v["ms_median"] for leg, v in res["legs"].items()}
+            if "collect" in med and "loop" in med:
+                res["loop_over_collect"] = med["loop"] / med["collect"]
+            print(json.dumps(res), flush=True)
+            results.append(res)
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(results, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
