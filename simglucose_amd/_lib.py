@@ -59,22 +59,21 @@ class Batch(C.Structure):
     ]
 
 
+# the accumulators and the four trace columns that t1d_pid, t1d_bb and t1d_mlp all carry, in the header's order
+_STATS_FIELDS = [(k, C.c_void_p) for k in ("sum_risk", "min_bg", "max_bg", "n_low", "n_high")]
+_TRACE_FIELDS = [(k, C.c_void_p) for k in ("bg_trace", "cgm_trace", "cho_trace", "insulin_trace")]
+
+
 class Pid(C.Structure):
     """struct t1d_pid (include/t1d.h)"""
     _fields_ = [("P", C.c_double), ("I", C.c_double), ("D", C.c_double), ("target", C.c_double),
-                ("integ", C.c_void_p), ("prev", C.c_void_p), ("sum_risk", C.c_void_p),
-                ("min_bg", C.c_void_p), ("max_bg", C.c_void_p), ("n_low", C.c_void_p), ("n_high", C.c_void_p),
-                ("bg_trace", C.c_void_p), ("cgm_trace", C.c_void_p), ("cho_trace", C.c_void_p),
-                ("insulin_trace", C.c_void_p), ("trace_row", C.c_int64)]
+                ("integ", C.c_void_p), ("prev", C.c_void_p)] + _STATS_FIELDS + _TRACE_FIELDS + [("trace_row", C.c_int64)]
 
 
 class Bb(C.Structure):
     """struct t1d_bb (include/t1d.h)"""
     _fields_ = [("target", C.c_double), ("basal", C.c_void_p), ("cr", C.c_void_p), ("cf", C.c_void_p),
-                ("prev_meal", C.c_void_p), ("sum_risk", C.c_void_p), ("min_bg", C.c_void_p), ("max_bg", C.c_void_p),
-                ("n_low", C.c_void_p), ("n_high", C.c_void_p),
-                ("bg_trace", C.c_void_p), ("cgm_trace", C.c_void_p), ("cho_trace", C.c_void_p),
-                ("insulin_trace", C.c_void_p), ("trace_row", C.c_int64)]
+                ("prev_meal", C.c_void_p)] + _STATS_FIELDS + _TRACE_FIELDS + [("trace_row", C.c_int64)]
 
 
 class Mlp(C.Structure):
@@ -84,10 +83,7 @@ class Mlp(C.Structure):
                 ("cgm_mean", C.c_double), ("cgm_scale", C.c_double), ("ins_scale", C.c_double), ("cho_scale", C.c_double),
                 ("out_scale", C.c_double), ("out_bias", C.c_double),
                 ("params", C.c_void_p), ("cgm_hist", C.c_void_p), ("ins_hist", C.c_void_p), ("prev_meal", C.c_void_p),
-                ("start_minute", C.c_void_p), ("sum_risk", C.c_void_p), ("min_bg", C.c_void_p), ("max_bg", C.c_void_p),
-                ("n_low", C.c_void_p), ("n_high", C.c_void_p),
-                ("bg_trace", C.c_void_p), ("cgm_trace", C.c_void_p), ("cho_trace", C.c_void_p),
-                ("insulin_trace", C.c_void_p), ("action_trace", C.c_void_p), ("trace_row", C.c_int64)]
+                ("start_minute", C.c_void_p)] + _STATS_FIELDS + _TRACE_FIELDS + [("action_trace", C.c_void_p), ("trace_row", C.c_int64)]
 
 
 class Outcome(C.Structure):

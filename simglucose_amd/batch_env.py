@@ -462,26 +462,65 @@ class BatchedT1DSimEnv:
         pid_state: dict(integ, prev) tensors [n] (created zeroed if None).  stats: optional dict
         with any of sum_risk, min_bg, max_bg (float [n]) and n_low, n_high (int32 [n])."""
         self._no_dopri5_rollout()
+        pid_state, p = self._pid_struct(P, I, D, target, pid_state, stats)
+        self._rollout(self._L.t1d_rollout_pid, (p,), n_steps, trace)
+        return pid_state
+
+    @staticmethod
+    def _n_steps(n_steps):
+        n_steps = int(n_steps)
+        if n_steps < 1:
+            raise ValueError("n_steps must be at least 1")
+        return n_steps
+
+    @staticmethod
+    def _set_stats(p, stats):
+        """stats: None or dict with any of the five accumulators -> the fields of a t1d_pid / t1d_bb / t1d_mlp"""
+        stats = stats or {}
+        for k in ("sum_risk", "min_bg", "max_bg", "n_low", "n_high"):
+            setattr(p, k, stats[k].data_ptr() if k in stats else None)
+
+    def _pid_struct(self, P, I, D, target, pid_state, stats):
+        """the t1d_pid of rollout_pid / rollout_pid_dopri5 / collect_pid -> (pid_state, created zeroed if None; struct)"""
         if pid_state is None:
             pid_state = {"integ": torch.zeros(self.n, dtype=self.dtype, device=self.device),
                          "prev": torch.zeros(self.n, dtype=self.dtype, device=self.device)}
         p = _lib.Pid()
         p.P, p.I, p.D, p.target = float(P), float(I), float(D), float(target)
         p.integ, p.prev = pid_state["integ"].data_ptr(), pid_state["prev"].data_ptr()
-        stats = stats or {}
-        for k in ("sum_risk", "min_bg", "max_bg", "n_low", "n_high"):
-            setattr(p, k, stats[k].data_ptr() if k in stats else None)
-        self._set_trace(p, trace, n_steps)
+        self._set_stats(p, stats)
+        return pid_state, p
+
+    def _bb_struct(self, target, bb_state, stats):
+        """the t1d_bb of rollout_bb / rollout_bb_dopri5 / collect_bb -> (bb_state, created from bb_constants() if None; struct)"""
+        if bb_state is None:
+            bb_state = self.bb_constants()
+            bb_state["prev_meal"] = torch.zeros(self.n, dtype=self.dtype, device=self.device)
+        p = _lib.Bb()
+        p.target = float(target)
+        for k in ("basal", "cr", "cf", "prev_meal"):
+            setattr(p, k, bb_state[k].data_ptr())
+        self._set_stats(p, stats)
+        return bb_state, p
+
+    def _rollout(self, fn, structs, n_steps, trace, restarts=False):
+        """The one fixed-step closed-loop launch: fn(ctx, batch, *structs, n_steps, minutes, n_sub, stream).  structs[0] is
+        the controller's, which carries the trace columns of _set_trace.  restarts: envs may start their next episode
+        inside the launch (on_done="restart"); they no longer share one clock afterwards."""
+        n_steps = self._n_steps(n_steps)
+        self._set_trace(structs[0], trace, n_steps)
         self._b.cho = None
         self._b.flags = self._flags0
-        clock, self._clock = self._clock, None
+        clock, self._clock = self._clock, None        # the shadow clock survives only a call that went through
+        ep0 = self.episode.clone() if (restarts and self._hist is not None) else None
         with torch.cuda.device(self.device):
-            _lib.check(self._L.t1d_rollout_pid(self._ctx, C.byref(self._b), C.byref(p), int(n_steps),
-                                               self.minutes_per_step, self.n_sub, self._stream()))
-        if clock is not None:
-            self._clock = clock + int(n_steps) * self.minutes_per_step
+            _lib.check(fn(self._ctx, C.byref(self._b), *[C.byref(s) for s in structs], n_steps, self.minutes_per_step,
+                          self.n_sub, self._stream()))
+        if clock is not None and not restarts:
+            self._clock = clock + n_steps * self.minutes_per_step
         self._hist_after_rollout()
-        return pid_state
+        if ep0 is not None:                           # CGM_hist of an env whose last step ended its episode = [sample #0]
+            self._hist_restart((self.episode != ep0) & (self.t == 0))
 
     def bb_constants(self):
         """Per-env BBController constants (basal_bolus_ctrller.py:54-64): basal = u2ss*BW/6000 U/min, CR and CF from
@@ -504,26 +543,8 @@ class BatchedT1DSimEnv:
         basal, cr, cf (see bb_constants) and prev_meal [n] (created if None; prev_meal = 0 right after reset).
         Meals come from the meal tables (set_meals).  stats as in rollout_pid."""
         self._no_dopri5_rollout()
-        if bb_state is None:
-            bb_state = self.bb_constants()
-            bb_state["prev_meal"] = torch.zeros(self.n, dtype=self.dtype, device=self.device)
-        p = _lib.Bb()
-        p.target = float(target)
-        for k in ("basal", "cr", "cf", "prev_meal"):
-            setattr(p, k, bb_state[k].data_ptr())
-        stats = stats or {}
-        for k in ("sum_risk", "min_bg", "max_bg", "n_low", "n_high"):
-            setattr(p, k, stats[k].data_ptr() if k in stats else None)
-        self._set_trace(p, trace, n_steps)
-        self._b.cho = None
-        self._b.flags = self._flags0
-        clock, self._clock = self._clock, None
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.t1d_rollout_bb(self._ctx, C.byref(self._b), C.byref(p), int(n_steps),
-                                              self.minutes_per_step, self.n_sub, self._stream()))
-        if clock is not None:
-            self._clock = clock + int(n_steps) * self.minutes_per_step
-        self._hist_after_rollout()
+        bb_state, p = self._bb_struct(target, bb_state, stats)
+        self._rollout(self._L.t1d_rollout_bb, (p,), n_steps, trace)
         return bb_state
 
     def new_policy_state(self, policy):
@@ -540,11 +561,7 @@ class BatchedT1DSimEnv:
         npol = int(policy.n_policies)
         if self.n % npol or (self.n // npol) % 64:
             raise ValueError("%s: %d envs do not split into %d policies of a multiple of 64 envs each" % (who, self.n, npol))
-        H = int(policy.history)
-        for k, shape in (("cgm_hist", (H, self.n)), ("ins_hist", (H, self.n)), ("prev_meal", (self.n,))):
-            t = policy_state.get(k)
-            if t is None or tuple(t.shape) != shape or t.dtype != self.dtype or t.device != self.device or not t.is_contiguous():
-                raise ValueError("policy_state['%s'] must be a contiguous %s tensor of the env's dtype on its device" % (k, shape))
+        self._check_policy_state(policy_state, policy.history)
         params = policy.device_params(self.device, self.dtype)          # uploaded once per policy, device and dtype
         p = _lib.Mlp()
         policy.fill_struct(p)
@@ -553,10 +570,27 @@ class BatchedT1DSimEnv:
         for k in ("cgm_hist", "ins_hist", "prev_meal"):
             setattr(p, k, policy_state[k].data_ptr())
         p.start_minute = self.start_minute.data_ptr() if self.start_minute is not None else None
-        stats = stats or {}
-        for k in ("sum_risk", "min_bg", "max_bg", "n_low", "n_high"):
-            setattr(p, k, stats[k].data_ptr() if k in stats else None)
+        self._set_stats(p, stats)
         return p, params
+
+    def _check_policy_state(self, policy_state, history):
+        H = int(history)
+        for k, shape in (("cgm_hist", (H, self.n)), ("ins_hist", (H, self.n)), ("prev_meal", (self.n,))):
+            t = policy_state.get(k)
+            if t is None or tuple(t.shape) != shape or t.dtype != self.dtype or t.device != self.device or not t.is_contiguous():
+                raise ValueError("policy_state['%s'] must be a contiguous %s tensor of the env's dtype on its device" % (k, shape))
+
+    def _feature_struct(self, features, policy_state):
+        """the t1d_mlp of collect_pid / collect_bb, where no network runs: history, the feature scales and the windows (and
+        the action_trace that the collector's builder sets); nothing else is read"""
+        self._check_policy_state(policy_state, features.history)
+        f = _lib.Mlp()
+        f.history = int(features.history)
+        f.cgm_mean, f.cgm_scale, f.ins_scale, f.cho_scale = features.cgm_mean, features.cgm_scale, features.ins_scale, features.cho_scale
+        for k in ("cgm_hist", "ins_hist", "prev_meal"):
+            setattr(f, k, policy_state[k].data_ptr())
+        f.start_minute = self.start_minute.data_ptr() if self.start_minute is not None else None
+        return f
 
     def policy_action(self, policy, policy_state):
         """The basal [n], before the pump, that the next step of rollout_mlp / rollout_mlp_dopri5 would ask for
@@ -603,8 +637,7 @@ class BatchedT1DSimEnv:
         rollout_pid_dopri5 -- lanes open their steps at different moments, and each moment runs the network for the few
         lanes that are there."""
         self._need_dopri5("rollout_mlp_dopri5")
-        if int(n_steps) < 1:
-            raise ValueError("n_steps must be at least 1")
+        n_steps = self._n_steps(n_steps)
         if policy_state is None:
             policy_state = self.new_policy_state(policy)
         p, params = self._mlp_struct("rollout_mlp_dopri5", policy, policy_state, stats)
@@ -620,23 +653,12 @@ class BatchedT1DSimEnv:
         roll-out can be cut anywhere and resumed.  The time-of-day features use the env's start_minute (0 if it has none).
         stats as in rollout_pid; trace may also hold "action" (new_trace)."""
         self._no_dopri5_rollout()
-        n_steps = int(n_steps)
-        if n_steps < 1:
-            raise ValueError("n_steps must be at least 1")
+        n_steps = self._n_steps(n_steps)
         if policy_state is None:
             policy_state = self.new_policy_state(policy)
         p, params = self._mlp_struct("rollout_mlp", policy, policy_state, stats)
-        self._set_trace(p, trace, n_steps)
-        self._b.cho = None
-        self._b.flags = self._flags0
-        clock, self._clock = self._clock, None
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.t1d_rollout_mlp(self._ctx, C.byref(self._b), C.byref(p), n_steps,
-                                               self.minutes_per_step, self.n_sub, self._stream()))
-        if clock is not None:
-            self._clock = clock + n_steps * self.minutes_per_step
+        self._rollout(self._L.t1d_rollout_mlp, (p,), n_steps, trace)
         self._keep = (params, policy_state)
-        self._hist_after_rollout()
         return policy_state
 
     def collect_mlp(self, n_steps, policy, sigma=None, explore_seed=None, policy_state=None, stats=None, trace=None,
@@ -676,126 +698,70 @@ class BatchedT1DSimEnv:
             ratio = (new - old).exp()
         """
         self._no_dopri5_rollout()
-        n_steps = int(n_steps)
-        policy_state, p, g, keep = self._collect_structs("collect_mlp", n_steps, policy, sigma, explore_seed, policy_state, stats,
-                                                         trace, on_done, days, terminal_obs, episode_stats, reset_outputs)
-        if g.restart:
-            g.restart.contents.h_carry = None
-        self._set_trace(p, trace, n_steps)
-        self._b.cho = None
-        self._b.flags = self._flags0
-        clock, self._clock = self._clock, None
-        ep0 = self.episode.clone() if (on_done == "restart" and self._hist is not None) else None
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.t1d_collect_mlp(self._ctx, C.byref(self._b), C.byref(p), C.byref(g), n_steps,
-                                               self.minutes_per_step, self.n_sub, self._stream()))
-        if clock is not None and on_done != "restart":         # restarted envs no longer share the clock
-            self._clock = clock + n_steps * self.minutes_per_step
+        policy_state, p, g, keep = self._collect_structs("collect_mlp", n_steps, policy, policy_state, stats, trace, on_done, days,
+                                                         terminal_obs, episode_stats, reset_outputs, draw=(sigma, explore_seed))
+        self._rollout(self._L.t1d_collect_mlp, (p, g), n_steps, trace, restarts=on_done == "restart")
         self._keep = keep
-        self._hist_after_rollout()
-        if ep0 is not None:                                     # CGM_hist of an env whose last step ended its episode = [sample #0]
-            self._hist_restart((self.episode != ep0) & (self.t == 0))
         return policy_state
 
-    def _collect_structs(self, who, n_steps, policy, sigma, explore_seed, policy_state, stats, trace, on_done, days,
-                         terminal_obs, episode_stats, reset_outputs):
-        """the t1d_mlp and t1d_collect of collect_mlp / collect_mlp_dopri5, checked; the five t1d_mlp trace columns are left to
-        _set_trace.  -> (policy_state, t1d_mlp, t1d_collect, what must stay alive until the launch has run)"""
-        if n_steps < 1:
-            raise ValueError("n_steps must be at least 1")
+    def _collect_structs(self, who, n_steps, policy, policy_state, stats, trace, on_done, days, terminal_obs, episode_stats,
+                         reset_outputs, draw, keep_h_carry=False):
+        """The t1d_mlp and t1d_collect of the four collectors, checked.  draw = (sigma, explore_seed): `policy` is the network
+        that acts, the call may record "eps", and the t1d_mlp's own five trace columns are left to _set_trace.  draw = None
+        (collect_pid / collect_bb): a controller acts, `policy` only forms the features, `stats` belong to the controller's
+        struct, there is no "eps" column and "action" is set here.  keep_h_carry: the exact mode, where a restart zeroes it.
+        -> (policy_state, t1d_mlp, t1d_collect, what must stay alive until the launch has run)"""
+        n_steps = self._n_steps(n_steps)
         if on_done not in ("continue", "restart"):
             raise ValueError("on_done must be 'continue' or 'restart'")
+        if draw is None:
+            if policy is None:
+                raise ValueError("%s: features= takes the MLPController whose history and scales form the features" % who)
+            if trace and trace.get("eps") is not None:
+                raise ValueError("%s: a controller draws no exploration noise, there is no 'eps' column" % who)
         if policy_state is None:
             policy_state = self.new_policy_state(policy)
-        p, params = self._mlp_struct(who, policy, policy_state, stats)
-        npol = int(policy.n_policies)
         g = _lib.Collect()
-        g.explore_seed = (self.seed ^ 0x5851F42D4C957F2D if explore_seed is None else int(explore_seed)) & 0xFFFFFFFFFFFFFFFF
-        if sigma is not None:
-            sigma = torch.as_tensor(sigma, dtype=self.dtype).detach().to(self.device).expand(npol).contiguous()
-            g.sigma = sigma.data_ptr()
+        params = sigma = None
+        if draw is None:
+            p = self._feature_struct(policy, policy_state)
+        else:
+            p, params = self._mlp_struct(who, policy, policy_state, stats)
+            sigma, explore_seed = draw
+            g.explore_seed = (self.seed ^ 0x5851F42D4C957F2D if explore_seed is None else int(explore_seed)) & 0xFFFFFFFFFFFFFFFF
+            if sigma is not None:
+                sigma = torch.as_tensor(sigma, dtype=self.dtype).detach().to(self.device).expand(int(policy.n_policies)).contiguous()
+                g.sigma = sigma.data_ptr()
         g.on_done, g.reserved = (_lib.T1D_COLLECT_RESTART if on_done == "restart" else _lib.T1D_COLLECT_CONTINUE), 0
         r = None
         if on_done == "restart":
             if self.noise == "host" or self.normals is not None:
                 raise _lib.T1DError("%s(on_done='restart') draws every episode on the device: not available with host normals" % who)
             r = self._restart_struct(int(days), terminal_obs, episode_stats or {}, reset_outputs, who)
+            if not keep_h_carry:
+                r.h_carry = None
             g.restart = C.pointer(r)
             p.start_minute = r.start_minute          # _restart_struct creates the array for an env that had none
             self._b.x0_override = None
-        F = 2 * int(policy.history) + 3
-        for k, f, dt, shape in (("reward", "reward_trace", self.dtype, (self.n,)), ("done", "done_trace", torch.uint8, (self.n,)),
-                                ("eps", "eps_trace", self.dtype, (self.n,)), ("features", "feat_trace", self.dtype, (F, self.n))):
-            t = trace.get(k) if trace else None
-            if t is not None:
-                if t.dtype != dt or tuple(t.shape[1:]) != shape or t.shape[0] < int(trace.get("row", 0)) + n_steps or not t.is_contiguous():
-                    raise ValueError("trace['%s'] must be contiguous [rows >= row + n_steps, %s] of %s" % (k, ", ".join(map(str, shape)), dt))
-                setattr(g, f, t.data_ptr())
-        return policy_state, p, g, (params, policy_state, sigma, r, terminal_obs, episode_stats, trace)
-
-    def _collect_ctrl(self, who, fn, ctl, n_steps, features, policy_state, stats, trace, on_done, days, terminal_obs,
-                      episode_stats, reset_outputs, keep):
-        """collect_pid / collect_bb: fn (t1d_collect_pid, t1d_collect_bb) with the controller's struct ctl -> policy_state"""
-        self._no_dopri5_rollout()
-        n_steps = int(n_steps)
-        if n_steps < 1:
-            raise ValueError("n_steps must be at least 1")
-        if on_done not in ("continue", "restart"):
-            raise ValueError("on_done must be 'continue' or 'restart'")
-        if features is None:
-            raise ValueError("%s: features= takes the MLPController whose history and scales form the features" % who)
-        if trace and trace.get("eps") is not None:
-            raise ValueError("%s: a controller draws no exploration noise, there is no 'eps' column" % who)
-        if policy_state is None:
-            policy_state = self.new_policy_state(features)
-        H = int(features.history)
-        for k, shape in (("cgm_hist", (H, self.n)), ("ins_hist", (H, self.n)), ("prev_meal", (self.n,))):
-            t = policy_state.get(k)
-            if t is None or tuple(t.shape) != shape or t.dtype != self.dtype or t.device != self.device or not t.is_contiguous():
-                raise ValueError("policy_state['%s'] must be a contiguous %s tensor of the env's dtype on its device" % (k, shape))
-        f = _lib.Mlp()                          # history, the feature scales, the windows and action_trace: nothing else is read
-        f.history = H
-        f.cgm_mean, f.cgm_scale, f.ins_scale, f.cho_scale = features.cgm_mean, features.cgm_scale, features.ins_scale, features.cho_scale
-        for k in ("cgm_hist", "ins_hist", "prev_meal"):
-            setattr(f, k, policy_state[k].data_ptr())
-        f.start_minute = self.start_minute.data_ptr() if self.start_minute is not None else None
-        stats = stats or {}
-        for k in ("sum_risk", "min_bg", "max_bg", "n_low", "n_high"):
-            setattr(ctl, k, stats[k].data_ptr() if k in stats else None)
-        g = _lib.Collect()
-        g.on_done, g.reserved = (_lib.T1D_COLLECT_RESTART if on_done == "restart" else _lib.T1D_COLLECT_CONTINUE), 0
-        r = None
-        if on_done == "restart":
-            if self.noise == "host" or self.normals is not None:
-                raise _lib.T1DError("%s(on_done='restart') draws every episode on the device: not available with host normals" % who)
-            r = self._restart_struct(int(days), terminal_obs, episode_stats or {}, reset_outputs, who)
-            r.h_carry = None
-            g.restart = C.pointer(r)
-            f.start_minute = r.start_minute          # _restart_struct creates the array for an env that had none
-            self._b.x0_override = None
         row = int(trace.get("row", 0)) if trace else 0
-        F = 2 * H + 3
+        F = 2 * int(policy.history) + 3
         for k, tgt, fld, dt, shape in (("reward", g, "reward_trace", self.dtype, (self.n,)), ("done", g, "done_trace", torch.uint8, (self.n,)),
-                                       ("features", g, "feat_trace", self.dtype, (F, self.n)), ("action", f, "action_trace", self.dtype, (self.n,))):
-            t = trace.get(k) if trace else None
+                                       ("eps", g, "eps_trace", self.dtype, (self.n,)), ("features", g, "feat_trace", self.dtype, (F, self.n)),
+                                       ("action", p, "action_trace", self.dtype, (self.n,))):
+            t = trace.get(k) if trace and (k != "action" or draw is None) else None
             if t is not None:
                 if t.dtype != dt or tuple(t.shape[1:]) != shape or t.shape[0] < row + n_steps or not t.is_contiguous():
                     raise ValueError("trace['%s'] must be contiguous [rows >= row + n_steps, %s] of %s" % (k, ", ".join(map(str, shape)), dt))
                 setattr(tgt, fld, t.data_ptr())
-        self._set_trace(ctl, trace, n_steps)          # bg, cgm, cho, insulin and the row every column of this call starts at
-        self._b.cho = None
-        self._b.flags = self._flags0
-        clock, self._clock = self._clock, None
-        ep0 = self.episode.clone() if (on_done == "restart" and self._hist is not None) else None
-        with torch.cuda.device(self.device):
-            _lib.check(fn(self._ctx, C.byref(self._b), C.byref(ctl), C.byref(f), C.byref(g), n_steps,
-                          self.minutes_per_step, self.n_sub, self._stream()))
-        if clock is not None and on_done != "restart":         # restarted envs no longer share the clock
-            self._clock = clock + n_steps * self.minutes_per_step
-        self._keep = (keep, policy_state, r, terminal_obs, episode_stats, stats, trace)
-        self._hist_after_rollout()
-        if ep0 is not None:                                     # CGM_hist of an env whose last step ended its episode = [sample #0]
-            self._hist_restart((self.episode != ep0) & (self.t == 0))
+        return policy_state, p, g, (params, policy_state, sigma, r, terminal_obs, episode_stats, stats, trace)
+
+    def _collect_ctrl(self, who, fn, ctl, ctl_state, n_steps, features, policy_state, stats, trace, on_done, days, terminal_obs,
+                      episode_stats, reset_outputs):
+        """collect_pid / collect_bb: fn (t1d_collect_pid, t1d_collect_bb) with the controller's struct ctl -> policy_state"""
+        policy_state, f, g, keep = self._collect_structs(who, n_steps, features, policy_state, stats, trace, on_done, days,
+                                                         terminal_obs, episode_stats, reset_outputs, draw=None)
+        self._rollout(fn, (ctl, f, g), n_steps, trace, restarts=on_done == "restart")
+        self._keep = keep + (ctl_state,)
         return policy_state
 
     def collect_pid(self, n_steps, P, I, D, target=140.0, features=None, pid_state=None, policy_state=None, stats=None, trace=None,
@@ -815,14 +781,10 @@ class BatchedT1DSimEnv:
         Dexcom, 32 steps, profiles/collect): at 64 Ki envs one launch is 2.2 - 3.3 times faster than that loop; at 1 Mi envs
         it wins by 20 % under the stock basal-bolus constants (0.27 % of the envs finish per step) and LOSES by 12 % where
         1 % finish per step, like collect_mlp.  -> (pid_state, policy_state)"""
-        if pid_state is None:
-            pid_state = {"integ": torch.zeros(self.n, dtype=self.dtype, device=self.device),
-                         "prev": torch.zeros(self.n, dtype=self.dtype, device=self.device)}
-        p = _lib.Pid()
-        p.P, p.I, p.D, p.target = float(P), float(I), float(D), float(target)
-        p.integ, p.prev = pid_state["integ"].data_ptr(), pid_state["prev"].data_ptr()
-        policy_state = self._collect_ctrl("collect_pid", self._L.t1d_collect_pid, p, n_steps, features, policy_state, stats, trace,
-                                          on_done, days, terminal_obs, episode_stats, reset_outputs, pid_state)
+        self._no_dopri5_rollout()
+        pid_state, p = self._pid_struct(P, I, D, target, pid_state, stats)
+        policy_state = self._collect_ctrl("collect_pid", self._L.t1d_collect_pid, p, pid_state, n_steps, features, policy_state, stats,
+                                          trace, on_done, days, terminal_obs, episode_stats, reset_outputs)
         return pid_state, policy_state
 
     def collect_bb(self, n_steps, target=140.0, features=None, bb_state=None, policy_state=None, stats=None, trace=None,
@@ -836,15 +798,10 @@ class BatchedT1DSimEnv:
             loss = value_loss(params, tr["features"][1:], pol, target=tr["action"][1:])
 
         -> (bb_state, policy_state)"""
-        if bb_state is None:
-            bb_state = self.bb_constants()
-            bb_state["prev_meal"] = torch.zeros(self.n, dtype=self.dtype, device=self.device)
-        p = _lib.Bb()
-        p.target = float(target)
-        for k in ("basal", "cr", "cf", "prev_meal"):
-            setattr(p, k, bb_state[k].data_ptr())
-        policy_state = self._collect_ctrl("collect_bb", self._L.t1d_collect_bb, p, n_steps, features, policy_state, stats, trace,
-                                          on_done, days, terminal_obs, episode_stats, reset_outputs, bb_state)
+        self._no_dopri5_rollout()
+        bb_state, p = self._bb_struct(target, bb_state, stats)
+        policy_state = self._collect_ctrl("collect_bb", self._L.t1d_collect_bb, p, bb_state, n_steps, features, policy_state, stats,
+                                          trace, on_done, days, terminal_obs, episode_stats, reset_outputs)
         return bb_state, policy_state
 
     def collect_mlp_dopri5(self, n_steps, policy, sigma=None, explore_seed=None, policy_state=None, stats=None, trace=None,
@@ -859,30 +816,26 @@ class BatchedT1DSimEnv:
         whose solver does not give up); with sigma=None and on_done="continue" it is rollout_mlp_dopri5's.  Measurements:
         profiles/collect (exact_collect_bench.json)."""
         self._need_dopri5("collect_mlp_dopri5")
-        n_steps = int(n_steps)
-        policy_state, p, g, keep = self._collect_structs("collect_mlp_dopri5", n_steps, policy, sigma, explore_seed, policy_state,
-                                                         stats, trace, on_done, days, terminal_obs, episode_stats, reset_outputs)
-        ep0 = self.episode.clone() if (on_done == "restart" and self._hist is not None) else None
-        self._rollout_dopri5(self._L.t1d_collect_mlp_dopri5, p, n_steps, trace, max_minutes_per_launch, extra=(C.byref(g),))
-        if on_done == "restart":                                # restarted envs no longer share the clock
-            self._clock = None
+        policy_state, p, g, keep = self._collect_structs("collect_mlp_dopri5", n_steps, policy, policy_state, stats, trace, on_done,
+                                                         days, terminal_obs, episode_stats, reset_outputs, draw=(sigma, explore_seed),
+                                                         keep_h_carry=True)
+        self._rollout_dopri5(self._L.t1d_collect_mlp_dopri5, p, n_steps, trace, max_minutes_per_launch, extra=(C.byref(g),),
+                             restarts=on_done == "restart")
         self._keep = keep
-        if ep0 is not None:                                     # CGM_hist of an env whose last step ended its episode = [sample #0]
-            self._hist_restart((self.episode != ep0) & (self.t == 0))
         return policy_state
 
-    def _rollout_dopri5(self, fn, p, n_steps, trace, max_minutes_per_launch, extra=()):
+    def _rollout_dopri5(self, fn, p, n_steps, trace, max_minutes_per_launch, extra=(), restarts=False):
         """the launches of one exact-mode roll-out: whole steps, at most max_minutes_per_launch simulated minutes each.
         State, controller state and h_carry carry over, so the cut changes no result; nfev is summed over the launches.
-        extra: the arguments between the controller's struct and h_carry (the collector's t1d_collect)."""
-        n_steps = int(n_steps)
-        if n_steps < 1:
-            raise ValueError("n_steps must be at least 1")
+        extra: the arguments between the controller's struct and h_carry (the collector's t1d_collect).  restarts: as in
+        _rollout."""
+        n_steps = self._n_steps(n_steps)
         per = max(1, int(max_minutes_per_launch) // self.minutes_per_step)
         self._set_trace(p, trace, n_steps)
         self._b.cho = None
         self._b.flags = self._flags0
         clock, self._clock = self._clock, None
+        ep0 = self.episode.clone() if (restarts and self._hist is not None) else None
         total = None if n_steps <= per else torch.zeros_like(self.nfev)
         with torch.cuda.device(self.device):
             done = 0
@@ -896,9 +849,11 @@ class BatchedT1DSimEnv:
                 done += k
         if total is not None:
             self.nfev.copy_(total)
-        if clock is not None:
+        if clock is not None and not restarts:         # restarted envs no longer share the clock
             self._clock = clock + n_steps * self.minutes_per_step
         self._hist_after_rollout()
+        if ep0 is not None:                            # CGM_hist of an env whose last step ended its episode = [sample #0]
+            self._hist_restart((self.episode != ep0) & (self.t == 0))
 
     def _need_dopri5(self, who):
         if self.integrator != "dopri5":
@@ -914,15 +869,7 @@ class BatchedT1DSimEnv:
         simulated minutes (whole steps) -- at 240 a wave costs 1.41 times its mean lane against 1.36 uncut, and a launch of
         1 Mi envs stays in the range of a second; the cut changes no result."""
         self._need_dopri5("rollout_pid_dopri5")
-        if pid_state is None:
-            pid_state = {"integ": torch.zeros(self.n, dtype=self.dtype, device=self.device),
-                         "prev": torch.zeros(self.n, dtype=self.dtype, device=self.device)}
-        p = _lib.Pid()
-        p.P, p.I, p.D, p.target = float(P), float(I), float(D), float(target)
-        p.integ, p.prev = pid_state["integ"].data_ptr(), pid_state["prev"].data_ptr()
-        stats = stats or {}
-        for k in ("sum_risk", "min_bg", "max_bg", "n_low", "n_high"):
-            setattr(p, k, stats[k].data_ptr() if k in stats else None)
+        pid_state, p = self._pid_struct(P, I, D, target, pid_state, stats)
         self._rollout_dopri5(self._L.t1d_rollout_pid_dopri5, p, n_steps, trace, max_minutes_per_launch)
         return pid_state
 
@@ -931,16 +878,7 @@ class BatchedT1DSimEnv:
         reference's own regression run.  Arguments and return value as rollout_bb; h_carry, nfev and
         max_minutes_per_launch as in rollout_pid_dopri5."""
         self._need_dopri5("rollout_bb_dopri5")
-        if bb_state is None:
-            bb_state = self.bb_constants()
-            bb_state["prev_meal"] = torch.zeros(self.n, dtype=self.dtype, device=self.device)
-        p = _lib.Bb()
-        p.target = float(target)
-        for k in ("basal", "cr", "cf", "prev_meal"):
-            setattr(p, k, bb_state[k].data_ptr())
-        stats = stats or {}
-        for k in ("sum_risk", "min_bg", "max_bg", "n_low", "n_high"):
-            setattr(p, k, stats[k].data_ptr() if k in stats else None)
+        bb_state, p = self._bb_struct(target, bb_state, stats)
         self._rollout_dopri5(self._L.t1d_rollout_bb_dopri5, p, n_steps, trace, max_minutes_per_launch)
         return bb_state
 

@@ -138,6 +138,25 @@ def plain_env(**kw):
     return BatchedT1DSimEnv(**kw)
 
 
+CLOSED_LOOP = {"rollout_pid": (1, 0.0, 0.0, 0.0), "rollout_bb": (1,), "rollout_mlp": (1, None), "collect_mlp": (1, None),
+               "collect_pid": (1, 0.0, 0.0, 0.0), "collect_bb": (1,)}         # the fixed-step methods with their shortest calls
+CLOSED_LOOP_EXACT = ("rollout_pid", "rollout_bb", "rollout_mlp", "collect_mlp")  # ... and those with a *_dopri5 sibling
+
+
+def mode_refusal(method, integrator):
+    """The T1DError text with which `method` turns away an env of the other mode.  The env is a bare object that has its
+    integrator and nothing else, so a method that reads anything before it refuses ends in an AttributeError instead.
+    Needs no device."""
+    import pytest
+    from simglucose_amd import _lib
+    from simglucose_amd.batch_env import BatchedT1DSimEnv
+    e = object.__new__(BatchedT1DSimEnv)
+    e.integrator = integrator
+    with pytest.raises(_lib.T1DError) as err:
+        getattr(e, method)(*CLOSED_LOOP[method[:-len("_dopri5")] if method.endswith("_dopri5") else method])
+    return str(err.value)
+
+
 def meal_day_env(n, dtype, env_offset=0, seed=5, meals=True, start=None, **kw):
     """all 30 patients, a random-meal day from START (or from `start`: int32 [n] minute of day per env), reset"""
     torch = gpu_torch()

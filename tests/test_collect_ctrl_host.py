@@ -5,7 +5,7 @@ import inspect
 import os
 import re
 
-from support import header_fields
+from support import CLOSED_LOOP, CLOSED_LOOP_EXACT, header_fields, mode_refusal
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("t1d_collect_pid", "t1d_collect_bb")
@@ -146,5 +146,17 @@ def test_env_has_the_methods():
         assert d["target"] == 140.0 and d["on_done"] == "continue"
         for k in tail[1:]:
             assert d[k] == mlp.parameters[k].default, k
-    # an exact-mode env is turned away as by the roll-outs
-    assert "_no_dopri5_rollout" in inspect.getsource(BatchedT1DSimEnv._collect_ctrl)
+
+
+def test_every_closed_loop_method_turns_the_other_mode_away_first():
+    """an exact-mode env is turned away by the six fixed-step methods, which name the exact-mode sibling or say that there is
+    none, and a fixed-step env by the four exact-mode methods, which name theirs -- before anything else of the env is read"""
+    for method in CLOSED_LOOP:
+        msg = mode_refusal(method, "dopri5")
+        if method in CLOSED_LOOP_EXACT:
+            assert method + "_dopri5" in msg, method
+        else:
+            assert "collect_pid and collect_bb have no exact-mode form" in msg, method
+    for method in CLOSED_LOOP_EXACT:
+        msg = mode_refusal(method + "_dopri5", None)
+        assert msg.startswith(method + "_dopri5 needs") and msg.endswith("(the fixed-step envs take %s)" % method), method

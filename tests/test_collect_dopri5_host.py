@@ -4,6 +4,8 @@ import ctypes as C
 import os
 import re
 
+from support import mode_refusal
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "t1d_collect_mlp_dopri5"
 
@@ -44,5 +46,5 @@ def test_env_has_the_method():
     # collect_mlp keeps its signature, still refuses exact-mode envs, and now says where to go
     old = inspect.signature(BatchedT1DSimEnv.collect_mlp)
     assert list(old.parameters)[1:] == list(sig.parameters)[1:-1]
-    assert "collect_mlp_dopri5" in inspect.getsource(BatchedT1DSimEnv._no_dopri5_rollout)
-    assert "_no_dopri5_rollout" in inspect.getsource(BatchedT1DSimEnv.collect_mlp)
+    assert "collect_mlp_dopri5" in mode_refusal("collect_mlp", "dopri5")
+    assert "(the fixed-step envs take collect_mlp)" in mode_refusal("collect_mlp_dopri5", None)

@@ -4,6 +4,8 @@ import ctypes as C
 import os
 import re
 
+from support import mode_refusal
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("t1d_rollout_mlp_dopri5", "t1d_mlp_action")
 
@@ -39,4 +41,5 @@ def test_env_has_both_methods():
     assert sig.parameters["max_minutes_per_launch"].default == 240
     assert list(inspect.signature(BatchedT1DSimEnv.policy_action).parameters)[1:] == ["policy", "policy_state"]
     # rollout_mlp still refuses exact-mode envs, and now says where to go
-    assert "rollout_mlp_dopri5" in inspect.getsource(BatchedT1DSimEnv._no_dopri5_rollout)
+    assert "rollout_mlp_dopri5" in mode_refusal("rollout_mlp", "dopri5")
+    assert "(the fixed-step envs take rollout_mlp)" in mode_refusal("rollout_mlp_dopri5", None)
