@@ -140,6 +140,21 @@ def _stale():
                                                for s in SOURCES)
 
 
+# The code-generation flags of the library: whatever compiles csrc/t1d_abi.hip to look at "the library's build" (the ISA
+# tools, the register and scratch figures the tests assert) takes them from here.
+# -fno-slp-vectorize: in the fp32 kernels the SLP vectoriser pairs a fifth of the arithmetic into v_pk_*_f32
+# and pays more than it gains in the register moves that line the operands up (1 Mi envs fp32: 45.5 -> 42.4 us)
+HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fno-slp-vectorize", "-std=c++17"]
+
+
+def build_command(out, verbose=False):
+    """the command line that compiles the library into `out`"""
+    cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + HIPCC_FLAGS + ["-shared", "-fPIC", "-o", out, SOURCES[0]]
+    if verbose:
+        cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
+    return cmd
+
+
 def build(force=False, verbose=False):
     """Compile libt1d_hip.so for gfx950 in-tree with hipcc (cross-compiles without a GPU).  Safe when several
     processes (one per GPU) find the library stale at once: one builds under a file lock into a temporary
@@ -151,15 +166,9 @@ def build(force=False, verbose=False):
         fcntl.flock(lock, fcntl.LOCK_EX)
         try:
             if force or _stale():
-                hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
                 tmp = "%s.tmp.%d" % (LIB_PATH, os.getpid())
-                # -fno-slp-vectorize: in the fp32 kernels the SLP vectoriser pairs a fifth of the arithmetic into v_pk_*_f32
-                # and pays more than it gains in the register moves that line the operands up (1 Mi envs fp32: 45.5 -> 42.4 us)
-                cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-fno-slp-vectorize", "-std=c++17", "-shared", "-fPIC", "-o", tmp, SOURCES[0]]
-                if verbose:
-                    cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
                 try:
-                    subprocess.check_call(cmd)
+                    subprocess.check_call(build_command(tmp, verbose))
                     os.replace(tmp, LIB_PATH)
                 finally:
                     if os.path.exists(tmp):

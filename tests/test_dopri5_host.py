@@ -59,8 +59,9 @@ def test_integrator_argument_is_checked_before_the_gpu():
 def test_dopri5_kernel_needs_no_scratch():
     """One wave per SIMD with the unified VGPR + AGPR file: the seven stage vectors, y, y1 and the stage input stay in
     registers (a spill would sit inside the stage loop)."""
-    out = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-fno-slp-vectorize", "-std=c++17",
-                          "--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage", "-o", os.devnull,
+    from simglucose_amd._lib import HIPCC_FLAGS
+    out = subprocess.run(["/opt/rocm/bin/hipcc"] + HIPCC_FLAGS +
+                         ["--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage", "-o", os.devnull,
                           os.path.join(ROOT, "simglucose_amd", "csrc", "t1d_abi.hip")],
                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900).stdout.decode()
     blocks = out.split("Function Name: ")

@@ -87,8 +87,9 @@ def test_wave_cost_model_on_a_hand_made_array():
 def test_rollout_kernel_needs_no_scratch_and_the_step_kernel_still_none():
     """Both exact-mode kernels keep the stage vectors in the unified VGPR + AGPR file: the roll-out's per-minute words wait
     in LDS between the minute boundaries instead of being spilled inside the step-attempt loop."""
-    out = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-fno-slp-vectorize", "-std=c++17",
-                          "--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage", "-o", os.devnull,
+    from simglucose_amd._lib import HIPCC_FLAGS
+    out = subprocess.run(["/opt/rocm/bin/hipcc"] + HIPCC_FLAGS +
+                         ["--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage", "-o", os.devnull,
                           os.path.join(ROOT, "simglucose_amd", "csrc", "t1d_abi.hip")],
                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900).stdout.decode()
     blocks = out.split("Function Name: ")

@@ -12,12 +12,8 @@ are alternated `reps` times.  One JSON line per batch size; --out writes them to
     rocprofv3 --kernel-trace --stats -d <dir> -- python tools/autoreset_bench.py --n 1048576 --legs device --reps 1
 """
 import argparse
-import json
-import os
-import sys
-import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import benchlib
 
 LEGS = {"none": False, "host": True, "device": "device", "lanes": "device"}
 
@@ -33,21 +29,19 @@ def run_leg(leg, n, steps, warmup, seed):
     for _ in range(warmup):
         env.step(a)
     ep0 = env.env.episode.long().sum()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        env.step(a)
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
+
+    def go():
+        for _ in range(steps):
+            env.step(a)
+    ms = benchlib.timed_pass(go, "host")[1]
     restarted = int(env.env.episode.long().sum() - ep0)
-    status = env.env.sync(raise_on_status=False)
-    env.env.close()
+    status = benchlib.close_leg(env.env)
     del env
     torch.cuda.empty_cache()
-    return {"ms_per_step": 1e3 * dt / steps, "restarts_per_env_step": restarted / (n * steps), "status": status}
+    return {"ms_per_step": ms / steps, "restarts_per_env_step": restarted / (n * steps), "status": status}
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="+", default=[1 << 20, 1 << 16])
     ap.add_argument("--steps", type=int, default=200)
@@ -56,28 +50,19 @@ def main():
     ap.add_argument("--legs", nargs="+", default=["none", "host", "device", "lanes"], choices=sorted(LEGS))
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    benchlib.require_gpu("autoreset_bench.py")
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("autoreset_bench.py measures on the GPU: none found")
     results = []
     for n in args.n:
-        runs = {leg: [] for leg in args.legs}
-        for _ in range(args.reps):
-            for leg in args.legs:
-                runs[leg].append(run_leg(leg, n, args.steps, args.warmup, args.seed))
+        runs = benchlib.alternate(args.legs, args.reps, lambda leg: run_leg(leg, n, args.steps, args.warmup, args.seed))
         res = {"n_envs": n, "steps": args.steps, "warmup": args.warmup, "sensor": "Dexcom", "dtype": "float64",
                "basal_U_per_min": 0.05, "device": torch.cuda.get_device_name(0), "legs": {}}
         for leg, rr in runs.items():
-            ms = sorted(r["ms_per_step"] for r in rr)
-            res["legs"][leg] = {"ms_per_step_median": ms[len(ms) // 2], "ms_per_step_runs": [r["ms_per_step"] for r in rr],
+            res["legs"][leg] = {**benchlib.summarise([r["ms_per_step"] for r in rr], "ms_per_step"),
                                 "restarts_per_env_step": rr[-1]["restarts_per_env_step"], "status": max(r["status"] for r in rr)}
-        print(json.dumps(res), flush=True)
-        results.append(res)
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(results, f, indent=1)
-            f.write("\n")
+        benchlib.emit(results, res)
+    benchlib.write(results, args.out)
 
 
 if __name__ == "__main__":

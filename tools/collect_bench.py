@@ -10,53 +10,38 @@ and four legs:
   plain    collect_mlp(K, on_done="continue", sigma=None), no new trace
   rollout  rollout_mlp(K): what `plain` must not be slower than
 Every leg: fresh env, `warm_steps` steps so that the batch is mixed, one warm-up pass, then K steps between two device
-synchronisations (host clock), `reps` times, legs alternated; the median is reported.  `finish_rate` is the share of
-env-steps of the timed window that ended an episode.  One JSON line per (policy, batch size); --out writes them as a list.
+synchronisations (host clock), `reps` times, legs alternated; the median is reported.  The timed window holds what a caller
+pays per batch of K steps, the allocation of the trace included.  `finish_rate` is the share of env-steps of the timed window
+that ended an episode.  One JSON line per (policy, batch size); --out writes them as a list.
 
     python tools/collect_bench.py --out profiles/collect/collect_bench.json
+
+--exact: the same legs in the exact mode (DOPRI5) on an integrator="dopri5" env: collect_mlp_dopri5 (one launch per 240
+simulated minutes) and rollout_mlp_dopri5, K steps between two events on the stream; minimum and maximum are reported beside
+the median, and `plain_minus_rollout_ms`.  Every repetition builds the same env from the same seed, so the finish rate is the
+same in each (`finish_rate_runs` shows it).
+
+    python tools/collect_bench.py --exact --out profiles/collect/exact_collect_bench.json
 """
 import argparse
-import json
-import math
-import os
-import sys
-import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import benchlib
+from benchlib import DAYS
 
-DAYS = 2
 COLUMNS = ("bg", "cgm", "cho", "insulin", "action", "reward", "done", "eps", "features")
 
 
 def make_policy(kind, history=4, basal=0.05):
-    import torch
-    from simglucose_amd.controller.mlp_ctrller import MLPController
-    F = 2 * history + 3
     if kind == "hypo":
-        return MLPController([(torch.zeros(1, F, dtype=torch.float64), torch.zeros(1, dtype=torch.float64))], history=history,
-                             output="identity", out_scale=1.0, out_bias=basal)
-    g = torch.Generator().manual_seed(0)
-    layers, n_in = [], F
-    for w in (16, 16, 1):
-        layers.append((torch.randn(1, w, n_in, generator=g, dtype=torch.float64) / math.sqrt(n_in),
-                       0.1 * torch.randn(1, w, generator=g, dtype=torch.float64)))
-        n_in = w
-    return MLPController(layers, history=history, hidden="tanh", output="logistic", out_scale=0.06)
+        return benchlib.constant_policy(history, basal)
+    return benchlib.random_policy(history, (16, 16, 1), hidden="tanh", output="logistic", out_scale=0.06)
 
 
-def make_env(n, seed):
+def run_leg(leg, n, pol, K, warm_steps, sigma, seed, exact):
     import torch
-    from simglucose_amd.batch_env import BatchedT1DSimEnv
-    e = BatchedT1DSimEnv(patient=["child#001", "adult#001"] * (n // 2), sensor="Dexcom", dtype=torch.float64, seed=seed,
-                         random_init_bg=True)
-    e.restart_done(mask=torch.ones(n, dtype=torch.uint8, device=e.device), days=DAYS, reset_outputs=True)
-    return e
-
-
-def run_leg(leg, n, pol, K, warm_steps, sigma, seed):
-    import torch
-    e = make_env(n, seed)
-    state = e.collect_mlp(warm_steps, pol, on_done="restart", days=DAYS) if warm_steps else e.new_policy_state(pol)
+    e = benchlib.mixed_env(n, seed, integrator="dopri5" if exact else None)
+    collect, rollout = (e.collect_mlp_dopri5, e.rollout_mlp_dopri5) if exact else (e.collect_mlp, e.rollout_mlp)
+    state = collect(warm_steps, pol, on_done="restart", days=DAYS) if warm_steps else e.new_policy_state(pol)
     zero = torch.zeros((), dtype=e.dtype, device=e.device)
     finished = torch.zeros((), dtype=torch.int64, device=e.device)
 
@@ -64,13 +49,13 @@ def run_leg(leg, n, pol, K, warm_steps, sigma, seed):
         nonlocal finished
         if leg == "collect":
             tr = e.new_trace(K, columns=COLUMNS, history=pol.history)
-            e.collect_mlp(K, pol, sigma=sigma, policy_state=state, trace=tr, on_done="restart", days=DAYS)
+            collect(K, pol, sigma=sigma, policy_state=state, trace=tr, on_done="restart", days=DAYS)
             finished = tr["done"][1:].sum()
         elif leg == "loop":
             tr = e.new_trace(K, columns=COLUMNS[:5])
             rew, don = [], []
             for _ in range(K):
-                e.rollout_mlp(1, pol, policy_state=state, trace=tr)
+                rollout(1, pol, policy_state=state, trace=tr)
                 done = e.done.bool()
                 rew.append(e.reward.clone()); don.append(e.done.clone())
                 e.restart_done(days=DAYS)
@@ -80,24 +65,18 @@ def run_leg(leg, n, pol, K, warm_steps, sigma, seed):
             tr["reward"], tr["done"] = torch.stack(rew), torch.stack(don)
             finished = tr["done"].sum()
         elif leg == "plain":
-            e.collect_mlp(K, pol, policy_state=state)
+            collect(K, pol, policy_state=state)
         else:
-            e.rollout_mlp(K, pol, policy_state=state)
-    go()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    go()
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    status = e.sync(raise_on_status=False)
+            rollout(K, pol, policy_state=state)
+    ms = benchlib.timed_leg(go, go, "events" if exact else "host")
+    status = benchlib.close_leg(e)
     rate = float(finished) / (K * n)
-    e.close()
-    del e
+    del e, collect, rollout                      # the bound methods hold the env too
     torch.cuda.empty_cache()
-    return {"ms": 1e3 * dt, "status": status, "finish_rate": rate}
+    return {"ms": ms, "status": status, "finish_rate": rate}
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="+", default=[1 << 16, 1 << 20])
     ap.add_argument("--policies", nargs="+", default=["net", "hypo"], choices=["net", "hypo"])
@@ -109,39 +88,38 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--label", default=None)
+    ap.add_argument("--exact", action="store_true", help="the four legs in the exact mode (integrator='dopri5'), timed with events")
     ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    benchlib.require_gpu("collect_bench.py")
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("collect_bench.py measures on the GPU: none found")
     results = []
     for kind in args.policies:
         pol = make_policy(kind, basal=args.hypo_basal)
         # the constant policy stays constant: noise on 0.05 U/min would be another workload
         sigma = None if kind == "hypo" or args.sigma <= 0 else args.sigma
         for n in args.n:
-            runs = {leg: [] for leg in args.legs}
-            for _ in range(args.reps):
-                for leg in args.legs:
-                    runs[leg].append(run_leg(leg, n, pol, args.steps, args.warm_steps, sigma, args.seed))
+            runs = benchlib.alternate(args.legs, args.reps,
+                                      lambda leg: run_leg(leg, n, pol, args.steps, args.warm_steps, sigma, args.seed, args.exact))
             res = {"policy": kind, "hypo_basal": args.hypo_basal if kind == "hypo" else None, "n_envs": n, "dtype": "float64",
-                   "steps": args.steps, "warm_steps": args.warm_steps, "sigma": sigma, "sensor": "Dexcom", "label": args.label,
-                   "device": torch.cuda.get_device_name(0), "legs": {}}
+                   "steps": args.steps, "warm_steps": args.warm_steps, "sigma": sigma, "sensor": "Dexcom"}
+            if args.exact:
+                res["integrator"] = "dopri5"
+            res.update({"label": args.label, "device": torch.cuda.get_device_name(0), "legs": {}})
             for leg, rr in runs.items():
-                ms = sorted(r["ms"] for r in rr)
-                res["legs"][leg] = {"ms_median": ms[len(ms) // 2], "ms_runs": [r["ms"] for r in rr],
+                res["legs"][leg] = {**benchlib.summarise([r["ms"] for r in rr], "ms", spread=args.exact),
                                     "status": max(r["status"] for r in rr), "finish_rate": rr[-1]["finish_rate"]}
+                if args.exact:
+                    res["legs"][leg]["finish_rate_runs"] = [r["finish_rate"] for r in rr]
             med = {leg: v["ms_median"] for leg, v in res["legs"].items()}
             if "collect" in med and "loop" in med:
                 res["loop_over_collect"] = med["loop"] / med["collect"]
             if "plain" in med and "rollout" in med:
                 res["plain_over_rollout"] = med["plain"] / med["rollout"]
-            print(json.dumps(res), flush=True)
-            results.append(res)
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(results, f, indent=1)
-            f.write("\n")
+                if args.exact:
+                    res["plain_minus_rollout_ms"] = med["plain"] - med["rollout"]
+            benchlib.emit(results, res)
+    benchlib.write(results, args.out)
 
 
 if __name__ == "__main__":

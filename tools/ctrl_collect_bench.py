@@ -15,37 +15,16 @@ the timed window that ended an episode.  One JSON line per (workload, batch size
     python tools/ctrl_collect_bench.py --out profiles/collect/ctrl_collect_bench.json
 """
 import argparse
-import json
-import os
-import sys
-import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import benchlib
+from benchlib import DAYS
 
-DAYS = 2
 COLUMNS = ("bg", "cgm", "cho", "insulin", "action", "reward", "done", "features")
-
-
-def make_features(history=4):
-    """only history and the feature scales matter to collect_bb; policy_features (the loop) asks for a complete network"""
-    import torch
-    from simglucose_amd.controller.mlp_ctrller import MLPController
-    return MLPController([(torch.zeros(1, 2 * history + 3, dtype=torch.float64), torch.zeros(1, dtype=torch.float64))], history=history)
-
-
-def make_env(n, seed):
-    import torch
-    from simglucose_amd.batch_env import BatchedT1DSimEnv
-    e = BatchedT1DSimEnv(patient=["child#001", "adult#001"] * (n // 2), sensor="Dexcom", dtype=torch.float64, seed=seed,
-                         random_init_bg=True)
-    e.set_option("rollout_launches", 0)
-    e.restart_done(mask=torch.ones(n, dtype=torch.uint8, device=e.device), days=DAYS, reset_outputs=True)
-    return e
 
 
 def run_leg(leg, workload, n, pol, K, warm_steps, hot_basal, seed):
     import torch
-    e = make_env(n, seed)
+    e = benchlib.mixed_env(n, seed, options=[("rollout_launches", 0)])
     bb = e.bb_constants()
     if workload == "hot":
         bb["basal"][n // 2:] = hot_basal
@@ -79,21 +58,15 @@ def run_leg(leg, workload, n, pol, K, warm_steps, hot_basal, seed):
                 bb["prev_meal"].copy_(torch.where(done, zero, bb["prev_meal"]))
             tr["reward"], tr["done"], tr["features"] = torch.stack(rew), torch.stack(don), torch.stack(feat)
             finished = tr["done"].sum()
-    go()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    go()
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    status = e.sync(raise_on_status=False)
+    ms = benchlib.timed_leg(go, go, "host")
+    status = benchlib.close_leg(e)
     rate = float(finished) / (K * n)
-    e.close()
     del e
     torch.cuda.empty_cache()
-    return {"ms": 1e3 * dt, "status": status, "finish_rate": rate}
+    return {"ms": ms, "status": status, "finish_rate": rate}
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="+", default=[1 << 16, 1 << 20])
     ap.add_argument("--workloads", nargs="+", default=["stock", "hot"], choices=["stock", "hot"])
@@ -105,34 +78,27 @@ def main():
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--label", default=None)
     ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    benchlib.require_gpu("ctrl_collect_bench.py")
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("ctrl_collect_bench.py measures on the GPU: none found")
-    pol = make_features()
+    # only history and the feature scales matter to collect_bb; policy_features (the loop) asks for a complete network
+    pol = benchlib.constant_policy(4, 0.0)
     results = []
     for workload in args.workloads:
         for n in args.n:
-            runs = {leg: [] for leg in args.legs}
-            for _ in range(args.reps):
-                for leg in args.legs:
-                    runs[leg].append(run_leg(leg, workload, n, pol, args.steps, args.warm_steps, args.hot_basal, args.seed))
+            runs = benchlib.alternate(args.legs, args.reps,
+                                      lambda leg: run_leg(leg, workload, n, pol, args.steps, args.warm_steps, args.hot_basal, args.seed))
             res = {"controller": "bb", "workload": workload, "hot_basal": args.hot_basal if workload == "hot" else None, "n_envs": n,
                    "dtype": "float64", "steps": args.steps, "warm_steps": args.warm_steps, "sensor": "Dexcom", "label": args.label,
                    "device": torch.cuda.get_device_name(0), "legs": {}}
             for leg, rr in runs.items():
-                ms = sorted(r["ms"] for r in rr)
-                res["legs"][leg] = {"ms_median": ms[len(ms) // 2], "ms_runs": [r["ms"] for r in rr],
+                res["legs"][leg] = {**benchlib.summarise([r["ms"] for r in rr], "ms"),
                                     "status": max(r["status"] for r in rr), "finish_rate": rr[-1]["finish_rate"]}
             med = {leg: v["ms_median"] for leg, v in res["legs"].items()}
             if "collect" in med and "loop" in med:
                 res["loop_over_collect"] = med["loop"] / med["collect"]
-            print(json.dumps(res), flush=True)
-            results.append(res)
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(results, f, indent=1)
-            f.write("\n")
+            benchlib.emit(results, res)
+    benchlib.write(results, args.out)
 
 
 if __name__ == "__main__":

@@ -29,7 +29,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from simglucose_amd.batch_env import BatchedT1DSimEnv  # noqa: E402
-from simglucose_amd import params, scenario_batch  # noqa: E402
+from simglucose_amd import _lib, params, scenario_batch  # noqa: E402
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 from dopri5_counts import wave_costs  # noqa: E402
 
@@ -204,10 +204,8 @@ def rollout_counts(n, launch_minutes=240):
 
 
 def resources(kernel="_ZN3t1d18dopri5_step_kernel"):
-    out = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-fno-slp-vectorize", "-std=c++17", "--cuda-device-only",
-                          "-c", "-Rpass-analysis=kernel-resource-usage", "-o", os.devnull,
-                          os.path.join(ROOT, "simglucose_amd", "csrc", "t1d_abi.hip")],
-                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT).stdout.decode()
+    out = subprocess.run(["/opt/rocm/bin/hipcc"] + _lib.HIPCC_FLAGS + ["--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage",
+                          "-o", os.devnull, _lib.SOURCES[0]], stdout=subprocess.PIPE, stderr=subprocess.STDOUT).stdout.decode()
     blk = [b for b in out.split("Function Name: ") if b.startswith(kernel)][0]
     get = lambda key: int(re.search(re.escape(key) + r": (\d+)", blk).group(1))
     return {"vgprs": get("VGPRs"), "agprs": get("AGPRs"), "scratch_bytes_per_lane": get("ScratchSize [bytes/lane]"),

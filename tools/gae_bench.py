@@ -11,11 +11,8 @@ per (dtype, batch size); --out writes them as a list.
     python tools/gae_bench.py --out profiles/policy/gae_bench.json
 """
 import argparse
-import json
-import os
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import benchlib
 
 
 def torch_loop(r, d, v, v_last, gamma, lam):
@@ -35,21 +32,11 @@ def torch_loop(r, d, v, v_last, gamma, lam):
 
 
 def timed(fn, reps):
-    import torch
-    fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        out = fn()
-        b.record()
-        torch.cuda.synchronize()
-        ms.append(a.elapsed_time(b))
-    return out, sorted(ms)[len(ms) // 2], ms
+    out, ms, _ = benchlib.event_timed(fn, reps)
+    return out, benchlib.median(ms), ms
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="+", default=[1 << 16, 1 << 20])
     ap.add_argument("--rows", type=int, default=32)
@@ -57,10 +44,9 @@ def main():
     ap.add_argument("--done-rate", type=float, default=0.015)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    benchlib.require_gpu("gae_bench.py")
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("gae_bench.py measures on the GPU: none found")
     from simglucose_amd.controller import gae
     dev = torch.device("cuda:0")
     K, gamma, lam = args.rows, 0.99, 0.95
@@ -85,13 +71,9 @@ def main():
                    "max_rel_diff_adv": float((adv - adv_t).abs().max() / adv_t.abs().max()),
                    "max_rel_diff_ret": float((ret - ret_t).abs().max() / ret_t.abs().max()),
                    "device_ms_all": all_dev, "device_moments_ms_all": all_mom, "torch_loop_ms_all": all_torch}
-            print(json.dumps(rec), flush=True)
-            results.append(rec)
+            benchlib.emit(results, rec)
             del r, v, v_last, d, adv, ret, adv_t, ret_t
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(results, f, indent=1)
+    benchlib.write(results, args.out)
 
 
 if __name__ == "__main__":

@@ -6,11 +6,11 @@ usage: isa_kernel.py <mangled-name substring> [-o kernel.s]"""
 import collections, os, re, subprocess, sys, tempfile
 pat = sys.argv[1]
 out = sys.argv[sys.argv.index("-o") + 1] if "-o" in sys.argv else None
-root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from simglucose_amd._lib import HIPCC_FLAGS, SOURCES  # noqa: E402
 tmp = tempfile.mkdtemp()
 asm = os.path.join(tmp, "t1d.s")
-subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-fno-slp-vectorize", "-std=c++17", "-S", "--cuda-device-only",
-                       "-o", asm, os.path.join(root, "simglucose_amd", "csrc", "t1d_abi.hip")], stderr=subprocess.DEVNULL)
+subprocess.check_call(["/opt/rocm/bin/hipcc"] + HIPCC_FLAGS + ["-S", "--cuda-device-only", "-o", asm, SOURCES[0]], stderr=subprocess.DEVNULL)
 s = open(asm).read()
 isins = lambda l: l.startswith("\t") and not l.startswith("\t.") and not l.startswith("\t;")
 for m in re.finditer(r"^(_Z\w+):\s*; @", s, re.M):

@@ -3,10 +3,11 @@
 v_writelane) / LDS / wait counts.   usage: isa_loops.py <kernel name regex> [hipcc flags...]   (compiles with -save-temps)"""
 import collections, os, re, subprocess, sys, tempfile
 pat = sys.argv[1]
-root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from simglucose_amd._lib import HIPCC_FLAGS, SOURCES  # noqa: E402
 tmp = tempfile.mkdtemp()
-subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-fno-slp-vectorize", "-std=c++17", "-shared", "-fPIC", "-save-temps"] + sys.argv[2:] +
-                      ["-o", os.path.join(tmp, "lib.so"), os.path.join(root, "simglucose_amd", "csrc", "t1d_abi.hip")], cwd=tmp, stderr=subprocess.DEVNULL)
+subprocess.check_call(["/opt/rocm/bin/hipcc"] + HIPCC_FLAGS + ["-shared", "-fPIC", "-save-temps"] + sys.argv[2:] +
+                      ["-o", os.path.join(tmp, "lib.so"), SOURCES[0]], cwd=tmp, stderr=subprocess.DEVNULL)
 s = open(os.path.join(tmp, "t1d_abi-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
 for m in re.finditer(r"^(_Z\w+):\s*; @", s, re.M):
     name = m.group(1)

@@ -17,27 +17,10 @@ and `nfev_mean`, the RHS evaluations per env over the timed steps, for the two r
     python tools/policy_bench.py --exact --out profiles/policy/exact_bench.json
 """
 import argparse
-import json
-import math
-import os
-import sys
-import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import benchlib
 
 START = 360
-
-
-def make_policy(history, widths, seed=0):
-    import torch
-    from simglucose_amd.controller.mlp_ctrller import MLPController
-    g = torch.Generator().manual_seed(seed)
-    layers, n_in = [], 2 * history + 3
-    for w in widths:
-        layers.append((torch.randn(1, w, n_in, generator=g, dtype=torch.float64) / math.sqrt(n_in),
-                       0.1 * torch.randn(1, w, generator=g, dtype=torch.float64)))
-        n_in = w
-    return MLPController(layers, history=history, hidden="tanh", output="logistic", out_scale=0.06)
 
 
 def make_env(n, dtype, seed, exact=False):
@@ -80,26 +63,19 @@ def run_leg(leg, n, dtype, pol, steps, warmup, seed, exact=False):
                 e.step(pol.forward(feat), zero)
                 pol.shift(state["cgm_hist"], state["ins_hist"], e.cgm, e.insulin)
                 state["prev_meal"].copy_(e.meal)
-    go(warmup)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    go(steps)
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    status = e.sync(raise_on_status=False)
-    mean_bg = float(e.bg.mean())
-    out = {"us_per_step": 1e6 * dt / steps, "status": status, "mean_bg": mean_bg}
+    ms = benchlib.timed_leg(lambda: go(warmup), lambda: go(steps), "host")
+    out = {"us_per_step": 1e3 * ms / steps, "mean_bg": float(e.bg.mean())}
     if exact:
-        out["ms"] = 1e3 * dt
+        out["ms"] = ms
         if leg != "host":                        # a roll-out leaves the RHS evaluations of the whole call in nfev
             out["nfev_mean"] = float(e.nfev.double().mean())
-    e.close()
+    out["status"] = benchlib.close_leg(e)
     del e
     torch.cuda.empty_cache()
     return out
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="+", default=[1 << 16, 1 << 20])
     ap.add_argument("--dtypes", nargs="+", default=["float64", "float32"])
@@ -113,31 +89,25 @@ def main():
     ap.add_argument("--label", default=None, help="free text kept in the output (e.g. which build was measured)")
     ap.add_argument("--exact", action="store_true", help="the three legs in the exact mode (integrator='dopri5', fp64)")
     ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.exact:
         args.dtypes = ["float64"]
+    benchlib.require_gpu("policy_bench.py")
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("policy_bench.py measures on the GPU: none found")
-    pol = make_policy(args.history, args.widths)
+    pol = benchlib.random_policy(args.history, args.widths, hidden="tanh", output="logistic", out_scale=0.06)
     results = []
     for name in args.dtypes:
         dtype = getattr(torch, name)
         for n in args.n:
-            runs = {leg: [] for leg in args.legs}
-            for _ in range(args.reps):
-                for leg in args.legs:
-                    runs[leg].append(run_leg(leg, n, dtype, pol, args.steps, args.warmup, args.seed, args.exact))
+            runs = benchlib.alternate(args.legs, args.reps,
+                                      lambda leg: run_leg(leg, n, dtype, pol, args.steps, args.warmup, args.seed, args.exact))
             res = {"n_envs": n, "dtype": name, "steps": args.steps, "warmup": args.warmup, "sensor": "Dexcom", "history": args.history,
                    "widths": args.widths, "label": args.label, "integrator": "dopri5" if args.exact else "fixed-step", "device": torch.cuda.get_device_name(0), "legs": {}}
             for leg, rr in runs.items():
-                us = sorted(r["us_per_step"] for r in rr)
-                res["legs"][leg] = {"us_per_step_median": us[len(us) // 2], "us_per_step_runs": [r["us_per_step"] for r in rr],
+                res["legs"][leg] = {**benchlib.summarise([r["us_per_step"] for r in rr], "us_per_step"),
                                     "status": max(r["status"] for r in rr), "mean_bg": rr[-1]["mean_bg"]}
                 if args.exact:
-                    ms = sorted(r["ms"] for r in rr)
-                    res["legs"][leg]["ms_median"] = ms[len(ms) // 2]
-                    res["legs"][leg]["ms_runs"] = [r["ms"] for r in rr]
+                    res["legs"][leg].update(benchlib.summarise([r["ms"] for r in rr], "ms"))
                     if "nfev_mean" in rr[-1]:
                         res["legs"][leg]["nfev_mean"] = rr[-1]["nfev_mean"]
             med = {leg: v["us_per_step_median"] for leg, v in res["legs"].items()}
@@ -147,12 +117,8 @@ def main():
                 res["net_share"] = 1.0 - med["pid"] / med["mlp"]
                 if args.exact:
                     res["mlp_over_pid"] = med["mlp"] / med["pid"]
-            print(json.dumps(res), flush=True)
-            results.append(res)
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(results, f, indent=1)
-            f.write("\n")
+            benchlib.emit(results, res)
+    benchlib.write(results, args.out)
 
 
 if __name__ == "__main__":

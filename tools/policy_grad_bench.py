@@ -12,24 +12,8 @@ writes them as a list.
     python tools/policy_grad_bench.py --out profiles/policy/grad_bench.json
 """
 import argparse
-import json
-import math
-import os
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-
-def make_policy(widths, history):
-    import torch
-    from simglucose_amd.controller.mlp_ctrller import MLPController
-    g = torch.Generator().manual_seed(0)
-    layers, n_in = [], 2 * history + 3
-    for w in widths:
-        layers.append((torch.randn(1, w, n_in, generator=g, dtype=torch.float64) / math.sqrt(n_in),
-                       0.1 * torch.randn(1, w, generator=g, dtype=torch.float64)))
-        n_in = w
-    return MLPController(layers, history=history, hidden="tanh")
+import benchlib
 
 
 def sequential_of(pol, device):
@@ -46,26 +30,7 @@ def sequential_of(pol, device):
     return nn.Sequential(*mods)
 
 
-def timed(fn, reps):
-    import torch
-    torch.cuda.synchronize()
-    base = torch.cuda.memory_allocated()          # before the warm-up pass: the device leg's cached workspace counts
-    fn()
-    torch.cuda.synchronize()
-    ms, peak = [], 0
-    for _ in range(reps):
-        torch.cuda.reset_peak_memory_stats()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        out = fn()
-        b.record()
-        torch.cuda.synchronize()
-        ms.append(a.elapsed_time(b))
-        peak = max(peak, torch.cuda.max_memory_allocated() - base)
-    return out, sorted(ms)[len(ms) // 2], ms, peak
-
-
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="+", default=[1 << 16, 1 << 20])
     ap.add_argument("--rows", type=int, default=32)
@@ -73,16 +38,15 @@ def main():
     ap.add_argument("--widths", nargs="+", default=["16,16,1", "32,32,32,1"])
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    benchlib.require_gpu("policy_grad_bench.py")
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("policy_grad_bench.py measures on the GPU: none found")
     from simglucose_amd.controller import mlp_pre_output
     dev = torch.device("cuda:0")
     results = []
     for ws in args.widths:
         widths = [int(w) for w in ws.split(",")]
-        pol = make_policy(widths, args.history)
+        pol = benchlib.random_policy(args.history, widths, hidden="tanh")
         for n in args.n:
             g = torch.Generator(device=dev).manual_seed(1)
             feat = torch.rand(args.rows, pol.n_features, n, generator=g, dtype=torch.float64, device=dev) * 4 - 2
@@ -100,23 +64,19 @@ def main():
                 (net(feat.transpose(1, 2)).squeeze(-1) * coef).sum().backward()
                 return torch.cat([torch.cat([m.weight.grad.reshape(-1), m.bias.grad]) for m in net if hasattr(m, "weight")])
 
-            gd, ms_d, runs_d, peak_d = timed(device_leg, args.reps)
+            gd, runs_d, peak_d = benchlib.event_timed(device_leg, args.reps)
             gd = gd.clone()
-            ga, ms_a, runs_a, peak_a = timed(autograd_leg, args.reps)
+            ga, runs_a, peak_a = benchlib.event_timed(autograd_leg, args.reps)
+            legs = {"device": {**benchlib.summarise(runs_d, "ms"), "peak_bytes": peak_d},
+                    "autograd": {**benchlib.summarise(runs_a, "ms"), "peak_bytes": peak_a}}
             res = {"widths": widths, "history": args.history, "n_envs": n, "rows": args.rows, "dtype": "float64",
-                   "device": torch.cuda.get_device_name(0),
-                   "legs": {"device": {"ms_median": ms_d, "ms_runs": runs_d, "peak_bytes": peak_d},
-                            "autograd": {"ms_median": ms_a, "ms_runs": runs_a, "peak_bytes": peak_a}},
-                   "autograd_over_device": ms_a / ms_d,
+                   "device": torch.cuda.get_device_name(0), "legs": legs,
+                   "autograd_over_device": legs["autograd"]["ms_median"] / legs["device"]["ms_median"],
                    "max_rel_grad_difference": float((gd.reshape(-1) - ga).abs().max() / ga.abs().max())}
-            print(json.dumps(res), flush=True)
-            results.append(res)
+            benchlib.emit(results, res)
             feat = coef = net = gd = ga = None
             torch.cuda.empty_cache()
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(results, f, indent=1)
-            f.write("\n")
+    benchlib.write(results, args.out)
 
 
 if __name__ == "__main__":

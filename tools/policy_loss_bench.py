@@ -14,28 +14,11 @@ relative to the largest entry).  One JSON line per (widths, batch size); --out w
     python tools/policy_loss_bench.py --out profiles/policy/policy_loss_bench.json
 """
 import argparse
-import json
-import os
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from tools.policy_grad_bench import make_policy  # noqa: E402
+import benchlib
 
 
-def one_pass(fn):
-    import torch
-    torch.cuda.synchronize()
-    torch.cuda.reset_peak_memory_stats()
-    before = torch.cuda.memory_allocated()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b), torch.cuda.max_memory_allocated() - before
-
-
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="+", default=[1 << 16, 1 << 20])
     ap.add_argument("--rows", type=int, default=32)
@@ -43,10 +26,9 @@ def main():
     ap.add_argument("--widths", nargs="+", default=["16,16,1", "32,32,32,1"])
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    benchlib.require_gpu("policy_loss_bench.py")
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("policy_loss_bench.py measures on the GPU: none found")
     from simglucose_amd.controller import mlp_pre_output, ppo_clip_loss, value_loss
     from simglucose_amd.controller.mlp_ctrller import MLPController
     dev = torch.device("cuda:0")
@@ -54,7 +36,7 @@ def main():
     results = []
     for ws in args.widths:
         widths = [int(w) for w in ws.split(",")]
-        pol = make_policy(widths, args.history)
+        pol = benchlib.random_policy(args.history, widths, hidden="tanh")
         for n in args.n:
             g = torch.Generator(device=dev).manual_seed(1)
             feat = torch.rand(args.rows, pol.n_features, n, generator=g, dtype=torch.float64, device=dev) * 4 - 2
@@ -68,7 +50,7 @@ def main():
             for name in ("fused", "torch"):
                 params, vparams = start.clone().requires_grad_(True), old.clone().requires_grad_(True)
                 legs[name] = {"params": params, "vparams": vparams, "opt": torch.optim.Adam([params], lr=3e-4),
-                              "vopt": torch.optim.Adam([vparams], lr=1e-3), "ms": [], "peak": 0}
+                              "vopt": torch.optim.Adam([vparams], lr=1e-3)}
 
             def fused(L):
                 L["opt"].zero_grad(); L["vopt"].zero_grad()
@@ -89,34 +71,23 @@ def main():
                 L["opt"].step(); L["vopt"].step()
 
             fns = {"fused": fused, "torch": torch_leg}
-            for name in ("fused", "torch"):                      # warm-up, and the gradients of the same first step
-                torch.cuda.synchronize()
-                base = torch.cuda.memory_allocated()
-                fns[name](legs[name])
-                torch.cuda.synchronize()
-                legs[name]["kept"] = torch.cuda.memory_allocated() - base
+            kept = {}
+            for name in fns:                                     # warm-up, and the gradients of the same first step
+                kept[name] = benchlib.kept_bytes(lambda: fns[name](legs[name]))
                 grads[name] = (legs[name]["params"].grad.clone(), legs[name]["vparams"].grad.clone())
-            for _ in range(args.reps):
-                for name in ("fused", "torch"):
-                    ms, peak = one_pass(lambda: fns[name](legs[name]))
-                    legs[name]["ms"].append(ms)
-                    legs[name]["peak"] = max(legs[name]["peak"], legs[name]["kept"] + peak)
-            med = {k: sorted(v["ms"])[len(v["ms"]) // 2] for k, v in legs.items()}
+            runs = benchlib.alternate(fns, args.reps, lambda name: benchlib.event_pass(lambda: fns[name](legs[name]))[1:])
+            out = {k: {**benchlib.summarise([ms for ms, _ in rr], "ms"), "peak_bytes": kept[k] + max(peak for _, peak in rr),
+                       "kept_bytes": kept[k]} for k, rr in runs.items()}
             rel = lambda a, b: float((a - b).abs().max() / b.abs().max())
             res = {"widths": widths, "history": args.history, "n_envs": n, "rows": args.rows, "dtype": "float64",
-                   "device": torch.cuda.get_device_name(0),
-                   "legs": {k: {"ms_median": med[k], "ms_runs": v["ms"], "peak_bytes": v["peak"], "kept_bytes": v["kept"]} for k, v in legs.items()},
-                   "torch_over_fused": med["torch"] / med["fused"],
+                   "device": torch.cuda.get_device_name(0), "legs": out,
+                   "torch_over_fused": out["torch"]["ms_median"] / out["fused"]["ms_median"],
                    "max_rel_grad_difference": {"actor": rel(grads["fused"][0], grads["torch"][0]),
                                                "critic": rel(grads["fused"][1], grads["torch"][1])}}
-            print(json.dumps(res), flush=True)
-            results.append(res)
+            benchlib.emit(results, res)
             feat = eps = adv = ret = y_old = z = old_logp = legs = grads = None
             torch.cuda.empty_cache()
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(results, f, indent=1)
-            f.write("\n")
+    benchlib.write(results, args.out)
 
 
 if __name__ == "__main__":

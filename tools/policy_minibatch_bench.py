@@ -16,16 +16,11 @@ launch starts, P * ceil(M / T).  One JSON line per (widths, batch size, B); --ou
     python tools/policy_minibatch_bench.py --out profiles/policy/minibatch_bench.json
 """
 import argparse
-import json
-import os
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from tools.policy_grad_bench import make_policy  # noqa: E402
-from tools.policy_loss_bench import one_pass  # noqa: E402
+import benchlib
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="+", default=[1 << 16, 1 << 20])
     ap.add_argument("--rows", type=int, default=32)
@@ -34,17 +29,16 @@ def main():
     ap.add_argument("--minibatches", type=int, nargs="+", default=[1, 4, 32])
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    benchlib.require_gpu("policy_minibatch_bench.py")
     import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("policy_minibatch_bench.py measures on the GPU: none found")
     from simglucose_amd.controller import gather_tiles, mlp_pre_output, ppo_clip_loss, tile_minibatches, value_loss
     dev = torch.device("cuda:0")
     sig, clip = 0.3, 0.2
     results = []
     for ws in args.widths:
         widths = [int(w) for w in ws.split(",")]
-        pol = make_policy(widths, args.history)
+        pol = benchlib.random_policy(args.history, widths, hidden="tanh")
         for n in args.n:
             g = torch.Generator(device=dev).manual_seed(1)
             feat = torch.rand(args.rows, pol.n_features, n, generator=g, dtype=torch.float64, device=dev) * 4 - 2
@@ -62,7 +56,7 @@ def main():
                 for name in names:
                     params, vparams = start.clone().requires_grad_(True), old.clone().requires_grad_(True)
                     legs[name] = {"params": params, "vparams": vparams, "opt": torch.optim.Adam([params], lr=3e-4),
-                                  "vopt": torch.optim.Adam([vparams], lr=1e-3), "ms": [], "peak": 0}
+                                  "vopt": torch.optim.Adam([vparams], lr=1e-3)}
 
                 def step(L, loss):
                     L["opt"].zero_grad(); L["vopt"].zero_grad()
@@ -83,35 +77,23 @@ def main():
                     step(L, lambda: ppo_clip_loss(L["params"], feat, pol, eps, y_old, adv, sig, clip=clip) + value_loss(L["vparams"], feat, pol, ret))
 
                 fns = {"tiles": tiles_leg, "gather": gather_leg, "plain": plain_leg}
-                for name in names:                                   # warm-up
-                    torch.cuda.synchronize()
-                    base = torch.cuda.memory_allocated()
-                    fns[name](legs[name])
-                    torch.cuda.synchronize()
-                    legs[name]["kept"] = torch.cuda.memory_allocated() - base
-                for _ in range(args.reps):
-                    for name in names:
-                        ms, peak = one_pass(lambda: fns[name](legs[name]))
-                        legs[name]["ms"].append(ms)
-                        legs[name]["peak"] = max(legs[name]["peak"], legs[name]["kept"] + peak)
-                med = {k: sorted(v["ms"])[len(v["ms"]) // 2] for k, v in legs.items()}
+                kept = {name: benchlib.kept_bytes(lambda: fns[name](legs[name])) for name in names}        # warm-up
+                runs = benchlib.alternate(names, args.reps, lambda name: benchlib.event_pass(lambda: fns[name](legs[name]))[1:])
+                out = {k: {**benchlib.summarise([ms for ms, _ in rr], "ms"), "peak_bytes": kept[k] + max(peak for _, peak in rr),
+                           "kept_bytes": kept[k]} for k, rr in runs.items()}
+                med = {k: v["ms_median"] for k, v in out.items()}
                 T = max(1, -(-M // 2048))
                 res = {"widths": widths, "history": args.history, "n_envs": n, "rows": args.rows, "dtype": "float64",
                        "device": torch.cuda.get_device_name(0), "minibatches": B, "tiles_per_minibatch": M, "waves": -(-M // T),
-                       "legs": {k: {"ms_median": med[k], "ms_runs": v["ms"], "peak_bytes": v["peak"], "kept_bytes": v["kept"]} for k, v in legs.items()},
-                       "gather_over_tiles": med["gather"] / med["tiles"]}
+                       "legs": out, "gather_over_tiles": med["gather"] / med["tiles"]}
                 if B == 1:
                     res["tiles_over_plain"] = med["tiles"] / med["plain"]
-                print(json.dumps(res), flush=True)
-                results.append(res)
+                benchlib.emit(results, res)
                 legs = mbs = None
                 torch.cuda.empty_cache()
             feat = eps = adv = ret = y_old = None
             torch.cuda.empty_cache()
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(results, f, indent=1)
-            f.write("\n")
+    benchlib.write(results, args.out)
 
 
 if __name__ == "__main__":
