@@ -30,6 +30,7 @@
  *                       (simglucose/envs/simglucose_gym_env.py:39-73)
  *   t1d_rollout_pid_dopri5, t1d_rollout_bb_dopri5 <- the two loops with scipy's dopri5 itself (the exact mode)
  *   t1d_rollout_mlp_dopri5, t1d_collect_mlp_dopri5 <- t1d_rollout_mlp and t1d_collect_mlp in the exact mode
+ *   t1d_collect_pid_dopri5, t1d_collect_bb_dopri5 <- t1d_collect_pid and t1d_collect_bb in the exact mode
  *   t1d_mlp_features <- the observation a gym trainer keeps for its critic's bootstrap: the network's inputs for the step that
  *                       would come next (no counterpart in the reference; its gym env hands back one CGM value, env.py:81)
  *   t1d_mlp_grad     <- the network again on a collected batch, and its weight gradient (what autograd does for a gym trainer)
@@ -312,7 +313,8 @@ typedef struct t1d_collect {
                                  t1d_restart_done would */
     int32_t reserved;         /* 0 */
     const t1d_restart* restart;   /* on_done = T1D_COLLECT_RESTART: as for t1d_restart_done (h_carry must be NULL; in
-                                     t1d_collect_mlp_dopri5 NULL or the call's h_carry); else ignored */
+                                     t1d_collect_mlp_dopri5 / t1d_collect_pid_dopri5 / t1d_collect_bb_dopri5 NULL or the
+                                     call's h_carry); else ignored */
     /* optional histories, rows as the traces of t1d_mlp (row mlp.trace_row + s = step s of this call), NULL to skip */
     void* reward_trace;       /* [rows][n]    risk_diff of every step: what batch.reward would hold after that step */
     uint8_t* done_trace;      /* [rows][n]    batch.done of every step */
@@ -557,7 +559,8 @@ int t1d_collect_mlp(t1d_ctx* ctx, const t1d_batch* batch, const t1d_mlp* mlp, co
  * T1D_E_INVALID before anything is launched, nothing changed: whatever t1d_rollout_pid / t1d_rollout_bb rejects; whatever
  *   t1d_collect_mlp rejects of collect and of the fields of feat that are read (history outside [1, 12], a NULL cgm_hist /
  *   ins_hist / prev_meal, with T1D_COLLECT_RESTART a start_minute that is neither NULL nor restart->start_minute); a non-NULL
- *   sigma or eps_trace; a non-NULL restart->h_carry (these two calls run the fixed-step integrators only). */
+ *   sigma or eps_trace; a non-NULL restart->h_carry (these two calls run the fixed-step integrators only; the exact mode's
+ *   are t1d_collect_pid_dopri5 / t1d_collect_bb_dopri5). */
 int t1d_collect_pid(t1d_ctx* ctx, const t1d_batch* batch, const t1d_pid* pid, const t1d_mlp* feat, const t1d_collect* collect,
                     int n_steps, int minutes, int n_sub, void* hip_stream);
 int t1d_collect_bb(t1d_ctx* ctx, const t1d_batch* batch, const t1d_bb* bb, const t1d_mlp* feat, const t1d_collect* collect,
@@ -636,6 +639,47 @@ int t1d_rollout_mlp_dopri5(t1d_ctx* ctx, const t1d_batch* b, const t1d_mlp* mlp,
  *   with T1D_COLLECT_RESTART an mlp.start_minute that is neither NULL nor restart->start_minute, as in t1d_collect_mlp. */
 int t1d_collect_mlp_dopri5(t1d_ctx* ctx, const t1d_batch* b, const t1d_mlp* mlp, const t1d_collect* collect,
                            double* h_carry, int32_t* nfev, int n_steps, int minutes, void* hip_stream);
+
+/* t1d_collect_pid / t1d_collect_bb in the exact mode: trajectories collected while a classical controller drives the envs on
+ * scipy's dopri5 as the reference drives it (t1dpatient.py:110-113,276) -- behaviour-cloning samples and the controller's
+ * return and length under the collectors' episode rules, on the integrator of t1d_collect_mlp_dopri5; with BBController the
+ * reference's own regression run (sim_results.csv).  All of t1d_collect_pid's contract -- the fields of feat that are read,
+ * the features, the action trace, reward and done, on_done, the accumulators; no sigma, no eps_trace -- on the solver and the
+ * free-running lanes of t1d_rollout_pid_dopri5: ONE launch in which every env walks through its minutes, its steps and its
+ * episodes at its own pace.  The two feature windows (a ring whose head each env keeps for itself) and the features are in
+ * LDS, 4 H + 3 words per lane.  fp64 batches only; meals from the meal tables; batch.n need not be a multiple of 64.
+ * Controller: the struct means what it means in t1d_rollout_pid_dopri5 / t1d_rollout_bb_dopri5, and the basal and bolus of a
+ *   step are the words that entry point computes from the same observation and state, without FMA contraction.
+ * Features: as in t1d_collect_pid -- of feat only history, the four feature scales, cgm_hist, ins_hist, prev_meal, start_minute
+ *   and action_trace are read, the network's fields may hold anything -- and the rows of feat_trace are the words
+ *   t1d_mlp_features would return at that moment, bit for bit.
+ * Action trace: feat->action_trace[trace_row + s] = basal + bolus of step s, one fp64 addition, before the pump.  trace_row is
+ *   the controller's, as for every row of this call: row trace_row + s describes step s for every env, although the envs reach
+ *   step s at different moments of the launch.
+ * on_done = T1D_COLLECT_RESTART: as in t1d_collect_mlp_dopri5 -- t1d_restart_done with restart->h_carry = h_carry for this env,
+ *   so the first minute of its new episode probes; its feature windows become those of a fresh reset and its controller state
+ *   what PIDController.reset / BBController.reset leave (integ = prev = 0, bb.prev_meal = 0).  restart->h_carry must be NULL or
+ *   h_carry: either way the env's entry of h_carry is zeroed.
+ * Equivalence: after the call batch.*, the env state, h_carry, the controller state, the feature windows, the accumulators, the
+ *   restart outputs and every trace row are what n_steps x (t1d_mlp_features; t1d_rollout_pid_dopri5(1) or
+ *   t1d_rollout_bb_dopri5(1); the shift of the windows with prev_meal = batch.meal; t1d_restart_done with h_carry; the reset of
+ *   the windows and of the controller state of the envs that were done) leave, bit for bit, whatever the other envs of the
+ *   batch do and wherever the call is cut.  With T1D_COLLECT_CONTINUE the env, the controller state, the accumulators, the
+ *   four trace columns, h_carry and nfev are what t1d_rollout_pid_dopri5(n_steps) / t1d_rollout_bb_dopri5(n_steps) leave.
+ *   nfev: the RHS evaluations of each env over the whole call, across its episodes.
+ * An env whose solver gives up raises T1D_ST_SOLVER_FAILED and keeps its last accepted state while its clock, meals and noise
+ *   go on, until the end of the call or of its episode, as in t1d_collect_mlp_dopri5; the equivalence above is for envs whose
+ *   solver does not fail.
+ * T1D_E_INVALID before anything is launched, nothing changed: whatever t1d_rollout_pid_dopri5 / t1d_rollout_bb_dopri5 rejects
+ *   (an fp32 batch, a NULL h_carry, dense cho, n_steps < 1, minutes out of range, NULL controller state); whatever
+ *   t1d_collect_pid rejects of feat and collect (history outside [1, 12], a NULL cgm_hist / ins_hist / prev_meal, with
+ *   T1D_COLLECT_RESTART a start_minute that is neither NULL nor restart->start_minute, a non-NULL sigma or eps_trace, on_done
+ *   outside {0, 1}, reserved != 0, and with T1D_COLLECT_RESTART everything t1d_restart_done rejects); a restart->h_carry that
+ *   is neither NULL nor h_carry. */
+int t1d_collect_pid_dopri5(t1d_ctx* ctx, const t1d_batch* b, const t1d_pid* pid, const t1d_mlp* feat, const t1d_collect* collect,
+                           double* h_carry, int32_t* nfev, int n_steps, int minutes, void* hip_stream);
+int t1d_collect_bb_dopri5(t1d_ctx* ctx, const t1d_batch* b, const t1d_bb* bb, const t1d_mlp* feat, const t1d_collect* collect,
+                          double* h_carry, int32_t* nfev, int n_steps, int minutes, void* hip_stream);
 
 /* The policy of t1d_mlp alone, one lane per env: action[i] (device [n], the batch's dtype) = the basal, before the pump,
  * that the next step of t1d_rollout_mlp / t1d_rollout_mlp_dopri5 would ask for env i -- from batch.cgm (CGM[0]), rows 1 ..

@@ -36,7 +36,8 @@ EXPORTS = ("t1d_abi_version", "t1d_last_error", "t1d_ctx_create", "t1d_ctx_set_o
            "t1d_collect_mlp", "t1d_rollout_mlp_dopri5", "t1d_mlp_action", "t1d_collect_mlp_dopri5",
            "t1d_mlp_grad_workspace", "t1d_mlp_grad", "t1d_mlp_features", "t1d_gae_workspace", "t1d_gae",
            "t1d_mlp_loss_workspace", "t1d_mlp_loss", "t1d_mlp_grad_tiles_workspace", "t1d_mlp_grad_tiles",
-           "t1d_mlp_loss_tiles_workspace", "t1d_mlp_loss_tiles", "t1d_collect_pid", "t1d_collect_bb")
+           "t1d_mlp_loss_tiles_workspace", "t1d_mlp_loss_tiles", "t1d_collect_pid", "t1d_collect_bb",
+           "t1d_collect_pid_dopri5", "t1d_collect_bb_dopri5")
 
 
 class T1DError(RuntimeError):
@@ -217,6 +218,10 @@ def lib():
     L.t1d_rollout_bb_dopri5.argtypes = [vp, C.POINTER(Batch), C.POINTER(Bb), vp, vp, C.c_int, C.c_int, vp]
     L.t1d_rollout_mlp_dopri5.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), vp, vp, C.c_int, C.c_int, vp]
     L.t1d_collect_mlp_dopri5.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), C.POINTER(Collect), vp, vp, C.c_int, C.c_int, vp]
+    L.t1d_collect_pid_dopri5.argtypes = [vp, C.POINTER(Batch), C.POINTER(Pid), C.POINTER(Mlp), C.POINTER(Collect), vp, vp,
+                                         C.c_int, C.c_int, vp]
+    L.t1d_collect_bb_dopri5.argtypes = [vp, C.POINTER(Batch), C.POINTER(Bb), C.POINTER(Mlp), C.POINTER(Collect), vp, vp,
+                                        C.c_int, C.c_int, vp]
     L.t1d_mlp_action.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), vp, vp]
     L.t1d_mlp_grad_workspace.argtypes = [C.POINTER(Mlp), C.c_int, i64, i64]
     L.t1d_mlp_grad.argtypes = [C.c_int, C.c_int, i64, C.POINTER(Mlp), C.POINTER(MlpBatch), vp]

@@ -455,7 +455,7 @@ class BatchedT1DSimEnv:
             raise _lib.T1DError("rollout_pid / rollout_bb / rollout_mlp / collect_mlp / collect_pid / collect_bb run the fixed-step "
                                 "kernels, which have no DOPRI5 path: an env with integrator='dopri5' takes rollout_pid_dopri5 / "
                                 "rollout_bb_dopri5 / rollout_mlp_dopri5 / collect_mlp_dopri5 (collect_pid and collect_bb have no "
-                                "exact-mode form)")
+                                "exact-mode form in these kernels: collect_pid_dopri5 / collect_bb_dopri5)")
 
     def rollout_pid(self, n_steps, P, I, D, target=140.0, pid_state=None, stats=None, trace=None):
         """n_steps closed-loop PID steps in one launch (PIDController.policy + env.step per step).
@@ -706,9 +706,9 @@ class BatchedT1DSimEnv:
 
     def _collect_structs(self, who, n_steps, policy, policy_state, stats, trace, on_done, days, terminal_obs, episode_stats,
                          reset_outputs, draw, keep_h_carry=False):
-        """The t1d_mlp and t1d_collect of the four collectors, checked.  draw = (sigma, explore_seed): `policy` is the network
+        """The t1d_mlp and t1d_collect of the six collectors, checked.  draw = (sigma, explore_seed): `policy` is the network
         that acts, the call may record "eps", and the t1d_mlp's own five trace columns are left to _set_trace.  draw = None
-        (collect_pid / collect_bb): a controller acts, `policy` only forms the features, `stats` belong to the controller's
+        (collect_pid / collect_bb and their *_dopri5 forms): a controller acts, `policy` only forms the features, `stats` belong to the controller's
         struct, there is no "eps" column and "action" is set here.  keep_h_carry: the exact mode, where a restart zeroes it.
         -> (policy_state, t1d_mlp, t1d_collect, what must stay alive until the launch has run)"""
         n_steps = self._n_steps(n_steps)
@@ -823,6 +823,58 @@ class BatchedT1DSimEnv:
                              restarts=on_done == "restart")
         self._keep = keep
         return policy_state
+
+    def _collect_ctrl_dopri5(self, who, fn, ctl, ctl_state, n_steps, features, policy_state, stats, trace, on_done, days,
+                             terminal_obs, episode_stats, reset_outputs, max_minutes_per_launch):
+        """collect_pid_dopri5 / collect_bb_dopri5: fn with the controller's struct ctl, whose trace_row -- the row of every
+        trace of these calls -- _rollout_dopri5 advances from launch to launch; the feature struct holds pointers only and
+        needs nothing advanced -> policy_state"""
+        policy_state, f, g, keep = self._collect_structs(who, n_steps, features, policy_state, stats, trace, on_done, days,
+                                                         terminal_obs, episode_stats, reset_outputs, draw=None, keep_h_carry=True)
+        self._rollout_dopri5(fn, ctl, n_steps, trace, max_minutes_per_launch, extra=(C.byref(f), C.byref(g)),
+                             restarts=on_done == "restart")
+        self._keep = keep + (ctl_state,)
+        return policy_state
+
+    def collect_pid_dopri5(self, n_steps, P, I, D, target=140.0, features=None, pid_state=None, policy_state=None, stats=None,
+                           trace=None, on_done="continue", days=2, terminal_obs=None, episode_stats=None, reset_outputs=False,
+                           max_minutes_per_launch=240):
+        """collect_pid in the exact mode (t1d_collect_pid_dopri5, include/t1d.h): the PID controller drives the envs on scipy's
+        dopri5, every env at its own pace inside a launch -- through its minutes, its steps and, with on_done="restart", its
+        episodes -- while every step records the features a network would have been given, basal + bolus, reward and done.
+        Arguments, trace columns and return value as collect_pid (n need not be a multiple of 64); h_carry, nfev (summed over
+        the whole call, across an env's episodes) and max_minutes_per_launch as in rollout_pid_dopri5 -- the cut changes no
+        result.  A restarted env's h_carry, integ and prev become 0.  The result is that of a loop of policy_features(),
+        rollout_pid_dopri5(1), the shift of the windows, restart_done() and the torch reset of both states, bit for bit (for
+        envs whose solver does not give up); with on_done="continue" the env, pid_state, stats and the four roll-out columns
+        are rollout_pid_dopri5's.  Measurements: profiles/collect (exact_ctrl_collect_bench.json).
+        -> (pid_state, policy_state)"""
+        self._need_dopri5("collect_pid_dopri5")
+        pid_state, p = self._pid_struct(P, I, D, target, pid_state, stats)
+        policy_state = self._collect_ctrl_dopri5("collect_pid_dopri5", self._L.t1d_collect_pid_dopri5, p, pid_state, n_steps,
+                                                 features, policy_state, stats, trace, on_done, days, terminal_obs, episode_stats,
+                                                 reset_outputs, max_minutes_per_launch)
+        return pid_state, policy_state
+
+    def collect_bb_dopri5(self, n_steps, target=140.0, features=None, bb_state=None, policy_state=None, stats=None, trace=None,
+                          on_done="continue", days=2, terminal_obs=None, episode_stats=None, reset_outputs=False,
+                          max_minutes_per_launch=240):
+        """collect_bb in the exact mode (t1d_collect_bb_dopri5, include/t1d.h): the basal-bolus controller on scipy's dopri5 --
+        the reference's own regression run -- with what collect_bb records; everything else as collect_pid_dopri5.  A restarted
+        env's bb_state["prev_meal"] becomes 0.  The warm start of a policy that is then trained and scored with
+        collect_mlp_dopri5 (INTEGRATION.md):
+
+            tr = env.new_trace(K, columns=("action", "features"), history=pol.history)
+            env.collect_bb_dopri5(K, features=pol, trace=tr, on_done="restart")
+            loss = value_loss(params, tr["features"][1:], pol, target=tr["action"][1:])
+
+        -> (bb_state, policy_state)"""
+        self._need_dopri5("collect_bb_dopri5")
+        bb_state, p = self._bb_struct(target, bb_state, stats)
+        policy_state = self._collect_ctrl_dopri5("collect_bb_dopri5", self._L.t1d_collect_bb_dopri5, p, bb_state, n_steps,
+                                                 features, policy_state, stats, trace, on_done, days, terminal_obs, episode_stats,
+                                                 reset_outputs, max_minutes_per_launch)
+        return bb_state, policy_state
 
     def _rollout_dopri5(self, fn, p, n_steps, trace, max_minutes_per_launch, extra=(), restarts=False):
         """the launches of one exact-mode roll-out: whole steps, at most max_minutes_per_launch simulated minutes each.

@@ -1330,6 +1330,50 @@ extern "C" int t1d_collect_mlp_dopri5(t1d_ctx* c, const t1d_batch* b, const t1d_
                              (const double*)c->d_raw64, h_carry, nfev);
 }
 
+// The exact mode's collectors under the PID controller pid or the basal-bolus controller bb, the other one NULL
+// (dopri5_ctrl_collect_kernel, t1d_dopri5.hpp): what t1d_collect_pid asks of feat and collect, then what
+// t1d_rollout_pid_dopri5 asks of the rest -- the batch's own checks last, so that a bad call is refused on any machine --
+// then one launch in the shape of t1d_rollout_mlp_dopri5 with a wave's columns of ctrl_collect_kernel.
+static int launch_collect_ctrl_dopri5(const char* who, t1d_ctx* c, const t1d_batch* b, const t1d_pid* pid, const t1d_bb* bb,
+                                      const t1d_mlp* feat, const t1d_collect* g, double* h_carry, int32_t* nfev, int n_steps,
+                                      int minutes, void* stream)
+{
+    const std::string w = std::string(who) + ": ";
+    if (!feat) return fail(T1D_E_INVALID, w + "feat is NULL");
+    if (feat->history < 1 || feat->history > kMlpMaxHistory) return fail(T1D_E_INVALID, w + "history must be in [1, 12]");
+    if (!feat->cgm_hist || !feat->ins_hist || !feat->prev_meal) return fail(T1D_E_INVALID, w + "cgm_hist / ins_hist / prev_meal must be set");
+    if (!h_carry) return fail(T1D_E_INVALID, w + "h_carry is NULL");
+    int rc = check_collect(who, b, feat, g, h_carry);
+    if (rc) return rc;
+    if (g->sigma || g->eps_trace) return fail(T1D_E_INVALID, w + "sigma and eps_trace must be NULL (a controller has no exploration noise)");
+    rc = check_dopri5(who, c, b, h_carry, n_steps, minutes);
+    if (rc) return rc;
+    const PidArgs<double> pa = pid ? make_pid<double>(pid, n_steps) : make_bb<double>(bb, n_steps);
+    const t1d_mlp fm = features_only(feat);
+    MlpArgs<double> fa = make_mlp<double>(&fm, n_steps);
+    const int cols = 4 * fm.history + 3;        // a wave's columns: the two windows and the F = 2 H + 3 features, no activations
+    fa.cols = cols;
+    RestartArgs<double> ra = g->on_done == T1D_COLLECT_RESTART ? make_restart<double>(g->restart) : RestartArgs<double>{};
+    if (g->on_done == T1D_COLLECT_RESTART) ra.h_carry = h_carry;      // the env's predicted step is part of what restarts
+    return launch_mlp_dopri5(who, c, b, cols, minutes, stream, dopri5_ctrl_collect_kernel, pa, fa, make_collect<double>(c, g), ra,
+                             (const double*)c->d_raw64, h_carry, nfev);
+}
+
+extern "C" int t1d_collect_pid_dopri5(t1d_ctx* c, const t1d_batch* b, const t1d_pid* pid, const t1d_mlp* feat, const t1d_collect* g,
+                                      double* h_carry, int32_t* nfev, int n_steps, int minutes, void* stream)
+{
+    if (!pid || !pid->integ || !pid->prev) return fail(T1D_E_INVALID, "t1d_collect_pid_dopri5: pid state is NULL");
+    return launch_collect_ctrl_dopri5("t1d_collect_pid_dopri5", c, b, pid, nullptr, feat, g, h_carry, nfev, n_steps, minutes, stream);
+}
+
+extern "C" int t1d_collect_bb_dopri5(t1d_ctx* c, const t1d_batch* b, const t1d_bb* bb, const t1d_mlp* feat, const t1d_collect* g,
+                                     double* h_carry, int32_t* nfev, int n_steps, int minutes, void* stream)
+{
+    if (!bb || !bb->basal || !bb->cr || !bb->cf || !bb->prev_meal)
+        return fail(T1D_E_INVALID, "t1d_collect_bb_dopri5: bb is NULL, or basal / cr / cf / prev_meal is not set");
+    return launch_collect_ctrl_dopri5("t1d_collect_bb_dopri5", c, b, nullptr, bb, feat, g, h_carry, nfev, n_steps, minutes, stream);
+}
+
 extern "C" int t1d_random_meals(int hip_device, uint64_t seed, int64_t env_offset, int64_t n, int dtype, int days,
                                 const int32_t* start_minute_of_day, int start_scalar, int32_t* meal_time, void* meal_amt,
                                 void* stream)

@@ -13,6 +13,16 @@ synchronisations (host clock), `reps` times, legs alternated; the median is repo
 the timed window that ended an episode.  One JSON line per (workload, batch size); --out writes them as a list.
 
     python tools/ctrl_collect_bench.py --out profiles/collect/ctrl_collect_bench.json
+
+--exact: the exact mode (DOPRI5) on an integrator="dopri5" env, as tools/collect_bench.py --exact: collect_bb_dopri5 (one launch
+per 240 simulated minutes) against the loop of policy_features, rollout_bb_dopri5(1), the window shift, restart_done and the
+torch resets, and two more legs:
+  plain    collect_bb_dopri5(K, on_done="continue") without a collector column
+  rollout  rollout_bb_dopri5(K) of the same build: what `plain` is measured against
+K steps between two events on the stream; minimum and maximum are reported beside the median, and `plain_minus_rollout_ms`.
+Every repetition builds the same env from the same seed, so the finish rate is the same in each (`finish_rate_runs` shows it).
+
+    python tools/ctrl_collect_bench.py --exact --out profiles/collect/exact_ctrl_collect_bench.json
 """
 import argparse
 
@@ -22,16 +32,17 @@ from benchlib import DAYS
 COLUMNS = ("bg", "cgm", "cho", "insulin", "action", "reward", "done", "features")
 
 
-def run_leg(leg, workload, n, pol, K, warm_steps, hot_basal, seed):
+def run_leg(leg, workload, n, pol, K, warm_steps, hot_basal, seed, exact=False):
     import torch
-    e = benchlib.mixed_env(n, seed, options=[("rollout_launches", 0)])
+    e = benchlib.mixed_env(n, seed, integrator="dopri5" if exact else None, options=[("rollout_launches", 0)])
+    collect, rollout = (e.collect_bb_dopri5, e.rollout_bb_dopri5) if exact else (e.collect_bb, e.rollout_bb)
     bb = e.bb_constants()
     if workload == "hot":
         bb["basal"][n // 2:] = hot_basal
     bb["prev_meal"] = torch.zeros(n, dtype=e.dtype, device=e.device)
     state = e.new_policy_state(pol)
     if warm_steps:
-        e.collect_bb(warm_steps, features=pol, bb_state=bb, policy_state=state, on_done="restart", days=DAYS)
+        collect(warm_steps, features=pol, bb_state=bb, policy_state=state, on_done="restart", days=DAYS)
     zero = torch.zeros((), dtype=e.dtype, device=e.device)
     finished = torch.zeros((), dtype=torch.int64, device=e.device)
 
@@ -39,14 +50,18 @@ def run_leg(leg, workload, n, pol, K, warm_steps, hot_basal, seed):
         nonlocal finished
         if leg == "collect":
             tr = e.new_trace(K, columns=COLUMNS, history=pol.history)
-            e.collect_bb(K, features=pol, bb_state=bb, policy_state=state, trace=tr, on_done="restart", days=DAYS)
+            collect(K, features=pol, bb_state=bb, policy_state=state, trace=tr, on_done="restart", days=DAYS)
             finished = tr["done"][1:].sum()
+        elif leg == "plain":
+            collect(K, features=pol, bb_state=bb, policy_state=state)
+        elif leg == "rollout":
+            rollout(K, bb_state=bb)
         else:
             tr = e.new_trace(K, columns=COLUMNS[:4])
             rew, don, feat = [], [], []
             for _ in range(K):
                 feat.append(e.policy_features(pol, state))
-                e.rollout_bb(1, bb_state=bb, trace=tr)
+                rollout(1, bb_state=bb, trace=tr)
                 pol.shift(state["cgm_hist"], state["ins_hist"], e.cgm, e.insulin)
                 state["prev_meal"].copy_(e.meal)
                 done = e.done.bool()
@@ -58,10 +73,10 @@ def run_leg(leg, workload, n, pol, K, warm_steps, hot_basal, seed):
                 bb["prev_meal"].copy_(torch.where(done, zero, bb["prev_meal"]))
             tr["reward"], tr["done"], tr["features"] = torch.stack(rew), torch.stack(don), torch.stack(feat)
             finished = tr["done"].sum()
-    ms = benchlib.timed_leg(go, go, "host")
+    ms = benchlib.timed_leg(go, go, "events" if exact else "host")
     status = benchlib.close_leg(e)
     rate = float(finished) / (K * n)
-    del e
+    del e, collect, rollout                      # the bound methods hold the env too
     torch.cuda.empty_cache()
     return {"ms": ms, "status": status, "finish_rate": rate}
 
@@ -70,15 +85,21 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="+", default=[1 << 16, 1 << 20])
     ap.add_argument("--workloads", nargs="+", default=["stock", "hot"], choices=["stock", "hot"])
-    ap.add_argument("--legs", nargs="+", default=["collect", "loop"], choices=["collect", "loop"])
+    ap.add_argument("--legs", nargs="+", default=None, choices=["collect", "loop", "plain", "rollout"],
+                    help="default: collect loop; with --exact also plain rollout, which only the exact mode has")
     ap.add_argument("--steps", type=int, default=32)
     ap.add_argument("--warm-steps", type=int, default=160, help="steps before the timed window, so that episodes end inside it")
     ap.add_argument("--hot-basal", type=float, default=0.05, help="U/min of the upper half of the envs on the hot workload")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--label", default=None)
+    ap.add_argument("--exact", action="store_true", help="the legs in the exact mode (integrator='dopri5'), timed with events")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
+    if args.legs is None:
+        args.legs = ["collect", "loop", "plain", "rollout"] if args.exact else ["collect", "loop"]
+    if not args.exact and set(args.legs) & {"plain", "rollout"}:
+        ap.error("the plain and rollout legs belong to --exact")
     benchlib.require_gpu("ctrl_collect_bench.py")
     import torch
     # only history and the feature scales matter to collect_bb; policy_features (the loop) asks for a complete network
@@ -87,16 +108,24 @@ def main(argv=None):
     for workload in args.workloads:
         for n in args.n:
             runs = benchlib.alternate(args.legs, args.reps,
-                                      lambda leg: run_leg(leg, workload, n, pol, args.steps, args.warm_steps, args.hot_basal, args.seed))
+                                      lambda leg: run_leg(leg, workload, n, pol, args.steps, args.warm_steps, args.hot_basal, args.seed,
+                                                          args.exact))
             res = {"controller": "bb", "workload": workload, "hot_basal": args.hot_basal if workload == "hot" else None, "n_envs": n,
-                   "dtype": "float64", "steps": args.steps, "warm_steps": args.warm_steps, "sensor": "Dexcom", "label": args.label,
-                   "device": torch.cuda.get_device_name(0), "legs": {}}
+                   "dtype": "float64", "steps": args.steps, "warm_steps": args.warm_steps, "sensor": "Dexcom"}
+            if args.exact:
+                res["integrator"] = "dopri5"
+            res.update({"label": args.label, "device": torch.cuda.get_device_name(0), "legs": {}})
             for leg, rr in runs.items():
-                res["legs"][leg] = {**benchlib.summarise([r["ms"] for r in rr], "ms"),
+                res["legs"][leg] = {**benchlib.summarise([r["ms"] for r in rr], "ms", spread=args.exact),
                                     "status": max(r["status"] for r in rr), "finish_rate": rr[-1]["finish_rate"]}
+                if args.exact:
+                    res["legs"][leg]["finish_rate_runs"] = [r["finish_rate"] for r in rr]
             med = {leg: v["ms_median"] for leg, v in res["legs"].items()}
             if "collect" in med and "loop" in med:
                 res["loop_over_collect"] = med["loop"] / med["collect"]
+            if "plain" in med and "rollout" in med:
+                res["plain_over_rollout"] = med["plain"] / med["rollout"]
+                res["plain_minus_rollout_ms"] = med["plain"] - med["rollout"]
             benchlib.emit(results, res)
     benchlib.write(results, args.out)
 
