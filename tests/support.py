@@ -29,6 +29,16 @@ def gpu_torch():
     return torch
 
 
+def kernel_asm():
+    """tools/kernel_asm.py, by bare name as the tools import it: the one device compile that every test reading the
+    library's assembly shares (kernel_asm().kernels(kernel_asm().device_asm()))"""
+    import sys
+    if os.path.join(ROOT, "tools") not in sys.path:
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import kernel_asm
+    return kernel_asm
+
+
 # ------------------------------------------------------------------------------------------------ comparisons
 def bits(t):
     """the words of a tensor as integers: equal bit patterns compare equal, also the NaN rows new_trace leaves unwritten"""

@@ -3,9 +3,10 @@ that need no device, the Python-side checks that run before the GPU check, and t
 import ctypes as C
 import os
 import re
-import subprocess
 
 import pytest
+
+from support import kernel_asm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -59,13 +60,6 @@ def test_integrator_argument_is_checked_before_the_gpu():
 def test_dopri5_kernel_needs_no_scratch():
     """One wave per SIMD with the unified VGPR + AGPR file: the seven stage vectors, y, y1 and the stage input stay in
     registers (a spill would sit inside the stage loop)."""
-    from simglucose_amd._lib import HIPCC_FLAGS
-    out = subprocess.run(["/opt/rocm/bin/hipcc"] + HIPCC_FLAGS +
-                         ["--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage", "-o", os.devnull,
-                          os.path.join(ROOT, "simglucose_amd", "csrc", "t1d_abi.hip")],
-                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900).stdout.decode()
-    blocks = out.split("Function Name: ")
-    mine = [bl for bl in blocks if bl.startswith("_ZN3t1d18dopri5_step_kernel")]
-    assert len(mine) == 1, out[-2000:]
-    scratch = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", mine[0])
-    assert scratch and int(scratch.group(1)) == 0, mine[0]
+    mine = [k for k in kernel_asm().kernels(kernel_asm().device_asm()).values() if k.name.startswith("_ZN3t1d18dopri5_step_kernel")]
+    assert len(mine) == 1, mine
+    assert mine[0].figures["scratch_bytes_per_lane"] == 0, mine[0].figures

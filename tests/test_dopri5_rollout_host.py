@@ -4,9 +4,10 @@ import ctypes as C
 import importlib.util
 import os
 import re
-import subprocess
 
 import numpy as np
+
+from support import kernel_asm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("t1d_rollout_pid_dopri5", "t1d_rollout_bb_dopri5")
@@ -87,14 +88,8 @@ def test_wave_cost_model_on_a_hand_made_array():
 def test_rollout_kernel_needs_no_scratch_and_the_step_kernel_still_none():
     """Both exact-mode kernels keep the stage vectors in the unified VGPR + AGPR file: the roll-out's per-minute words wait
     in LDS between the minute boundaries instead of being spilled inside the step-attempt loop."""
-    from simglucose_amd._lib import HIPCC_FLAGS
-    out = subprocess.run(["/opt/rocm/bin/hipcc"] + HIPCC_FLAGS +
-                         ["--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage", "-o", os.devnull,
-                          os.path.join(ROOT, "simglucose_amd", "csrc", "t1d_abi.hip")],
-                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900).stdout.decode()
-    blocks = out.split("Function Name: ")
+    ks = kernel_asm().kernels(kernel_asm().device_asm()).values()
     for prefix in ("_ZN3t1d21dopri5_rollout_kernel", "_ZN3t1d18dopri5_step_kernel"):
-        mine = [bl for bl in blocks if bl.startswith(prefix)]
-        assert len(mine) == 1, (prefix, out[-2000:])
-        scratch = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", mine[0])
-        assert scratch and int(scratch.group(1)) == 0, mine[0]
+        mine = [k for k in ks if k.name.startswith(prefix)]
+        assert len(mine) == 1, (prefix, mine)
+        assert mine[0].figures["scratch_bytes_per_lane"] == 0, mine[0].figures

@@ -6,7 +6,7 @@ Timing legs (1 Mi, 256 Ki, 128 Ki envs): us per launch from events over >= 200 l
 mean RHS evaluations per env-minute and the mean over waves (64 consecutive envs) of each wave's maximum -- what a wave
 costs, since it runs until its slowest lane is done.  Accuracy leg: 1 024 env-days (24 h) replayed on the oracle's
 dopri (the reference's numbers) and on a tight solve (classical RK4, 48 sub-steps): max / p99 / median of each env-day's
-max |BG difference|.  The kernel's registers come from a resource-usage compile.
+max |BG difference|.  The kernel's registers come from the device assembly (tools/kernel_asm.py).
 
 --rollout: the closed-loop leg instead (Dexcom steps, BB controller and PID with mild gains, 160 steps = 8 h, 1 Mi and 256 Ki
 envs): a step() loop with the controller in torch on the device between the launches (what the exact mode offered before
@@ -19,8 +19,6 @@ usage: dopri5_bench.py [--out FILE] [--launches N] [--no-accuracy]   (GPU box; p
 import argparse
 import json
 import os
-import re
-import subprocess
 import sys
 
 import numpy as np
@@ -31,6 +29,7 @@ sys.path.insert(0, ROOT)
 from simglucose_amd.batch_env import BatchedT1DSimEnv  # noqa: E402
 from simglucose_amd import _lib, params, scenario_batch  # noqa: E402
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+import kernel_asm  # noqa: E402
 from dopri5_counts import wave_costs  # noqa: E402
 
 
@@ -204,12 +203,8 @@ def rollout_counts(n, launch_minutes=240):
 
 
 def resources(kernel="_ZN3t1d18dopri5_step_kernel"):
-    out = subprocess.run(["/opt/rocm/bin/hipcc"] + _lib.HIPCC_FLAGS + ["--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage",
-                          "-o", os.devnull, _lib.SOURCES[0]], stdout=subprocess.PIPE, stderr=subprocess.STDOUT).stdout.decode()
-    blk = [b for b in out.split("Function Name: ") if b.startswith(kernel)][0]
-    get = lambda key: int(re.search(re.escape(key) + r": (\d+)", blk).group(1))
-    return {"vgprs": get("VGPRs"), "agprs": get("AGPRs"), "scratch_bytes_per_lane": get("ScratchSize [bytes/lane]"),
-            "occupancy_waves_per_simd": get("Occupancy [waves/SIMD]")}
+    k = [k for k in kernel_asm.kernels(kernel_asm.device_asm()).values() if k.name.startswith(kernel)][0]
+    return {key: k.figures[key] for key in ("vgprs", "agprs", "scratch_bytes_per_lane", "occupancy_waves_per_simd")}
 
 
 def main():
