@@ -238,7 +238,8 @@ typedef struct t1d_bb {
  * width[l - 1].  Accumulation order, part of the contract so that a host can restate it: acc = b[o], then for j = 0, 1, ..
  * ascending acc = fma(W[o][j], in[j], acc).  Hidden activation (one for the whole net): tanh(v) = sign(v) (1 - E) / (1 + E),
  * E = exp(-2 |v|), or relu(v) = max(v, 0).  Output: basal = fma(out_scale, g(y), out_bias), g(y) = y or the logistic
- * 1 / (1 + exp(-y)); bolus = 0; then the pump quantiser and the step exactly as in t1d_step.
+ * 1 / (1 + exp(-y)); bolus = 0 (the *_bolus calls: the meal bolus of t1d_meal_bolus below); then the pump quantiser and the
+ * step exactly as in t1d_step.
  * Env i uses policy i / envs_per_policy; batch.n == n_policies * envs_per_policy; envs_per_policy is a multiple of 64 (a
  * wave, and a 64-env chunk, has one weight set).
  * State: cgm_hist [H][n] and ins_hist [H][n], row k = CGM[-k] / INS[-1-k], read and written, shifted once per step (row 0 of
@@ -266,6 +267,28 @@ typedef struct t1d_mlp {
     /* optional history on the device, as in t1d_pid; action_trace [rows][n]: the basal the network asked for, before the pump */
     void* bg_trace; void* cgm_trace; void* cho_trace; void* insulin_trace; void* action_trace; int64_t trace_row;
 } t1d_mlp;
+
+/* A hybrid closed loop: the network of t1d_mlp commands the basal rate, and a bolus calculator doses each announced meal by
+ * BBController's rule (basal_bolus_ctrller.py:64-79) -- the rule of t1d_rollout_bb -- from words the step already holds.
+ * Before every step of env i, after the network has produced its basal u (the exploration term of t1d_collect included):
+ *   obs   = CGM[0]                        the observation the step starts from (what the features read)
+ *   pm    = prev_meal                     mean announced CHO of the previous step, g/min (t1d_mlp.prev_meal)
+ *   st    = the sensor's sample time, minutes
+ *   corr  = obs > 150 ? (obs - target) / cf[i] : 0
+ *   bolus = pm > 0 ? ((pm * st) / cr[i] + corr) / st : 0        U/min
+ * in this operation order, every operation rounded once in the batch's dtype: the expressions of t1d_rollout_bb, so that under
+ * a network whose output is the patient's basal rate the roll-out is t1d_rollout_bb's, bit for bit.  u and bolus then go through
+ * the pump and the step exactly as t1d_step takes basal and bolus.  A restarted env (T1D_COLLECT_RESTART) has prev_meal = 0,
+ * hence no bolus on its first step.  A NaN in pm or obs gives bolus 0 through the comparisons; a non-finite network output
+ * raises what it raises without the bolus (T1D_ST_NONFINITE; in the exact mode the solver gives up on the NaN insulin and the
+ * state stays: T1D_ST_SOLVER_FAILED), and the bolus of that step is still the rule's finite word.  The bolus is a deterministic function of the state: the policy's density, eps,
+ * the features, t1d_mlp_grad, t1d_mlp_loss and t1d_gae are untouched.  cr, cf and bolus_trace have the batch's dtype. */
+typedef struct t1d_meal_bolus {
+    double target;        /* BBController.target, 140 mg/dL */
+    const void* cr;       /* [n] carbohydrate ratio, g/U */
+    const void* cf;       /* [n] correction factor, mg/dL/U */
+    void* bolus_trace;    /* [rows][n] or NULL: row mlp.trace_row + s = the bolus of step s, before the pump */
+} t1d_meal_bolus;
 
 /* Per-env outcome statistics of a BG history kept on the device (analysis/report.py), one lane per env:
  *   counts     int32 [5][n]: samples with BG > 180, BG < 70, 70 <= BG <= 180, BG > 250, BG < 50  (percent_stats,
@@ -699,6 +722,25 @@ int t1d_mlp_action(t1d_ctx* ctx, const t1d_batch* b, const t1d_mlp* mlp, void* a
  * (t1d_gae_batch.last_value).  It changes nothing: no state is written and no step is taken; the weights are not read.
  * fp64 and fp32, any integrator, any state layout.  T1D_E_INVALID: a NULL feat, and whatever t1d_mlp_action rejects. */
 int t1d_mlp_features(t1d_ctx* ctx, const t1d_batch* b, const t1d_mlp* mlp, void* feat, void* hip_stream);
+
+/* t1d_rollout_mlp, t1d_collect_mlp and t1d_rollout_mlp_dopri5 with the meal bolus of t1d_meal_bolus in every step, in one
+ * launch as their siblings: everything else -- arguments, state, traces, draws, restarts, the cut that changes no result -- is
+ * the sibling's, and the result is that of a loop of t1d_mlp_action, t1d_mlp_bolus, t1d_step (t1d_step_dopri5) with that basal
+ * and bolus, the shift of the windows and prev_meal = batch.meal, bit for bit.  T1D_E_INVALID before anything is launched,
+ * nothing changed: a NULL meal_bolus, cr or cf, and whatever the sibling rejects, with its texts under the call's own name.
+ * The exact mode's collector has no such form: t1d_collect_mlp_dopri5 always runs with bolus = 0. */
+int t1d_rollout_mlp_bolus(t1d_ctx* ctx, const t1d_batch* batch, const t1d_mlp* mlp, const t1d_meal_bolus* meal_bolus, int n_steps,
+                          int minutes, int n_sub, void* hip_stream);
+int t1d_collect_mlp_bolus(t1d_ctx* ctx, const t1d_batch* batch, const t1d_mlp* mlp, const t1d_collect* collect,
+                          const t1d_meal_bolus* meal_bolus, int n_steps, int minutes, int n_sub, void* hip_stream);
+int t1d_rollout_mlp_dopri5_bolus(t1d_ctx* ctx, const t1d_batch* b, const t1d_mlp* mlp, const t1d_meal_bolus* meal_bolus,
+                                 double* h_carry, int32_t* nfev, int n_steps, int minutes, void* hip_stream);
+
+/* The rule of t1d_meal_bolus alone, one lane per env, beside t1d_mlp_action: bolus[i] (device [n], the batch's dtype) = the
+ * bolus, before the pump, that the next step of a *_bolus call would ask for env i -- from batch.cgm (CGM[0]) and
+ * mlp.prev_meal, with the kernels' own function, so the word is theirs.  It changes nothing (bolus_trace is not used).
+ * T1D_E_INVALID: a NULL meal_bolus, cr, cf or bolus, and whatever t1d_mlp_action rejects. */
+int t1d_mlp_bolus(t1d_ctx* ctx, const t1d_batch* b, const t1d_mlp* mlp, const t1d_meal_bolus* meal_bolus, void* bolus, void* hip_stream);
 
 /* The network of t1d_mlp on recorded features, and the gradient of a scalar loss with respect to its weights: the other half of
  * a policy-gradient iteration after t1d_collect_mlp / t1d_collect_mlp_dopri5.  No ctx; nothing is allocated, the call only

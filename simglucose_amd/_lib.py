@@ -37,7 +37,8 @@ EXPORTS = ("t1d_abi_version", "t1d_last_error", "t1d_ctx_create", "t1d_ctx_set_o
            "t1d_mlp_grad_workspace", "t1d_mlp_grad", "t1d_mlp_features", "t1d_gae_workspace", "t1d_gae",
            "t1d_mlp_loss_workspace", "t1d_mlp_loss", "t1d_mlp_grad_tiles_workspace", "t1d_mlp_grad_tiles",
            "t1d_mlp_loss_tiles_workspace", "t1d_mlp_loss_tiles", "t1d_collect_pid", "t1d_collect_bb",
-           "t1d_collect_pid_dopri5", "t1d_collect_bb_dopri5")
+           "t1d_collect_pid_dopri5", "t1d_collect_bb_dopri5", "t1d_rollout_mlp_bolus", "t1d_collect_mlp_bolus",
+           "t1d_rollout_mlp_dopri5_bolus", "t1d_mlp_bolus")
 
 
 class T1DError(RuntimeError):
@@ -85,6 +86,11 @@ class Mlp(C.Structure):
                 ("out_scale", C.c_double), ("out_bias", C.c_double),
                 ("params", C.c_void_p), ("cgm_hist", C.c_void_p), ("ins_hist", C.c_void_p), ("prev_meal", C.c_void_p),
                 ("start_minute", C.c_void_p)] + _STATS_FIELDS + _TRACE_FIELDS + [("action_trace", C.c_void_p), ("trace_row", C.c_int64)]
+
+
+class MealBolus(C.Structure):
+    """struct t1d_meal_bolus (include/t1d.h)"""
+    _fields_ = [("target", C.c_double), ("cr", C.c_void_p), ("cf", C.c_void_p), ("bolus_trace", C.c_void_p)]
 
 
 class Outcome(C.Structure):
@@ -223,6 +229,11 @@ def lib():
     L.t1d_collect_bb_dopri5.argtypes = [vp, C.POINTER(Batch), C.POINTER(Bb), C.POINTER(Mlp), C.POINTER(Collect), vp, vp,
                                         C.c_int, C.c_int, vp]
     L.t1d_mlp_action.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), vp, vp]
+    mb = C.POINTER(MealBolus)
+    L.t1d_rollout_mlp_bolus.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), mb, C.c_int, C.c_int, C.c_int, vp]
+    L.t1d_collect_mlp_bolus.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), C.POINTER(Collect), mb, C.c_int, C.c_int, C.c_int, vp]
+    L.t1d_rollout_mlp_dopri5_bolus.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), mb, vp, vp, C.c_int, C.c_int, vp]
+    L.t1d_mlp_bolus.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), mb, vp, vp]
     L.t1d_mlp_grad_workspace.argtypes = [C.POINTER(Mlp), C.c_int, i64, i64]
     L.t1d_mlp_grad.argtypes = [C.c_int, C.c_int, i64, C.POINTER(Mlp), C.POINTER(MlpBatch), vp]
     L.t1d_mlp_loss_workspace.argtypes = [C.POINTER(Mlp), C.c_int, i64, i64]

@@ -429,7 +429,8 @@ class BatchedT1DSimEnv:
         """Device-resident history for the next `n_steps` roll-out steps, laid out as T1DSimEnv's history lists
         (simulation/env.py:119-155,169-180): row 0 holds what reset() recorded (BG0 and CGM sample #0; CHO and
         insulin have no row for the last time stamp, so their row r is the action of step r), row r >= 1 step r.
-        "action" (rollout_mlp, collect_mlp) is the basal the policy asked for in step r, before the pump.
+        "action" (rollout_mlp, collect_mlp) is the basal the policy asked for in step r, before the pump; "bolus" (a policy
+        with meal_bolus) the meal bolus of step r, before the pump.
         collect_mlp only: "reward", "done" (uint8) and "eps" of step r, and "features" [n_steps + 1, F, n], what the
         network was given in step r (F = 2 history + 3: pass the policy's history=); their row 0 is NaN (0 for "done").
         Call right after reset(); pass the dict as rollout_*(trace=...)."""
@@ -592,6 +593,52 @@ class BatchedT1DSimEnv:
         f.start_minute = self.start_minute.data_ptr() if self.start_minute is not None else None
         return f
 
+    def _meal_bolus_struct(self, who, policy, trace=None, n_steps=0):
+        """The t1d_meal_bolus of a policy with meal_bolus on this env, None for a policy without: the target of its
+        BBController, cr and cf from bb_constants() (made once per env object and kept), and the "bolus" column of `trace`
+        from the row the call starts at.  Call before _set_trace advances trace["row"]."""
+        bb = getattr(policy, "meal_bolus", None)
+        t = trace.get("bolus") if trace else None
+        if bb is None:
+            if t is not None:
+                raise ValueError("%s: trace['bolus'] needs a policy with meal_bolus" % who)
+            return None
+        if getattr(self, "_bolus_constants", None) is None:
+            k = self.bb_constants()
+            self._bolus_constants = (k["cr"], k["cf"])
+        m = _lib.MealBolus()
+        m.target = float(bb.target)
+        m.cr, m.cf = self._bolus_constants[0].data_ptr(), self._bolus_constants[1].data_ptr()
+        m.bolus_trace = None
+        if t is not None:
+            row = int(trace.get("row", 0))
+            if t.dtype != self.dtype or tuple(t.shape[1:]) != (self.n,) or t.shape[0] < row + n_steps or not t.is_contiguous():
+                raise ValueError("trace['bolus'] must be contiguous [rows >= row + n_steps, %d] of %s" % (self.n, self.dtype))
+            m.bolus_trace = t.data_ptr()
+        return m
+
+    def policy_bolus(self, policy, policy_state):
+        """The meal bolus [n], before the pump, that the next step of rollout_mlp / collect_mlp / rollout_mlp_dopri5 would
+        ask for under a policy with meal_bolus (t1d_mlp_bolus, include/t1d.h): BBController's rule on the current observation
+        (env.cgm) and policy_state["prev_meal"], by the roll-outs' own device function, so the word is theirs.  Nothing is
+        changed and no step is taken; works in every mode.  A policy without meal_bolus asks for none: zeros.  The step()
+        loop of a hybrid policy:
+
+            st = env.new_policy_state(pol)
+            env.step(env.policy_action(pol, st), env.policy_bolus(pol, st))
+            pol.shift(st["cgm_hist"], st["ins_hist"], env.cgm, env.insulin); st["prev_meal"] = env.meal.clone()
+        """
+        m = self._meal_bolus_struct("policy_bolus", policy)
+        if m is None:
+            return torch.zeros(self.n, dtype=self.dtype, device=self.device)
+        p, params = self._mlp_struct("policy_bolus", policy, policy_state)
+        self._set_trace(p, None, 0)
+        out = torch.empty(self.n, dtype=self.dtype, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.t1d_mlp_bolus(self._ctx, C.byref(self._b), C.byref(p), C.byref(m), C.c_void_p(out.data_ptr()), self._stream()))
+        self._keep = (params, policy_state, out)
+        return out
+
     def policy_action(self, policy, policy_state):
         """The basal [n], before the pump, that the next step of rollout_mlp / rollout_mlp_dopri5 would ask for
         (t1d_mlp_action, include/t1d.h): the network on the current observation (env.cgm), rows 1 .. of
@@ -632,7 +679,8 @@ class BatchedT1DSimEnv:
         """rollout_mlp in the exact mode (t1d_rollout_mlp_dopri5): n_steps closed-loop steps under the in-kernel network with
         scipy's dopri5, every env at its own pace inside a launch -- SimObj.simulate as the reference would run it with that
         policy.  Results as a loop of policy_action(), step(u, 0) and the shift of the policy state, bit for bit.  Arguments
-        and return value as rollout_mlp; h_carry, nfev and max_minutes_per_launch as in rollout_pid_dopri5.  Measured on an
+        and return value as rollout_mlp; h_carry, nfev and max_minutes_per_launch as in rollout_pid_dopri5.  A policy with
+        meal_bolus runs t1d_rollout_mlp_dopri5_bolus: the loop with step(u, policy_bolus()); trace may hold "bolus".  Measured on an
         MI355X (160 steps, 1 Mi envs, H = 4, width 16; profiles/policy): 502 ms against 1 260 ms for that loop and 246 ms for
         rollout_pid_dopri5 -- lanes open their steps at different moments, and each moment runs the network for the few
         lanes that are there."""
@@ -641,7 +689,11 @@ class BatchedT1DSimEnv:
         if policy_state is None:
             policy_state = self.new_policy_state(policy)
         p, params = self._mlp_struct("rollout_mlp_dopri5", policy, policy_state, stats)
-        self._rollout_dopri5(self._L.t1d_rollout_mlp_dopri5, p, n_steps, trace, max_minutes_per_launch)
+        m = self._meal_bolus_struct("rollout_mlp_dopri5", policy, trace, n_steps)
+        if m is None:
+            self._rollout_dopri5(self._L.t1d_rollout_mlp_dopri5, p, n_steps, trace, max_minutes_per_launch)
+        else:
+            self._rollout_dopri5(self._L.t1d_rollout_mlp_dopri5_bolus, p, n_steps, trace, max_minutes_per_launch, extra=(C.byref(m),))
         self._keep = (params, policy_state)
         return policy_state
 
@@ -651,13 +703,23 @@ class BatchedT1DSimEnv:
         set i // (n // P), and n // P must be a multiple of 64.  policy_state: dict(cgm_hist, ins_hist, prev_meal) as
         new_policy_state() makes it (created if None: call right after reset()), updated in place and returned, so a
         roll-out can be cut anywhere and resumed.  The time-of-day features use the env's start_minute (0 if it has none).
-        stats as in rollout_pid; trace may also hold "action" (new_trace)."""
+        stats as in rollout_pid; trace may also hold "action" (new_trace).
+        A policy built with meal_bolus= is a hybrid closed loop (t1d_rollout_mlp_bolus): beside the network's basal every
+        announced meal gets BBController's bolus, formed in the kernel from the env's CR and CF (bb_constants()); trace may
+        then hold "bolus", and the result is the loop of policy_action(), policy_bolus() and step(u, bolus), bit for bit.
+        Measured on an MI355X (fp64 Dexcom, 160 steps, H = 4, width 16; profiles/policy): the bolus adds 2 - 3 % to the launch;
+        against that loop one launch is 1.7 times faster at 64 Ki envs and LOSES at 1 Mi envs (701 against 409 us per step), as
+        the bolus-free rollout_mlp does."""
         self._no_dopri5_rollout()
         n_steps = self._n_steps(n_steps)
         if policy_state is None:
             policy_state = self.new_policy_state(policy)
         p, params = self._mlp_struct("rollout_mlp", policy, policy_state, stats)
-        self._rollout(self._L.t1d_rollout_mlp, (p,), n_steps, trace)
+        m = self._meal_bolus_struct("rollout_mlp", policy, trace, n_steps)
+        if m is None:
+            self._rollout(self._L.t1d_rollout_mlp, (p,), n_steps, trace)
+        else:
+            self._rollout(self._L.t1d_rollout_mlp_bolus, (p, m), n_steps, trace)
         self._keep = (params, policy_state)
         return policy_state
 
@@ -678,7 +740,8 @@ class BatchedT1DSimEnv:
         finish per step (episodes shorter than ~120 steps: by 22 % on the hypo workload, 1.6 % per step) and wins below.
         trace: as rollout_mlp, and "reward", "done", "eps", "features" (new_trace).  Row s always describes step s: for an env
         that finished there trace["cgm"][s] is the terminal observation, the new episode's first one shows in
-        trace["features"][s + 1] and in env.cgm.  -> policy_state.
+        trace["features"][s + 1] and in env.cgm.  A policy with meal_bolus runs t1d_collect_mlp_bolus (see rollout_mlp; "bolus"
+        in trace); a restarted env has prev_meal = 0, hence no bolus on its first step.  -> policy_state.
 
         The PPO ratio from a collected batch, with the network evaluated again on the device by the collector's own code
         (controller.mlp_pre_output: differentiable in the weights, no activations stored; at unchanged weights y_new is
@@ -700,7 +763,11 @@ class BatchedT1DSimEnv:
         self._no_dopri5_rollout()
         policy_state, p, g, keep = self._collect_structs("collect_mlp", n_steps, policy, policy_state, stats, trace, on_done, days,
                                                          terminal_obs, episode_stats, reset_outputs, draw=(sigma, explore_seed))
-        self._rollout(self._L.t1d_collect_mlp, (p, g), n_steps, trace, restarts=on_done == "restart")
+        m = self._meal_bolus_struct("collect_mlp", policy, trace, self._n_steps(n_steps))
+        if m is None:
+            self._rollout(self._L.t1d_collect_mlp, (p, g), n_steps, trace, restarts=on_done == "restart")
+        else:
+            self._rollout(self._L.t1d_collect_mlp_bolus, (p, g, m), n_steps, trace, restarts=on_done == "restart")
         self._keep = keep
         return policy_state
 
@@ -814,8 +881,12 @@ class BatchedT1DSimEnv:
         result.  A restarted env's h_carry becomes 0: its first minute probes the step size, as after reset().  The result is
         that of a loop of rollout_mlp_dopri5(1), restart_done() and the torch reset of policy_state, bit for bit (for envs
         whose solver does not give up); with sigma=None and on_done="continue" it is rollout_mlp_dopri5's.  Measurements:
-        profiles/collect (exact_collect_bench.json)."""
+        profiles/collect (exact_collect_bench.json).  A policy with meal_bolus is refused: the exact mode's collector has no
+        meal bolus (there is no t1d_collect_mlp_dopri5_bolus), and it does not drop it silently."""
         self._need_dopri5("collect_mlp_dopri5")
+        if getattr(policy, "meal_bolus", None) is not None:
+            raise _lib.T1DError("collect_mlp_dopri5: the exact-mode collector has no meal bolus (there is no t1d_collect_mlp_dopri5_bolus): "
+                                "a policy with meal_bolus takes rollout_mlp_dopri5, or collect_mlp on a fixed-step env")
         policy_state, p, g, keep = self._collect_structs("collect_mlp_dopri5", n_steps, policy, policy_state, stats, trace, on_done,
                                                          days, terminal_obs, episode_stats, reset_outputs, draw=(sigma, explore_seed),
                                                          keep_h_carry=True)

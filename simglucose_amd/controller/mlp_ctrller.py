@@ -11,18 +11,29 @@ in ``include/t1d.h``, ``csrc/t1d_policy.hpp``) for a whole batch:
                              prev_meal cho_scale                               mean announced CHO of the last step, g/min
                              sin(2 pi m / 1440), cos(2 pi m / 1440)            m = minute of day at the start of the step
     layers:                  x <- act(W x + b), the last one without activation and of width 1
-    basal = out_scale g(y) + out_bias,  g = identity or logistic;  bolus = 0
+    basal = out_scale g(y) + out_bias,  g = identity or logistic;  bolus = 0, or with meal_bolus= the meal bolus below
 
 The kernel accumulates ``b[o]`` first and then ``W[o][j] x[j]`` for j ascending with one fused multiply-add each;
 ``forward(..., ordered=True)`` adds in that order, ``ordered=False`` is a plain ``torch.matmul``.
 ``BatchedT1DSimEnv.collect_mlp`` adds ``sigma * eps`` to the last layer's output before ``g``; ``log_prob`` is the
 density of that sample.
+
+``meal_bolus=`` makes the policy a hybrid closed loop: the network commands the basal rate and a bolus calculator doses each
+announced meal by ``BBController``'s rule (``basal_bolus_ctrller.py``), from the words a step already holds:
+
+    corr  = CGM[0] > 150 ? (CGM[0] - target) / CF : 0
+    bolus = prev_meal > 0 ? ((prev_meal st) / CR + corr) / st : 0        U/min, st = the sensor's sample time
+
+``rollout_mlp``, ``collect_mlp`` and ``rollout_mlp_dopri5`` then run the ``*_bolus`` entry points of ``include/t1d.h``, which form
+that bolus inside the kernel beside the network's basal; ``BatchedT1DSimEnv.policy_bolus`` gives it for a ``step()`` loop.  The
+density, ``eps`` and the features are untouched: the bolus is a deterministic function of the state.
 """
 import math
 
 import torch
 
 from .base import Action, Controller
+from .basal_bolus_ctrller import BBController
 
 MAX_HISTORY, MAX_LAYERS, MAX_WIDTH = 12, 4, 32
 _HIDDEN = {"tanh": 0, "relu": 1}
@@ -32,10 +43,16 @@ _OUTPUT = {"identity": 0, "logistic": 1}
 class MLPController(Controller):
     """layers: list of (W, b) with W [out, in] and b [out] -- or W [P, out, in] and b [P, out] for a stack of P weight
     sets (the multi-policy roll-out: env i uses set i // (n // P)).  The first layer takes F = 2 history + 3 inputs, the
-    last has one output.  Weights are kept as float64 CPU tensors."""
+    last has one output.  Weights are kept as float64 CPU tensors.  meal_bolus: None (the policy commands a basal rate and
+    nothing else), a target in mg/dL, or a BBController whose target is used -- kept as a BBController in .meal_bolus."""
 
     def __init__(self, layers, history=4, hidden="tanh", output="identity", cgm_mean=140.0, cgm_scale=0.01,
-                 ins_scale=10.0, cho_scale=0.1, out_scale=1.0, out_bias=0.0):
+                 ins_scale=10.0, cho_scale=0.1, out_scale=1.0, out_bias=0.0, meal_bolus=None):
+        if meal_bolus is not None and not isinstance(meal_bolus, BBController):
+            if isinstance(meal_bolus, bool) or not isinstance(meal_bolus, (int, float)) or not math.isfinite(meal_bolus):
+                raise ValueError("meal_bolus must be None, a target in mg/dL or a BBController")
+            meal_bolus = BBController(target=meal_bolus)
+        self.meal_bolus = meal_bolus
         history = int(history)
         if not 1 <= history <= MAX_HISTORY:
             raise ValueError("history must be in [1, %d]" % MAX_HISTORY)
@@ -267,7 +284,8 @@ class MLPController(Controller):
     def policy(self, observation, reward, done, **info):
         """One env, as SimObj calls it.  The CGM window starts filled with the first observation.  INS uses
         info['insulin'] where the env reports it (the batched env does), else this controller's own last command;
-        the time of day comes from info['time'] (a datetime) if present."""
+        the time of day comes from info['time'] (a datetime) if present.  With meal_bolus the bolus is that controller's,
+        from info['patient_name'], info['meal'] and info['sample_time'] as SimObj passes them."""
         if self.n_policies != 1:
             raise ValueError("policy() drives one env: it needs a controller with one weight set")
         cgm = torch.tensor([float(observation.CGM)], dtype=torch.float64)
@@ -281,4 +299,7 @@ class MLPController(Controller):
         meal = torch.tensor([float(info.get("meal", 0.0))], dtype=torch.float64)
         feat = self.features(self._cgm, self._ins, meal, torch.tensor([minute]))
         self._last_basal = float(self.forward(feat, ordered=True)[0])
-        return Action(basal=self._last_basal, bolus=0)
+        if self.meal_bolus is None:
+            return Action(basal=self._last_basal, bolus=0)
+        bb = self.meal_bolus._bb_policy(info.get("patient_name"), info.get("meal", 0.0), observation.CGM, info.get("sample_time", 1))
+        return Action(basal=self._last_basal, bolus=bb.bolus)

@@ -960,33 +960,78 @@ static Shape shape_mlp_alone(const t1d_ctx* c, int64_t n, int cols)
     return sh;
 }
 
+// ---- t1d_meal_bolus: the bolus calculator of the *_bolus entry points (BolusArgs, t1d_policy.hpp) ------------------------
+// needs no device: every *_bolus call checks it first, so that a bad call is refused on any machine
+static int check_meal_bolus(const char* who, const t1d_meal_bolus* mb)
+{
+    const std::string w = std::string(who) + ": ";
+    if (!mb) return fail(T1D_E_INVALID, w + "meal_bolus is NULL");
+    if (!mb->cr || !mb->cf) return fail(T1D_E_INVALID, w + "meal_bolus.cr / cf must be set");
+    return T1D_OK;
+}
+
 template <typename T>
-static int run_rollout_mlp(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* m, Plan p, int cols, int n_steps, int minutes, int n_sub, hipStream_t s)
+static BolusArgs<T> make_bolus(const t1d_meal_bolus* mb)
+{
+    return BolusArgs<T>{(T)mb->target, (const T*)mb->cr, (const T*)mb->cf, (T*)mb->bolus_trace};
+}
+
+template <typename T> using CollectFn = KernelFn<T, MlpArgs<T>, CollectArgs<T>, RestartArgs<T>>;
+template <typename T> using CollectBolusFn = KernelFn<T, MlpArgs<T>, CollectArgs<T>, RestartArgs<T>, BolusArgs<T>>;
+template <typename T>
+static CollectBolusFn<T> mlp_collect_bolus_fn(int variant)
+{
+    return by_variant<T>(variant, [](auto v) -> CollectBolusFn<T> { return mlp_collect_bolus_kernel<decltype(v)::value, T>; });
+}
+
+// mb == NULL: t1d_rollout_mlp, mlp_rollout_kernel.  With mb (t1d_rollout_mlp_bolus): the collector's kernel with no sigma, no
+// collector traces and T1D_COLLECT_CONTINUE -- the form in which it computes what mlp_rollout_kernel computes, word for word
+// (mlp_collect_body), at the same cost (README.md) -- so that the bolus needs one new kernel family and not two.
+template <typename T>
+static int run_rollout_mlp(const char* who, t1d_ctx* c, const t1d_batch* b, const t1d_mlp* m, const t1d_meal_bolus* mb, Plan p, int cols,
+                           int n_steps, int minutes, int n_sub, hipStream_t s)
 {
     MlpArgs<T> ma = make_mlp<T>(m, n_steps);
-    const int rc = shape_mlp<T>("t1d_rollout_mlp", c, b, cols, p, ma);
+    const int rc = shape_mlp<T>(who, c, b, cols, p, ma);
     if (rc) return rc;
-    return launch(c, b, p, minutes, n_sub, s, mlp_rollout_fn<T>(p.variant), ma);
+    if (!mb) return launch(c, b, p, minutes, n_sub, s, mlp_rollout_fn<T>(p.variant), ma);
+    CollectArgs<T> ga = {};
+    ga.on_done = T1D_COLLECT_CONTINUE;
+    return launch(c, b, p, minutes, n_sub, s, mlp_collect_bolus_fn<T>(p.variant), ma, ga, RestartArgs<T>{}, make_bolus<T>(mb));
+}
+
+static int rollout_mlp_entry(const char* who, t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_meal_bolus* mb, int n_steps,
+                             int minutes, int n_sub, void* stream)
+{
+    int rc = check_closed_loop(who, c, b, n_steps);
+    if (rc) return rc;
+    int cols = 0;
+    rc = check_mlp(who, b, mlp, &cols);
+    if (rc) return rc;
+    // the plan of a roll-out that keeps all its steps in one launch: variant, refill and the propagator table's LDS
+    Plan p;
+    rc = plan_and_tables(who, c, b, minutes, n_sub, true, &p, true);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    rc = p.f64 ? run_rollout_mlp<double>(who, c, b, mlp, mb, p, cols, n_steps, minutes, n_sub, s)
+               : run_rollout_mlp<float>(who, c, b, mlp, mb, p, cols, n_steps, minutes, n_sub, s);
+    if (rc) return rc;
+    T1D_HIP(hipGetLastError());
+    return T1D_OK;
 }
 
 extern "C" int t1d_rollout_mlp(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, int n_steps, int minutes,
                                int n_sub, void* stream)
 {
-    int rc = check_closed_loop("t1d_rollout_mlp", c, b, n_steps);
+    return rollout_mlp_entry("t1d_rollout_mlp", c, b, mlp, nullptr, n_steps, minutes, n_sub, stream);
+}
+
+extern "C" int t1d_rollout_mlp_bolus(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_meal_bolus* mb, int n_steps,
+                                     int minutes, int n_sub, void* stream)
+{
+    const int rc = check_meal_bolus("t1d_rollout_mlp_bolus", mb);
     if (rc) return rc;
-    int cols = 0;
-    rc = check_mlp("t1d_rollout_mlp", b, mlp, &cols);
-    if (rc) return rc;
-    // the plan of a roll-out that keeps all its steps in one launch: variant, refill and the propagator table's LDS
-    Plan p;
-    rc = plan_and_tables("t1d_rollout_mlp", c, b, minutes, n_sub, true, &p, true);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    rc = p.f64 ? run_rollout_mlp<double>(c, b, mlp, p, cols, n_steps, minutes, n_sub, s)
-               : run_rollout_mlp<float>(c, b, mlp, p, cols, n_steps, minutes, n_sub, s);
-    if (rc) return rc;
-    T1D_HIP(hipGetLastError());
-    return T1D_OK;
+    return rollout_mlp_entry("t1d_rollout_mlp_bolus", c, b, mlp, mb, n_steps, minutes, n_sub, stream);
 }
 
 // The exact mode's roll-outs (t1d_dopri5.hpp): all n_steps in one launch of dopri5_rollout_kernel on the grid of
@@ -1032,10 +1077,10 @@ static int launch_mlp_dopri5(const char* who, t1d_ctx* c, const t1d_batch* b, in
 }
 
 // The exact mode's roll-out under the policy of t1d_mlp (dopri5_mlp_rollout_kernel, t1d_dopri5.hpp).
-extern "C" int t1d_rollout_mlp_dopri5(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, double* h_carry, int32_t* nfev,
-                                      int n_steps, int minutes, void* stream)
+// mb == NULL: t1d_rollout_mlp_dopri5; with mb dopri5_mlp_rollout_bolus_kernel (t1d_rollout_mlp_dopri5_bolus)
+static int rollout_mlp_dopri5_entry(const char* who, t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_meal_bolus* mb,
+                                    double* h_carry, int32_t* nfev, int n_steps, int minutes, void* stream)
 {
-    const char* who = "t1d_rollout_mlp_dopri5";
     int rc = check_dopri5(who, c, b, h_carry, n_steps, minutes);
     if (rc) return rc;
     int cols = 0;
@@ -1043,7 +1088,23 @@ extern "C" int t1d_rollout_mlp_dopri5(t1d_ctx* c, const t1d_batch* b, const t1d_
     if (rc) return rc;
     MlpArgs<double> ma = make_mlp<double>(mlp, n_steps);
     ma.cols = cols;
-    return launch_mlp_dopri5(who, c, b, cols, minutes, stream, dopri5_mlp_rollout_kernel, ma, (const double*)c->d_raw64, h_carry, nfev);
+    if (!mb) return launch_mlp_dopri5(who, c, b, cols, minutes, stream, dopri5_mlp_rollout_kernel, ma, (const double*)c->d_raw64, h_carry, nfev);
+    return launch_mlp_dopri5(who, c, b, cols, minutes, stream, dopri5_mlp_rollout_bolus_kernel, ma, make_bolus<double>(mb),
+                             (const double*)c->d_raw64, h_carry, nfev);
+}
+
+extern "C" int t1d_rollout_mlp_dopri5(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, double* h_carry, int32_t* nfev,
+                                      int n_steps, int minutes, void* stream)
+{
+    return rollout_mlp_dopri5_entry("t1d_rollout_mlp_dopri5", c, b, mlp, nullptr, h_carry, nfev, n_steps, minutes, stream);
+}
+
+extern "C" int t1d_rollout_mlp_dopri5_bolus(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_meal_bolus* mb, double* h_carry,
+                                            int32_t* nfev, int n_steps, int minutes, void* stream)
+{
+    const int rc = check_meal_bolus("t1d_rollout_mlp_dopri5_bolus", mb);
+    if (rc) return rc;
+    return rollout_mlp_dopri5_entry("t1d_rollout_mlp_dopri5_bolus", c, b, mlp, mb, h_carry, nfev, n_steps, minutes, stream);
 }
 
 // The policy alone (mlp_action_kernel, t1d_dopri5.hpp) or its features alone (mlp_features_kernel, t1d_policy.hpp), of
@@ -1076,6 +1137,28 @@ extern "C" int t1d_mlp_action(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp
 extern "C" int t1d_mlp_features(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, void* feat, void* stream)
 {
     return launch_mlp_alone("t1d_mlp_features", "feat", c, b, mlp, feat, stream, [](auto t) { return mlp_features_kernel<decltype(t)>; });
+}
+
+// The meal bolus alone (mlp_bolus_kernel, t1d_policy.hpp), beside t1d_mlp_action: t1d_mlp_action's checks, one lane per env,
+// no LDS.
+extern "C" int t1d_mlp_bolus(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_meal_bolus* mb, void* bolus, void* stream)
+{
+    const char* who = "t1d_mlp_bolus";
+    int rc = check_meal_bolus(who, mb);
+    if (rc) return rc;
+    rc = check_batch(who, c, b, false);
+    if (rc) return rc;
+    if (!bolus) return fail(T1D_E_INVALID, std::string(who) + ": bolus is NULL");
+    int cols = 0;
+    rc = check_mlp(who, b, mlp, &cols);
+    if (rc) return rc;
+    by_dtype(b->dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(mlp_bolus_kernel<T>, dim3((unsigned)((b->n + T1D_POLICY_THREADS - 1) / T1D_POLICY_THREADS)), dim3(T1D_POLICY_THREADS),
+                           0, (hipStream_t)stream, make_args<T>(c, b, 1, 1), make_mlp<T>(mlp, 0), make_bolus<T>(mb), (T*)bolus);
+    });
+    T1D_HIP(hipGetLastError());
+    return T1D_OK;
 }
 
 // the six meal windows of RandomScenario.create_scenario (scenario_gen.py:38-45) as the kernels take them
@@ -1157,7 +1240,6 @@ extern "C" int t1d_restart_done(t1d_ctx* c, const t1d_batch* b, const uint8_t* m
 }
 
 // ---- t1d_collect_mlp (t1d_policy.hpp) ---------------------------------------------------------------------------------
-template <typename T> using CollectFn = KernelFn<T, MlpArgs<T>, CollectArgs<T>, RestartArgs<T>>;
 template <typename T>
 static CollectFn<T> mlp_collect_fn(int variant)
 {
@@ -1174,15 +1256,17 @@ static CollectArgs<T> make_collect(const t1d_ctx* c, const t1d_collect* g)
     return ga;
 }
 
+// mb == NULL: t1d_collect_mlp; with mb the same kernel family with the bolus switched on (t1d_collect_mlp_bolus)
 template <typename T>
-static int run_collect_mlp(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* m, const t1d_collect* g, Plan p, int cols, int n_steps,
-                           int minutes, int n_sub, hipStream_t s)
+static int run_collect_mlp(const char* who, t1d_ctx* c, const t1d_batch* b, const t1d_mlp* m, const t1d_collect* g, const t1d_meal_bolus* mb,
+                           Plan p, int cols, int n_steps, int minutes, int n_sub, hipStream_t s)
 {
     MlpArgs<T> ma = make_mlp<T>(m, n_steps);
-    const int rc = shape_mlp<T>("t1d_collect_mlp", c, b, cols, p, ma);
+    const int rc = shape_mlp<T>(who, c, b, cols, p, ma);
     if (rc) return rc;
     const RestartArgs<T> ra = g->on_done == T1D_COLLECT_RESTART ? make_restart<T>(g->restart) : RestartArgs<T>{};
-    return launch(c, b, p, minutes, n_sub, s, mlp_collect_fn<T>(p.variant), ma, make_collect<T>(c, g), ra);
+    if (!mb) return launch(c, b, p, minutes, n_sub, s, mlp_collect_fn<T>(p.variant), ma, make_collect<T>(c, g), ra);
+    return launch(c, b, p, minutes, n_sub, s, mlp_collect_bolus_fn<T>(p.variant), ma, make_collect<T>(c, g), ra, make_bolus<T>(mb));
 }
 
 // what a t1d_collect must be, for both collectors, and the policy beside it (checked by check_mlp; NULL is left to
@@ -1210,10 +1294,9 @@ static int check_collect(const char* who, const t1d_batch* b, const t1d_mlp* m, 
     return T1D_OK;
 }
 
-extern "C" int t1d_collect_mlp(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_collect* g, int n_steps, int minutes,
-                               int n_sub, void* stream)
+static int collect_mlp_entry(const char* who, t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_collect* g,
+                             const t1d_meal_bolus* mb, int n_steps, int minutes, int n_sub, void* stream)
 {
-    const char* who = "t1d_collect_mlp";
     int rc = check_collect(who, b, mlp, g, nullptr);
     if (rc) return rc;
     rc = check_closed_loop(who, c, b, n_steps);
@@ -1225,11 +1308,25 @@ extern "C" int t1d_collect_mlp(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* ml
     rc = plan_and_tables(who, c, b, minutes, n_sub, true, &p, true);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    rc = p.f64 ? run_collect_mlp<double>(c, b, mlp, g, p, cols, n_steps, minutes, n_sub, s)
-               : run_collect_mlp<float>(c, b, mlp, g, p, cols, n_steps, minutes, n_sub, s);
+    rc = p.f64 ? run_collect_mlp<double>(who, c, b, mlp, g, mb, p, cols, n_steps, minutes, n_sub, s)
+               : run_collect_mlp<float>(who, c, b, mlp, g, mb, p, cols, n_steps, minutes, n_sub, s);
     if (rc) return rc;
     T1D_HIP(hipGetLastError());
     return T1D_OK;
+}
+
+extern "C" int t1d_collect_mlp(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_collect* g, int n_steps, int minutes,
+                               int n_sub, void* stream)
+{
+    return collect_mlp_entry("t1d_collect_mlp", c, b, mlp, g, nullptr, n_steps, minutes, n_sub, stream);
+}
+
+extern "C" int t1d_collect_mlp_bolus(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_collect* g, const t1d_meal_bolus* mb,
+                                     int n_steps, int minutes, int n_sub, void* stream)
+{
+    const int rc = check_meal_bolus("t1d_collect_mlp_bolus", mb);
+    if (rc) return rc;
+    return collect_mlp_entry("t1d_collect_mlp_bolus", c, b, mlp, g, mb, n_steps, minutes, n_sub, stream);
 }
 
 // ---- t1d_collect_pid / t1d_collect_bb (ctrl_collect_kernel, t1d_policy.hpp) ----------------------------------------------

@@ -302,11 +302,78 @@ __device__ T1D_COLLECT_RESTART_ATTR void collect_restart(KArgs<T> a, RestartArgs
     if (restart_front(a, r, a.done, i)) restart_env(a, r, *ms, i);
 }
 
+// ---- t1d_meal_bolus: a bolus calculator beside the network (the *_bolus entry points of include/t1d.h) ---------------------
+// The network commands the basal rate; each announced meal is dosed by BBController's rule, rollout_body's expressions
+// (t1d_kernels.hpp) in its operation order, from words the stepping kernels hold anyway: the observation the step starts from
+// (CGM[0]) and prev_meal.  A NaN in pm or obs gives 0 through the comparisons.  Every kernel that forms the bolus calls
+// meal_bolus, so the word is theirs.
+//   cr[i], cf[i]   per-lane vector loads.  T1D_BOLUS_LOAD_ONCE = 0: at their use, inside the pm > 0 branch -- a step without
+//                  an announced meal reads neither, and nothing of the rule is alive across the step.  1: once per launch,
+//                  two more words alive through every step.  The instances' scratch is within 8 bytes per lane between the
+//                  two forms and above the bolus-free siblings' in both (profiles/policy/kernel_resources_bolus.txt), and the
+//                  clock does not separate them either (profiles/policy/README.md), so the default is the form that keeps
+//                  nothing alive.
+#ifndef T1D_BOLUS_LOAD_ONCE
+#define T1D_BOLUS_LOAD_ONCE 0
+#endif
+template <typename T> struct BolusArgs {
+    T target;                             // BBController.target
+    const T* cr; const T* cf;             // [n]
+    T* bolus_trace;                       // [rows][n] or null: row mlp.trace_row + s = the bolus of step s, before the pump
+};
+template <typename T> struct BolusLane { T cr, cf; };           // the lane's two constants where they are loaded once
+
+template <typename T>
+__device__ __forceinline__ BolusLane<T> bolus_lane(const BolusArgs<T>& m, unsigned i)
+{
+    if (T1D_BOLUS_LOAD_ONCE) return BolusLane<T>{at(m.cr, i), at(m.cf, i)};
+    return BolusLane<T>{T(1), T(1)};
+}
+
+template <typename T>
+__device__ __forceinline__ T meal_bolus(const BolusArgs<T>& m, const BolusLane<T>& l, unsigned i, T st, T obs, T pm)
+{
+    T bolus = T(0);
+    if (pm > T(0)) {
+        // BBController._bb_policy (basal_bolus_ctrller.py:64-79)
+        const T cr = T1D_BOLUS_LOAD_ONCE ? l.cr : (T)at(m.cr, i);
+        const T corr = obs > T(150) ? (obs - m.target) / (T1D_BOLUS_LOAD_ONCE ? l.cf : (T)at(m.cf, i)) : T(0);
+        bolus = ((pm * st) / cr + corr) / st;
+    }
+    return bolus;
+}
+
+// the bolus of a step of a kernel built with one BolusArgs behind its arguments, and its trace word
+template <typename T>
+__device__ __forceinline__ T step_bolus(const BolusArgs<T>& m, const BolusLane<T>& l, unsigned i, T st, T obs, T pm, int64_t trow)
+{
+    const T bolus = meal_bolus(m, l, i, st, obs, pm);
+    if (m.bolus_trace) m.bolus_trace[trow] = bolus;
+    return bolus;
+}
+// the first (the only) member of a kernel's trailing pack
+template <typename A, typename... R> __device__ __forceinline__ const A& pack_first(const A& a, const R&...) { return a; }
+
+// t1d_mlp_bolus: the rule alone, one lane per env -- the bolus the next step of a *_bolus roll-out would ask for, from
+// batch.cgm (CGM[0]) and the policy's prev_meal.  Reads only; writes bolus [n].
+template <typename T>
+__global__ __launch_bounds__(T1D_POLICY_THREADS) void mlp_bolus_kernel(const KArgs<T> a, const MlpArgs<T> c, const BolusArgs<T> m, T* bolus)
+{
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    __builtin_assume(i < (1u << 28));          // host guarantees n <= 2^28: i * sizeof(T) fits a 32-bit voffset
+    if ((int64_t)i >= a.n) return;
+    const T obs = at(a.cgm, i), pm = at(c.prev_meal, i);
+    at(bolus, i) = meal_bolus(m, bolus_lane(m, i), i, T(a.sen.st), obs, pm);
+}
+
 // mlp_rollout_body with the exploration draw, the per-step reward / done / feature histories and the restart of finished
 // envs.  Without sigma and with on_done = 0 it computes what mlp_rollout_body computes, word for word.
-template <int VARIANT, typename T, typename P, typename PR = NoProp>
+// MB: nothing (bolus 0: t1d_collect_mlp) or one BolusArgs (t1d_collect_mlp_bolus, and t1d_rollout_mlp_bolus in the form just
+// named): the meal bolus of the step goes into the pump's bolus slot beside the network's basal.  A restarted env has
+// prev_meal = 0, hence no bolus on its first step.
+template <int VARIANT, typename T, typename P, typename PR = NoProp, typename... MB>
 __device__ __forceinline__ void mlp_collect_body(const KArgs<T>& a, const MlpArgs<T>& c, const CollectArgs<T>& g, const RestartArgs<T>& r,
-                                                 P& p, unsigned i, uint32_t pid, Env<T>& e, T* col, PR pr = PR())
+                                                 P& p, unsigned i, uint32_t pid, Env<T>& e, T* col, PR pr = PR(), const MB&... mb)
 {
     constexpr int MATH = VariantMath<VARIANT>::value;
     typedef const __attribute__((address_space(4))) T* WPtr;
@@ -329,6 +396,8 @@ __device__ __forceinline__ void mlp_collect_body(const KArgs<T>& a, const MlpArg
     StepOut<T> o{T(0), T(0), T(0), T(0)};
     T rp = e.prev_risk;                         // risk of the observation the last step started from
     bool fresh = false;                         // the last step ended the episode: outputs and state are in memory already
+    BolusLane<T> bl{T(1), T(1)};
+    if constexpr (sizeof...(MB) > 0) bl = bolus_lane(pack_first(mb...), i);
 #pragma unroll 1
     for (int s = 0; s < c.n_steps; ++s) {
         const int64_t trow = (c.trace_row + s) * a.n + i;
@@ -342,8 +411,10 @@ __device__ __forceinline__ void mlp_collect_body(const KArgs<T>& a, const MlpArg
             y = fma(sg, eps, y);
         }
         const T u = mlp_output(c, y);
+        T bolus = T(0);
+        if constexpr (sizeof...(MB) > 0) bolus = step_bolus(pack_first(mb...), bl, i, T(a.sen.st), col[head * 64], prev_meal, trow);
         rp = e.prev_risk;
-        o = step_body<MATH, T, P, true, PR, VariantInfo<VARIANT>::tiered>(a, p, i, e, u, T(0), true, pr);
+        o = step_body<MATH, T, P, true, PR, VariantInfo<VARIANT>::tiered>(a, p, i, e, u, bolus, true, pr);
         // the step's reward and done, as write_outputs forms them
         T rl, rh, rc;
         risk_index1<MATH>(o.cgm, rl, rh, rc);
@@ -435,6 +506,43 @@ __global__ __launch_bounds__(T1D_POLICY_THREADS) void mlp_collect_kernel(const K
     } else {
         ParsLds<T> p{lds, (int)pid};
         mlp_collect_body<VARIANT>(a, c, g, r, p, i, pid, e, col);
+    }
+}
+
+// mlp_collect_kernel with the meal bolus of m in every step (t1d_collect_mlp_bolus, t1d_rollout_mlp_bolus): the same body with
+// one BolusArgs in its trailing pack.  A kernel of its own name and not an instance of one template with the pack, so that the
+// bolus-free instances keep their symbols from build to build (tools/isa_diff.py compares by symbol).
+template <int VARIANT, typename T>
+__global__ __launch_bounds__(T1D_POLICY_THREADS) void mlp_collect_bolus_kernel(const KArgs<T> a, const MlpArgs<T> c, const CollectArgs<T> g,
+                                                                               const RestartArgs<T> r, const BolusArgs<T> m)
+{
+    using VI = VariantInfo<VARIANT>;
+    constexpr int kParRows = VI::split ? DP_COUNT : DP_RK4_COUNT;
+    __shared__ T lds[VI::lds_pars ? kParRows * kMaxPatients : 1];
+    if (VI::lds_pars) stage_pars(a, lds, kParRows);
+    if (VI::split) stage_prop(a, (T*)t1d_dyn_lds);
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    __builtin_assume(i < (1u << 28));          // host guarantees n <= 2^28: i * sizeof(T) fits a 32-bit voffset
+    if ((int64_t)i >= a.n) return;
+    T* const col = (T*)(t1d_dyn_lds + c.lds_off) + (threadIdx.x >> 6) * (c.cols * 64) + (threadIdx.x & 63u);
+    const uint32_t meta = at(a.meta, i);
+    const uint32_t pid = T1D_META_PID(meta);
+    Env<T> e;
+    load_env(a, i, meta, e);
+    if constexpr (VARIANT == 4 || VARIANT == 6) {
+        ParsReg<T> p;
+        p.load(a.dpar, (int)pid);
+        mlp_collect_body<VARIANT>(a, c, g, r, p, i, pid, e, col, PropLds<T>{(const T*)t1d_dyn_lds, a.np_pad, (int)pid}, m);
+    } else if constexpr (VARIANT == 7) {
+        ParsLds<T> p{lds, (int)pid};
+        mlp_collect_body<VARIANT>(a, c, g, r, p, i, pid, e, col, PropLds<T>{(const T*)t1d_dyn_lds, a.np_pad, (int)pid}, m);
+    } else if constexpr (VARIANT == 3) {
+        ParsReg<T> p;
+        p.load(a.dpar, (int)pid);
+        mlp_collect_body<VARIANT>(a, c, g, r, p, i, pid, e, col, NoProp(), m);
+    } else {
+        ParsLds<T> p{lds, (int)pid};
+        mlp_collect_body<VARIANT>(a, c, g, r, p, i, pid, e, col, NoProp(), m);
     }
 }
 

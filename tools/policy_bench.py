@@ -15,6 +15,20 @@ the windows and the wider register budget cost.  One JSON line per (dtype, batch
 and `nfev_mean`, the RHS evaluations per env over the timed steps, for the two roll-outs.
 
     python tools/policy_bench.py --exact --out profiles/policy/exact_bench.json
+
+--meal-bolus: what the meal bolus of MLPController(meal_bolus=140) costs inside the launch and what one launch is worth
+against the step loop, with or without --exact; the legs become
+  mlp          rollout_mlp (rollout_mlp_dopri5) under the bolus-free policy: the yardstick for "no cost", in the same run
+  collect      fixed-step only: collect_mlp(sigma=None, on_done="continue") under the bolus-free policy -- the kernel family
+               t1d_rollout_mlp_bolus launches, without the bolus: what of `mlp_bolus - mlp` is the family and what the bolus
+  mlp_bolus    the same call under the same weights with meal_bolus=140 (t1d_rollout_mlp_bolus / t1d_rollout_mlp_dopri5_bolus)
+  loop_bolus   policy_action() + policy_bolus() + step(u, bolus) per step: the only hybrid there is without the new calls
+and `finish_rate`: the share of env-steps that end an episode under the two policies with collect_mlp(on_done="restart") on
+the meal workload of tools/collect_bench.py (child#001 / adult#001, random initial glucose, random-meal days, sigma 0.1), over
+`steps` steps after 128 steps that mix the batch -- what the bolus buys a trainer (fixed-step mode only: the exact mode's
+collector takes no meal bolus).
+
+    python tools/policy_bench.py --meal-bolus --dtypes float64 --reps 5 --out profiles/policy/bolus_bench.json
 """
 import argparse
 
@@ -37,6 +51,8 @@ def make_env(n, dtype, seed, exact=False):
 
 def run_leg(leg, n, dtype, pol, steps, warmup, seed, exact=False):
     import torch
+    if isinstance(pol, dict):                        # --meal-bolus: the policy of the leg
+        pol = pol[leg]
     e = make_env(n, dtype, seed, exact)
     zero = torch.zeros(n, dtype=dtype, device=e.device)
     state = e.new_policy_state(pol)
@@ -44,7 +60,12 @@ def run_leg(leg, n, dtype, pol, steps, warmup, seed, exact=False):
 
     def go(k):
         nonlocal pid_state
-        if exact and leg == "mlp":
+        if leg == "loop_bolus":
+            for _ in range(k):
+                e.step(e.policy_action(pol, state), e.policy_bolus(pol, state))
+                pol.shift(state["cgm_hist"], state["ins_hist"], e.cgm, e.insulin)
+                state["prev_meal"].copy_(e.meal)
+        elif exact and leg in ("mlp", "mlp_bolus"):
             e.rollout_mlp_dopri5(k, pol, policy_state=state)
         elif exact and leg == "pid":
             pid_state = e.rollout_pid_dopri5(k, 1.5e-4, 4e-7, 5e-4, pid_state=pid_state)
@@ -53,8 +74,10 @@ def run_leg(leg, n, dtype, pol, steps, warmup, seed, exact=False):
                 e.step(e.policy_action(pol, state), zero)
                 pol.shift(state["cgm_hist"], state["ins_hist"], e.cgm, e.insulin)
                 state["prev_meal"].copy_(e.meal)
-        elif leg == "mlp":
+        elif leg in ("mlp", "mlp_bolus"):
             e.rollout_mlp(k, pol, policy_state=state)
+        elif leg == "collect":
+            e.collect_mlp(k, pol, policy_state=state)
         elif leg == "pid":
             pid_state = e.rollout_pid(k, 1.5e-4, 4e-7, 5e-4, pid_state=pid_state)
         else:
@@ -67,12 +90,26 @@ def run_leg(leg, n, dtype, pol, steps, warmup, seed, exact=False):
     out = {"us_per_step": 1e3 * ms / steps, "mean_bg": float(e.bg.mean())}
     if exact:
         out["ms"] = ms
-        if leg != "host":                        # a roll-out leaves the RHS evaluations of the whole call in nfev
+        if leg not in ("host", "loop_bolus"):    # a roll-out leaves the RHS evaluations of the whole call in nfev
             out["nfev_mean"] = float(e.nfev.double().mean())
     out["status"] = benchlib.close_leg(e)
     del e
     torch.cuda.empty_cache()
     return out
+
+
+def finish_rate(n, pol, steps, seed, warm_steps=128, sigma=0.1):
+    """the share of env-steps that end an episode under `pol` on benchlib.mixed_env, restarts on the device"""
+    import torch
+    e = benchlib.mixed_env(n, seed)
+    state = e.collect_mlp(warm_steps, pol, sigma=sigma, on_done="restart", days=benchlib.DAYS)
+    tr = e.new_trace(steps, columns=("done",))
+    e.collect_mlp(steps, pol, sigma=sigma, policy_state=state, trace=tr, on_done="restart", days=benchlib.DAYS)
+    rate = float(tr["done"][1:].sum()) / (steps * n)
+    benchlib.close_leg(e)
+    del e
+    torch.cuda.empty_cache()
+    return rate
 
 
 def main(argv=None):
@@ -88,6 +125,7 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=5)
     ap.add_argument("--label", default=None, help="free text kept in the output (e.g. which build was measured)")
     ap.add_argument("--exact", action="store_true", help="the three legs in the exact mode (integrator='dopri5', fp64)")
+    ap.add_argument("--meal-bolus", action="store_true", help="legs mlp, mlp_bolus, loop_bolus: the cost and the worth of the in-kernel meal bolus")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     if args.exact:
@@ -95,6 +133,10 @@ def main(argv=None):
     benchlib.require_gpu("policy_bench.py")
     import torch
     pol = benchlib.random_policy(args.history, args.widths, hidden="tanh", output="logistic", out_scale=0.06)
+    if args.meal_bolus:
+        hybrid = benchlib.random_policy(args.history, args.widths, hidden="tanh", output="logistic", out_scale=0.06, meal_bolus=140.0)
+        args.legs = ["mlp", "mlp_bolus", "loop_bolus"] if args.exact else ["mlp", "collect", "mlp_bolus", "loop_bolus"]
+        pol = {"mlp": pol, "collect": pol, "mlp_bolus": hybrid, "loop_bolus": hybrid}
     results = []
     for name in args.dtypes:
         dtype = getattr(torch, name)
@@ -111,6 +153,13 @@ def main(argv=None):
                     if "nfev_mean" in rr[-1]:
                         res["legs"][leg]["nfev_mean"] = rr[-1]["nfev_mean"]
             med = {leg: v["us_per_step_median"] for leg, v in res["legs"].items()}
+            if args.meal_bolus:
+                res["bolus_over_mlp"] = med["mlp_bolus"] / med["mlp"]
+                res["loop_over_bolus"] = med["loop_bolus"] / med["mlp_bolus"]
+                res["mlp_spread"] = [min(r["us_per_step"] for r in runs["mlp"]), max(r["us_per_step"] for r in runs["mlp"])]
+                if not args.exact:
+                    res["bolus_over_collect"] = med["mlp_bolus"] / med["collect"]
+                    res["finish_rate"] = {leg: finish_rate(n, pol[leg], args.steps, args.seed) for leg in ("mlp", "mlp_bolus")}
             if "mlp" in med and "host" in med:
                 res["host_over_mlp"] = med["host"] / med["mlp"]
             if "mlp" in med and "pid" in med:
