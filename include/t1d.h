@@ -410,6 +410,18 @@ typedef struct t1d_gae_batch {
     void* workspace; int64_t workspace_bytes;   /* needed with moments */
 } t1d_gae_batch;
 
+/* A patient-relative policy output: in the *_rel calls basal = fma(scale[i], g(y), bias[i]) replaces
+ * fma(out_scale, g(y), out_bias) of t1d_mlp -- one weight set then commands "a multiple of the patient's own basal rate" for a
+ * cohort whose basal rates differ by a factor of four.  t1d_mlp.out_scale and out_bias are not read; g, the accumulation order
+ * and the place of the collector's exploration term (in y, before g) are unchanged, and so are the pump, the bolus and the step.
+ * Both arrays have the batch's dtype and are read per env, never per wave.  A non-finite scale or bias raises what a non-finite
+ * network output raises (T1D_ST_NONFINITE; T1D_ST_SOLVER_FAILED in the exact mode).  The trainer's calls (t1d_mlp_grad,
+ * t1d_mlp_loss, t1d_gae, t1d_mlp_features) are untouched: the policy's density lives in y. */
+typedef struct t1d_env_output {
+    const void* scale;   /* [n], batch dtype */
+    const void* bias;    /* [n], batch dtype */
+} t1d_env_output;
+
 int t1d_abi_version(void);
 const char* t1d_last_error(void);
 
@@ -741,6 +753,27 @@ int t1d_rollout_mlp_dopri5_bolus(t1d_ctx* ctx, const t1d_batch* b, const t1d_mlp
  * mlp.prev_meal, with the kernels' own function, so the word is theirs.  It changes nothing (bolus_trace is not used).
  * T1D_E_INVALID: a NULL meal_bolus, cr, cf or bolus, and whatever t1d_mlp_action rejects. */
 int t1d_mlp_bolus(t1d_ctx* ctx, const t1d_batch* b, const t1d_mlp* mlp, const t1d_meal_bolus* meal_bolus, void* bolus, void* hip_stream);
+
+/* The *_bolus calls above under the patient-relative output of t1d_env_output, in one launch each: arguments, state, traces,
+ * draws, restarts and cuts are the sibling's, and the result is that of a loop of t1d_mlp_action_rel, t1d_mlp_bolus (with a
+ * meal_bolus), t1d_step (t1d_step_dopri5), the shift of the windows and prev_meal = batch.meal, bit for bit.  meal_bolus may be
+ * NULL: no bolus, the result of t1d_rollout_mlp / t1d_collect_mlp / t1d_rollout_mlp_dopri5 with the per-env pair.
+ * T1D_E_INVALID before anything is launched, nothing changed: a NULL env_output, scale or bias; a meal_bolus without cr or cf;
+ * and whatever the sibling rejects.  The exact mode's collector has no such form. */
+int t1d_rollout_mlp_rel(t1d_ctx* ctx, const t1d_batch* batch, const t1d_mlp* mlp, const t1d_env_output* env_output,
+                        const t1d_meal_bolus* meal_bolus, int n_steps, int minutes, int n_sub, void* hip_stream);
+int t1d_collect_mlp_rel(t1d_ctx* ctx, const t1d_batch* batch, const t1d_mlp* mlp, const t1d_collect* collect,
+                        const t1d_env_output* env_output, const t1d_meal_bolus* meal_bolus, int n_steps, int minutes, int n_sub,
+                        void* hip_stream);
+int t1d_rollout_mlp_dopri5_rel(t1d_ctx* ctx, const t1d_batch* b, const t1d_mlp* mlp, const t1d_env_output* env_output,
+                               const t1d_meal_bolus* meal_bolus, double* h_carry, int32_t* nfev, int n_steps, int minutes,
+                               void* hip_stream);
+
+/* t1d_mlp_action under t1d_env_output: action[i] = the basal, before the pump, that the next step of a *_rel call would ask for
+ * env i, by the kernels' own function.  It takes no meal_bolus: t1d_mlp_bolus is the bolus half of a step loop, with or without
+ * a relative output.  T1D_E_INVALID: a NULL env_output, scale or bias, and whatever t1d_mlp_action rejects. */
+int t1d_mlp_action_rel(t1d_ctx* ctx, const t1d_batch* b, const t1d_mlp* mlp, const t1d_env_output* env_output, void* action,
+                       void* hip_stream);
 
 /* The network of t1d_mlp on recorded features, and the gradient of a scalar loss with respect to its weights: the other half of
  * a policy-gradient iteration after t1d_collect_mlp / t1d_collect_mlp_dopri5.  No ctx; nothing is allocated, the call only

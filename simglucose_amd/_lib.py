@@ -38,7 +38,8 @@ EXPORTS = ("t1d_abi_version", "t1d_last_error", "t1d_ctx_create", "t1d_ctx_set_o
            "t1d_mlp_loss_workspace", "t1d_mlp_loss", "t1d_mlp_grad_tiles_workspace", "t1d_mlp_grad_tiles",
            "t1d_mlp_loss_tiles_workspace", "t1d_mlp_loss_tiles", "t1d_collect_pid", "t1d_collect_bb",
            "t1d_collect_pid_dopri5", "t1d_collect_bb_dopri5", "t1d_rollout_mlp_bolus", "t1d_collect_mlp_bolus",
-           "t1d_rollout_mlp_dopri5_bolus", "t1d_mlp_bolus")
+           "t1d_rollout_mlp_dopri5_bolus", "t1d_mlp_bolus", "t1d_rollout_mlp_rel", "t1d_collect_mlp_rel",
+           "t1d_rollout_mlp_dopri5_rel", "t1d_mlp_action_rel")
 
 
 class T1DError(RuntimeError):
@@ -91,6 +92,11 @@ class Mlp(C.Structure):
 class MealBolus(C.Structure):
     """struct t1d_meal_bolus (include/t1d.h)"""
     _fields_ = [("target", C.c_double), ("cr", C.c_void_p), ("cf", C.c_void_p), ("bolus_trace", C.c_void_p)]
+
+
+class EnvOutput(C.Structure):
+    """struct t1d_env_output (include/t1d.h)"""
+    _fields_ = [("scale", C.c_void_p), ("bias", C.c_void_p)]
 
 
 class Outcome(C.Structure):
@@ -234,6 +240,11 @@ def lib():
     L.t1d_collect_mlp_bolus.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), C.POINTER(Collect), mb, C.c_int, C.c_int, C.c_int, vp]
     L.t1d_rollout_mlp_dopri5_bolus.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), mb, vp, vp, C.c_int, C.c_int, vp]
     L.t1d_mlp_bolus.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), mb, vp, vp]
+    eo = C.POINTER(EnvOutput)
+    L.t1d_rollout_mlp_rel.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), eo, mb, C.c_int, C.c_int, C.c_int, vp]
+    L.t1d_collect_mlp_rel.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), C.POINTER(Collect), eo, mb, C.c_int, C.c_int, C.c_int, vp]
+    L.t1d_rollout_mlp_dopri5_rel.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), eo, mb, vp, vp, C.c_int, C.c_int, vp]
+    L.t1d_mlp_action_rel.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), eo, vp, vp]
     L.t1d_mlp_grad_workspace.argtypes = [C.POINTER(Mlp), C.c_int, i64, i64]
     L.t1d_mlp_grad.argtypes = [C.c_int, C.c_int, i64, C.POINTER(Mlp), C.POINTER(MlpBatch), vp]
     L.t1d_mlp_loss_workspace.argtypes = [C.POINTER(Mlp), C.c_int, i64, i64]

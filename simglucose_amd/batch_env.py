@@ -506,7 +506,7 @@ class BatchedT1DSimEnv:
 
     def _rollout(self, fn, structs, n_steps, trace, restarts=False):
         """The one fixed-step closed-loop launch: fn(ctx, batch, *structs, n_steps, minutes, n_sub, stream).  structs[0] is
-        the controller's, which carries the trace columns of _set_trace.  restarts: envs may start their next episode
+        the controller's, which carries the trace columns of _set_trace; a struct that is None goes as NULL.  restarts: envs may start their next episode
         inside the launch (on_done="restart"); they no longer share one clock afterwards."""
         n_steps = self._n_steps(n_steps)
         self._set_trace(structs[0], trace, n_steps)
@@ -515,7 +515,7 @@ class BatchedT1DSimEnv:
         clock, self._clock = self._clock, None        # the shadow clock survives only a call that went through
         ep0 = self.episode.clone() if (restarts and self._hist is not None) else None
         with torch.cuda.device(self.device):
-            _lib.check(fn(self._ctx, C.byref(self._b), *[C.byref(s) for s in structs], n_steps, self.minutes_per_step,
+            _lib.check(fn(self._ctx, C.byref(self._b), *[C.byref(s) if s is not None else None for s in structs], n_steps, self.minutes_per_step,
                           self.n_sub, self._stream()))
         if clock is not None and not restarts:
             self._clock = clock + n_steps * self.minutes_per_step
@@ -527,6 +527,12 @@ class BatchedT1DSimEnv:
         """Per-env BBController constants (basal_bolus_ctrller.py:54-64): basal = u2ss*BW/6000 U/min, CR and CF from
         Quest.csv; patients Quest.csv does not list get the reference's 'Average' row (CR 1/15, CF 1/50,
         u2ss 1.43, BW 57).  -> dict of tensors [n]."""
+        basal, cr, cf = self._bb_rows()
+        mk = lambda v: torch.as_tensor(v[self.patient_idx], dtype=self.dtype, device=self.device).contiguous()
+        return {"basal": mk(basal), "cr": mk(cr), "cf": mk(cf)}
+
+    def _bb_rows(self):
+        """bb_constants() per row of self.names, in float64 before its cast -> numpy (basal, cr, cf)"""
         quest = params.quest_table()
         basal = np.empty(len(self.names)); cr = np.empty(len(self.names)); cf = np.empty(len(self.names))
         for k, name in enumerate(self.names):
@@ -535,8 +541,7 @@ class BatchedT1DSimEnv:
                 basal[k] = params.basal_rate(self.table[k])
             else:
                 cr[k], cf[k], basal[k] = 1.0 / 15.0, 1.0 / 50.0, 1.43 * 57.0 / 6000.0
-        mk = lambda v: torch.as_tensor(v[self.patient_idx], dtype=self.dtype, device=self.device).contiguous()
-        return {"basal": mk(basal), "cr": mk(cr), "cf": mk(cf)}
+        return basal, cr, cf
 
     def rollout_bb(self, n_steps, target=140.0, bb_state=None, stats=None, trace=None):
         """n_steps closed-loop BBController steps in one launch (SimObj.simulate with BBController: policy from
@@ -617,6 +622,22 @@ class BatchedT1DSimEnv:
             m.bolus_trace = t.data_ptr()
         return m
 
+    def _env_output_struct(self, policy):
+        """The t1d_env_output of a policy with relative_to="basal" on this env, None for a policy without: scale[i] =
+        out_scale basal[i] and bias[i] = out_bias basal[i], basal the float64 word bb_constants() computes, the product formed
+        in float64 and rounded once to the env's dtype.  Made once per (env, out_scale, out_bias) and kept."""
+        if getattr(policy, "relative_to", None) is None:
+            return None
+        key = (float(policy.out_scale), float(policy.out_bias))
+        kept = getattr(self, "_rel_constants", None)
+        if kept is None or kept[0] != key:
+            basal64 = self._bb_rows()[0][self.patient_idx]
+            mk = lambda v: torch.as_tensor(v, dtype=self.dtype, device=self.device).contiguous()
+            kept = self._rel_constants = (key, mk(key[0] * basal64), mk(key[1] * basal64))
+        o = _lib.EnvOutput()
+        o.scale, o.bias = kept[1].data_ptr(), kept[2].data_ptr()
+        return o
+
     def policy_bolus(self, policy, policy_state):
         """The meal bolus [n], before the pump, that the next step of rollout_mlp / collect_mlp / rollout_mlp_dopri5 would
         ask for under a policy with meal_bolus (t1d_mlp_bolus, include/t1d.h): BBController's rule on the current observation
@@ -650,15 +671,19 @@ class BatchedT1DSimEnv:
             u = env.policy_action(pol, st); env.step(u, 0 * u)
             pol.shift(st["cgm_hist"], st["ins_hist"], env.cgm, env.insulin); st["prev_meal"] = env.meal.clone()
         """
+        o = self._env_output_struct(policy)
+        if o is not None:                   # relative_to="basal": the word of the *_rel roll-outs
+            return self._policy_alone("policy_action", self._L.t1d_mlp_action_rel, policy, policy_state, (self.n,), front=(C.byref(o),))
         return self._policy_alone("policy_action", self._L.t1d_mlp_action, policy, policy_state, (self.n,))
 
-    def _policy_alone(self, who, fn, policy, policy_state, shape):
-        """policy_action / policy_features: fn (t1d_mlp_action, t1d_mlp_features) on the state as it is -> its output"""
+    def _policy_alone(self, who, fn, policy, policy_state, shape, front=()):
+        """policy_action / policy_features: fn (t1d_mlp_action, t1d_mlp_action_rel, t1d_mlp_features) on the state as it is ->
+        its output.  front: the arguments between the policy's struct and the output."""
         p, params = self._mlp_struct(who, policy, policy_state)
         self._set_trace(p, None, 0)
         out = torch.empty(*shape, dtype=self.dtype, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(fn(self._ctx, C.byref(self._b), C.byref(p), C.c_void_p(out.data_ptr()), self._stream()))
+            _lib.check(fn(self._ctx, C.byref(self._b), C.byref(p), *front, C.c_void_p(out.data_ptr()), self._stream()))
         self._keep = (params, policy_state, out)
         return out
 
@@ -690,7 +715,11 @@ class BatchedT1DSimEnv:
             policy_state = self.new_policy_state(policy)
         p, params = self._mlp_struct("rollout_mlp_dopri5", policy, policy_state, stats)
         m = self._meal_bolus_struct("rollout_mlp_dopri5", policy, trace, n_steps)
-        if m is None:
+        o = self._env_output_struct(policy)
+        if o is not None:
+            self._rollout_dopri5(self._L.t1d_rollout_mlp_dopri5_rel, p, n_steps, trace, max_minutes_per_launch,
+                                 extra=(C.byref(o), C.byref(m) if m is not None else None))
+        elif m is None:
             self._rollout_dopri5(self._L.t1d_rollout_mlp_dopri5, p, n_steps, trace, max_minutes_per_launch)
         else:
             self._rollout_dopri5(self._L.t1d_rollout_mlp_dopri5_bolus, p, n_steps, trace, max_minutes_per_launch, extra=(C.byref(m),))
@@ -709,14 +738,22 @@ class BatchedT1DSimEnv:
         then hold "bolus", and the result is the loop of policy_action(), policy_bolus() and step(u, bolus), bit for bit.
         Measured on an MI355X (fp64 Dexcom, 160 steps, H = 4, width 16; profiles/policy): the bolus adds 2 - 3 % to the launch;
         against that loop one launch is 1.7 times faster at 64 Ki envs and LOSES at 1 Mi envs (701 against 409 us per step), as
-        the bolus-free rollout_mlp does."""
+        the bolus-free rollout_mlp does.
+        A policy built with relative_to="basal" commands a multiple of each env's own basal rate (t1d_rollout_mlp_rel, with or
+        without meal_bolus): basal = fma(scale[i], g(y), bias[i]) with scale = out_scale basal_i and bias = out_bias basal_i
+        rounded once to the env's dtype, basal_i the word of bb_constants().  One weight set then serves a mixed cohort: the zero
+        network with last bias 1 and meal_bolus=140 is rollout_bb for every patient at once, bit for bit.  collect_mlp,
+        rollout_mlp_dopri5 and policy_action follow the policy in the same way; collect_mlp_dopri5 refuses it."""
         self._no_dopri5_rollout()
         n_steps = self._n_steps(n_steps)
         if policy_state is None:
             policy_state = self.new_policy_state(policy)
         p, params = self._mlp_struct("rollout_mlp", policy, policy_state, stats)
         m = self._meal_bolus_struct("rollout_mlp", policy, trace, n_steps)
-        if m is None:
+        o = self._env_output_struct(policy)
+        if o is not None:
+            self._rollout(self._L.t1d_rollout_mlp_rel, (p, o, m), n_steps, trace)
+        elif m is None:
             self._rollout(self._L.t1d_rollout_mlp, (p,), n_steps, trace)
         else:
             self._rollout(self._L.t1d_rollout_mlp_bolus, (p, m), n_steps, trace)
@@ -764,7 +801,10 @@ class BatchedT1DSimEnv:
         policy_state, p, g, keep = self._collect_structs("collect_mlp", n_steps, policy, policy_state, stats, trace, on_done, days,
                                                          terminal_obs, episode_stats, reset_outputs, draw=(sigma, explore_seed))
         m = self._meal_bolus_struct("collect_mlp", policy, trace, self._n_steps(n_steps))
-        if m is None:
+        o = self._env_output_struct(policy)
+        if o is not None:
+            self._rollout(self._L.t1d_collect_mlp_rel, (p, g, o, m), n_steps, trace, restarts=on_done == "restart")
+        elif m is None:
             self._rollout(self._L.t1d_collect_mlp, (p, g), n_steps, trace, restarts=on_done == "restart")
         else:
             self._rollout(self._L.t1d_collect_mlp_bolus, (p, g, m), n_steps, trace, restarts=on_done == "restart")
@@ -887,6 +927,10 @@ class BatchedT1DSimEnv:
         if getattr(policy, "meal_bolus", None) is not None:
             raise _lib.T1DError("collect_mlp_dopri5: the exact-mode collector has no meal bolus (there is no t1d_collect_mlp_dopri5_bolus): "
                                 "a policy with meal_bolus takes rollout_mlp_dopri5, or collect_mlp on a fixed-step env")
+        if getattr(policy, "relative_to", None) is not None:
+            raise _lib.T1DError("collect_mlp_dopri5: the exact-mode collector has no patient-relative output (relative_to=%r; there is no "
+                                "t1d_collect_mlp_dopri5_rel): such a policy takes rollout_mlp_dopri5, or collect_mlp on a fixed-step env"
+                                % (policy.relative_to,))
         policy_state, p, g, keep = self._collect_structs("collect_mlp_dopri5", n_steps, policy, policy_state, stats, trace, on_done,
                                                          days, terminal_obs, episode_stats, reset_outputs, draw=(sigma, explore_seed),
                                                          keep_h_carry=True)

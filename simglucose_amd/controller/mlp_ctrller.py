@@ -27,6 +27,11 @@ announced meal by ``BBController``'s rule (``basal_bolus_ctrller.py``), from the
 ``rollout_mlp``, ``collect_mlp`` and ``rollout_mlp_dopri5`` then run the ``*_bolus`` entry points of ``include/t1d.h``, which form
 that bolus inside the kernel beside the network's basal; ``BatchedT1DSimEnv.policy_bolus`` gives it for a ``step()`` loop.  The
 density, ``eps`` and the features are untouched: the bolus is a deterministic function of the state.
+
+``relative_to="basal"`` makes the output a multiple of the patient's own basal rate, ``basal = (out_scale g(y) + out_bias) basal_i``
+with ``basal_i = u2ss BW / 6000`` (``BBController``'s basal): the ``*_rel`` entry points read ``scale[i] = out_scale basal_i`` and
+``bias[i] = out_bias basal_i`` per env, so one weight set serves a cohort whose basal rates differ by a factor of four.  Noise is
+added before ``g`` as ever; the density lives in ``y`` and the trainer's calls are untouched.
 """
 import math
 
@@ -44,10 +49,14 @@ class MLPController(Controller):
     """layers: list of (W, b) with W [out, in] and b [out] -- or W [P, out, in] and b [P, out] for a stack of P weight
     sets (the multi-policy roll-out: env i uses set i // (n // P)).  The first layer takes F = 2 history + 3 inputs, the
     last has one output.  Weights are kept as float64 CPU tensors.  meal_bolus: None (the policy commands a basal rate and
-    nothing else), a target in mg/dL, or a BBController whose target is used -- kept as a BBController in .meal_bolus."""
+    nothing else), a target in mg/dL, or a BBController whose target is used -- kept as a BBController in .meal_bolus.
+    relative_to: None (out_scale and out_bias are U/min) or "basal" (they are multiples of the patient's basal rate)."""
 
     def __init__(self, layers, history=4, hidden="tanh", output="identity", cgm_mean=140.0, cgm_scale=0.01,
-                 ins_scale=10.0, cho_scale=0.1, out_scale=1.0, out_bias=0.0, meal_bolus=None):
+                 ins_scale=10.0, cho_scale=0.1, out_scale=1.0, out_bias=0.0, meal_bolus=None, relative_to=None):
+        if relative_to not in (None, "basal"):
+            raise ValueError("relative_to must be None or 'basal'")
+        self.relative_to = relative_to
         if meal_bolus is not None and not isinstance(meal_bolus, BBController):
             if isinstance(meal_bolus, bool) or not isinstance(meal_bolus, (int, float)) or not math.isfinite(meal_bolus):
                 raise ValueError("meal_bolus must be None, a target in mg/dL or a BBController")
@@ -213,11 +222,13 @@ class MLPController(Controller):
                 x = torch.tanh(x) if self.hidden == "tanh" else torch.relu(x)
         return x.reshape(n)
 
-    def forward(self, feat, ordered=False):
-        """feat [F, n] -> basal [n], U/min: out_scale g(pre_output(feat, ordered)) + out_bias."""
+    def forward(self, feat, ordered=False, ref=None):
+        """feat [F, n] -> basal [n], U/min: out_scale g(pre_output(feat, ordered)) + out_bias, times ref [n] when given
+        (relative_to="basal": each env's basal rate)."""
         y = self.pre_output(feat, ordered)
         g = torch.sigmoid(y) if self.output == "logistic" else y
-        return self.out_scale * g + self.out_bias
+        u = self.out_scale * g + self.out_bias
+        return u if ref is None else u * ref
 
     def grad_reference(self, feat_rows, coef, params=None, info=False):
         """What t1d_mlp_grad (controller.mlp_pre_output's backward) computes, in plain torch and fp64 on the device of
@@ -285,7 +296,8 @@ class MLPController(Controller):
         """One env, as SimObj calls it.  The CGM window starts filled with the first observation.  INS uses
         info['insulin'] where the env reports it (the batched env does), else this controller's own last command;
         the time of day comes from info['time'] (a datetime) if present.  With meal_bolus the bolus is that controller's,
-        from info['patient_name'], info['meal'] and info['sample_time'] as SimObj passes them."""
+        from info['patient_name'], info['meal'] and info['sample_time'] as SimObj passes them.  With relative_to="basal" the
+        output multiplies the basal rate BBController gives for info['patient_name']."""
         if self.n_policies != 1:
             raise ValueError("policy() drives one env: it needs a controller with one weight set")
         cgm = torch.tensor([float(observation.CGM)], dtype=torch.float64)
@@ -298,7 +310,11 @@ class MLPController(Controller):
         minute = 0 if now is None else now.hour * 60 + now.minute
         meal = torch.tensor([float(info.get("meal", 0.0))], dtype=torch.float64)
         feat = self.features(self._cgm, self._ins, meal, torch.tensor([minute]))
-        self._last_basal = float(self.forward(feat, ordered=True)[0])
+        ref = None
+        if self.relative_to is not None:
+            bb = self.meal_bolus if self.meal_bolus is not None else BBController()
+            ref = torch.tensor([bb._bb_policy(info.get("patient_name"), 0.0, 0.0, 1).basal], dtype=torch.float64)
+        self._last_basal = float(self.forward(feat, ordered=True, ref=ref)[0])
         if self.meal_bolus is None:
             return Action(basal=self._last_basal, bolus=0)
         bb = self.meal_bolus._bb_policy(info.get("patient_name"), info.get("meal", 0.0), observation.CGM, info.get("sample_time", 1))

@@ -976,6 +976,29 @@ static BolusArgs<T> make_bolus(const t1d_meal_bolus* mb)
     return BolusArgs<T>{(T)mb->target, (const T*)mb->cr, (const T*)mb->cf, (T*)mb->bolus_trace};
 }
 
+// ---- t1d_env_output: the per-env scale and bias of the *_rel entry points (EnvOutArgs, t1d_policy.hpp) -------------------
+// needs no device, like check_meal_bolus; a *_rel call's meal_bolus may be NULL (no bolus), and is checked when it is not
+static int check_env_output(const char* who, const t1d_env_output* eo, const t1d_meal_bolus* mb)
+{
+    const std::string w = std::string(who) + ": ";
+    if (!eo) return fail(T1D_E_INVALID, w + "env_output is NULL");
+    if (!eo->scale || !eo->bias) return fail(T1D_E_INVALID, w + "env_output.scale / bias must be set");
+    return mb ? check_meal_bolus(who, mb) : T1D_OK;
+}
+
+template <typename T>
+static EnvOutArgs<T> make_env_out(const t1d_env_output* eo)
+{
+    return EnvOutArgs<T>{(const T*)eo->scale, (const T*)eo->bias};
+}
+
+// the BolusArgs of a *_rel kernel: all NULL switches the bolus off
+template <typename T>
+static BolusArgs<T> make_bolus_or_none(const t1d_meal_bolus* mb)
+{
+    return mb ? make_bolus<T>(mb) : BolusArgs<T>{};
+}
+
 template <typename T> using CollectFn = KernelFn<T, MlpArgs<T>, CollectArgs<T>, RestartArgs<T>>;
 template <typename T> using CollectBolusFn = KernelFn<T, MlpArgs<T>, CollectArgs<T>, RestartArgs<T>, BolusArgs<T>>;
 template <typename T>
@@ -984,24 +1007,35 @@ static CollectBolusFn<T> mlp_collect_bolus_fn(int variant)
     return by_variant<T>(variant, [](auto v) -> CollectBolusFn<T> { return mlp_collect_bolus_kernel<decltype(v)::value, T>; });
 }
 
+template <typename T> using CollectRelFn = KernelFn<T, MlpArgs<T>, CollectArgs<T>, RestartArgs<T>, EnvOutArgs<T>, BolusArgs<T>>;
+template <typename T>
+static CollectRelFn<T> mlp_collect_rel_fn(int variant)
+{
+    return by_variant<T>(variant, [](auto v) -> CollectRelFn<T> { return mlp_collect_rel_kernel<decltype(v)::value, T>; });
+}
+
 // mb == NULL: t1d_rollout_mlp, mlp_rollout_kernel.  With mb (t1d_rollout_mlp_bolus): the collector's kernel with no sigma, no
 // collector traces and T1D_COLLECT_CONTINUE -- the form in which it computes what mlp_rollout_kernel computes, word for word
 // (mlp_collect_body), at the same cost (README.md) -- so that the bolus needs one new kernel family and not two.
+// With eo (t1d_rollout_mlp_rel): the relative policy's family in that same form, with or without mb.
 template <typename T>
-static int run_rollout_mlp(const char* who, t1d_ctx* c, const t1d_batch* b, const t1d_mlp* m, const t1d_meal_bolus* mb, Plan p, int cols,
-                           int n_steps, int minutes, int n_sub, hipStream_t s)
+static int run_rollout_mlp(const char* who, t1d_ctx* c, const t1d_batch* b, const t1d_mlp* m, const t1d_env_output* eo,
+                           const t1d_meal_bolus* mb, Plan p, int cols, int n_steps, int minutes, int n_sub, hipStream_t s)
 {
     MlpArgs<T> ma = make_mlp<T>(m, n_steps);
     const int rc = shape_mlp<T>(who, c, b, cols, p, ma);
     if (rc) return rc;
-    if (!mb) return launch(c, b, p, minutes, n_sub, s, mlp_rollout_fn<T>(p.variant), ma);
+    if (!eo && !mb) return launch(c, b, p, minutes, n_sub, s, mlp_rollout_fn<T>(p.variant), ma);
     CollectArgs<T> ga = {};
     ga.on_done = T1D_COLLECT_CONTINUE;
+    if (eo)
+        return launch(c, b, p, minutes, n_sub, s, mlp_collect_rel_fn<T>(p.variant), ma, ga, RestartArgs<T>{}, make_env_out<T>(eo),
+                      make_bolus_or_none<T>(mb));
     return launch(c, b, p, minutes, n_sub, s, mlp_collect_bolus_fn<T>(p.variant), ma, ga, RestartArgs<T>{}, make_bolus<T>(mb));
 }
 
-static int rollout_mlp_entry(const char* who, t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_meal_bolus* mb, int n_steps,
-                             int minutes, int n_sub, void* stream)
+static int rollout_mlp_entry(const char* who, t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_env_output* eo,
+                             const t1d_meal_bolus* mb, int n_steps, int minutes, int n_sub, void* stream)
 {
     int rc = check_closed_loop(who, c, b, n_steps);
     if (rc) return rc;
@@ -1013,8 +1047,8 @@ static int rollout_mlp_entry(const char* who, t1d_ctx* c, const t1d_batch* b, co
     rc = plan_and_tables(who, c, b, minutes, n_sub, true, &p, true);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    rc = p.f64 ? run_rollout_mlp<double>(who, c, b, mlp, mb, p, cols, n_steps, minutes, n_sub, s)
-               : run_rollout_mlp<float>(who, c, b, mlp, mb, p, cols, n_steps, minutes, n_sub, s);
+    rc = p.f64 ? run_rollout_mlp<double>(who, c, b, mlp, eo, mb, p, cols, n_steps, minutes, n_sub, s)
+               : run_rollout_mlp<float>(who, c, b, mlp, eo, mb, p, cols, n_steps, minutes, n_sub, s);
     if (rc) return rc;
     T1D_HIP(hipGetLastError());
     return T1D_OK;
@@ -1023,7 +1057,7 @@ static int rollout_mlp_entry(const char* who, t1d_ctx* c, const t1d_batch* b, co
 extern "C" int t1d_rollout_mlp(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, int n_steps, int minutes,
                                int n_sub, void* stream)
 {
-    return rollout_mlp_entry("t1d_rollout_mlp", c, b, mlp, nullptr, n_steps, minutes, n_sub, stream);
+    return rollout_mlp_entry("t1d_rollout_mlp", c, b, mlp, nullptr, nullptr, n_steps, minutes, n_sub, stream);
 }
 
 extern "C" int t1d_rollout_mlp_bolus(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_meal_bolus* mb, int n_steps,
@@ -1031,7 +1065,15 @@ extern "C" int t1d_rollout_mlp_bolus(t1d_ctx* c, const t1d_batch* b, const t1d_m
 {
     const int rc = check_meal_bolus("t1d_rollout_mlp_bolus", mb);
     if (rc) return rc;
-    return rollout_mlp_entry("t1d_rollout_mlp_bolus", c, b, mlp, mb, n_steps, minutes, n_sub, stream);
+    return rollout_mlp_entry("t1d_rollout_mlp_bolus", c, b, mlp, nullptr, mb, n_steps, minutes, n_sub, stream);
+}
+
+extern "C" int t1d_rollout_mlp_rel(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_env_output* eo, const t1d_meal_bolus* mb,
+                                   int n_steps, int minutes, int n_sub, void* stream)
+{
+    const int rc = check_env_output("t1d_rollout_mlp_rel", eo, mb);
+    if (rc) return rc;
+    return rollout_mlp_entry("t1d_rollout_mlp_rel", c, b, mlp, eo, mb, n_steps, minutes, n_sub, stream);
 }
 
 // The exact mode's roll-outs (t1d_dopri5.hpp): all n_steps in one launch of dopri5_rollout_kernel on the grid of
@@ -1077,9 +1119,10 @@ static int launch_mlp_dopri5(const char* who, t1d_ctx* c, const t1d_batch* b, in
 }
 
 // The exact mode's roll-out under the policy of t1d_mlp (dopri5_mlp_rollout_kernel, t1d_dopri5.hpp).
-// mb == NULL: t1d_rollout_mlp_dopri5; with mb dopri5_mlp_rollout_bolus_kernel (t1d_rollout_mlp_dopri5_bolus)
-static int rollout_mlp_dopri5_entry(const char* who, t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_meal_bolus* mb,
-                                    double* h_carry, int32_t* nfev, int n_steps, int minutes, void* stream)
+// mb == NULL: t1d_rollout_mlp_dopri5; with mb dopri5_mlp_rollout_bolus_kernel (t1d_rollout_mlp_dopri5_bolus); with eo
+// dopri5_mlp_rollout_rel_kernel, with or without mb (t1d_rollout_mlp_dopri5_rel)
+static int rollout_mlp_dopri5_entry(const char* who, t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_env_output* eo,
+                                    const t1d_meal_bolus* mb, double* h_carry, int32_t* nfev, int n_steps, int minutes, void* stream)
 {
     int rc = check_dopri5(who, c, b, h_carry, n_steps, minutes);
     if (rc) return rc;
@@ -1088,6 +1131,9 @@ static int rollout_mlp_dopri5_entry(const char* who, t1d_ctx* c, const t1d_batch
     if (rc) return rc;
     MlpArgs<double> ma = make_mlp<double>(mlp, n_steps);
     ma.cols = cols;
+    if (eo)
+        return launch_mlp_dopri5(who, c, b, cols, minutes, stream, dopri5_mlp_rollout_rel_kernel, ma, make_env_out<double>(eo),
+                                 make_bolus_or_none<double>(mb), (const double*)c->d_raw64, h_carry, nfev);
     if (!mb) return launch_mlp_dopri5(who, c, b, cols, minutes, stream, dopri5_mlp_rollout_kernel, ma, (const double*)c->d_raw64, h_carry, nfev);
     return launch_mlp_dopri5(who, c, b, cols, minutes, stream, dopri5_mlp_rollout_bolus_kernel, ma, make_bolus<double>(mb),
                              (const double*)c->d_raw64, h_carry, nfev);
@@ -1096,7 +1142,7 @@ static int rollout_mlp_dopri5_entry(const char* who, t1d_ctx* c, const t1d_batch
 extern "C" int t1d_rollout_mlp_dopri5(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, double* h_carry, int32_t* nfev,
                                       int n_steps, int minutes, void* stream)
 {
-    return rollout_mlp_dopri5_entry("t1d_rollout_mlp_dopri5", c, b, mlp, nullptr, h_carry, nfev, n_steps, minutes, stream);
+    return rollout_mlp_dopri5_entry("t1d_rollout_mlp_dopri5", c, b, mlp, nullptr, nullptr, h_carry, nfev, n_steps, minutes, stream);
 }
 
 extern "C" int t1d_rollout_mlp_dopri5_bolus(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_meal_bolus* mb, double* h_carry,
@@ -1104,13 +1150,23 @@ extern "C" int t1d_rollout_mlp_dopri5_bolus(t1d_ctx* c, const t1d_batch* b, cons
 {
     const int rc = check_meal_bolus("t1d_rollout_mlp_dopri5_bolus", mb);
     if (rc) return rc;
-    return rollout_mlp_dopri5_entry("t1d_rollout_mlp_dopri5_bolus", c, b, mlp, mb, h_carry, nfev, n_steps, minutes, stream);
+    return rollout_mlp_dopri5_entry("t1d_rollout_mlp_dopri5_bolus", c, b, mlp, nullptr, mb, h_carry, nfev, n_steps, minutes, stream);
+}
+
+extern "C" int t1d_rollout_mlp_dopri5_rel(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_env_output* eo,
+                                          const t1d_meal_bolus* mb, double* h_carry, int32_t* nfev, int n_steps, int minutes, void* stream)
+{
+    const int rc = check_env_output("t1d_rollout_mlp_dopri5_rel", eo, mb);
+    if (rc) return rc;
+    return rollout_mlp_dopri5_entry("t1d_rollout_mlp_dopri5_rel", c, b, mlp, eo, mb, h_carry, nfev, n_steps, minutes, stream);
 }
 
 // The policy alone (mlp_action_kernel, t1d_dopri5.hpp) or its features alone (mlp_features_kernel, t1d_policy.hpp), of
 // the state as it is: nothing is stepped.  what: the name of the output in the messages.
-template <typename K>
-static int launch_mlp_alone(const char* who, const char* what, t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, void* out, void* stream, K kernel)
+// front: what the kernel takes between MlpArgs and the output, as a function of the dtype tag (t1d_mlp_action_rel: the pair).
+template <typename K, typename... F>
+static int launch_mlp_alone(const char* who, const char* what, t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, void* out, void* stream, K kernel,
+                            F... front)
 {
     int rc = check_batch(who, c, b, false);
     if (rc) return rc;
@@ -1123,7 +1179,7 @@ static int launch_mlp_alone(const char* who, const char* what, t1d_ctx* c, const
         MlpArgs<T> ma = make_mlp<T>(mlp, 0);
         ma.cols = cols;
         const Shape sh = shape_mlp_alone<T>(c, b->n, cols);
-        hipLaunchKernelGGL(kernel(t), dim3(sh.grid), dim3(sh.threads), sh.lds, (hipStream_t)stream, make_args<T>(c, b, 1, 1), ma, (T*)out);
+        hipLaunchKernelGGL(kernel(t), dim3(sh.grid), dim3(sh.threads), sh.lds, (hipStream_t)stream, make_args<T>(c, b, 1, 1), ma, front(t)..., (T*)out);
     });
     T1D_HIP(hipGetLastError());
     return T1D_OK;
@@ -1132,6 +1188,14 @@ static int launch_mlp_alone(const char* who, const char* what, t1d_ctx* c, const
 extern "C" int t1d_mlp_action(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, void* action, void* stream)
 {
     return launch_mlp_alone("t1d_mlp_action", "action", c, b, mlp, action, stream, [](auto t) { return mlp_action_kernel<decltype(t)>; });
+}
+
+extern "C" int t1d_mlp_action_rel(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_env_output* eo, void* action, void* stream)
+{
+    const int rc = check_env_output("t1d_mlp_action_rel", eo, nullptr);
+    if (rc) return rc;
+    return launch_mlp_alone("t1d_mlp_action_rel", "action", c, b, mlp, action, stream, [](auto t) { return mlp_action_rel_kernel<decltype(t)>; },
+                            [eo](auto t) { return make_env_out<decltype(t)>(eo); });
 }
 
 extern "C" int t1d_mlp_features(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, void* feat, void* stream)
@@ -1256,15 +1320,19 @@ static CollectArgs<T> make_collect(const t1d_ctx* c, const t1d_collect* g)
     return ga;
 }
 
-// mb == NULL: t1d_collect_mlp; with mb the same kernel family with the bolus switched on (t1d_collect_mlp_bolus)
+// mb == NULL: t1d_collect_mlp; with mb the same kernel family with the bolus switched on (t1d_collect_mlp_bolus); with eo the
+// relative policy's family, with or without mb (t1d_collect_mlp_rel)
 template <typename T>
-static int run_collect_mlp(const char* who, t1d_ctx* c, const t1d_batch* b, const t1d_mlp* m, const t1d_collect* g, const t1d_meal_bolus* mb,
-                           Plan p, int cols, int n_steps, int minutes, int n_sub, hipStream_t s)
+static int run_collect_mlp(const char* who, t1d_ctx* c, const t1d_batch* b, const t1d_mlp* m, const t1d_collect* g, const t1d_env_output* eo,
+                           const t1d_meal_bolus* mb, Plan p, int cols, int n_steps, int minutes, int n_sub, hipStream_t s)
 {
     MlpArgs<T> ma = make_mlp<T>(m, n_steps);
     const int rc = shape_mlp<T>(who, c, b, cols, p, ma);
     if (rc) return rc;
     const RestartArgs<T> ra = g->on_done == T1D_COLLECT_RESTART ? make_restart<T>(g->restart) : RestartArgs<T>{};
+    if (eo)
+        return launch(c, b, p, minutes, n_sub, s, mlp_collect_rel_fn<T>(p.variant), ma, make_collect<T>(c, g), ra, make_env_out<T>(eo),
+                      make_bolus_or_none<T>(mb));
     if (!mb) return launch(c, b, p, minutes, n_sub, s, mlp_collect_fn<T>(p.variant), ma, make_collect<T>(c, g), ra);
     return launch(c, b, p, minutes, n_sub, s, mlp_collect_bolus_fn<T>(p.variant), ma, make_collect<T>(c, g), ra, make_bolus<T>(mb));
 }
@@ -1295,7 +1363,7 @@ static int check_collect(const char* who, const t1d_batch* b, const t1d_mlp* m, 
 }
 
 static int collect_mlp_entry(const char* who, t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_collect* g,
-                             const t1d_meal_bolus* mb, int n_steps, int minutes, int n_sub, void* stream)
+                             const t1d_env_output* eo, const t1d_meal_bolus* mb, int n_steps, int minutes, int n_sub, void* stream)
 {
     int rc = check_collect(who, b, mlp, g, nullptr);
     if (rc) return rc;
@@ -1308,8 +1376,8 @@ static int collect_mlp_entry(const char* who, t1d_ctx* c, const t1d_batch* b, co
     rc = plan_and_tables(who, c, b, minutes, n_sub, true, &p, true);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    rc = p.f64 ? run_collect_mlp<double>(who, c, b, mlp, g, mb, p, cols, n_steps, minutes, n_sub, s)
-               : run_collect_mlp<float>(who, c, b, mlp, g, mb, p, cols, n_steps, minutes, n_sub, s);
+    rc = p.f64 ? run_collect_mlp<double>(who, c, b, mlp, g, eo, mb, p, cols, n_steps, minutes, n_sub, s)
+               : run_collect_mlp<float>(who, c, b, mlp, g, eo, mb, p, cols, n_steps, minutes, n_sub, s);
     if (rc) return rc;
     T1D_HIP(hipGetLastError());
     return T1D_OK;
@@ -1318,7 +1386,7 @@ static int collect_mlp_entry(const char* who, t1d_ctx* c, const t1d_batch* b, co
 extern "C" int t1d_collect_mlp(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_collect* g, int n_steps, int minutes,
                                int n_sub, void* stream)
 {
-    return collect_mlp_entry("t1d_collect_mlp", c, b, mlp, g, nullptr, n_steps, minutes, n_sub, stream);
+    return collect_mlp_entry("t1d_collect_mlp", c, b, mlp, g, nullptr, nullptr, n_steps, minutes, n_sub, stream);
 }
 
 extern "C" int t1d_collect_mlp_bolus(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_collect* g, const t1d_meal_bolus* mb,
@@ -1326,7 +1394,15 @@ extern "C" int t1d_collect_mlp_bolus(t1d_ctx* c, const t1d_batch* b, const t1d_m
 {
     const int rc = check_meal_bolus("t1d_collect_mlp_bolus", mb);
     if (rc) return rc;
-    return collect_mlp_entry("t1d_collect_mlp_bolus", c, b, mlp, g, mb, n_steps, minutes, n_sub, stream);
+    return collect_mlp_entry("t1d_collect_mlp_bolus", c, b, mlp, g, nullptr, mb, n_steps, minutes, n_sub, stream);
+}
+
+extern "C" int t1d_collect_mlp_rel(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_collect* g, const t1d_env_output* eo,
+                                   const t1d_meal_bolus* mb, int n_steps, int minutes, int n_sub, void* stream)
+{
+    const int rc = check_env_output("t1d_collect_mlp_rel", eo, mb);
+    if (rc) return rc;
+    return collect_mlp_entry("t1d_collect_mlp_rel", c, b, mlp, g, eo, mb, n_steps, minutes, n_sub, stream);
 }
 
 // ---- t1d_collect_pid / t1d_collect_bb (ctrl_collect_kernel, t1d_policy.hpp) ----------------------------------------------

@@ -725,6 +725,92 @@ __global__ __launch_bounds__(kBlock, 1) void dopri5_mlp_rollout_bolus_kernel(con
     dopri5_mlp_store_windows(a, c, i, col, s);
 }
 
+// ---- t1d_rollout_mlp_dopri5_rel: the roll-out under a relative policy (t1d_env_output, t1d_policy.hpp) ----------------------
+// dopri5_mlp_rollout_bolus_kernel line for line, with the action formed under the lane's scale and bias and the meal bolus a
+// wave-uniform switch (mb.cr == NULL: none).  The pair is loaded in the boundary block where a step opens, next to the network:
+// like the network's words and the bolus, nothing of it is in a register across dopri5_attempt.  A kernel of its own for the
+// reason given above: the kernels that exist keep their machine code.
+__global__ __launch_bounds__(kBlock, 1) void dopri5_mlp_rollout_rel_kernel(const KArgs<double> a, const MlpArgs<double> c,
+                                                                           const EnvOutArgs<double> eo, const BolusArgs<double> mb,
+                                                                           const double* __restrict__ raw, double* h_carry, int32_t* nfev)
+{
+    typedef RollColdT<64> Cold;
+    __shared__ double lds[kRawPars * kMaxPatients];
+    for (int j = threadIdx.x; j < kRawPars * kMaxPatients; j += blockDim.x) lds[j] = raw[j];
+    __syncthreads();
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    __builtin_assume(i < (1u << 28));          // host guarantees n <= 2^28: i * sizeof(T) fits a 32-bit voffset
+    if ((int64_t)i >= a.n) return;             // n is a multiple of 64: whole waves leave
+    const MlpLaneLds piece = dopri5_mlp_lane_lds(c);
+    const Cold cold = piece.cold;
+    double* const col = piece.col;
+    const int H = c.history;
+    double* const buf = col + 2 * H * 64;
+    const uint32_t meta = at(a.meta, i);
+    const uint32_t pid = T1D_META_PID(meta);
+    Env<double> e;
+    load_env(a, i, meta, e);
+    const ParsRaw p{lds, (int)pid};
+    NoDerivedPars nop;
+    const double div = double(a.minutes);
+    dopri5_mlp_load_windows(a, c, i, col);
+    double hc = at(h_carry, i), noise = 0.0, insulin = 0.0, d_mg = 0.0;
+    StepOut<double> o{0.0, 0.0, 0.0, 0.0};
+    Dopri5Run r{};
+    int nf = 0, m = 0, s = 0;
+    bool due = false, failed = false, boundary = true, fresh = true;
+    cold.save(e, o, noise, hc);
+    for (;;) {
+        if (boundary) {
+            cold.load(e, o, noise, hc);
+            if (!fresh) {
+                e.t += 1;
+                const double gsub = e.x[12] / p(T1D_P_VG);                                    // t1dpatient.py:217-218
+                const double cgm = measure_apply(a, e, gsub, noise, due);                     // env.py:62
+                o.bg += gsub / div; o.cgm += cgm / div;                                       // env.py:80-81
+                if (++m == a.minutes) {                  // the step is complete: what t1d_step_dopri5 leaves, then the roll-out's own
+                    const double rp = e.prev_risk;
+                    write_outputs<0>(a, i, e, o, rp);
+                    dopri5_mlp_step_words(c, i, (c.trace_row + s) * a.n + i, o);
+                    m = 0; ++s;
+                    const int q = s % H, head = q ? H - q : 0;  // the oldest row becomes the newest
+                    col[head * 64] = o.cgm; col[(H + head) * 64] = o.ins;
+                }
+            }
+            if (s == c.n_steps) break;
+            if (m == 0) {                                // a step opens: the network under the lane's pair, the meal bolus, the pump
+                const int q = s % H, head = q ? H - q : 0;
+                const int start = c.start_minute ? (int)at(c.start_minute, i) : 0;
+                const double prev_meal = at(c.prev_meal, i);
+                const double u = mlp_action(c, mlp_wave_weights(c, i), col, buf, head, prev_meal, start + e.t, env_out_lane(eo, i));
+                if (c.act_trace) c.act_trace[(c.trace_row + s) * a.n + i] = u;
+                double bolus = 0.0;
+                if (mb.cr)                               // wave-uniform
+                    bolus = step_bolus(mb, bolus_lane(mb, i), i, double(a.sen.st), col[head * 64], prev_meal, (c.trace_row + s) * a.n + i);
+                insulin = dopri5_mlp_pump(a, u, bolus);
+                o = StepOut<double>{0.0, 0.0, 0.0, 0.0};
+            }
+            const double meal = meal_lookup(a, i, e);                                         // env.py:50
+            noise = measure_noise<true>(a, i, e, due);
+            const MinuteIn<double> u = eat_minute<0, double>(nop, e.x, meal, insulin, e.planned, e.lq, e.lf, e.eating);
+            d_mg = u.d_mg;
+            o.meal += meal / div; o.ins += insulin / div;                                     // env.py:78-79
+            if (!failed) dopri5_enter(p, e.x, d_mg, insulin, e.lq, e.lf, hc, (double)e.t, r, nf);
+            cold.save(e, o, noise, hc);
+            fresh = false; boundary = false;
+        }
+        if (failed) { boundary = true; continue; }
+        const int rc = dopri5_attempt(p, e.x, d_mg, insulin, e.lq, e.lf, cold.f[Cold::HC * 64], (double)e.t + 1.0, r, nf);
+        failed = rc < 0;
+        boundary = rc != 0;
+    }
+    store_env(a, i, pid, e);
+    at(h_carry, i) = hc;
+    if (nfev) at(nfev, i) = nf;
+    if (failed) atomicOr(a.status, T1D_ST_SOLVER_FAILED);
+    dopri5_mlp_store_windows(a, c, i, col, s);
+}
+
 // ---- trajectories for a policy-gradient trainer in the exact mode (t1d_collect_mlp_dopri5) ------------------------------
 // dopri5_mlp_rollout_kernel with the collector's work (mlp_collect_body, t1d_policy.hpp) in the boundary block; solver
 // loop, Cold words, columns, per-lane ring head and weights are that kernel's, line for line.  A kernel of its own: the
@@ -1027,6 +1113,24 @@ __global__ __launch_bounds__(T1D_POLICY_THREADS) void mlp_action_kernel(const KA
     const T prev_meal = at(c.prev_meal, i);
     const int t = at(a.t, i);
     action[i] = mlp_action(c, mlp_wave_weights(c, i), col, col + 2 * H * 64, 0, prev_meal, start + t);
+}
+
+// t1d_mlp_action_rel: mlp_action_kernel under a relative policy -- the action with the lane's scale and bias (t1d_env_output)
+template <typename T>
+__global__ __launch_bounds__(T1D_POLICY_THREADS) void mlp_action_rel_kernel(const KArgs<T> a, const MlpArgs<T> c, const EnvOutArgs<T> eo, T* action)
+{
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    __builtin_assume(i < (1u << 28));          // host guarantees n <= 2^28: i * sizeof(T) fits a 32-bit voffset
+    if ((int64_t)i >= a.n) return;
+    T* const col = (T*)t1d_dyn_lds + (threadIdx.x >> 6) * (c.cols * 64) + (threadIdx.x & 63u);
+    const int H = c.history;
+    col[0] = at(a.cgm, i);
+    for (int k = 1; k < H; ++k) col[k * 64] = at(rowv(c.cgm_hist, a.n, k), i);
+    for (int k = 0; k < H; ++k) col[(H + k) * 64] = at(rowv(c.ins_hist, a.n, k), i);
+    const int start = c.start_minute ? (int)at(c.start_minute, i) : 0;
+    const T prev_meal = at(c.prev_meal, i);
+    const int t = at(a.t, i);
+    action[i] = mlp_action(c, mlp_wave_weights(c, i), col, col + 2 * H * 64, 0, prev_meal, start + t, env_out_lane(eo, i));
 }
 
 } // namespace t1d

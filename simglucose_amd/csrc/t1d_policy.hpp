@@ -354,6 +354,50 @@ __device__ __forceinline__ T step_bolus(const BolusArgs<T>& m, const BolusLane<T
 // the first (the only) member of a kernel's trailing pack
 template <typename A, typename... R> __device__ __forceinline__ const A& pack_first(const A& a, const R&...) { return a; }
 
+// ---- t1d_env_output: a patient-relative output (the *_rel entry points of include/t1d.h) ------------------------------------
+// basal = fma(scale[i], g(y), bias[i]) in the place of fma(out_scale, g(y), out_bias): one weight set commands "a multiple of
+// the patient's own basal rate" for a mixed cohort.  The lanes of a wave belong to different patients, so the pair is two
+// per-lane vector loads and nothing of it is wave-uniform.  Every *_rel kernel forms the action through the mlp_output below,
+// so the word is theirs.  A non-finite scale or bias gives a non-finite basal: what a non-finite network output raises.
+//   scale[i], bias[i]   T1D_REL_LOAD_ONCE = 1: once per launch, two more words alive through every step (the fixed-step kernels
+//                       only: in the exact mode the pair is always loaded where a step opens).  0: at their use, once per
+//                       step -- nothing of the pair is alive across the step.  Loaded once, three of the four fp32 instances
+//                       keep 8 bytes per lane less in scratch and one fp64 instance 4 bytes less; the other four are equal
+//                       (profiles/policy/kernel_resources_rel.txt).  So once per launch is the default.
+#ifndef T1D_REL_LOAD_ONCE
+#define T1D_REL_LOAD_ONCE 1
+#endif
+template <typename T> struct EnvOutArgs { const T* scale; const T* bias; };          // [n] each
+template <typename T> struct EnvOutLane { T scale, bias; };
+
+template <typename T>
+__device__ __forceinline__ EnvOutLane<T> env_out_lane(const EnvOutArgs<T>& eo, unsigned i)
+{
+    return EnvOutLane<T>{at(eo.scale, i), at(eo.bias, i)};
+}
+
+// the basal a relative policy asks for: mlp_output with the lane's pair in the place of out_scale / out_bias, g unchanged
+template <typename T>
+__device__ __forceinline__ T mlp_output(const MlpArgs<T>& c, T y, const EnvOutLane<T>& l)
+{
+    return fma(l.scale, c.out_act == 0 ? y : mlp_logistic(y), l.bias);
+}
+
+// mlp_action under the lane's pair: the action of one step of a relative policy
+template <typename T>
+__device__ __forceinline__ T mlp_action(const MlpArgs<T>& c, const __attribute__((address_space(4))) T* w, const T* col, T* buf,
+                                        int head, T prev_meal, int clock, const EnvOutLane<T>& l)
+{
+    mlp_features(c, col, buf, head, prev_meal, clock);
+    return mlp_output(c, mlp_layers(c, w, buf, 2 * c.history + 3), l);
+}
+
+// what mlp_collect_body's trailing pack means: one BolusArgs -- the *_bolus kernels, a bolus in every step; a BolusArgs and an
+// EnvOutArgs -- the *_rel kernels, the bolus a wave-uniform run-time switch (cr is NULL for a policy without meal_bolus)
+template <typename T> __device__ __forceinline__ bool bolus_on(const BolusArgs<T>&) { return true; }
+template <typename T> __device__ __forceinline__ bool bolus_on(const BolusArgs<T>& m, const EnvOutArgs<T>&) { return m.cr != nullptr; }
+template <typename A, typename B> __device__ __forceinline__ const B& pack_second(const A&, const B& b) { return b; }
+
 // t1d_mlp_bolus: the rule alone, one lane per env -- the bolus the next step of a *_bolus roll-out would ask for, from
 // batch.cgm (CGM[0]) and the policy's prev_meal.  Reads only; writes bolus [n].
 template <typename T>
@@ -366,11 +410,39 @@ __global__ __launch_bounds__(T1D_POLICY_THREADS) void mlp_bolus_kernel(const KAr
     at(bolus, i) = meal_bolus(m, bolus_lane(m, i), i, T(a.sen.st), obs, pm);
 }
 
+// write_outputs (t1d_kernels.hpp) with the risk of o.cgm handed in -- the word the collector's body formed the step's reward
+// with -- instead of evaluated once more.  mlp_collect_body evaluates that risk in its loop, and write_outputs again where a
+// finished env's step goes to memory and where the launch ends; the compiler is free to contract each inlined copy differently,
+// and in an fp64 instance of mlp_collect_rel_kernel the copy in the finished-env branch came out 2 ulp from the loop's for one
+// ending in about five hundred: the env's last_return then was not the loop of one-step launches' word.  The *_rel kernels
+// therefore have one evaluation per step, and everything written about the step comes from it.
+template <int MATH, typename T>
+__device__ __forceinline__ void write_outputs_rc(const KArgs<T>& a, unsigned i, Env<T>& e, const StepOut<T>& o, T rp, T rc)
+{
+    if (ab_flag(a, 0x100)) rc = T(0);
+    at(a.reward, i) = rp - rc;
+    e.prev_risk = rc;
+    at(a.cgm, i) = o.cgm; at(a.bg, i) = o.bg;
+    at(a.done, i) = (o.bg < T(70) || o.bg > T(350)) ? 1 : 0;  // env.py:103
+    if (a.lbgi || a.hbgi || a.risk) {
+        T l, h, r;
+        risk_index1<MATH>(o.bg, l, h, r);                 // env.py:85
+        if (a.lbgi) at(a.lbgi, i) = l;
+        if (a.hbgi) at(a.hbgi, i) = h;
+        if (a.risk) at(a.risk, i) = r;
+    }
+    if (a.meal) at(a.meal, i) = o.meal;
+    if (a.insulin) at(a.insulin, i) = o.ins;
+    if (!(fabs((double)e.x[12]) <= 1.0e300)) atomicOr(a.status, T1D_ST_NONFINITE);
+}
+
 // mlp_rollout_body with the exploration draw, the per-step reward / done / feature histories and the restart of finished
 // envs.  Without sigma and with on_done = 0 it computes what mlp_rollout_body computes, word for word.
 // MB: nothing (bolus 0: t1d_collect_mlp) or one BolusArgs (t1d_collect_mlp_bolus, and t1d_rollout_mlp_bolus in the form just
 // named): the meal bolus of the step goes into the pump's bolus slot beside the network's basal.  A restarted env has
 // prev_meal = 0, hence no bolus on its first step.
+// MB = one BolusArgs and one EnvOutArgs (the *_rel entry points): the action is formed with the lane's scale and bias, and the
+// bolus is there when the BolusArgs has a cr.
 template <int VARIANT, typename T, typename P, typename PR = NoProp, typename... MB>
 __device__ __forceinline__ void mlp_collect_body(const KArgs<T>& a, const MlpArgs<T>& c, const CollectArgs<T>& g, const RestartArgs<T>& r,
                                                  P& p, unsigned i, uint32_t pid, Env<T>& e, T* col, PR pr = PR(), const MB&... mb)
@@ -397,7 +469,9 @@ __device__ __forceinline__ void mlp_collect_body(const KArgs<T>& a, const MlpArg
     T rp = e.prev_risk;                         // risk of the observation the last step started from
     bool fresh = false;                         // the last step ended the episode: outputs and state are in memory already
     BolusLane<T> bl{T(1), T(1)};
-    if constexpr (sizeof...(MB) > 0) bl = bolus_lane(pack_first(mb...), i);
+    if constexpr (sizeof...(MB) > 0) { if (bolus_on(mb...)) bl = bolus_lane(pack_first(mb...), i); }
+    EnvOutLane<T> el{T(1), T(0)};
+    if constexpr (sizeof...(MB) == 2 && T1D_REL_LOAD_ONCE) el = env_out_lane(pack_second(mb...), i);
 #pragma unroll 1
     for (int s = 0; s < c.n_steps; ++s) {
         const int64_t trow = (c.trace_row + s) * a.n + i;
@@ -410,9 +484,11 @@ __device__ __forceinline__ void mlp_collect_body(const KArgs<T>& a, const MlpArg
             eps = (T)philox_pair(g.explore_seed, (uint64_t)(a.env_offset + i), ep, (uint32_t)e.t).x;
             y = fma(sg, eps, y);
         }
-        const T u = mlp_output(c, y);
+        T u;
+        if constexpr (sizeof...(MB) == 2) u = mlp_output(c, y, T1D_REL_LOAD_ONCE ? el : env_out_lane(pack_second(mb...), i));
+        else u = mlp_output(c, y);
         T bolus = T(0);
-        if constexpr (sizeof...(MB) > 0) bolus = step_bolus(pack_first(mb...), bl, i, T(a.sen.st), col[head * 64], prev_meal, trow);
+        if constexpr (sizeof...(MB) > 0) { if (bolus_on(mb...)) bolus = step_bolus(pack_first(mb...), bl, i, T(a.sen.st), col[head * 64], prev_meal, trow); }
         rp = e.prev_risk;
         o = step_body<MATH, T, P, true, PR, VariantInfo<VARIANT>::tiered>(a, p, i, e, u, bolus, true, pr);
         // the step's reward and done, as write_outputs forms them
@@ -440,7 +516,8 @@ __device__ __forceinline__ void mlp_collect_body(const KArgs<T>& a, const MlpArg
         if (g.on_done) {
             if (fin) {
                 // the finished step goes to memory as the end of a launch leaves it; the restart works on those words
-                write_outputs<MATH>(a, i, e, o, rp);
+                if constexpr (sizeof...(MB) == 2) write_outputs_rc<MATH>(a, i, e, o, rp, rc);
+                else write_outputs<MATH>(a, i, e, o, rp);
                 store_env(a, i, pid, e);
                 collect_restart<T>(a, r, g.slots, i);
                 load_env(a, i, at(a.meta, i), e);
@@ -458,7 +535,8 @@ __device__ __forceinline__ void mlp_collect_body(const KArgs<T>& a, const MlpArg
         }
     }
     if (!fresh) {
-        write_outputs<MATH>(a, i, e, o, rp);
+        if constexpr (sizeof...(MB) == 2) write_outputs_rc<MATH>(a, i, e, o, rp, e.prev_risk);     // the last step's risk
+        else write_outputs<MATH>(a, i, e, o, rp);
         store_env(a, i, pid, e);
     }
     for (int k = 0, q = head; k < H; ++k) {                     // the windows back in window order
@@ -543,6 +621,43 @@ __global__ __launch_bounds__(T1D_POLICY_THREADS) void mlp_collect_bolus_kernel(c
     } else {
         ParsLds<T> p{lds, (int)pid};
         mlp_collect_body<VARIANT>(a, c, g, r, p, i, pid, e, col, NoProp(), m);
+    }
+}
+
+// mlp_collect_kernel under a relative policy (t1d_collect_mlp_rel, t1d_rollout_mlp_rel): the same body with a BolusArgs and an
+// EnvOutArgs in its trailing pack.  m.cr == NULL: no meal bolus, a wave-uniform branch in every step -- one family for the
+// relative policy with and without the bolus.
+template <int VARIANT, typename T>
+__global__ __launch_bounds__(T1D_POLICY_THREADS) void mlp_collect_rel_kernel(const KArgs<T> a, const MlpArgs<T> c, const CollectArgs<T> g,
+                                                                               const RestartArgs<T> r, const EnvOutArgs<T> eo, const BolusArgs<T> m)
+{
+    using VI = VariantInfo<VARIANT>;
+    constexpr int kParRows = VI::split ? DP_COUNT : DP_RK4_COUNT;
+    __shared__ T lds[VI::lds_pars ? kParRows * kMaxPatients : 1];
+    if (VI::lds_pars) stage_pars(a, lds, kParRows);
+    if (VI::split) stage_prop(a, (T*)t1d_dyn_lds);
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    __builtin_assume(i < (1u << 28));          // host guarantees n <= 2^28: i * sizeof(T) fits a 32-bit voffset
+    if ((int64_t)i >= a.n) return;
+    T* const col = (T*)(t1d_dyn_lds + c.lds_off) + (threadIdx.x >> 6) * (c.cols * 64) + (threadIdx.x & 63u);
+    const uint32_t meta = at(a.meta, i);
+    const uint32_t pid = T1D_META_PID(meta);
+    Env<T> e;
+    load_env(a, i, meta, e);
+    if constexpr (VARIANT == 4 || VARIANT == 6) {
+        ParsReg<T> p;
+        p.load(a.dpar, (int)pid);
+        mlp_collect_body<VARIANT>(a, c, g, r, p, i, pid, e, col, PropLds<T>{(const T*)t1d_dyn_lds, a.np_pad, (int)pid}, m, eo);
+    } else if constexpr (VARIANT == 7) {
+        ParsLds<T> p{lds, (int)pid};
+        mlp_collect_body<VARIANT>(a, c, g, r, p, i, pid, e, col, PropLds<T>{(const T*)t1d_dyn_lds, a.np_pad, (int)pid}, m, eo);
+    } else if constexpr (VARIANT == 3) {
+        ParsReg<T> p;
+        p.load(a.dpar, (int)pid);
+        mlp_collect_body<VARIANT>(a, c, g, r, p, i, pid, e, col, NoProp(), m, eo);
+    } else {
+        ParsLds<T> p{lds, (int)pid};
+        mlp_collect_body<VARIANT>(a, c, g, r, p, i, pid, e, col, NoProp(), m, eo);
     }
 }
 

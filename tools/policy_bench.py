@@ -29,6 +29,15 @@ the meal workload of tools/collect_bench.py (child#001 / adult#001, random initi
 collector takes no meal bolus).
 
     python tools/policy_bench.py --meal-bolus --dtypes float64 --reps 5 --out profiles/policy/bolus_bench.json
+
+--relative: what the per-env scale and bias of MLPController(relative_to="basal") cost inside the launch, beside the plain and the
+*_bolus calls of the same run, with or without --exact; the legs become
+  mlp, mlp_bolus    as above: the plain policy without and with meal_bolus=140, the two reference points
+  rel, rel_bolus    the same weights with relative_to="basal" (out_scale 3: up to three basal rates), without and with
+                    meal_bolus=140 (t1d_rollout_mlp_rel / t1d_rollout_mlp_dopri5_rel)
+  loop_rel_bolus    policy_action() + policy_bolus() + step(u, bolus) per step under the relative hybrid policy
+
+    python tools/policy_bench.py --relative --dtypes float64 --reps 5 --out profiles/policy/rel_bench.json
 """
 import argparse
 
@@ -51,7 +60,7 @@ def make_env(n, dtype, seed, exact=False):
 
 def run_leg(leg, n, dtype, pol, steps, warmup, seed, exact=False):
     import torch
-    if isinstance(pol, dict):                        # --meal-bolus: the policy of the leg
+    if isinstance(pol, dict):                        # --meal-bolus, --relative: the policy of the leg
         pol = pol[leg]
     e = make_env(n, dtype, seed, exact)
     zero = torch.zeros(n, dtype=dtype, device=e.device)
@@ -60,12 +69,12 @@ def run_leg(leg, n, dtype, pol, steps, warmup, seed, exact=False):
 
     def go(k):
         nonlocal pid_state
-        if leg == "loop_bolus":
+        if leg in ("loop_bolus", "loop_rel_bolus"):
             for _ in range(k):
                 e.step(e.policy_action(pol, state), e.policy_bolus(pol, state))
                 pol.shift(state["cgm_hist"], state["ins_hist"], e.cgm, e.insulin)
                 state["prev_meal"].copy_(e.meal)
-        elif exact and leg in ("mlp", "mlp_bolus"):
+        elif exact and leg in ("mlp", "mlp_bolus", "rel", "rel_bolus"):
             e.rollout_mlp_dopri5(k, pol, policy_state=state)
         elif exact and leg == "pid":
             pid_state = e.rollout_pid_dopri5(k, 1.5e-4, 4e-7, 5e-4, pid_state=pid_state)
@@ -74,7 +83,7 @@ def run_leg(leg, n, dtype, pol, steps, warmup, seed, exact=False):
                 e.step(e.policy_action(pol, state), zero)
                 pol.shift(state["cgm_hist"], state["ins_hist"], e.cgm, e.insulin)
                 state["prev_meal"].copy_(e.meal)
-        elif leg in ("mlp", "mlp_bolus"):
+        elif leg in ("mlp", "mlp_bolus", "rel", "rel_bolus"):
             e.rollout_mlp(k, pol, policy_state=state)
         elif leg == "collect":
             e.collect_mlp(k, pol, policy_state=state)
@@ -90,7 +99,7 @@ def run_leg(leg, n, dtype, pol, steps, warmup, seed, exact=False):
     out = {"us_per_step": 1e3 * ms / steps, "mean_bg": float(e.bg.mean())}
     if exact:
         out["ms"] = ms
-        if leg not in ("host", "loop_bolus"):    # a roll-out leaves the RHS evaluations of the whole call in nfev
+        if leg not in ("host", "loop_bolus", "loop_rel_bolus"):    # a roll-out leaves the RHS evaluations of the whole call in nfev
             out["nfev_mean"] = float(e.nfev.double().mean())
     out["status"] = benchlib.close_leg(e)
     del e
@@ -126,6 +135,7 @@ def main(argv=None):
     ap.add_argument("--label", default=None, help="free text kept in the output (e.g. which build was measured)")
     ap.add_argument("--exact", action="store_true", help="the three legs in the exact mode (integrator='dopri5', fp64)")
     ap.add_argument("--meal-bolus", action="store_true", help="legs mlp, mlp_bolus, loop_bolus: the cost and the worth of the in-kernel meal bolus")
+    ap.add_argument("--relative", action="store_true", help="legs mlp, mlp_bolus, rel, rel_bolus, loop_rel_bolus: the cost of the per-env output")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     if args.exact:
@@ -137,6 +147,12 @@ def main(argv=None):
         hybrid = benchlib.random_policy(args.history, args.widths, hidden="tanh", output="logistic", out_scale=0.06, meal_bolus=140.0)
         args.legs = ["mlp", "mlp_bolus", "loop_bolus"] if args.exact else ["mlp", "collect", "mlp_bolus", "loop_bolus"]
         pol = {"mlp": pol, "collect": pol, "mlp_bolus": hybrid, "loop_bolus": hybrid}
+    if args.relative:
+        mk = lambda **kw: benchlib.random_policy(args.history, args.widths, hidden="tanh", output="logistic", **kw)
+        args.legs = ["mlp", "mlp_bolus", "rel", "rel_bolus", "loop_rel_bolus"]
+        pol = {"mlp": mk(out_scale=0.06), "mlp_bolus": mk(out_scale=0.06, meal_bolus=140.0), "rel": mk(out_scale=3.0, relative_to="basal"),
+               "rel_bolus": mk(out_scale=3.0, relative_to="basal", meal_bolus=140.0)}
+        pol["loop_rel_bolus"] = pol["rel_bolus"]
     results = []
     for name in args.dtypes:
         dtype = getattr(torch, name)
@@ -160,6 +176,12 @@ def main(argv=None):
                 if not args.exact:
                     res["bolus_over_collect"] = med["mlp_bolus"] / med["collect"]
                     res["finish_rate"] = {leg: finish_rate(n, pol[leg], args.steps, args.seed) for leg in ("mlp", "mlp_bolus")}
+            if args.relative:
+                res["bolus_over_mlp"] = med["mlp_bolus"] / med["mlp"]
+                res["rel_over_mlp"] = med["rel"] / med["mlp"]
+                res["rel_bolus_over_mlp_bolus"] = med["rel_bolus"] / med["mlp_bolus"]
+                res["loop_over_rel_bolus"] = med["loop_rel_bolus"] / med["rel_bolus"]
+                res["mlp_spread"] = [min(r["us_per_step"] for r in runs["mlp"]), max(r["us_per_step"] for r in runs["mlp"])]
             if "mlp" in med and "host" in med:
                 res["host_over_mlp"] = med["host"] / med["mlp"]
             if "mlp" in med and "pid" in med:
