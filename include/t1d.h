@@ -926,7 +926,25 @@ int t1d_gae(int hip_device, int dtype, int64_t n, const t1d_gae_batch* io, void*
  * INT32_MAX) and meal_amt [6 (days + 1)][n] (grams, dtype T1D_F64/F32) covering `days` days of an episode
  * that starts at start_minute_of_day[i] (device int32 [n]) or, if that is NULL, at start_scalar for every
  * env.  Statistical counterpart of the reference's numpy stream (Philox, subsequence = env_offset + i);
- * exact replays of a reference scenario go through explicit tables instead.  No ctx needed. */
+ * exact replays of a reference scenario go through explicit tables instead.  No ctx needed.
+ * The stream, draw for draw (restated on the host in oracle/t1d_streams.py): Philox4x32-10 as rocRAND runs it -- counter =
+ * (block lo, block hi, subsequence lo, subsequence hi), key = (key lo, key hi), the block of word offset o is o / 4 -- with
+ *   key = seed ^ 0x5ce9a7105ce9a710: a key domain of the scenario's own, so that a batch and its meal tables may share a seed;
+ *   subsequence g = env_offset + i, all 64 bits of it;
+ *   candidate k = 0 .. 5 (breakfast, snack, lunch, snack, dinner, snack) of calendar day d = 0 .. days (day 0 is the day the
+ *   episode starts in) owns the two blocks at word offset 8 (6 d + k): the first as rocrand_uniform_double2 -> (u.x, u.y) in
+ *   (0, 1], the second as rocrand_normal_double2 -> (g.x, g.y); g.y is not used.
+ * With the windows (p, lb, ub, mu [hours], sd [minutes], grams mean, grams sd) = (.95, 5, 9, 7, 60, 45, 10), (.3, 9, 10, 9.5, 30,
+ * 10, 5), (.95, 10, 14, 12, 60, 70, 10), (.3, 14, 16, 15, 30, 10, 5), (.95, 16, 20, 18, 60, 80, 10), (.3, 20, 23, 21.5, 30, 10, 5)
+ * and Phi the standard normal CDF:
+ *   present = u.x <= p                                                          (rand() < p, :48)
+ *   tod     = rint(60 mu + sd Phi^-1(Phi_a + u.y (Phi_b - Phi_a))) minutes, Phi_a = Phi((60 lb - 60 mu) / sd), Phi_b likewise of
+ *             ub; rint rounds to nearest, ties to even (np.round, :49-54); then clamped to [60 lb, 60 ub] (a guard)
+ *   grams   = max(rint(mean + sd_grams g.x), 0), the zero a +0                   (:56-57)
+ *   minute  = 1440 d + tod - start
+ * A candidate becomes the next row of the env's column if it is present, 0 <= minute < 1440 days, and minute differs from the
+ * minute of the row written before it: windows meet at their bounds, and the reference's scenario keeps one meal per minute,
+ * the earlier one here.  Rows are in candidate order, which is ascending time. */
 int t1d_random_meals(int hip_device, uint64_t seed, int64_t env_offset, int64_t n, int dtype, int days,
                      const int32_t* start_minute_of_day, int start_scalar, int32_t* meal_time, void* meal_amt,
                      void* stream);
@@ -939,7 +957,12 @@ int t1d_outcome_stats(int hip_device, int dtype, int64_t n, int64_t n_rows, cons
  * (draw0 + r) of env (env_offset + i), doubles [n_draws][n] on the device.  Draw 0 is the AR(1)
  * initial value, draws 1.. are the block normals in consumption order (so the array can be fed
  * back as `normals`); draws -3..-1 are the three random_init_bg normals (x[3], x[4], x[12]).
- * Lets a test replay a Philox run through the oracle. */
+ * Lets a test replay a Philox run through the oracle.
+ * philox_pair(seed, g, episode, m) = rocrand_normal_double2 of the Philox4x32-10 block (episode << 24) + m (word offset four
+ * times that; counter and key as under t1d_random_meals) of subsequence g = env_offset + i under key = seed: two Box-Muller
+ * normals (.x, .y).  An episode has 2^24 pairs of its own; episode is the value of batch.episode during it (1 after the
+ * first t1d_reset).  Draw 0 is pair 0 .x; draws -3, -2, -1 are pair 1 .x, pair 1 .y, pair 2 .x; draw 1 + 10 b + j (j = 0 .. 9,
+ * noise block b) is pair 3 + 5 b + j / 2, .x for even j and .y for odd j. */
 int t1d_philox_normals(t1d_ctx* ctx, uint64_t seed, int64_t env_offset, int64_t n, uint32_t episode,
                        int32_t draw0, int32_t n_draws, double* out_device, void* hip_stream);
 

@@ -583,3 +583,78 @@ def status_env(sensor="Navigator", n=STATUS_N, feed=3, options=(), dtype=None, e
     e.set_meals(torch.as_tensor(inp["mt"]), torch.as_tensor(inp["ma"]))
     e.reset()
     return e
+
+
+# ------------------------------------------------------------------------------------------------ the random streams
+# test_streams_host.py, test_gpu_streams.py: what the device draws against oracle/t1d_streams.py, the host restatement written
+# from include/t1d.h and rocRAND's headers.  The cases live here so that the host test can take its census of rounding ties
+# over exactly what the GPU test compares.  Importing and building the references touches no device.
+STREAM_SEED = 11
+STREAM_OFF = 2 ** 32 - 65                 # 130 envs from here straddle 2^32
+# envs of seed 11, start 0, days = 2 in which a meal lands on the minute of the meal before it (found by the restatement
+# among the first 2^21 envs: for c in range(8): random_meals(11, c << 18, 1 << 18, 2, 0).cand["same_minute"])
+SAME_MINUTE_GIDS = (740847, 749116, 1298792, 1588297, 203870, 1617688, 1452703, 418289, 1937777, 1867863)
+# name -> (env_offset, n, start: a minute of day, or "table" for start_table(n))
+MEAL_CASES = {"start0": (0, 4096, 0), "start14h": (0, 4096, 14 * 60), "start_table": (0, 4096, "table"),
+              "past_2_32": (STREAM_OFF, 130, 0)}
+MEAL_CASES.update({"same_minute_%d" % g: (g - 1, 3, 0) for g in SAME_MINUTE_GIDS})
+RESTART_SEED, RESTART_N, RESTART_EPISODES = 3, 130, (0, 1, 5)
+NORMALS_N, NORMALS_DRAW0, NORMALS_DRAWS = 130, -3, 29
+NORMALS_OFFSETS = (0, 2 ** 32 - 65, 2 ** 40 + 3)
+NORMALS_EPISODES = (0, 1, 255, 256, 2 ** 32 - 1)
+NORMALS_SEEDS = (0, 0x9E3779B97F4A7C15)
+
+
+def streams():
+    """oracle/t1d_streams.py"""
+    from oracle import t1d_streams
+    return t1d_streams
+
+
+def start_table(n):
+    """a start minute per env that is no whole hour: every minute of the day comes up"""
+    return ((np.arange(n, dtype=np.int64) * 37 + 5) % 1440).astype(np.int32)
+
+
+@functools.lru_cache(maxsize=None)
+def meal_reference(case):
+    """the restatement's Meals of a case of MEAL_CASES; computed once, treat as read-only"""
+    off, n, start = MEAL_CASES[case]
+    return streams().random_meals(STREAM_SEED, off, n, DAYS, start_table(n) if isinstance(start, str) else start)
+
+
+@functools.lru_cache(maxsize=None)
+def restart_reference(k):
+    """what t1d_restart_done gives env STREAM_OFF + i of seed RESTART_SEED at episode index k: (start_minute int64 [n], the
+    restatement's Meals under seed * 7919 + k); the start hour by the package's host formula"""
+    import torch
+    from simglucose_amd.envs.batched_gym_env import start_hours
+    gid = torch.arange(RESTART_N, dtype=torch.int64) + STREAM_OFF
+    start = 60 * start_hours(RESTART_SEED, k, gid).numpy()
+    return start, streams().random_meals(RESTART_SEED * 7919 + k, STREAM_OFF, RESTART_N, DAYS, start)
+
+
+@functools.lru_cache(maxsize=None)
+def normals_reference(seed, env_offset, episode):
+    """the restatement's Normals (float64 and high precision) of one case of the NORMALS_* cross product"""
+    return streams().normals(seed, env_offset, NORMALS_N, episode, NORMALS_DRAW0, NORMALS_DRAWS, mp=True)
+
+
+def normal_error(z, ref):
+    """|z - (hi + lo)| in units of eps * s, s the sqrt(-2 ln u) of the draw's pair: the error of a set of normals against
+    the high-precision values -> array like z"""
+    return np.abs((z - ref.hi) - ref.lo) / (np.finfo(np.float64).eps * ref.s)
+
+
+def meal_tables_cover_the_branches():
+    """so that an exact comparison of the MEAL_CASES cannot pass on nothing; asserted on the restatement alone"""
+    for case in ("start0", "start14h", "start_table", "past_2_32"):
+        c = meal_reference(case).cand
+        assert (~c["present"]).any() and (c["present"] & ~c["in_range"]).any(), case         # absent; present but filtered
+        assert (c["kept"] & (c["g_raw"] < -0.5)).any() and (c["kept"] & (c["grams"] > 0)).any(), case   # grams clamped to 0
+    c0, c14, ctab = (meal_reference(case).cand for case in ("start0", "start14h", "start_table"))
+    for c in (c14, ctab):                                                      # filtered on both sides of the episode
+        assert (c["present"] & (c["minute"] < 0)).any() and (c["present"] & (c["minute"] >= 1440 * DAYS)).any()
+    assert c0["kept"][DAYS - 1].all(axis=0).any()                                # a full last day: all six meals of it
+    assert c14["kept"][DAYS].any() and not c0["kept"][DAYS].any()                # ... and a cut one after a late start
+    assert any(meal_reference("same_minute_%d" % g).cand["same_minute"].any() for g in SAME_MINUTE_GIDS)
