@@ -525,13 +525,14 @@ __global__ __launch_bounds__(kBlock, T1D_WAVES) void step_kernel(const KArgs<T> 
 // one workgroup fills a CU: T1D_S1_WAVES waves on each of its 4 SIMDs in fp64, T1D_S1D_WAVES_F32 in fp32 (see s1d_threads)
 template <typename T> constexpr int s1_threads();
 #ifndef T1D_S1D_WAVES
-#define T1D_S1D_WAVES 3
+#define T1D_S1D_WAVES 4
 #endif
 #ifndef T1D_S1D_WAVES_F32
 #define T1D_S1D_WAVES_F32 4
 #endif
-// step1d_kernel: three waves per SIMD in fp64 (<= 168 VGPRs); the fp32 instantiation fits four (<= 128: 45.8 against 48.3 us
-// at 1 Mi envs -- there the vector pipe and the memory floor are level, and the fourth wave buys overlap)
+// step1d_kernel: four waves per SIMD (<= 128 VGPRs) in both precisions: 64 chunks per CU are four even rounds for sixteen waves,
+// and the fourth wave covers memory waits (fp32: 45.8 against 48.3 us at 1 Mi envs; fp64: 79.8 against 81.8).  In fp64 that
+// takes both passes on LDS parameters (kS1DLean below): with VGPR parameters the kernel needs 168 registers, three waves
 template <typename T> constexpr int s1d_threads() { return 256 * (sizeof(T) == 4 ? T1D_S1D_WAVES_F32 : T1D_S1D_WAVES); }
 template <typename T> constexpr int s1_threads() { return 256 * (sizeof(T) == 4 ? T1D_S1D_WAVES_F32 : T1D_S1_WAVES); }
 // EXTRA: the optional outputs (lbgi, hbgi, risk, meal, insulin) exist; without them their five pointers and the
@@ -597,6 +598,13 @@ __device__ __forceinline__ S1In<T> s1_unpark(const T* pt, const int* pi, int slo
     return in;
 }
 
+// The two passes of step1d_kernel (modes 2, 3) in fp64 fit 128 VGPRs without scratch only with nothing constant in vector
+// registers across the sub-step loops: split_level_lean, whatever REG says.  lconst then holds the step sizes of level 1 and of
+// level 2 behind the limits (kS1DConstHc), formed once per workgroup.  (The list pass on VGPR parameters spills 56 values there,
+// 19 scratch accesses in its sub-step loop: 88.6 us.)
+template <typename T, int MODE> constexpr bool kS1DLean = sizeof(T) == 8 && (MODE == 2 || MODE == 3);
+constexpr int kS1DConstHc(int level) { return level == 1 ? 8 : 13; }
+constexpr int kS1DConst = 18;
 template <bool REG, typename T, int STRIDE, bool EXTRA, int MODE, typename ONLEVEL>
 __device__ __forceinline__ void s1_chunk(const KArgs<T>& a, T* ldp, T* lpr, T* lconst, unsigned i, const S1In<T>& in,
                                          ONLEVEL&& on_level, long long* tr, int tk)
@@ -678,6 +686,9 @@ __device__ __forceinline__ void s1_chunk(const KArgs<T>& a, T* ldp, T* lpr, T* l
         PropLdsS<T, STRIDE> pr{lpr, (int)pid};
         if (MODE == 1) {
             split_minute_tiered(pl, pr, u, e.x, a.n_sub);
+        } else if constexpr (kS1DLean<T, MODE>) {
+            ParsLdsH<T, STRIDE> ph{ldp, (int)pid};
+            split_level_lean<LEVEL, T, ParsLdsH<T, STRIDE>, decltype(pr), MODE == 2>(ph, pr, u, e.x, a.n_sub, f1, lconst + kS1DConstHc(LEVEL));
         } else if (REG) {
             ParsReg<T> p;
 #pragma unroll
@@ -855,8 +866,10 @@ __global__ __launch_bounds__(s1_threads<T>(), 1) void step1_kernel(const KArgs<T
 // the last eighth of the chunks in a pool any CU draws from through counters in device memory once its own run is done
 // (one counter: the draws serialise, +30 us; one per XCD: no faster than without); two waves per SIMD with the next
 // chunk's loads issued ahead of the integration: 88 us against 83.)
-// The list pass too takes its parameters from VGPRs: it ends the launch alone on its SIMDs, where LDS round trips in the
-// dependent chains count.
+// In fp32 the list pass too takes its parameters from VGPRs: it ends the launch alone on its SIMDs, where LDS round trips in the
+// dependent chains count.  In fp64 both passes read them from LDS (kS1DLean): the list pass then takes 11.3 us where it took
+// 10 (13.6 with the parameters read again at every stage, when it hung off the end of the four even rounds), and ends beside
+// the last chunks of the main pass (profiles/r05/README.md).
 template <typename T, bool EXTRA>
 __global__ __launch_bounds__(s1d_threads<T>(), 1) void step1d_kernel(const KArgs<T> a, int nchunks)
 {
@@ -872,9 +885,18 @@ __global__ __launch_bounds__(s1d_threads<T>(), 1) void step1d_kernel(const KArgs
     // [per_block * 64] envs of level 2, as offsets from the workgroup's first env (< 65536: t1d_step)
     uint16_t* const list = (uint16_t*)(park_i + 3 * kS1DPark);
     __shared__ int queue, taken, listed, passed;
-    __shared__ T lconst[8];
+    __shared__ T lconst[kS1DLean<T, 2> ? kS1DConst : 8];
     s1_stage_image<T, s1d_threads<T>()>(a, ldp, lconst);
     if (threadIdx.x == 0) { queue = 0; taken = 0; listed = 0; passed = 0; }
+    if constexpr (kS1DLean<T, 2>) {
+        if (threadIdx.x == 0) {
+            T hc[5];
+            split_step_sizes<T>(a.n_sub, hc);
+            for (int k = 0; k < 5; ++k) lconst[kS1DConstHc(1) + k] = hc[k];
+            split_step_sizes<T>(2 * a.n_sub, hc);
+            for (int k = 0; k < 5; ++k) lconst[kS1DConstHc(2) + k] = hc[k];
+        }
+    }
     __syncthreads();
     const int first = (int)blockIdx.x * per_block;
     const int count = nchunks - first < per_block ? nchunks - first : per_block;

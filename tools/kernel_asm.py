@@ -143,6 +143,47 @@ def loops(kernel):
     return out
 
 
+NestLoop = collections.namedtuple("NestLoop", "header depth parent children lines")
+
+
+def loop_nest(kernel):
+    """The kernel's loops as the compiler saw them, from the comments it leaves on every basic block (`=>This Loop Header:
+    Depth=d`, `Parent Loop BBf_n Depth=d` above it, `in Loop: Header=BBf_n Depth=d` on the other blocks): header label ->
+    NestLoop(header, depth, parent header or None, child headers, the body lines of the loop's own blocks -- those of its child
+    loops are theirs), in body order.  Unlike loops(), which goes by back edges, a block the layout has moved behind its
+    loop's latch still counts to that loop."""
+    out, parents, current = {}, [], None
+    for l in kernel.body:
+        block = re.match(r"(?:\.L(BB\d+_\d+)|; %bb\.\d+):", l)
+        if block:
+            parents, current = [], None
+        m = re.search(r";\s+Parent Loop (BB\d+_\d+) Depth=(\d+)", l)
+        if m:
+            parents.append(m.group(1))
+        m = re.search(r"; =>\s*This (?:Inner )?Loop Header: Depth=(\d+)", l)
+        if m:
+            # a header's own line either carries the mark or opens the comment block that ends with it
+            header = block.group(1) if block else pending
+            parent = parents[-1] if parents else None
+            out[header] = NestLoop(header, int(m.group(1)), parent, [], [])
+            if parent in out:
+                out[parent].children.append(header)
+            current = header
+        if block:
+            pending = block.group(1)
+            m = re.search(r"in Loop: Header=(BB\d+_\d+) Depth=\d+", l)
+            if m:
+                current = m.group(1)
+        if current in out:
+            out[current].lines.append(l)
+    return out
+
+
+def nest_lines(nest, header):
+    """the body lines of a loop of loop_nest() with those of every loop inside it"""
+    return nest[header].lines + [l for c in nest[header].children for l in nest_lines(nest, c)]
+
+
 def instruction_stream(kernel):
     """What two builds are compared on: the instruction and label lines without comments, `.LBB<f>_<n>` without the
     function's index f, and every mangled symbol as one token (the kernel's own name in its first line included)."""

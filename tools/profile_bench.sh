@@ -3,7 +3,8 @@
 # and the SQ instruction counters in passes of their own (MI355X_MICROARCH.md: counters are collected without any trace
 # domain).  The trace pass times 4 000 launches behind 400 warm-up ones.  Writes gpurun_out/<round>_*_TAG and
 # gpurun_out/traffic_TAG.json (copy into profiles/<round>/traffic.json for bench.py to pick up).
-# usage: tools/profile_bench.sh TAG [bench args]
+# Every pass runs under a time limit of its own (T1D_PASS_TIMEOUT seconds, default 600) and the first one that fails ends the script.
+# usage: [T1D_ROUND=r05] tools/profile_bench.sh TAG [bench args]
 set -e
 tag=${1:-v1}; shift || true
 round=${T1D_ROUND:-r03}
@@ -12,10 +13,11 @@ out=$root/gpurun_out
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 common="--no-cpu-baseline --no-accuracy"
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/${round}_stats_$tag -- python3 $root/bench.py --prewarm 0 --warmup 400 --steps 4000 $common "$@" > $out/bench_prof_$tag.json 2> $out/bench_prof_$tag.err
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/${round}_fetch_$tag -- python3 $root/bench.py --prewarm 0 --steps 20 --warmup 5 $common "$@" > /dev/null 2> $out/fetch_$tag.err
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/${round}_write_$tag -- python3 $root/bench.py --prewarm 0 --steps 20 --warmup 5 $common "$@" > /dev/null 2> $out/write_$tag.err
-rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY --output-format csv -d $out/${round}_sq_$tag -- python3 $root/bench.py --prewarm 0 --steps 20 --warmup 5 $common "$@" > /dev/null 2> $out/sq_$tag.err
+limit="timeout -k 10 ${T1D_PASS_TIMEOUT:-600}"
+$limit rocprofv3 --kernel-trace --stats --output-format csv -d $out/${round}_stats_$tag -- python3 $root/bench.py --prewarm 0 --warmup 400 --steps 4000 $common "$@" > $out/bench_prof_$tag.json 2> $out/bench_prof_$tag.err
+$limit rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/${round}_fetch_$tag -- python3 $root/bench.py --prewarm 0 --steps 20 --warmup 5 $common "$@" > /dev/null 2> $out/fetch_$tag.err
+$limit rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/${round}_write_$tag -- python3 $root/bench.py --prewarm 0 --steps 20 --warmup 5 $common "$@" > /dev/null 2> $out/write_$tag.err
+$limit rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY --output-format csv -d $out/${round}_sq_$tag -- python3 $root/bench.py --prewarm 0 --steps 20 --warmup 5 $common "$@" > /dev/null 2> $out/sq_$tag.err
 cd $root
 python3 - "$tag" "$round" <<'PY'
 import csv, glob, json, statistics, sys
