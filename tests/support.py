@@ -270,12 +270,13 @@ def header_fields(name):
 TRACES = MLP_TRACE + ("reward", "done", "eps", "features")
 
 
-def loop_of_entry_points(e, pol, K, acc, tr, term, es, exact=False):
+def loop_of_entry_points(e, pol, K, acc, tr, term, es, exact=False, st=None, restart=True):
     """what a trainer does without the collector: per step rollout_mlp(1) or rollout_mlp_dopri5(1), restart_done, the torch
-    reset of the policy state -> policy state, low endings, high endings, summed nfev"""
+    reset of the policy state -> policy state, low endings, high endings, summed nfev.  st: the policy state of an earlier
+    call, to go on from it; restart=False: no restart_done (term and es are not used), the loop a multi-step roll-out is"""
     torch = gpu_torch()
     rollout = e.rollout_mlp_dopri5 if exact else e.rollout_mlp
-    st = e.new_policy_state(pol)
+    st = e.new_policy_state(pol) if st is None else st
     low = high = 0
     zero = torch.zeros((), dtype=e.dtype, device=e.device)
     nf = torch.zeros(e.n, dtype=torch.int64, device=e.device)
@@ -286,6 +287,8 @@ def loop_of_entry_points(e, pol, K, acc, tr, term, es, exact=False):
         done = e.done.bool()
         tr["reward"][row] = e.reward; tr["done"][row] = e.done
         low = low + (done & (e.bg < 70)).sum(); high = high + (done & (e.bg > 350)).sum()
+        if not restart:
+            continue
         e.restart_done(days=DAYS, terminal_obs=term, episode_stats=es)
         st["cgm_hist"].copy_(torch.where(done, e.cgm, st["cgm_hist"]))           # new_policy_state for the envs that restarted
         st["ins_hist"].copy_(torch.where(done, zero, st["ins_hist"]))
@@ -570,19 +573,122 @@ def status_oracle(sensor="Navigator", exact=False, poison=None, n=STATUS_N, feed
     return out
 
 
-def status_env(sensor="Navigator", n=STATUS_N, feed=3, options=(), dtype=None, exact=False, z=None, meal_step=1, **kw):
+def status_env(sensor="Navigator", n=STATUS_N, feed=3, options=(), dtype=None, exact=False, z=None, meal_step=1, make=None, **kw):
     """the device env of the status inputs: host normals (z: others), the meal table, `options` as (name, value) pairs
-    set before reset(), reset"""
+    set before reset(), reset.  make: what builds the env from BatchedT1DSimEnv's arguments (test_gpu_parity._env with its
+    variant bound, for the generic kernel's other schemes), None: BatchedT1DSimEnv itself"""
     torch = gpu_torch()
     from simglucose_amd.batch_env import BatchedT1DSimEnv
     inp = status_inputs(sensor, n, feed, meal_step)
-    e = BatchedT1DSimEnv(patient=inp["pid"], sensor=sensor, noise="host", normals=inp["z"] if z is None else z, n_sub=4,
-                         dtype=dtype or torch.float64, integrator="dopri5" if exact else None, **kw)
+    e = (make or BatchedT1DSimEnv)(patient=inp["pid"], sensor=sensor, noise="host", normals=inp["z"] if z is None else z, n_sub=4,
+                                   dtype=dtype or torch.float64, integrator="dopri5" if exact else None, **kw)
     for name, value in options:
         e.set_option(name, value)
     e.set_meals(torch.as_tensor(inp["mt"]), torch.as_tensor(inp["ma"]))
     e.reset()
     return e
+
+
+# ------------------------------------------------------------------------------------------------ model branch points
+# test_edge_states_host.py, test_gpu_edge_states.py: the status inputs again, but what is written after the STATUS_PRE steps
+# is finite: states at which the model itself branches.  One function edits the oracle's state and the device's.
+EDGE_LANES = {                                   # kind -> lanes: each kind in chunk 0, in chunk 1 and in the partial chunk
+    "held3": (64, 70, 101, 149, 12),             # x3 < 0: the reference holds it (t1d_oracle.c:58)
+    "cross_m1": (20, 90, 140),                   # x3 falls through 0 in the first minute after the edit ...
+    "cross_m2": (22, 92, 142),                   # ... in the second: the middle minute of a Dexcom step
+    "neg4": (3, 17, 40, 130, 100),               # x4 < 0, held (:63)
+    "neg12": (5, 17, 63, 131, 80),               # x12 < 0, held (:82): BG < 0, `done`
+    "ke2_down": (7, 71, 133),                    # x3 falls through the renal threshold ke2 in the first minute (:55)
+    "ke2_up": (9, 72, 135),                      # ... rises through it
+    "egp_neg": (11, 74, 137),                    # EGPt < 0, clamped (:57)
+    "done_high": (40, 100, 145),                 # BG a little above 350 mg/dL (lanes 40 and 100: also neg4)
+    "done_low": (42, 104, 147),                  # BG a little below 70 mg/dL
+}
+EDGE_CROSSING = {"cross_m1": 1, "cross_m2": 2}   # kind -> the minute after the edit in which x3 reaches 0
+EDGE_HELD = {"held3": (3, -0.25), "neg4": (4, -1e-3), "neg12": (12, -2e-3)}     # kind -> the word the reference holds, its value
+EDGE_SNAP = -1e-10                               # where the fixed-step scheme leaves an x3 that a step took below 0 (o_knob[3])
+EDGE_OUT = GRID_OUT + ("last_cgm", "x")
+
+
+def edge_states(x, pid):
+    """x: the state [13, n] of the oracle (numpy) or of a device env (torch), n >= 150, edited in place after the STATUS_PRE
+    steps; pid: the patient row per env.  Every value is formed on the host in fp64 and written as a Python float, so the
+    oracle and an fp64 env receive the same words.  -> EDGE_LANES.
+    done_high and done_low write x3 along with x12: x12 follows x3 at ksc (0.06 to 0.2 per minute), so a lone x12 = 351 Vg is
+    back at 332 to 335 mg/dL, and a lone 69.5 Vg at 76 to 78, by the end of the first minute and `done` is never raised
+    (test_edge_states_host.py shows it on the oracle).  With x3 = 380 Vg (62 Vg) beside it, BG stays within 3 mg/dL of the
+    threshold for the first step after the edit, beyond it in some lanes and short of it in others."""
+    from simglucose_amd import params
+    _, tab = params.patient_table()
+    pid = np.asarray(pid)
+    ke2, vg = tab[pid, params.P_COL["ke2"]], tab[pid, params.P_COL["Vg"]]
+
+    def put(word, i, value):
+        x[word][i] = float(value)
+
+    L = EDGE_LANES
+    for kind, (word, value) in EDGE_HELD.items():
+        for i in L[kind]:
+            put(word, i, value)
+    for i in L["cross_m1"] + L["cross_m2"]:
+        put(3, i, 0.05 if i in L["cross_m1"] else 1.4); put(4, i, 0.0); put(8, i, 500.0)
+    for i in L["ke2_down"]:
+        put(3, i, ke2[i] + 0.3)
+    for i in L["ke2_up"]:
+        put(3, i, ke2[i] - 0.3); put(4, i, float(x[4][i]) * 1.5)
+    for i in L["egp_neg"]:
+        put(8, i, 500.0)
+    for i in L["done_high"]:
+        put(12, i, 351.0 * vg[i]); put(3, i, 380.0 * vg[i])
+    for i in L["done_low"]:
+        put(12, i, 69.5 * vg[i]); put(3, i, 62.0 * vg[i])
+    return L
+
+
+def edge_lanes(*kinds):
+    """the lanes of the given kinds, sorted, each once"""
+    return sorted({i for k in kinds for i in EDGE_LANES[k]})
+
+
+def edge_oracle_run(sensor="Navigator", integrator="split_adaptive", feed=3, meal_step=1, after_edit=None, minutes=False):
+    """The oracle over the status inputs with edge_states written after STATUS_PRE steps (after_edit(x): a further edit of
+    the state, in place).  minutes: the same patients' minutes under a one-minute sensor, minute by minute, as status_lanes
+    drives them -- the patient does not depend on the sensor.
+    -> dict: EDGE_OUT after every step (minute) as arrays [K, n] (x: [K, 13, n]), x_edit = the state as written, level2 =
+    lane-minutes at level 2 per step [K], final = the last x, lanes = EDGE_LANES.  A solver that gives up raises."""
+    from oracle import t1d_oracle as O
+    inp = status_inputs(sensor, STATUS_N, feed, meal_step)
+    st = inp["st"]
+    if minutes:
+        orc = O.OracleEnv(inp["pid"], sensor="Navigator", normals=inp["z"], integrator=integrator, n_sub=4)
+        assert orc.sample_time == 1
+    else:
+        orc = status_oracle_env(inp, integrator)
+    per = st if minutes else 1                                   # oracle steps per step of the inputs
+    orc.reset()
+    rows = {k: [] for k in EDGE_OUT + ("level2",)}
+    x_edit = None
+    for k in range(inp["K"] * per):
+        if k == STATUS_PRE * per:
+            edge_states(orc.x, inp["pid"])
+            if after_edit is not None:
+                after_edit(orc.x)
+            x_edit = orc.x.copy()
+        before = int(orc.level_count[2])
+        r = orc.step(grid_action(inp, k // per), None, inp["cho"][k:k + 1] if minutes else inp["cho"][k * st:(k + 1) * st])
+        for key in GRID_OUT:
+            rows[key].append(r[key].copy())
+        rows["last_cgm"].append(orc.last_cgm.copy()); rows["x"].append(orc.x.copy())
+        rows["level2"].append(int(orc.level_count[2]) - before)
+    out = {k: np.stack(v) for k, v in rows.items()}
+    out.update(x_edit=x_edit, final=orc.x.copy(), lanes=EDGE_LANES)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def edge_oracle(sensor="Navigator", integrator="split_adaptive", feed=3, meal_step=1):
+    """edge_oracle_run, computed once per argument set; treat as read-only"""
+    return edge_oracle_run(sensor, integrator, feed, meal_step)
 
 
 # ------------------------------------------------------------------------------------------------ the random streams

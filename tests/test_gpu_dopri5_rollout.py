@@ -20,9 +20,10 @@ STATE = ("x", "t", "cgm", "bg", "reward", "last_cgm", "prev_risk", "planned", "h
 MILD = (1.5e-4, 4e-7, 5e-4)
 
 
-def _step_loop(e, kind, K, gains=MILD, target=140.0):
+def _step_loop(e, kind, K, gains=MILD, target=140.0, state=None):
     """A: one launch per step, the controller in torch fp64 between the launches, in the order rollout_body writes it
-    (torch does not fuse: every product is rounded before it is added).  -> controller state, trace rows, summed nfev"""
+    (torch does not fuse: every product is rounded before it is added).  state: the controller state an earlier call
+    returned, to go on from it.  -> controller state, trace rows, summed nfev"""
     import torch
     n, dv = e.n, e.device
     zero = torch.zeros(n, dtype=torch.float64, device=dv)
@@ -31,10 +32,10 @@ def _step_loop(e, kind, K, gains=MILD, target=140.0):
     obs = e.cgm.clone()
     if kind == "bb":
         c = e.bb_constants()
-        meal = zero.clone()
+        meal = zero.clone() if state is None else state["prev_meal"].clone()
     else:
         P, I, D = gains
-        integ, prev = zero.clone(), zero.clone()
+        integ, prev = (zero.clone(), zero.clone()) if state is None else (state["integ"].clone(), state["prev"].clone())
     for k in range(K):
         if kind == "bb":
             corr = torch.where(obs > 150.0, (obs - target) / c["cf"], zero)

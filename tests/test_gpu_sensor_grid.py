@@ -190,18 +190,21 @@ PID = (0.001, 0.00001, 0.001, 140.0)                            # P, I, D, targe
 LOOP_KEYS = ("x", "t", "cgm", "bg", "last_cgm", "prev_risk", "reward", "planned", "meal", "insulin")
 
 
-def _step_by_step(st, ctrl):
+def _step_by_step(st, ctrl, e=None, K=None, before=None):
     """K x (controller on the host with the custom sample time + t1d_step) -> the env's LOOP_KEYS and the controller state,
-    on the host"""
+    on the host.  e, K: another env of sample time st and its number of steps (test_gpu_edge_states.py), None: the grid's;
+    before(k): called ahead of step k"""
     torch = _torch()
-    K = grid_inputs(st)["K"]
-    e = grid_env(st)
+    K = grid_inputs(st)["K"] if K is None else K
+    e = grid_env(st) if e is None else e
     n = e.n
     obs = e.cgm.clone()
     if ctrl == "pid":
         P, I, D, target = PID
         integ = torch.zeros(n, dtype=torch.float64, device=e.device); prev = torch.zeros_like(integ)
         for k in range(K):                                      # pid_ctrller.py:17-36
+            if before is not None:
+                before(k)
             u = P * (obs - target) + I * integ + D * (obs - prev) / float(st)
             prev = obs.clone(); integ = integ + (obs - target) * float(st)
             e.step(u, torch.zeros_like(u))
@@ -212,6 +215,8 @@ def _step_by_step(st, ctrl):
         meal = torch.zeros(n, dtype=torch.float64, device=e.device)
         boluses = 0
         for k in range(K):                                      # basal_bolus_ctrller.py:34-80
+            if before is not None:
+                before(k)
             bolus = torch.where(meal > 0, ((meal * st) / c["cr"] + (obs > 150) * (obs - 140.0) / c["cf"]) / st, torch.zeros_like(meal))
             boluses += int((bolus > 0).sum())
             e.step(c["basal"], bolus)
