@@ -5,9 +5,11 @@
 // sees one coalesced read and one coalesced write of the struct-of-arrays state per launch.
 //
 // Per-patient parameters reach the RHS in one of two ways (template policy):
-//   ParsLds / ParsLdsS  the table is staged in LDS (param-major: lanes holding different patients hit
+//   ParsLdsS    the table is staged in LDS (param-major: lanes holding different patients hit
 //               different banks, equal patients broadcast) and each evaluation re-reads what it
-//               needs, so no parameter occupies a VGPR across the sub-step loops;
+//               needs, so no parameter occupies a VGPR across the sub-step loops.  One template with
+//               the row stride and the hold property as arguments; ParsLds<T> (the device table's
+//               stride) and ParsLdsH<T, STRIDE> (reads held across the stages of a step) are aliases;
 //   ParsReg     gathered once per lane into VGPRs (no LDS round trip in the dependent chains).
 //
 // Reference behaviour restated here (paths relative to the reference checkout):
@@ -39,22 +41,27 @@ constexpr int DP_RK4_COUNT = DP_CF;    // rows the classical-RK4 kernels stage
 constexpr int kMaxPatients = 64;       // row stride of the table (device and LDS): 47 x 64 x 8 B = 23.5 KiB
 constexpr int kBlock = 256;
 
-// parameters re-read from LDS at every use; refresh() makes the base opaque so the compiler
-// cannot hoist the reads out of an RHS evaluation and pin them in VGPRs
-template <typename T> struct ParsLds {
+// parameters re-read from LDS at every use; refresh_block() makes the base opaque so the compiler cannot hoist the reads
+// above it and pin them in VGPRs.  refresh() is what every RHS evaluation calls (rhs, glucose_rhs, ...): the same barrier,
+// unless HOLD -- then a read may be kept from one stage to the next, and only the caller says where reads start afresh
+// (split_level does at every gut step and glucose step).
+template <typename T, int STRIDE, bool HOLD = false> struct ParsLdsS {
     static constexpr bool kSplitRk4 = false;   // measured (1 Mi envs, fp64): 93 us/minute unsplit vs 98 split
-    const T* base;     // the __shared__ table, [DP_COUNT][kMaxPatients]: one ds_read with an immediate offset per use
+    static constexpr bool kHold = HOLD;
+    const T* base;     // the __shared__ table, [DP_COUNT][STRIDE]: one ds_read with an immediate offset per use
     int pid;
-    __device__ __forceinline__ T operator()(int idx) const { return base[idx * kMaxPatients + pid]; }
-    __device__ __forceinline__ void refresh() { asm volatile("" : "+v"(pid)); }
+    __device__ __forceinline__ T operator()(int idx) const { return base[idx * STRIDE + pid]; }
+    __device__ __forceinline__ void refresh_block() { asm volatile("" : "+v"(pid)); }
+    __device__ __forceinline__ void refresh() { if (!HOLD) refresh_block(); }
     __device__ __forceinline__ void pin() {}
     __device__ __forceinline__ void pin_split() {}
 };
+template <typename T> using ParsLds = ParsLdsS<T, kMaxPatients>;                    // the table at the device's row stride
+template <typename T, int STRIDE> using ParsLdsH = ParsLdsS<T, STRIDE, true>;
 // the parameters the fast-math RHS reads (everything else is per-minute set-up)
 __device__ constexpr int kRhsPars[] = {DP_KMAX, DP_DK, DP_KABS, DP_RATC, DP_KP1, DP_KP2, DP_KP3, DP_FSNC, DP_KE1, DP_KE2,
                                        DP_K1, DP_K2, DP_VM0, DP_VMX, DP_KM0, DP_M24, DP_M1, DP_KA1, DP_KA2, DP_IVI, DP_P2U,
                                        DP_IB, DP_KI, DP_M130, DP_M2, DP_KA1KD, DP_KD, DP_KSC};
-// the parameters the split integrator reads inside its loops
 // the parameters the split integrator reads inside its loops (the x2 weights by level: kSplitW below)
 __device__ constexpr int kSplitPars[] = {DP_KMAX, DP_DK, DP_RATC, DP_KP1, DP_KP2, DP_KP3, DP_FSNC, DP_KE1, DP_KE2, DP_K1, DP_K2,
                                          DP_VM0, DP_VMX, DP_KM0, DP_KSC, DP_CF};
@@ -62,9 +69,11 @@ __host__ __device__ constexpr int kSplitW(int level) { return level == 1 ? DP_X2
 // parameters gathered once per lane from the (L2-resident) table and held in VGPRs for the launch
 template <typename T> struct ParsReg {
     static constexpr bool kSplitRk4 = true;    // measured: 75 us/minute split vs 79 unsplit, and far fewer spills around the loop
+    static constexpr bool kHold = false;
     T v[DP_COUNT];
     __device__ __forceinline__ T operator()(int idx) const { return v[idx]; }
     __device__ __forceinline__ void refresh() {}
+    __device__ __forceinline__ void refresh_block() {}
     // make the RHS parameters register-resident HERE (any spill reload happens before this point)
     __device__ __forceinline__ void pin()
     {
@@ -410,27 +419,8 @@ __device__ __forceinline__ void rk4_substeps_split(P& p, const MinuteIn<T>& u, T
 __host__ __device__ constexpr int kPropRows(int n_sub) { return 28 * n_sub + 21; }
 
 struct NoProp { static constexpr bool kSplit = false; };
-// compact LDS tables with a compile-time row stride (persistent single-minute kernel): every read is one
-// ds_read_b64 with an immediate offset
-template <typename T, int STRIDE> struct ParsLdsS {
-    static constexpr bool kSplitRk4 = false;
-    const T* base; int pid;
-    __device__ __forceinline__ T operator()(int idx) const { return base[idx * STRIDE + pid]; }
-    __device__ __forceinline__ void refresh() { asm volatile("" : "+v"(pid)); }
-    __device__ __forceinline__ void pin() {}
-    __device__ __forceinline__ void pin_split() {}
-};
-// as ParsLdsS, but refresh() -- which glucose_rhs calls at every stage -- does nothing: a read may be kept from one stage to the
-// next, and the caller says where reads start afresh (refresh_block: split_level_lean does at every gut step and glucose step)
-template <typename T, int STRIDE> struct ParsLdsH {
-    static constexpr bool kSplitRk4 = false;
-    const T* base; int pid;
-    __device__ __forceinline__ T operator()(int idx) const { return base[idx * STRIDE + pid]; }
-    __device__ __forceinline__ void refresh() {}
-    __device__ __forceinline__ void refresh_block() { asm volatile("" : "+v"(pid)); }
-    __device__ __forceinline__ void pin() {}
-    __device__ __forceinline__ void pin_split() {}
-};
+// compact LDS tables with a compile-time row stride (persistent single-minute kernel, as ParsLdsS<T, 32>): every read is
+// one ds_read_b64 with an immediate offset
 template <typename T, int STRIDE> struct PropLdsS {
     static constexpr bool kSplit = true;
     const T* base; int pid;
@@ -520,12 +510,29 @@ __device__ __forceinline__ void split_level(P& p, const PR& pr, const MinuteIn<T
                                             bool refine = false, const T* hc = nullptr)
 {
     // (HC at LEVEL 0: hc holds level 1's five words followed by level 2's)
+    // kLean: a kernel with no register to spare (step1d_kernel in fp64: four waves per SIMD, 128 VGPRs) hands in a view that
+    // holds its reads (ParsLdsH).  The same arithmetic in the same order, so the same bits; what differs is where the
+    // constants wait:
+    //   * every parameter is read from LDS in the gut step or the glucose step that uses it and kept for that step only
+    //     -- read again at each of the glucose step's four stages (ParsLdsS) the same launch takes 85.0 us against 79.8;
+    //   * the x2 weights are read where the gut step ends, not at the top of the minute;
+    //   * the five step sizes (hc: split_step_sizes' words in LDS) are the same in every lane and wait in scalar registers.
+    constexpr bool kLean = P::kHold;
+    static_assert(!kLean || (HC && LEVEL != 0 && sizeof(T) == 8), "a holding view: levels 1 and 2 in fp64, step sizes from hc");
     const bool r2 = LEVEL == 2 || (LEVEL == 0 && refine);        // this lane at level 2
     const int sb = r2 ? 1 : 2;                                    // propagator blocks per glucose half step
     const int nh = r2 ? 2 * n_sub : n_sub;                        // glucose half steps = gut steps in the minute
     const int ns = nh >> 1;
     T h, H, H6, hh, h6;                                           // h: glucose half step = gut step
-    if (HC) {
+    if constexpr (kLean) {
+        auto uniform = [&](int k) -> T {                          // a word every lane reads alike, as a scalar pair
+            const double v = (double)hc[k];
+            const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)__double2loint(v));
+            const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)__double2hiint(v));
+            return (T)__hiloint2double((int)hi, (int)lo);
+        };
+        h = uniform(0); hh = uniform(1); h6 = uniform(2); H = uniform(3); H6 = uniform(4);
+    } else if (HC) {
         int z = LEVEL == 0 && r2 ? 5 : 0;
         asm volatile("" : "+v"(z));
         h = hc[z]; hh = hc[z + 1]; h6 = hc[z + 2]; H = hc[z + 3]; H6 = hc[z + 4];
@@ -533,118 +540,11 @@ __device__ __forceinline__ void split_level(P& p, const PR& pr, const MinuteIn<T
         h = T(1) / T(nh);
         H = h + h; H6 = H / T(6); hh = T(0.5) * h; h6 = h / T(6);
     }
-    const T wE = r2 ? p(DP_X2E2) : p(DP_X2E), wA = r2 ? p(DP_X2WA2) : p(DP_X2WA);
-    const T wM = r2 ? p(DP_X2WM2) : p(DP_X2WM), wB = r2 ? p(DP_X2WB2) : p(DP_X2WB);
-    const T s5 = x[5], s6 = x[6], s7 = x[7], s8 = x[8], s9 = x[9], s10 = x[10], s11 = x[11], ui = u.ins;
-    T g0 = x[0], g1 = x[1], x2 = x[2], R = T(0);      // R: mass that left x2 through kabs since the minute began
-    T x3a = x[3], x4 = x[4], x12 = x[12];             // x3 itself is carried from step to step: a held value stays bit for bit
-    T cRa = T(0), cDa = p(DP_RATC) * x2, x6a = s6, x8a = s8;      // c R, c R', X, XL at the start of the glucose step
-    auto kgutF = [&](T q0, T q1) -> T { return kgut_flux(p, u, q0, q1); };
-    // One RK4 step of (x0, x1) + the exponential update of x2.  `pre(k)` / `post(k)` run before / after stage k's
-    // gastric-emptying evaluation: the caller issues the LDS reads of a propagator row in pre() and consumes them
-    // in post(), so that their latency hides behind ~50 dependent VALU instructions instead of being waited out.
-    auto gut_step = [&](auto&& pre, auto&& post, bool have_f1) {
-        p.refresh();
-        const T kmax = p(DP_KMAX);
-        pre(0);
-        T F1;
-        if (HAVE_F1 && have_f1) F1 = f1_pre; else F1 = kgutF(g0, g1);
-        post(0, F1);
-        const T a0 = u.d_mg - kmax * g0, a1 = kmax * g0 - F1;
-        T y0 = g0 + hh * a0, y1 = g1 + hh * a1;
-        pre(1);
-        const T F2 = kgutF(y0, y1);
-        post(1, F2);
-        const T b0 = u.d_mg - kmax * y0, b1 = kmax * y0 - F2;
-        y0 = g0 + hh * b0; y1 = g1 + hh * b1;
-        pre(2);
-        const T F3 = kgutF(y0, y1);
-        post(2, F3);
-        const T c0 = u.d_mg - kmax * y0, c1 = kmax * y0 - F3;
-        y0 = g0 + h * c0; y1 = g1 + h * c1;
-        pre(3);
-        const T F4 = kgutF(y0, y1);
-        post(3, F4);
-        const T e0 = u.d_mg - kmax * y0, e1 = kmax * y0 - F4;
-        const T F23 = F2 + F3;
-        g0 += h6 * (a0 + T(2) * (b0 + c0) + e0);
-        g1 += h6 * (a1 + T(2) * (b1 + c1) + e1);
-        const T x2n = wE * x2 + wA * F1 + wM * (T(0.5) * F23) + wB * F4;
-        R += (x2 - x2n) + h6 * (F1 + T(2) * F23 + F4);     // d(x2 + R) = kgut x1 dt
-        x2 = x2n;
-    };
-    auto no_pre = [](int) {};
-    auto no_post = [](int, T) {};
-
-    for (int s = 0; s < ns; ++s) {
-        // the four propagator rows of this glucose step (x6, x8 at its middle and at its end) ride along the four
-        // stages of its first gut step: one row at a time (28 table reads in flight at once would cost 56 VGPRs)
-        const int rm = ((2 * s + 1) * sb - 1) * 14, re = rm + sb * 14;
-        T cf[7], x6m, x8m, x6b, x8b;
-        auto pre = [&](int k) {
-            const int r = (k < 2 ? rm : re) + 7 * (k & 1);
-#pragma unroll
-            for (int j = 0; j < 7; ++j) cf[j] = pr(r + j);
-            __builtin_amdgcn_sched_barrier(0);           // the reads are issued here, ahead of the stage
-        };
-        auto post = [&](int k, T F) {
-            // pin: the coefficients are waited for, and the dot product formed, only once this stage's F exists
-            asm volatile("" : "+v"(cf[0]), "+v"(cf[1]), "+v"(cf[2]), "+v"(cf[3]), "+v"(cf[4]), "+v"(cf[5]), "+v"(cf[6]) : "v"(F));
-            const T v6 = cf[0] * s6 + cf[1] * s5 + cf[2] * s9 + cf[3] * s10 + cf[4] * s11 + cf[5] * ui + cf[6];
-            const T v8 = cf[0] * s8 + cf[1] * s7 + cf[2] * s5 + cf[3] * s9 + cf[4] * s10 + cf[5] * s11 + cf[6] * ui;
-            if (k == 0) x6m = v6; else if (k == 1) x8m = v8; else if (k == 2) x6b = v6; else x8b = v8;
-        };
-        gut_step(pre, post, s == 0);
-        const T cRm = p(DP_CF) * R, cDm = p(DP_RATC) * x2;
-        gut_step(no_pre, no_post, false);
-        const T cRb = p(DP_CF) * R, cDb = p(DP_RATC) * x2;
-        const bool hold = x3a < T(0);
-        T z3 = x3a - cRa;
-        T k3, k4, k12, a3, a4, a12;
-        glucose_rhs(p, z3, x4, x12, cRa, cDa, x6a, x8a, hold, x3a, k3, k4, k12);
-        a3 = k3; a4 = k4; a12 = k12;
-        glucose_rhs(p, z3 + h * k3, x4 + h * k4, x12 + h * k12, cRm, cDm, x6m, x8m, hold, x3a, k3, k4, k12);
-        a3 += T(2) * k3; a4 += T(2) * k4; a12 += T(2) * k12;
-        glucose_rhs(p, z3 + h * k3, x4 + h * k4, x12 + h * k12, cRm, cDm, x6m, x8m, hold, x3a, k3, k4, k12);
-        a3 += T(2) * k3; a4 += T(2) * k4; a12 += T(2) * k12;
-        glucose_rhs(p, z3 + H * k3, x4 + H * k4, x12 + H * k12, cRb, cDb, x6b, x8b, hold, x3a, k3, k4, k12);
-        z3 += H6 * (a3 + k3); x4 += H6 * (a4 + k4); x12 += H6 * (a12 + k12);
-        const T x3b = z3 + cRb;
-        x3a = hold ? x3a : (x3b < T(0) ? T(-1e-10) : x3b);
-        cRa = cRb; cDa = cDb; x6a = x6b; x8a = x8b;
+    T wE, wA, wM, wB;                                             // the x2 weights of this lane's level
+    if constexpr (!kLean) {
+        wE = r2 ? p(DP_X2E2) : p(DP_X2E); wA = r2 ? p(DP_X2WA2) : p(DP_X2WA);
+        wM = r2 ? p(DP_X2WM2) : p(DP_X2WM); wB = r2 ? p(DP_X2WB2) : p(DP_X2WB);
     }
-    const int t0 = 28 * n_sub;
-    x[0] = g0; x[1] = g1; x[2] = x2;
-    x[3] = x3a; x[4] = x4; x[12] = x12;
-    x[6] = x6a; x[8] = x8a;
-    x[5] = pr(t0) * s5 + pr(t0 + 1) * s9 + pr(t0 + 2) * s10 + pr(t0 + 3) * s11 + pr(t0 + 4) * ui;
-    x[9] = pr(t0 + 5) * s5 + pr(t0 + 6) * s9 + pr(t0 + 7) * s10 + pr(t0 + 8) * s11 + pr(t0 + 9) * ui;
-    x[10] = pr(t0 + 10) * s10 + pr(t0 + 11) * ui;
-    x[11] = pr(t0 + 12) * s10 + pr(t0 + 13) * s11 + pr(t0 + 14) * ui;
-    x[7] = pr(t0 + 15) * s7 + pr(t0 + 16) * s5 + pr(t0 + 17) * s9 + pr(t0 + 18) * s10 + pr(t0 + 19) * s11 + pr(t0 + 20) * ui;
-}
-
-// split_level for a kernel with no register to spare (step1d_kernel in fp64: four waves per SIMD, 128 VGPRs), levels 1 and 2,
-// fp64.  The same arithmetic in the same order, so the same bits; what differs is where the constants wait:
-//   * P is ParsLdsH: every parameter is read from LDS in the gut step or the glucose step that uses it and kept for that
-//     step only -- read again at each of the glucose step's four stages (ParsLdsS) the same launch takes 85.0 us against 79.8;
-//   * the x2 weights are read where the gut step ends;
-//   * the five step sizes (hc: split_step_sizes' words in LDS) are the same in every lane and wait in scalar registers.
-template <int LEVEL, typename T, typename P, typename PR, bool HAVE_F1>
-__device__ __forceinline__ void split_level_lean(P& p, const PR& pr, const MinuteIn<T>& u, T (&x)[13], int n_sub, T f1_pre, const T* hc)
-{
-    static_assert((LEVEL == 1 || LEVEL == 2) && sizeof(T) == 8, "levels 1 and 2 in fp64");
-    const bool r2 = LEVEL == 2;                                   // this lane at level 2
-    const int sb = r2 ? 1 : 2;                                    // propagator blocks per glucose half step
-    const int nh = r2 ? 2 * n_sub : n_sub;                        // glucose half steps = gut steps in the minute
-    const int ns = nh >> 1;
-    auto uniform = [&](int k) -> T {                              // a word every lane reads alike, as a scalar pair
-        const double v = (double)hc[k];
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)__double2loint(v));
-        const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)__double2hiint(v));
-        return (T)__hiloint2double((int)hi, (int)lo);
-    };
-    const T h = uniform(0), hh = uniform(1), h6 = uniform(2), H = uniform(3), H6 = uniform(4);    // h: glucose half step = gut step
     const T s5 = x[5], s6 = x[6], s7 = x[7], s8 = x[8], s9 = x[9], s10 = x[10], s11 = x[11], ui = u.ins;
     T g0 = x[0], g1 = x[1], x2 = x[2], R = T(0);      // R: mass that left x2 through kabs since the minute began
     T x3a = x[3], x4 = x[4], x12 = x[12];             // x3 itself is carried from step to step: a held value stays bit for bit
@@ -677,8 +577,10 @@ __device__ __forceinline__ void split_level_lean(P& p, const PR& pr, const Minut
         post(3, F4);
         const T e0 = u.d_mg - kmax * y0, e1 = kmax * y0 - F4;
         const T F23 = F2 + F3;
-        p.refresh_block();
-        const T wE = p(kSplitW(LEVEL)), wA = p(kSplitW(LEVEL) + 1), wM = p(kSplitW(LEVEL) + 2), wB = p(kSplitW(LEVEL) + 3);
+        if constexpr (kLean) {
+            p.refresh_block();
+            wE = p(kSplitW(LEVEL)); wA = p(kSplitW(LEVEL) + 1); wM = p(kSplitW(LEVEL) + 2); wB = p(kSplitW(LEVEL) + 3);
+        }
         g0 += h6 * (a0 + T(2) * (b0 + c0) + e0);
         g1 += h6 * (a1 + T(2) * (b1 + c1) + e1);
         const T x2n = wE * x2 + wA * F1 + wM * (T(0.5) * F23) + wB * F4;
@@ -711,7 +613,7 @@ __device__ __forceinline__ void split_level_lean(P& p, const PR& pr, const Minut
         gut_step(no_pre, no_post, false);
         const T cRb = p(DP_CF) * R, cDb = p(DP_RATC) * x2;
         const bool hold = x3a < T(0);
-        p.refresh_block();
+        if constexpr (kLean) p.refresh_block();       // the glucose step's reads start afresh here, once for its four stages
         T z3 = x3a - cRa;
         T k3, k4, k12, a3, a4, a12;
         glucose_rhs(p, z3, x4, x12, cRa, cDa, x6a, x8a, hold, x3a, k3, k4, k12);

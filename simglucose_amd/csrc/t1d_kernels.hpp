@@ -599,12 +599,26 @@ __device__ __forceinline__ S1In<T> s1_unpark(const T* pt, const int* pi, int slo
 }
 
 // The two passes of step1d_kernel (modes 2, 3) in fp64 fit 128 VGPRs without scratch only with nothing constant in vector
-// registers across the sub-step loops: split_level_lean, whatever REG says.  lconst then holds the step sizes of level 1 and of
-// level 2 behind the limits (kS1DConstHc), formed once per workgroup.  (The list pass on VGPR parameters spills 56 values there,
-// 19 scratch accesses in its sub-step loop: 88.6 us.)
+// registers across the sub-step loops: split_level on a view that holds its reads (ParsLdsH, which switches on its kLean),
+// whatever REG says.  lconst then holds the step sizes of level 1 and of level 2 behind the limits (kLcHc), formed once per
+// workgroup.  (The list pass on VGPR parameters spills 56 values there, 19 scratch accesses in its sub-step loop: 88.6 us.)
 template <typename T, int MODE> constexpr bool kS1DLean = sizeof(T) == 8 && (MODE == 2 || MODE == 3);
-constexpr int kS1DConstHc(int level) { return level == 1 ? 8 : 13; }
-constexpr int kS1DConst = 18;
+// lconst, the words every lane of a workgroup reads alike: the pump's limits 0-5 (increment, minimum, maximum of the basal
+// channel, then of the bolus channel), the sensor's range 6-7 and, in the kernels that take their step sizes from LDS,
+// split_step_sizes' five words of level 1 and of level 2 behind them
+constexpr int kLcVmin = 6, kLcVmax = 7, kLcLimits = 8, kLcHc1 = kLcLimits, kLcHc2 = kLcHc1 + 5, kLcSize = kLcHc2 + 5;
+constexpr int kLcHc(int level) { return level == 1 ? kLcHc1 : kLcHc2; }
+// InsulinPump on both channels, its limits read from lconst (env.py:51-52); without a bolus channel: the pump's smallest bolus
+template <typename T>
+__device__ __forceinline__ void pump_lconst(const T* lconst, T basal, T bolus, bool has_bolus, T& q_basal, T& q_bolus)
+{
+    int z = 0;
+    asm volatile("" : "+v"(z));                      // opaque index: the reads below stay inside the caller's loop
+    const T* lc = lconst + z;
+    q_basal = pump_quantise(basal, lc[0], lc[1], lc[2]);                                       // env.py:51
+    q_bolus = lc[4] > T(0) ? lc[4] : T(0);
+    if (has_bolus) q_bolus = pump_quantise(bolus, lc[3], lc[4], lc[5]);                        // env.py:52
+}
 template <bool REG, typename T, int STRIDE, bool EXTRA, int MODE, typename ONLEVEL>
 __device__ __forceinline__ void s1_chunk(const KArgs<T>& a, T* ldp, T* lpr, T* lconst, unsigned i, const S1In<T>& in,
                                          ONLEVEL&& on_level, long long* tr, int tk)
@@ -633,12 +647,7 @@ __device__ __forceinline__ void s1_chunk(const KArgs<T>& a, T* ldp, T* lpr, T* l
     if (a.flags & T1D_BATCH_NO_PUMP) {
         q_basal = basal; q_bolus = a.bolus ? bolus : T(0);
     } else {
-        int z = 0;
-        asm volatile("" : "+v"(z));                  // opaque index: the reads below stay inside the chunk loop
-        const T* lc = lconst + z;
-        q_basal = pump_quantise(basal, lc[0], lc[1], lc[2]);                                   // env.py:51
-        q_bolus = lc[4] > T(0) ? lc[4] : T(0);
-        if (a.bolus) q_bolus = pump_quantise(bolus, lc[3], lc[4], lc[5]);                      // env.py:52
+        pump_lconst(lconst, basal, bolus, a.bolus != nullptr, q_basal, q_bolus);
     }
     const T insulin = q_basal + q_bolus;
     T meal;                                                                                    // env.py:50
@@ -688,7 +697,7 @@ __device__ __forceinline__ void s1_chunk(const KArgs<T>& a, T* ldp, T* lpr, T* l
             split_minute_tiered(pl, pr, u, e.x, a.n_sub);
         } else if constexpr (kS1DLean<T, MODE>) {
             ParsLdsH<T, STRIDE> ph{ldp, (int)pid};
-            split_level_lean<LEVEL, T, ParsLdsH<T, STRIDE>, decltype(pr), MODE == 2>(ph, pr, u, e.x, a.n_sub, f1, lconst + kS1DConstHc(LEVEL));
+            split_level<LEVEL, T, ParsLdsH<T, STRIDE>, decltype(pr), MODE == 2, true>(ph, pr, u, e.x, a.n_sub, f1, false, lconst + kLcHc(LEVEL));
         } else if (REG) {
             ParsReg<T> p;
 #pragma unroll
@@ -726,7 +735,7 @@ __device__ __forceinline__ void s1_chunk(const KArgs<T>& a, T* ldp, T* lpr, T* l
         T c = gsub + noise;
         int z = 0;
         asm volatile("" : "+v"(z));
-        const T vmin = lconst[6 + z], vmax = lconst[7 + z];
+        const T vmin = lconst[kLcVmin + z], vmax = lconst[kLcVmax + z];
         in_range = vmin > T(1) && vmax < T(__builtin_huge_val());
         c = c > vmin ? c : vmin;
         c = c < vmax ? c : vmax;
@@ -761,7 +770,7 @@ __device__ __forceinline__ void s1_chunk(const KArgs<T>& a, T* ldp, T* lpr, T* l
 struct S1NoLevel { __device__ __forceinline__ void operator()(bool) const {} };
 
 // words of the table image behind its rows: pump and sensor limits in lconst's order
-constexpr int kImgConst = 8;
+constexpr int kImgConst = kLcLimits;
 // The tables of a CU at row stride 32 from their image (KArgs.img: [DP_COUNT + prop_rows][32], zero beyond np, then
 // kImgConst words; t1d_abi.hip builds it with the tables): a straight copy, 16 bytes per lane and load, four loads in flight
 // before the first is waited for -- one round trip for the tables of n_sub = 4 where s1_stage_tables makes eight dependent
@@ -805,7 +814,7 @@ __device__ __forceinline__ void s1_stage_tables(const KArgs<T>& a, T* ldp, T* lp
     if (threadIdx.x == 0) {
         lconst[0] = a.pump.inc_basal; lconst[1] = a.pump.min_basal; lconst[2] = a.pump.max_basal;
         lconst[3] = a.pump.inc_bolus; lconst[4] = a.pump.min_bolus; lconst[5] = a.pump.max_bolus;
-        lconst[6] = a.sen.vmin; lconst[7] = a.sen.vmax;
+        lconst[kLcVmin] = a.sen.vmin; lconst[kLcVmax] = a.sen.vmax;
     }
 }
 
@@ -819,7 +828,7 @@ __global__ __launch_bounds__(s1_threads<T>(), 1) void step1_kernel(const KArgs<T
     T* const ldp = (T*)t1d_dyn_lds;                        // [DP_COUNT][STRIDE]
     T* const lpr = ldp + DP_COUNT * STRIDE;                // [prop_rows][STRIDE]
     __shared__ int queue;
-    __shared__ T lconst[8];                              // pump and sensor limits: read from LDS where used, so that they
+    __shared__ T lconst[kLcLimits];                      // pump and sensor limits: read from LDS where used, so that they
                                                          // do not sit in (spilled) scalar registers across the whole kernel
     if constexpr (STRIDE == 32) s1_stage_image<T, s1_threads<T>()>(a, ldp, lconst);
     else s1_stage_tables<T, STRIDE>(a, ldp, lpr, lconst);
@@ -885,16 +894,16 @@ __global__ __launch_bounds__(s1d_threads<T>(), 1) void step1d_kernel(const KArgs
     // [per_block * 64] envs of level 2, as offsets from the workgroup's first env (< 65536: t1d_step)
     uint16_t* const list = (uint16_t*)(park_i + 3 * kS1DPark);
     __shared__ int queue, taken, listed, passed;
-    __shared__ T lconst[kS1DLean<T, 2> ? kS1DConst : 8];
+    __shared__ T lconst[kS1DLean<T, 2> ? kLcSize : kLcLimits];
     s1_stage_image<T, s1d_threads<T>()>(a, ldp, lconst);
     if (threadIdx.x == 0) { queue = 0; taken = 0; listed = 0; passed = 0; }
     if constexpr (kS1DLean<T, 2>) {
         if (threadIdx.x == 0) {
             T hc[5];
             split_step_sizes<T>(a.n_sub, hc);
-            for (int k = 0; k < 5; ++k) lconst[kS1DConstHc(1) + k] = hc[k];
+            for (int k = 0; k < 5; ++k) lconst[kLcHc1 + k] = hc[k];
             split_step_sizes<T>(2 * a.n_sub, hc);
-            for (int k = 0; k < 5; ++k) lconst[kS1DConstHc(2) + k] = hc[k];
+            for (int k = 0; k < 5; ++k) lconst[kLcHc2 + k] = hc[k];
         }
     }
     __syncthreads();
@@ -1003,7 +1012,6 @@ template <typename T> struct SnLane {
 };
 constexpr int kSnParkT = 21, kSnParkI = 5;           // words of a record: 21 of T, 5 ints
 constexpr int kSnDirtyShift = 9;                     // the three dirty bits ride in bits 9-11 of the record's meta word
-constexpr int kSnConst = 20;                         // lconst: pump 0-5, sensor limits 6-7, step sizes of level 1 8-12, of level 2 13-17
 constexpr int kSnSpinLimit = 1 << 20;                // polls before a waiting wave gives up and raises T1D_ST_STALL (never, by design)
 
 // the record's minute word doubles as its "written" flag: -1 until the lane that owns the slot has stored everything else
@@ -1071,7 +1079,8 @@ __global__ __launch_bounds__(sn_threads<T>(), 1) void stepn_kernel(const KArgs<T
     const int per_block = (nchunks + (int)gridDim.x - 1) / (int)gridDim.x;
     unsigned long long* const redo = (unsigned long long*)(park_i + kSnParkI * park_cap + ((kSnParkI * park_cap) & 1));   // [per_block]: envs to take again
     __shared__ int queue, taken, parked, passed, redo_any, redo_next;
-    __shared__ T lconst[kSnConst];
+    __shared__ T lconst[kLcSize + 2];                    // (two words more than the layout's, as since round 3: the other __shared__
+                                                         // words of the kernel keep their addresses, and the kernel its machine code)
     s1_stage_tables<T, STRIDE>(a, ldp, lpr, lconst);
     const int first = (int)blockIdx.x * per_block;
     const int count = nchunks - first < per_block ? nchunks - first : per_block;
@@ -1081,9 +1090,9 @@ __global__ __launch_bounds__(sn_threads<T>(), 1) void stepn_kernel(const KArgs<T
         queue = 0; taken = 0; parked = 0; passed = all_redo ? count : 0; redo_any = 0; redo_next = 0;
         T hc[5];
         split_step_sizes<T>(a.n_sub, hc);
-        for (int k = 0; k < 5; ++k) lconst[8 + k] = hc[k];
+        for (int k = 0; k < 5; ++k) lconst[kLcHc1 + k] = hc[k];
         split_step_sizes<T>(2 * a.n_sub, hc);
-        for (int k = 0; k < 5; ++k) lconst[13 + k] = hc[k];
+        for (int k = 0; k < 5; ++k) lconst[kLcHc2 + k] = hc[k];
     }
     for (int j = threadIdx.x; j < park_cap; j += NT) park_i[4 * park_cap + j] = -1;
     for (int j = threadIdx.x; j < per_block; j += NT) {
@@ -1144,12 +1153,7 @@ __global__ __launch_bounds__(sn_threads<T>(), 1) void stepn_kernel(const KArgs<T
         if (a.flags & T1D_BATCH_NO_PUMP) {
             q_basal = basal; q_bolus = has_bolus ? bolus : T(0);
         } else {
-            int z = 0;
-            asm volatile("" : "+v"(z));
-            const T* lc = lconst + z;
-            q_basal = pump_quantise(basal, lc[0], lc[1], lc[2]);                               // env.py:51
-            q_bolus = lc[4] > T(0) ? lc[4] : T(0);
-            if (has_bolus) q_bolus = pump_quantise(bolus, lc[3], lc[4], lc[5]);                // env.py:52
+            pump_lconst(lconst, basal, bolus, has_bolus, q_basal, q_bolus);
         }
         L.insulin = q_basal + q_bolus;
         L.bg_sum = T(0); L.cgm_sum = T(0); L.meal_sum = T(0);
@@ -1189,7 +1193,7 @@ __global__ __launch_bounds__(sn_threads<T>(), 1) void stepn_kernel(const KArgs<T
     auto integrate = [&](ParsReg<T>& p, SnLane<T>& L, const MinuteIn<T>& u, T f1) {
         PropLdsS<T, STRIDE> pr{lpr, (int)L.pid};
         p.pin_split();
-        split_level<1, T, ParsReg<T>, decltype(pr), true, true>(p, pr, u, L.x, a.n_sub, f1, false, lconst + 8);
+        split_level<1, T, ParsReg<T>, decltype(pr), true, true>(p, pr, u, L.x, a.n_sub, f1, false, lconst + kLcHc1);
     };
     // clock, Gsub (t1dpatient.py:217-218), the CGM sample if one is due (cgm.py:26-36), the step's means (env.py:78-81)
     auto minute_tail = [&](SnLane<T>& L, T meal) {
@@ -1210,7 +1214,7 @@ __global__ __launch_bounds__(sn_threads<T>(), 1) void stepn_kernel(const KArgs<T
             }
             int z = 0;
             asm volatile("" : "+v"(z));
-            const T vmin = lconst[6 + z], vmax = lconst[7 + z];
+            const T vmin = lconst[kLcVmin + z], vmax = lconst[kLcVmax + z];
             T cv = gsub + noise;
             cv = cv > vmin ? cv : vmin;
             cv = cv < vmax ? cv : vmax;
@@ -1365,7 +1369,7 @@ __global__ __launch_bounds__(sn_threads<T>(), 1) void stepn_kernel(const KArgs<T
                     PropLdsS<T, STRIDE> pr{lpr, (int)L.pid};
                     if constexpr (kRecReg) {
                         p.pin_split();
-                        split_level<0, T, ParsReg<T>, decltype(pr), true, true>(p, pr, u, L.x, a.n_sub, tp.f1, tp.level2, lconst + 8);
+                        split_level<0, T, ParsReg<T>, decltype(pr), true, true>(p, pr, u, L.x, a.n_sub, tp.f1, tp.level2, lconst + kLcHc1);
                     } else {
                         ParsLdsS<T, STRIDE> pl{ldp, (int)L.pid};
                         split_level<0, T, ParsLdsS<T, STRIDE>, decltype(pr), true>(pl, pr, u, L.x, a.n_sub, tp.f1, tp.level2);
