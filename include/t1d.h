@@ -422,6 +422,20 @@ typedef struct t1d_env_output {
     const void* bias;    /* [n], batch dtype */
 } t1d_env_output;
 
+/* t1d_collect_mlp_limit: episodes with a time limit (max_episode_steps).  cut_feat has the batch's dtype. */
+typedef struct t1d_time_limit {
+    int32_t max_minutes;   /* >= 1: an episode whose clock t (minutes since its reset) is >= max_minutes when a step closes is cut */
+    int32_t reserved;      /* 0 */
+    uint8_t* cut_trace;    /* [rows][n] or NULL: 1 where step s was cut (never where done = 1), else 0; rows as t1d_collect's */
+    void* cut_feat;        /* [F][n] or NULL, batch dtype: the features of the state a cut episode ended in; written for cut envs only */
+} t1d_time_limit;
+
+/* t1d_gae_limit: the second mask of a batch collected under a time limit.  cut_value has the call's dtype. */
+typedef struct t1d_gae_cut {
+    const uint8_t* truncated;  /* [K][n]: t1d_time_limit.cut_trace */
+    const void* cut_value;     /* [n] or NULL = 0, call dtype: V of the state in cut_feat */
+} t1d_gae_cut;
+
 int t1d_abi_version(void);
 const char* t1d_last_error(void);
 
@@ -769,6 +783,31 @@ int t1d_rollout_mlp_dopri5_rel(t1d_ctx* ctx, const t1d_batch* b, const t1d_mlp* 
                                const t1d_meal_bolus* meal_bolus, double* h_carry, int32_t* nfev, int n_steps, int minutes,
                                void* hip_stream);
 
+/* t1d_collect_mlp, t1d_collect_mlp_bolus and t1d_collect_mlp_rel with a time limit, in one launch as they are: the matching
+ * existing call is t1d_collect_mlp_rel with an env_output, else t1d_collect_mlp_bolus with a meal_bolus, else t1d_collect_mlp,
+ * and everything the limit does not touch -- arguments, state, traces, draws -- is that call's.
+ * When a step is cut: after a step closes, done is formed as ever; cut = !done && t >= max_minutes, t the env's clock after the
+ *   step (minutes since its reset).  Termination wins over truncation.
+ * What is recorded for a cut step: done_trace holds 0, cut_trace holds 1 and batch.done stays 0.  cut_feat[j][i] holds the F =
+ *   2 H + 3 features of the state after that step, formed by the collectors' own device function from the shifted windows,
+ *   prev_meal = the step's meal and the clock start_minute + t: what t1d_mlp_features would return at that moment, bit for
+ *   bit -- the state a critic bootstraps from (t1d_gae_cut.cut_value).  cut_feat is written for cut envs only.
+ * What happens to a cut env: what happens to a finished one, which is t1d_restart_done with its mask byte set -- the episode
+ *   accumulators move to last_*, terminal_cgm is written, the env gets a new start hour, a new meal column, a reset and
+ *   episode + 1 -- and its policy state becomes that of a fresh reset.
+ * Equivalence: after the call everything is what n_steps x (the matching one-step call; cut = !done && t >= max_minutes;
+ *   t1d_mlp_features for the cut envs; t1d_restart_done(mask = done | cut); the reset of the policy state of the masked envs)
+ *   leave, bit for bit, wherever the call is cut into launches.  With a max_minutes no env reaches the result is the matching
+ *   existing call's, bit for bit.
+ * T1D_E_INVALID before anything is launched, nothing changed: whatever the matching existing call rejects; a NULL limit,
+ *   max_minutes < 1 or reserved != 0; on_done != T1D_COLLECT_RESTART (a cut restarts); n_steps * minutes > max_minutes -- so an
+ *   env is cut at most once per call and one cut_feat column per env is enough.
+ * The other collectors (t1d_collect_mlp_dopri5, t1d_collect_pid, t1d_collect_bb and their exact forms) have no time limit. */
+int t1d_collect_mlp_limit(t1d_ctx* ctx, const t1d_batch* batch, const t1d_mlp* mlp, const t1d_collect* collect,
+                          const t1d_env_output* env_output /* NULL = t1d_mlp's out_scale / out_bias */,
+                          const t1d_meal_bolus* meal_bolus /* NULL = no bolus */,
+                          const t1d_time_limit* limit, int n_steps, int minutes, int n_sub, void* hip_stream);
+
 /* t1d_mlp_action under t1d_env_output: action[i] = the basal, before the pump, that the next step of a *_rel call would ask for
  * env i, by the kernels' own function.  It takes no meal_bolus: t1d_mlp_bolus is the bolus half of a step loop, with or without
  * a relative output.  T1D_E_INVALID: a NULL env_output, scale or bias, and whatever t1d_mlp_action rejects. */
@@ -900,8 +939,14 @@ int t1d_mlp_loss_tiles(int hip_device, int dtype, int64_t n, const t1d_mlp* mlp,
  *   vn and an are SELECTED, never multiplied by zero: a NaN or a stale word in value[s+1] or last_value behind a done does
  *   not reach row s.  That matters with T1D_COLLECT_RESTART: row s + 1 of a collector's traces belongs to the NEXT episode of
  *   an env that finished in row s, and so does the critic's value of it.  A NULL value or last_value reads as 0.
- *   done is a true termination (BG left [70, 350], batch.done): the simulator has no time-limit truncation, so there is no
- *   second mask for episodes that were cut rather than ended; the cut at the end of the batch is what last_value is for.
+ *   done is a true termination (BG left [70, 350], batch.done); the cut at the end of the batch is what last_value is for.
+ *   Episodes cut by a time limit (t1d_collect_mlp_limit) have a second mask and take t1d_gae_limit:
+ *     ended = done && done[s] != 0
+ *     trunc = !ended && truncated[s] != 0
+ *     vn    = ended ? 0 : trunc ? cut_value[i] : (s == K-1 ? last_value : value[s+1])
+ *     an    = (ended || trunc) ? 0 : (s == K-1 ? 0 : adv[s+1])
+ *   and the rest unchanged.  Both are selected, never multiplied: a NaN in value[s+1] or adv[s+1] behind a cut does not reach
+ *   row s, and neither does a NaN in the cut_value of an env that was not cut.  A NULL cut_value reads as 0.
  * moments[p] = (sum of adv, sum of adv^2) over the K E samples of policy p, in double whatever the dtype.  Deterministic and
  *   portable: no floating-point atomics, and the summation order depends only on (n, n_policies, n_rows, dtype) -- not on the
  *   CU count, the grid or timing; two calls give identical bits, and a policy's pair depends on its own envs' words alone.
@@ -920,6 +965,10 @@ int t1d_mlp_loss_tiles(int hip_device, int dtype, int64_t n, const t1d_mlp* mlp,
  * The workspace needs the alignment of a double, no more. */
 int64_t t1d_gae_workspace(int dtype, int64_t n, const t1d_gae_batch* io);
 int t1d_gae(int hip_device, int dtype, int64_t n, const t1d_gae_batch* io, void* hip_stream);
+/* t1d_gae with the truncation mask (the recurrence above): workspace, moments order and determinism are t1d_gae's, and with an
+ * all-zero truncated the outputs are t1d_gae's bits.  T1D_E_INVALID, before the device is touched: a NULL cut or truncated, and
+ * whatever t1d_gae rejects. */
+int t1d_gae_limit(int hip_device, int dtype, int64_t n, const t1d_gae_batch* io, const t1d_gae_cut* cut, void* hip_stream);
 
 /* RandomScenario.create_scenario (simulation/scenario_gen.py:33-60) for n envs on the device: fills per-env
  * meal tables meal_time int32 [6 (days + 1)][n] (minutes since the episode start, ascending, unused =

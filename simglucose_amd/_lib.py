@@ -39,7 +39,7 @@ EXPORTS = ("t1d_abi_version", "t1d_last_error", "t1d_ctx_create", "t1d_ctx_set_o
            "t1d_mlp_loss_tiles_workspace", "t1d_mlp_loss_tiles", "t1d_collect_pid", "t1d_collect_bb",
            "t1d_collect_pid_dopri5", "t1d_collect_bb_dopri5", "t1d_rollout_mlp_bolus", "t1d_collect_mlp_bolus",
            "t1d_rollout_mlp_dopri5_bolus", "t1d_mlp_bolus", "t1d_rollout_mlp_rel", "t1d_collect_mlp_rel",
-           "t1d_rollout_mlp_dopri5_rel", "t1d_mlp_action_rel")
+           "t1d_rollout_mlp_dopri5_rel", "t1d_mlp_action_rel", "t1d_collect_mlp_limit", "t1d_gae_limit")
 
 
 class T1DError(RuntimeError):
@@ -97,6 +97,16 @@ class MealBolus(C.Structure):
 class EnvOutput(C.Structure):
     """struct t1d_env_output (include/t1d.h)"""
     _fields_ = [("scale", C.c_void_p), ("bias", C.c_void_p)]
+
+
+class TimeLimit(C.Structure):
+    """struct t1d_time_limit (include/t1d.h)"""
+    _fields_ = [("max_minutes", C.c_int32), ("reserved", C.c_int32), ("cut_trace", C.c_void_p), ("cut_feat", C.c_void_p)]
+
+
+class GaeCut(C.Structure):
+    """struct t1d_gae_cut (include/t1d.h)"""
+    _fields_ = [("truncated", C.c_void_p), ("cut_value", C.c_void_p)]
 
 
 class Outcome(C.Structure):
@@ -245,6 +255,8 @@ def lib():
     L.t1d_collect_mlp_rel.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), C.POINTER(Collect), eo, mb, C.c_int, C.c_int, C.c_int, vp]
     L.t1d_rollout_mlp_dopri5_rel.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), eo, mb, vp, vp, C.c_int, C.c_int, vp]
     L.t1d_mlp_action_rel.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), eo, vp, vp]
+    L.t1d_collect_mlp_limit.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), C.POINTER(Collect), eo, mb, C.POINTER(TimeLimit),
+                                        C.c_int, C.c_int, C.c_int, vp]
     L.t1d_mlp_grad_workspace.argtypes = [C.POINTER(Mlp), C.c_int, i64, i64]
     L.t1d_mlp_grad.argtypes = [C.c_int, C.c_int, i64, C.POINTER(Mlp), C.POINTER(MlpBatch), vp]
     L.t1d_mlp_loss_workspace.argtypes = [C.POINTER(Mlp), C.c_int, i64, i64]
@@ -256,6 +268,7 @@ def lib():
     L.t1d_mlp_features.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), vp, vp]
     L.t1d_gae_workspace.argtypes = [C.c_int, i64, C.POINTER(GaeBatch)]
     L.t1d_gae.argtypes = [C.c_int, C.c_int, i64, C.POINTER(GaeBatch), vp]
+    L.t1d_gae_limit.argtypes = [C.c_int, C.c_int, i64, C.POINTER(GaeBatch), C.POINTER(GaeCut), vp]
     L.t1d_restart_done.argtypes = [vp, C.POINTER(Batch), vp, C.POINTER(Restart), vp]
     L.t1d_random_meals.argtypes = [C.c_int, u64, i64, i64, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]
     L.t1d_outcome_stats.argtypes = [C.c_int, C.c_int, i64, i64, vp, C.POINTER(Outcome), vp]

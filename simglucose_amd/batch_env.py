@@ -433,10 +433,11 @@ class BatchedT1DSimEnv:
         with meal_bolus) the meal bolus of step r, before the pump.
         collect_mlp only: "reward", "done" (uint8) and "eps" of step r, and "features" [n_steps + 1, F, n], what the
         network was given in step r (F = 2 history + 3: pass the policy's history=); their row 0 is NaN (0 for "done").
+        "truncated" (uint8, collect_mlp_limit): 1 where step r was cut by the time limit; row 0 is 0.
         Call right after reset(); pass the dict as rollout_*(trace=...)."""
         tr = {"row": 1}
         for k in columns:
-            if k == "done":
+            if k in ("done", "truncated"):
                 tr[k] = torch.zeros(int(n_steps) + 1, self.n, dtype=torch.uint8, device=self.device)
                 continue
             shape = (int(n_steps) + 1, self.n)
@@ -810,6 +811,68 @@ class BatchedT1DSimEnv:
             self._rollout(self._L.t1d_collect_mlp_bolus, (p, g, m), n_steps, trace, restarts=on_done == "restart")
         self._keep = keep
         return policy_state
+
+    def collect_mlp_limit(self, n_steps, policy, max_episode_steps, cut_features=None, sigma=None, explore_seed=None,
+                          policy_state=None, stats=None, trace=None, on_done="restart", days=2, terminal_obs=None,
+                          episode_stats=None, reset_outputs=False):
+        """collect_mlp(on_done="restart") with a time limit on every episode (t1d_collect_mlp_limit, include/t1d.h; one entry
+        point and one kernel family for the plain, the hybrid and the relative policy).  max_episode_steps = L >= 1: an env
+        that did not finish and whose clock has reached L * minutes_per_step when a step closes is cut (truncated).  Its row
+        has done = 0 and trace["truncated"] = 1 (termination wins, never both); cut_features (a contiguous [F, n] tensor of
+        the env's dtype, or None) receives, for the cut envs only, the features of the state the episode ended in -- what
+        policy_features() would return at that moment, bit for bit: what the critic bootstraps from (controller.gae:
+        truncated=, cut_value=).  The cut env then goes through what a finished one goes through.  on_done must be "restart"
+        (a cut env starts its next episode) and n_steps <= L (an env is then cut at most once per call, so one cut_features
+        column per env is enough; a longer batch takes several calls): else ValueError before anything is launched.  Every
+        other argument, and the return value, as collect_mlp; trace may hold "truncated" (new_trace).  The result is that of
+        n_steps times this loop, bit for bit, wherever the call is cut into launches:
+
+            env.rollout_mlp(1, pol, policy_state=st)         # or collect_mlp(1, ..., on_done="continue") with sigma
+            cut = ~env.done.bool() & (env.t >= L * env.minutes_per_step)
+            cut_features[:, cut] = env.policy_features(pol, st)[:, cut]
+            env.restart_done(mask=env.done.bool() | cut, ...)
+            ...                                              # new_policy_state() for the masked envs
+
+        With a limit no env reaches, the result is collect_mlp(on_done="restart")'s, bit for bit.  A method of its own and not
+        two keywords of collect_mlp, whose parameter list is that of collect_mlp_dopri5 and stays so; collect_mlp_dopri5,
+        collect_pid and collect_bb (both modes) have no time limit.  Measurements: profiles/collect/README.md."""
+        self._no_dopri5_rollout()
+        lim = self._time_limit_struct(n_steps, policy, trace, on_done, max_episode_steps, cut_features)
+        policy_state, p, g, keep = self._collect_structs("collect_mlp_limit", n_steps, policy, policy_state, stats, trace, on_done, days,
+                                                         terminal_obs, episode_stats, reset_outputs, draw=(sigma, explore_seed))
+        m = self._meal_bolus_struct("collect_mlp_limit", policy, trace, self._n_steps(n_steps))
+        o = self._env_output_struct(policy)
+        self._rollout(self._L.t1d_collect_mlp_limit, (p, g, o, m, lim), n_steps, trace, restarts=True)
+        self._keep = keep + (cut_features,)
+        return policy_state
+
+    def _time_limit_struct(self, n_steps, policy, trace, on_done, max_episode_steps, cut_features):
+        """The t1d_time_limit of collect_mlp_limit, checked before anything is launched.  Call before _set_trace advances
+        trace["row"]: "truncated" is written from the row the call starts at."""
+        t = trace.get("truncated") if trace else None
+        n_steps, L = self._n_steps(n_steps), int(max_episode_steps)
+        if L < 1:
+            raise ValueError("collect_mlp_limit: max_episode_steps must be at least 1")
+        if on_done != "restart":
+            raise ValueError("collect_mlp_limit: max_episode_steps needs on_done='restart' (a cut env starts its next episode)")
+        if n_steps > L:
+            raise ValueError("collect_mlp_limit: n_steps must not exceed max_episode_steps (an env is cut at most once per call); "
+                             "take the batch in several calls")
+        lim = _lib.TimeLimit()
+        lim.max_minutes, lim.reserved = L * self.minutes_per_step, 0
+        lim.cut_trace = lim.cut_feat = None
+        if cut_features is not None:
+            F = 2 * int(policy.history) + 3
+            if not isinstance(cut_features, torch.Tensor) or cut_features.dtype != self.dtype or cut_features.device != self.device \
+                    or tuple(cut_features.shape) != (F, self.n) or not cut_features.is_contiguous():
+                raise ValueError("collect_mlp_limit: cut_features must be a contiguous [%d, %d] tensor of %s on the env's device" % (F, self.n, self.dtype))
+            lim.cut_feat = cut_features.data_ptr()
+        if t is not None:
+            row = int(trace.get("row", 0))
+            if t.dtype != torch.uint8 or tuple(t.shape[1:]) != (self.n,) or t.shape[0] < row + n_steps or not t.is_contiguous():
+                raise ValueError("trace['truncated'] must be contiguous [rows >= row + n_steps, %d] of torch.uint8" % self.n)
+            lim.cut_trace = t.data_ptr()
+        return lim
 
     def _collect_structs(self, who, n_steps, policy, policy_state, stats, trace, on_done, days, terminal_obs, episode_stats,
                          reset_outputs, draw, keep_h_carry=False):

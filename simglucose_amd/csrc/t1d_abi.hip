@@ -1320,16 +1320,48 @@ static CollectArgs<T> make_collect(const t1d_ctx* c, const t1d_collect* g)
     return ga;
 }
 
+// ---- t1d_time_limit: the limit of t1d_collect_mlp_limit (LimitArgs, t1d_policy.hpp) ---------------------------------------
+// needs no device.  n_steps * minutes <= max_minutes: an env is cut at most once per call, so cut_feat has one column per env
+static int check_time_limit(const char* who, const t1d_collect* g, const t1d_time_limit* lim, int n_steps, int minutes)
+{
+    const std::string w = std::string(who) + ": ";
+    if (!lim) return fail(T1D_E_INVALID, w + "limit is NULL");
+    if (lim->max_minutes < 1) return fail(T1D_E_INVALID, w + "limit.max_minutes < 1");
+    if (lim->reserved != 0) return fail(T1D_E_INVALID, w + "limit.reserved must be 0");
+    if (g && g->on_done != T1D_COLLECT_RESTART) return fail(T1D_E_INVALID, w + "a time limit needs on_done = T1D_COLLECT_RESTART (a cut env restarts)");
+    if (n_steps > 0 && minutes > 0 && (int64_t)n_steps * minutes > lim->max_minutes)
+        return fail(T1D_E_INVALID, w + "n_steps * minutes must not exceed limit.max_minutes (an env is cut at most once per call)");
+    return T1D_OK;
+}
+
+template <typename T>
+static LimitArgs<T> make_limit(const t1d_time_limit* lim)
+{
+    return LimitArgs<T>{lim->max_minutes, lim->cut_trace, (T*)lim->cut_feat};
+}
+
+template <typename T> using CollectLimitFn = KernelFn<T, MlpArgs<T>, CollectArgs<T>, RestartArgs<T>, EnvOutArgs<T>, BolusArgs<T>, LimitArgs<T>>;
+template <typename T>
+static CollectLimitFn<T> mlp_collect_limit_fn(int variant)
+{
+    return by_variant<T>(variant, [](auto v) -> CollectLimitFn<T> { return mlp_collect_limit_kernel<decltype(v)::value, T>; });
+}
+
 // mb == NULL: t1d_collect_mlp; with mb the same kernel family with the bolus switched on (t1d_collect_mlp_bolus); with eo the
-// relative policy's family, with or without mb (t1d_collect_mlp_rel)
+// relative policy's family, with or without mb (t1d_collect_mlp_rel); with lim the time limit's family, with or without either
+// (t1d_collect_mlp_limit)
 template <typename T>
 static int run_collect_mlp(const char* who, t1d_ctx* c, const t1d_batch* b, const t1d_mlp* m, const t1d_collect* g, const t1d_env_output* eo,
-                           const t1d_meal_bolus* mb, Plan p, int cols, int n_steps, int minutes, int n_sub, hipStream_t s)
+                           const t1d_meal_bolus* mb, const t1d_time_limit* lim, Plan p, int cols, int n_steps, int minutes, int n_sub,
+                           hipStream_t s)
 {
     MlpArgs<T> ma = make_mlp<T>(m, n_steps);
     const int rc = shape_mlp<T>(who, c, b, cols, p, ma);
     if (rc) return rc;
     const RestartArgs<T> ra = g->on_done == T1D_COLLECT_RESTART ? make_restart<T>(g->restart) : RestartArgs<T>{};
+    if (lim)
+        return launch(c, b, p, minutes, n_sub, s, mlp_collect_limit_fn<T>(p.variant), ma, make_collect<T>(c, g), ra,
+                      eo ? make_env_out<T>(eo) : EnvOutArgs<T>{}, make_bolus_or_none<T>(mb), make_limit<T>(lim));
     if (eo)
         return launch(c, b, p, minutes, n_sub, s, mlp_collect_rel_fn<T>(p.variant), ma, make_collect<T>(c, g), ra, make_env_out<T>(eo),
                       make_bolus_or_none<T>(mb));
@@ -1363,7 +1395,8 @@ static int check_collect(const char* who, const t1d_batch* b, const t1d_mlp* m, 
 }
 
 static int collect_mlp_entry(const char* who, t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_collect* g,
-                             const t1d_env_output* eo, const t1d_meal_bolus* mb, int n_steps, int minutes, int n_sub, void* stream)
+                             const t1d_env_output* eo, const t1d_meal_bolus* mb, int n_steps, int minutes, int n_sub, void* stream,
+                             const t1d_time_limit* lim = nullptr)
 {
     int rc = check_collect(who, b, mlp, g, nullptr);
     if (rc) return rc;
@@ -1376,8 +1409,8 @@ static int collect_mlp_entry(const char* who, t1d_ctx* c, const t1d_batch* b, co
     rc = plan_and_tables(who, c, b, minutes, n_sub, true, &p, true);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    rc = p.f64 ? run_collect_mlp<double>(who, c, b, mlp, g, eo, mb, p, cols, n_steps, minutes, n_sub, s)
-               : run_collect_mlp<float>(who, c, b, mlp, g, eo, mb, p, cols, n_steps, minutes, n_sub, s);
+    rc = p.f64 ? run_collect_mlp<double>(who, c, b, mlp, g, eo, mb, lim, p, cols, n_steps, minutes, n_sub, s)
+               : run_collect_mlp<float>(who, c, b, mlp, g, eo, mb, lim, p, cols, n_steps, minutes, n_sub, s);
     if (rc) return rc;
     T1D_HIP(hipGetLastError());
     return T1D_OK;
@@ -1403,6 +1436,18 @@ extern "C" int t1d_collect_mlp_rel(t1d_ctx* c, const t1d_batch* b, const t1d_mlp
     const int rc = check_env_output("t1d_collect_mlp_rel", eo, mb);
     if (rc) return rc;
     return collect_mlp_entry("t1d_collect_mlp_rel", c, b, mlp, g, eo, mb, n_steps, minutes, n_sub, stream);
+}
+
+// the three calls above under a time limit (mlp_collect_limit_kernel): their checks under this call's name, then the limit's
+extern "C" int t1d_collect_mlp_limit(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_collect* g, const t1d_env_output* eo,
+                                     const t1d_meal_bolus* mb, const t1d_time_limit* lim, int n_steps, int minutes, int n_sub, void* stream)
+{
+    const char* who = "t1d_collect_mlp_limit";
+    int rc = eo ? check_env_output(who, eo, mb) : mb ? check_meal_bolus(who, mb) : T1D_OK;
+    if (rc) return rc;
+    rc = check_time_limit(who, g, lim, n_steps, minutes);
+    if (rc) return rc;
+    return collect_mlp_entry(who, c, b, mlp, g, eo, mb, n_steps, minutes, n_sub, stream, lim);
 }
 
 // ---- t1d_collect_pid / t1d_collect_bb (ctrl_collect_kernel, t1d_policy.hpp) ----------------------------------------------
@@ -1870,8 +1915,9 @@ extern "C" int64_t t1d_gae_workspace(int dtype, int64_t n, const t1d_gae_batch* 
     return io->n_policies * tiles * 2 * (int64_t)sizeof(double);
 }
 
+// cut == NULL: t1d_gae, gae_kernel; else t1d_gae_limit, gae_limit_kernel with the second mask
 template <typename T>
-static void launch_gae(int64_t n, const t1d_gae_batch* io, int64_t tiles, hipStream_t s)
+static void launch_gae(int64_t n, const t1d_gae_batch* io, const t1d_gae_cut* cut, int64_t tiles, hipStream_t s)
 {
     GaeArgs<T> a;
     a.reward = (const T*)io->reward; a.done = io->done; a.value = (const T*)io->value; a.last_value = (const T*)io->last_value;
@@ -1882,29 +1928,47 @@ static void launch_gae(int64_t n, const t1d_gae_batch* io, int64_t tiles, hipStr
     const dim3 grid((a.n_waves + kGaeBlock / 64 - 1) / (kGaeBlock / 64));
     // every array given: the streaming form, whose loads and stores the compiler can count
     const bool full = io->done && io->value && io->adv && io->ret;
-    if (io->moments) {
+    if (cut) {
+        const GaeCutArgs<T> ca{cut->truncated, (const T*)cut->cut_value};
+        if (io->moments) hipLaunchKernelGGL((full ? gae_limit_kernel<T, true, true> : gae_limit_kernel<T, true, false>), grid, dim3(kGaeBlock), 0, s, a, ca);
+        else hipLaunchKernelGGL((full ? gae_limit_kernel<T, false, true> : gae_limit_kernel<T, false, false>), grid, dim3(kGaeBlock), 0, s, a, ca);
+    } else if (io->moments) {
         hipLaunchKernelGGL((full ? gae_kernel<T, true, true> : gae_kernel<T, true, false>), grid, dim3(kGaeBlock), 0, s, a);
-        hipLaunchKernelGGL(gae_moments_kernel, dim3((unsigned)io->n_policies), dim3(64), 0, s, (const double*)io->workspace, io->moments,
-                           a.tiles);
     } else {
         hipLaunchKernelGGL((full ? gae_kernel<T, false, true> : gae_kernel<T, false, false>), grid, dim3(kGaeBlock), 0, s, a);
     }
+    if (io->moments)
+        hipLaunchKernelGGL(gae_moments_kernel, dim3((unsigned)io->n_policies), dim3(64), 0, s, (const double*)io->workspace, io->moments,
+                           a.tiles);
+}
+
+// t1d_gae (cut == NULL, limit = false) and t1d_gae_limit
+static int gae_entry(const char* who, int hip_device, int dtype, int64_t n, const t1d_gae_batch* io, const t1d_gae_cut* cut, bool limit,
+                     void* stream)
+{
+    const std::string w = std::string(who) + ": ";
+    int64_t tiles = 0;
+    const int rc = check_gae(who, dtype, n, io, &tiles);
+    if (rc) return rc;
+    if (!io->reward) return fail(T1D_E_INVALID, w + "reward is NULL");
+    if (!io->adv && !io->ret && !io->moments) return fail(T1D_E_INVALID, w + "adv, ret and moments are all NULL");
+    if (io->moments && (!io->workspace || io->workspace_bytes < io->n_policies * tiles * 2 * (int64_t)sizeof(double)))
+        return fail(T1D_E_INVALID, w + "moments need a workspace of t1d_gae_workspace() bytes");
+    if (limit && (!cut || !cut->truncated)) return fail(T1D_E_INVALID, w + "cut and cut.truncated must be set");
+    T1D_HIP(hipSetDevice(hip_device));
+    by_dtype(dtype, [&](auto t) { launch_gae<decltype(t)>(n, io, cut, tiles, (hipStream_t)stream); });
+    T1D_HIP(hipGetLastError());
+    return T1D_OK;
 }
 
 extern "C" int t1d_gae(int hip_device, int dtype, int64_t n, const t1d_gae_batch* io, void* stream)
 {
-    const char* who = "t1d_gae";
-    int64_t tiles = 0;
-    const int rc = check_gae(who, dtype, n, io, &tiles);
-    if (rc) return rc;
-    if (!io->reward) return fail(T1D_E_INVALID, "t1d_gae: reward is NULL");
-    if (!io->adv && !io->ret && !io->moments) return fail(T1D_E_INVALID, "t1d_gae: adv, ret and moments are all NULL");
-    if (io->moments && (!io->workspace || io->workspace_bytes < io->n_policies * tiles * 2 * (int64_t)sizeof(double)))
-        return fail(T1D_E_INVALID, "t1d_gae: moments need a workspace of t1d_gae_workspace() bytes");
-    T1D_HIP(hipSetDevice(hip_device));
-    by_dtype(dtype, [&](auto t) { launch_gae<decltype(t)>(n, io, tiles, (hipStream_t)stream); });
-    T1D_HIP(hipGetLastError());
-    return T1D_OK;
+    return gae_entry("t1d_gae", hip_device, dtype, n, io, nullptr, false, stream);
+}
+
+extern "C" int t1d_gae_limit(int hip_device, int dtype, int64_t n, const t1d_gae_batch* io, const t1d_gae_cut* cut, void* stream)
+{
+    return gae_entry("t1d_gae_limit", hip_device, dtype, n, io, cut, true, stream);
 }
 
 extern "C" int t1d_philox_normals(t1d_ctx* c, uint64_t seed, int64_t env_offset, int64_t n, uint32_t episode,

@@ -1772,6 +1772,22 @@ __device__ __forceinline__ bool restart_front(const KArgs<T>& a, const RestartAr
     return fin;
 }
 
+// restart_front for an env i < n that restarts whatever its mask byte says: the decision is the caller's (an env cut by a time
+// limit, t1d_collect_mlp_limit).  Written out beside restart_front, not called by it: with the flag handed through, every kernel
+// that inlines restart_front came out with other registers.
+template <typename T>
+__device__ __forceinline__ void restart_front_set(const KArgs<T>& a, const RestartArgs<T>& r, unsigned i)
+{
+    if (r.ep_return) {
+        const T sum = at(r.ep_return, i) + at(a.reward, i);
+        const int len = at(r.ep_length, i) + 1;
+        if (r.last_return) at(r.last_return, i) = sum;
+        if (r.last_length) at(r.last_length, i) = len;
+        at(r.ep_return, i) = T(0); at(r.ep_length, i) = 0;
+    }
+    if (r.terminal_cgm) { const T obs = at(a.cgm, i); at(r.terminal_cgm, i) = obs; }
+}
+
 template <typename T>
 __device__ __forceinline__ void restart_env(const KArgs<T>& a, const RestartArgs<T>& r, const MealSlots& ms, unsigned i)
 {

@@ -302,6 +302,15 @@ __device__ T1D_COLLECT_RESTART_ATTR void collect_restart(KArgs<T> a, RestartArgs
     if (restart_front(a, r, a.done, i)) restart_env(a, r, *ms, i);
 }
 
+// collect_restart with the decision taken by the caller instead of read from batch.done: t1d_restart_done for one env whose mask
+// byte is set.  An env cut by a time limit restarts with done = 0 in memory (mlp_collect_limit_kernel).
+template <typename T>
+__device__ T1D_COLLECT_RESTART_ATTR void collect_restart_masked(KArgs<T> a, RestartArgs<T> r, const MealSlots* ms, unsigned i)
+{
+    restart_front_set(a, r, i);
+    restart_env(a, r, *ms, i);
+}
+
 // ---- t1d_meal_bolus: a bolus calculator beside the network (the *_bolus entry points of include/t1d.h) ---------------------
 // The network commands the basal rate; each announced meal is dosed by BBController's rule, rollout_body's expressions
 // (t1d_kernels.hpp) in its operation order, from words the stepping kernels hold anyway: the observation the step starts from
@@ -392,11 +401,34 @@ __device__ __forceinline__ T mlp_action(const MlpArgs<T>& c, const __attribute__
     return mlp_output(c, mlp_layers(c, w, buf, 2 * c.history + 3), l);
 }
 
+// ---- t1d_time_limit: episodes cut at max_minutes (t1d_collect_mlp_limit of include/t1d.h) -----------------------------------
+// After a step closes, an env that did not finish and whose clock e.t has reached max_minutes is cut: its step is recorded with
+// done = 0 and cut = 1, the features of the state it ended in go to cut_feat (mlp_features on the shifted windows, the step's
+// meal and the clock start + e.t: the words t1d_mlp_features would return), and the env restarts as a finished one does.  Of all
+// this only max_minutes (wave-uniform) is looked at outside the cut branch, and nothing of it is alive across step_body.
+template <typename T> struct LimitArgs {
+    int max_minutes;
+    uint8_t* cut_trace;                   // [rows][n] or null
+    T* cut_feat;                          // [F][n] or null
+};
+
 // what mlp_collect_body's trailing pack means: one BolusArgs -- the *_bolus kernels, a bolus in every step; a BolusArgs and an
-// EnvOutArgs -- the *_rel kernels, the bolus a wave-uniform run-time switch (cr is NULL for a policy without meal_bolus)
+// EnvOutArgs -- the *_rel kernels, the bolus a wave-uniform run-time switch (cr is NULL for a policy without meal_bolus); with a
+// LimitArgs behind the two -- the *_limit kernels, the *_rel form with the time limit, in which the pair is a wave-uniform
+// switch as well (scale is NULL for a policy that is not relative: the lane's pair is then out_scale, out_bias, and fma forms
+// the word mlp_output forms from them)
 template <typename T> __device__ __forceinline__ bool bolus_on(const BolusArgs<T>&) { return true; }
-template <typename T> __device__ __forceinline__ bool bolus_on(const BolusArgs<T>& m, const EnvOutArgs<T>&) { return m.cr != nullptr; }
-template <typename A, typename B> __device__ __forceinline__ const B& pack_second(const A&, const B& b) { return b; }
+template <typename T, typename... L> __device__ __forceinline__ bool bolus_on(const BolusArgs<T>& m, const EnvOutArgs<T>&, const L&...) { return m.cr != nullptr; }
+template <typename A, typename B, typename... L> __device__ __forceinline__ const B& pack_second(const A&, const B& b, const L&...) { return b; }
+template <typename A, typename B, typename C> __device__ __forceinline__ const C& pack_third(const A&, const B&, const C& c) { return c; }
+
+// the lane's pair under a *_limit kernel
+template <typename T>
+__device__ __forceinline__ EnvOutLane<T> env_out_lane_or(const MlpArgs<T>& c, const EnvOutArgs<T>& eo, unsigned i)
+{
+    if (eo.scale) return env_out_lane(eo, i);                  // wave-uniform
+    return EnvOutLane<T>{c.out_scale, c.out_bias};
+}
 
 // t1d_mlp_bolus: the rule alone, one lane per env -- the bolus the next step of a *_bolus roll-out would ask for, from
 // batch.cgm (CGM[0]) and the policy's prev_meal.  Reads only; writes bolus [n].
@@ -443,11 +475,14 @@ __device__ __forceinline__ void write_outputs_rc(const KArgs<T>& a, unsigned i, 
 // prev_meal = 0, hence no bolus on its first step.
 // MB = one BolusArgs and one EnvOutArgs (the *_rel entry points): the action is formed with the lane's scale and bias, and the
 // bolus is there when the BolusArgs has a cr.
+// MB = those two and one LimitArgs (t1d_collect_mlp_limit): the same, the pair there when the EnvOutArgs has a scale, and an env
+// whose clock has reached max_minutes when a step closes is cut and restarts (LimitArgs above).
 template <int VARIANT, typename T, typename P, typename PR = NoProp, typename... MB>
 __device__ __forceinline__ void mlp_collect_body(const KArgs<T>& a, const MlpArgs<T>& c, const CollectArgs<T>& g, const RestartArgs<T>& r,
                                                  P& p, unsigned i, uint32_t pid, Env<T>& e, T* col, PR pr = PR(), const MB&... mb)
 {
     constexpr int MATH = VariantMath<VARIANT>::value;
+    constexpr bool REL = sizeof...(MB) >= 2, LIMIT = sizeof...(MB) == 3;
     typedef const __attribute__((address_space(4))) T* WPtr;
     const int H = c.history, F = 2 * H + 3;
     T* const buf = col + 2 * H * 64;
@@ -471,7 +506,8 @@ __device__ __forceinline__ void mlp_collect_body(const KArgs<T>& a, const MlpArg
     BolusLane<T> bl{T(1), T(1)};
     if constexpr (sizeof...(MB) > 0) { if (bolus_on(mb...)) bl = bolus_lane(pack_first(mb...), i); }
     EnvOutLane<T> el{T(1), T(0)};
-    if constexpr (sizeof...(MB) == 2 && T1D_REL_LOAD_ONCE) el = env_out_lane(pack_second(mb...), i);
+    if constexpr (LIMIT && T1D_REL_LOAD_ONCE) el = env_out_lane_or(c, pack_second(mb...), i);
+    else if constexpr (REL && T1D_REL_LOAD_ONCE) el = env_out_lane(pack_second(mb...), i);
 #pragma unroll 1
     for (int s = 0; s < c.n_steps; ++s) {
         const int64_t trow = (c.trace_row + s) * a.n + i;
@@ -485,7 +521,8 @@ __device__ __forceinline__ void mlp_collect_body(const KArgs<T>& a, const MlpArg
             y = fma(sg, eps, y);
         }
         T u;
-        if constexpr (sizeof...(MB) == 2) u = mlp_output(c, y, T1D_REL_LOAD_ONCE ? el : env_out_lane(pack_second(mb...), i));
+        if constexpr (LIMIT) u = mlp_output(c, y, T1D_REL_LOAD_ONCE ? el : env_out_lane_or(c, pack_second(mb...), i));
+        else if constexpr (REL) u = mlp_output(c, y, T1D_REL_LOAD_ONCE ? el : env_out_lane(pack_second(mb...), i));
         else u = mlp_output(c, y);
         T bolus = T(0);
         if constexpr (sizeof...(MB) > 0) { if (bolus_on(mb...)) bolus = step_bolus(pack_first(mb...), bl, i, T(a.sen.st), col[head * 64], prev_meal, trow); }
@@ -513,13 +550,29 @@ __device__ __forceinline__ void mlp_collect_body(const KArgs<T>& a, const MlpArg
         max_bg = o.bg > max_bg ? o.bg : max_bg;
         n_low += o.bg < T(70); n_high += o.bg > T(180);
         fresh = false;
+        bool cut = false;                       // the time limit ends the episode here (never a finished one)
+        if constexpr (LIMIT) {
+            const LimitArgs<T>& lim = pack_third(mb...);
+            cut = !fin && e.t >= lim.max_minutes;
+            if (lim.cut_trace) lim.cut_trace[trow] = cut ? 1 : 0;
+        }
         if (g.on_done) {
-            if (fin) {
+            if (fin || cut) {
+                if constexpr (LIMIT) {
+                    // the features of the state the cut episode ended in: the windows are shifted, prev_meal is the step's meal
+                    // and e.t the clock after the step -- what t1d_mlp_features would read; buf is free between two steps
+                    const LimitArgs<T>& lim = pack_third(mb...);
+                    if (cut && lim.cut_feat) {
+                        mlp_features(c, col, buf, head, prev_meal, start + e.t);
+                        for (int j = 0; j < F; ++j) at(rowv(lim.cut_feat, a.n, j), i) = buf[j * 64];
+                    }
+                }
                 // the finished step goes to memory as the end of a launch leaves it; the restart works on those words
-                if constexpr (sizeof...(MB) == 2) write_outputs_rc<MATH>(a, i, e, o, rp, rc);
+                if constexpr (REL) write_outputs_rc<MATH>(a, i, e, o, rp, rc);
                 else write_outputs<MATH>(a, i, e, o, rp);
                 store_env(a, i, pid, e);
-                collect_restart<T>(a, r, g.slots, i);
+                if constexpr (LIMIT) collect_restart_masked<T>(a, r, g.slots, i);      // a cut env's done is 0
+                else collect_restart<T>(a, r, g.slots, i);
                 load_env(a, i, at(a.meta, i), e);
                 const T first = at(a.cgm, i);                   // the new episode's first observation
                 for (int k = 0; k < H; ++k) { col[k * 64] = first; col[(H + k) * 64] = T(0); }
@@ -535,7 +588,7 @@ __device__ __forceinline__ void mlp_collect_body(const KArgs<T>& a, const MlpArg
         }
     }
     if (!fresh) {
-        if constexpr (sizeof...(MB) == 2) write_outputs_rc<MATH>(a, i, e, o, rp, e.prev_risk);     // the last step's risk
+        if constexpr (REL) write_outputs_rc<MATH>(a, i, e, o, rp, e.prev_risk);     // the last step's risk
         else write_outputs<MATH>(a, i, e, o, rp);
         store_env(a, i, pid, e);
     }
@@ -658,6 +711,44 @@ __global__ __launch_bounds__(T1D_POLICY_THREADS) void mlp_collect_rel_kernel(con
     } else {
         ParsLds<T> p{lds, (int)pid};
         mlp_collect_body<VARIANT>(a, c, g, r, p, i, pid, e, col, NoProp(), m, eo);
+    }
+}
+
+// mlp_collect_rel_kernel with episodes cut at a time limit (t1d_collect_mlp_limit): the same body with a LimitArgs behind the
+// BolusArgs and the EnvOutArgs.  eo.scale == NULL: the policy's own out_scale / out_bias, m.cr == NULL: no meal bolus -- one
+// family for the plain, the hybrid and the relative policy under a limit.
+template <int VARIANT, typename T>
+__global__ __launch_bounds__(T1D_POLICY_THREADS) void mlp_collect_limit_kernel(const KArgs<T> a, const MlpArgs<T> c, const CollectArgs<T> g,
+                                                                               const RestartArgs<T> r, const EnvOutArgs<T> eo, const BolusArgs<T> m,
+                                                                               const LimitArgs<T> lim)
+{
+    using VI = VariantInfo<VARIANT>;
+    constexpr int kParRows = VI::split ? DP_COUNT : DP_RK4_COUNT;
+    __shared__ T lds[VI::lds_pars ? kParRows * kMaxPatients : 1];
+    if (VI::lds_pars) stage_pars(a, lds, kParRows);
+    if (VI::split) stage_prop(a, (T*)t1d_dyn_lds);
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    __builtin_assume(i < (1u << 28));          // host guarantees n <= 2^28: i * sizeof(T) fits a 32-bit voffset
+    if ((int64_t)i >= a.n) return;
+    T* const col = (T*)(t1d_dyn_lds + c.lds_off) + (threadIdx.x >> 6) * (c.cols * 64) + (threadIdx.x & 63u);
+    const uint32_t meta = at(a.meta, i);
+    const uint32_t pid = T1D_META_PID(meta);
+    Env<T> e;
+    load_env(a, i, meta, e);
+    if constexpr (VARIANT == 4 || VARIANT == 6) {
+        ParsReg<T> p;
+        p.load(a.dpar, (int)pid);
+        mlp_collect_body<VARIANT>(a, c, g, r, p, i, pid, e, col, PropLds<T>{(const T*)t1d_dyn_lds, a.np_pad, (int)pid}, m, eo, lim);
+    } else if constexpr (VARIANT == 7) {
+        ParsLds<T> p{lds, (int)pid};
+        mlp_collect_body<VARIANT>(a, c, g, r, p, i, pid, e, col, PropLds<T>{(const T*)t1d_dyn_lds, a.np_pad, (int)pid}, m, eo, lim);
+    } else if constexpr (VARIANT == 3) {
+        ParsReg<T> p;
+        p.load(a.dpar, (int)pid);
+        mlp_collect_body<VARIANT>(a, c, g, r, p, i, pid, e, col, NoProp(), m, eo, lim);
+    } else {
+        ParsLds<T> p{lds, (int)pid};
+        mlp_collect_body<VARIANT>(a, c, g, r, p, i, pid, e, col, NoProp(), m, eo, lim);
     }
 }
 

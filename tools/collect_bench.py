@@ -22,6 +22,20 @@ the median, and `plain_minus_rollout_ms`.  Every repetition builds the same env 
 same in each (`finish_rate_runs` shows it).
 
     python tools/collect_bench.py --exact --out profiles/collect/exact_collect_bench.json
+
+--limit: what a time limit costs (collect_mlp_limit, t1d_collect_mlp_limit), fixed-step mode, these legs instead:
+  collect       as above: today's call, no limit
+  limit_far     the same call with a limit nobody reaches (10^6 steps): the cost of the check, against `collect` of the same run
+  limit         max_episode_steps = --limit-steps in the warm steps and in the window: the envs' clocks are spread by then, and
+                about 1 / limit-steps of them are cut per step beside those that finish
+  loop_limit    the reference loop: K x (the one-step call, cut = ~done & (t >= limit), policy_features into cut_features where
+                cut, restart_done(mask = done | cut), the torch reset of the windows, stacking reward, done and truncated)
+  collect_sync  `collect` on envs that all start together (no warm steps)
+  limit_sync    the launch that holds the step in which envs that started together are all cut at once: no warm steps,
+                max_episode_steps = K, so the last step of the window cuts every env that has not finished
+`cut_rate` is the share of env-steps of the timed window that were cut.
+
+    python tools/collect_bench.py --limit --policies net --out profiles/collect/limit_bench.json
 """
 import argparse
 
@@ -76,6 +90,87 @@ def run_leg(leg, n, pol, K, warm_steps, sigma, seed, exact):
     return {"ms": ms, "status": status, "finish_rate": rate}
 
 
+LIMIT_LEGS = ("collect", "limit_far", "limit", "loop_limit", "collect_sync", "limit_sync")
+
+
+def run_limit_leg(leg, n, pol, K, warm_steps, sigma, seed, limit_steps):
+    import torch
+    e = benchlib.mixed_env(n, seed)
+    sync = leg.endswith("_sync")
+    L = {"limit_far": 10 ** 6, "limit": limit_steps, "loop_limit": limit_steps, "limit_sync": K}.get(leg)
+    cut_features = torch.zeros(2 * pol.history + 3, n, dtype=e.dtype, device=e.device)
+
+    def collect(k, **kw):                       # today's call, or the one with the limit
+        if L is None:
+            return e.collect_mlp(k, pol, policy_state=state, on_done="restart", days=DAYS, **kw)
+        return e.collect_mlp_limit(k, pol, L, cut_features, policy_state=state, days=DAYS, **kw)
+    state = e.new_policy_state(pol)
+    left = 0 if sync else warm_steps
+    while left:                                 # a call with a limit takes at most max_episode_steps steps
+        k = min(left, L or left)
+        collect(k)
+        left -= k
+    zero = torch.zeros((), dtype=e.dtype, device=e.device)
+    finished = cuts = torch.zeros((), dtype=torch.int64, device=e.device)
+
+    def go():
+        nonlocal finished, cuts
+        if leg != "loop_limit":
+            tr = e.new_trace(K, columns=COLUMNS + (("truncated",) if L is not None else ()), history=pol.history)
+            collect(K, sigma=sigma, trace=tr)
+            finished = tr["done"][1:].sum()
+            cuts = tr["truncated"][1:].sum() if L is not None else cuts
+            return
+        tr = e.new_trace(K, columns=COLUMNS if sigma is not None else COLUMNS[:5], history=pol.history)
+        rew, don, trn = [], [], []
+        for _ in range(K):
+            if sigma is not None:
+                e.collect_mlp(1, pol, sigma=sigma, policy_state=state, trace=tr)
+            else:
+                e.rollout_mlp(1, pol, policy_state=state, trace=tr)
+            done = e.done.bool()
+            cut = ~done & (e.t >= L * e.minutes_per_step)
+            rew.append(e.reward.clone()); don.append(e.done.clone()); trn.append(cut)
+            cut_features.copy_(torch.where(cut, e.policy_features(pol, state), cut_features))
+            mask = done | cut
+            e.restart_done(mask=mask, days=DAYS)
+            state["cgm_hist"].copy_(torch.where(mask, e.cgm, state["cgm_hist"]))
+            state["ins_hist"].copy_(torch.where(mask, zero, state["ins_hist"]))
+            state["prev_meal"].copy_(torch.where(mask, zero, state["prev_meal"]))
+        tr["reward"], tr["done"], tr["truncated"] = torch.stack(rew), torch.stack(don), torch.stack(trn)
+        finished, cuts = tr["done"].sum(), tr["truncated"].sum()
+    ms = benchlib.timed_leg(go, go, "host")
+    status = benchlib.close_leg(e)
+    rates = float(finished) / (K * n), float(cuts) / (K * n)
+    del e
+    torch.cuda.empty_cache()
+    return {"ms": ms, "status": status, "finish_rate": rates[0], "cut_rate": rates[1]}
+
+
+def limit_main(args):
+    import torch
+    results = []
+    for kind in args.policies:
+        pol = make_policy(kind, basal=args.hypo_basal)
+        sigma = None if kind == "hypo" or args.sigma <= 0 else args.sigma
+        for n in args.n:
+            runs = benchlib.alternate(LIMIT_LEGS, args.reps, lambda leg: run_limit_leg(leg, n, pol, args.steps, args.warm_steps, sigma,
+                                                                                     args.seed, args.limit_steps))
+            res = {"policy": kind, "hypo_basal": args.hypo_basal if kind == "hypo" else None, "n_envs": n, "dtype": "float64",
+                   "steps": args.steps, "warm_steps": args.warm_steps, "limit_steps": args.limit_steps, "sigma": sigma,
+                   "sensor": "Dexcom", "label": args.label, "device": torch.cuda.get_device_name(0), "legs": {}}
+            for leg, rr in runs.items():
+                res["legs"][leg] = {**benchlib.summarise([r["ms"] for r in rr], "ms", spread=True), "status": max(r["status"] for r in rr),
+                                    "finish_rate": rr[-1]["finish_rate"], "cut_rate": rr[-1]["cut_rate"]}
+            med = {leg: v["ms_median"] for leg, v in res["legs"].items()}
+            res["limit_far_over_collect"] = med["limit_far"] / med["collect"]
+            res["limit_over_collect"] = med["limit"] / med["collect"]
+            res["loop_limit_over_limit"] = med["loop_limit"] / med["limit"]
+            res["limit_sync_over_collect_sync"] = med["limit_sync"] / med["collect_sync"]
+            benchlib.emit(results, res)
+    benchlib.write(results, args.out)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, nargs="+", default=[1 << 16, 1 << 20])
@@ -89,9 +184,15 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--label", default=None)
     ap.add_argument("--exact", action="store_true", help="the four legs in the exact mode (integrator='dopri5'), timed with events")
+    ap.add_argument("--limit", action="store_true", help="the legs of a time limit (collect_mlp_limit) instead")
+    ap.add_argument("--limit-steps", type=int, default=48, help="max_episode_steps of the limit and loop_limit legs (>= --steps)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     benchlib.require_gpu("collect_bench.py")
+    if args.limit:
+        if args.exact or args.limit_steps < args.steps:
+            raise SystemExit("--limit runs the fixed-step mode and needs --limit-steps >= --steps")
+        return limit_main(args)
     import torch
     results = []
     for kind in args.policies:
