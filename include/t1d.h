@@ -293,12 +293,21 @@ typedef struct t1d_meal_bolus {
 /* Per-env outcome statistics of a BG history kept on the device (analysis/report.py), one lane per env:
  *   counts     int32 [5][n]: samples with BG > 180, BG < 70, 70 <= BG <= 180, BG > 250, BG < 50  (percent_stats,
  *              report.py:74-92; divide by n_rows for the percentages)
- *   pct        [2][n]: np.percentile(BG, q_lo) and (BG, q_hi) per env, exact (linear interpolation between order
- *              statistics, found by radix selection), and zone uint8 [n]: CVGA zone 0..4 = A..E, 5 = none, from
- *              the clipped percentiles (CVGA_analysis, report.py:198-217; q = 2.5 / 97.5 there)
+ *   pct        [2][n]: np.percentile(BG, q_lo) and (BG, q_hi) per env: the order statistics a, b at rank
+ *              floor(pos) and the next, pos = (n_rows - 1) q / 100, are found exactly (radix selection) and
+ *              interpolated in fp64 as numpy's 'linear' method does.  Against the exact a + (b - a)(pos - floor(pos))
+ *              the result is within (2 pos + 3) u |b - a| + (2 u + u_T) |pct|, u = 2^-53, u_T = 0 (fp64) or 2^-24
+ *              (fp32), unless it underflows; numpy's own result meets the same bound and may differ in the last bits
+ *              (it forms (n_rows - 1) (q / 100)).  A column that holds a NaN has NaN percentiles, as in numpy.  Between
+ *              equal order statistics the result is that value (b == a -> a), also for infinities, where numpy's lerp
+ *              gives NaN (inf - inf).
+ *              zone uint8 [n]: CVGA zone 0..4 = A..E, 5 = none, from the clipped percentiles (CVGA_analysis,
+ *              report.py:198-217; q = 2.5 / 97.5 there); NaN percentiles are in no zone (5)
  *   risk_trace [n_chunks][2][n]: LBGI and HBGI of every chunk of `chunk` samples, from the chunk mean of
- *              f(BG) = 1.509 (ln(BG)^1.084 - 5.381) over BG > 0 (risk_index_trace, report.py:95-110; chunk = 60)
- * Any output pointer may be NULL.  n_chunks = ceil(n_rows / chunk). */
+ *              f(BG) = 1.509 (ln(BG)^1.084 - 5.381) over BG > 0 (risk_index_trace, report.py:95-110; chunk = 60);
+ *              NaN samples and 0 < BG < 1 are skipped as BG <= 0 is, a chunk without a usable sample is NaN, and a
+ *              chunk that holds +Inf reads LBGI = 0, HBGI = +Inf
+ * A NaN sample is counted in no range.  Any output pointer may be NULL.  n_chunks = ceil(n_rows / chunk). */
 typedef struct t1d_outcome {
     int32_t* counts; void* pct; uint8_t* zone; void* risk_trace;
     double q_lo, q_hi;

@@ -413,11 +413,12 @@ def report_percent_stats(BG):
                      (BG < 50).sum(0)]) / n * 100.0
 
 
-def report_cvga(BG):
+def report_cvga(BG, q_lo=2.5, q_hi=97.5):
     """CVGA_analysis (analysis/report.py:198-217) -> BG_min, BG_max (clipped 2.5th / 97.5th percentiles per env),
-    zone fractions (A, B, C, D, E) and the per-env zone code 0..4 (5 = none).  Pinned by fixture G11."""
+    zone fractions (A, B, C, D, E) and the per-env zone code 0..4 (5 = none).  Pinned by fixture G11.  q_lo, q_hi: other
+    percentiles than the reference's (tests; a column that holds a NaN has NaN percentiles and so no zone)."""
     BG = np.asarray(BG, dtype=np.float64)
-    mn = np.clip(np.percentile(BG, 2.5, axis=0), 50, 400); mx = np.clip(np.percentile(BG, 97.5, axis=0), 50, 400)
+    mn = np.clip(np.percentile(BG, q_lo, axis=0), 50, 400); mx = np.clip(np.percentile(BG, q_hi, axis=0), 50, 400)
     A = (mn > 90) & (mn <= 110) & (mx >= 110) & (mx < 180)
     B = (mn > 70) & (mn <= 110) & (mx >= 110) & (mx < 300)
     Cz = ((mn > 90) & (mn <= 110) & (mx >= 300)) | ((mn <= 70) & (mx >= 110) & (mx < 180))

@@ -45,7 +45,8 @@ def outcome_stats(bg, chunk=60, q_lo=2.5, q_hi=97.5, counts=True, percentiles=Tr
                                        C.c_void_p(bg.data_ptr()), C.byref(o), stream))
     if counts:
         out["counts"] = cnt
-        out["percent"] = cnt.to(torch.float64) / float(rows) * 100.0
+        # a tensor divisor: by a Python scalar torch multiplies with the reciprocal, one ulp off the reference's count / n * 100
+        out["percent"] = cnt.to(torch.float64) / torch.tensor(float(rows), dtype=torch.float64, device=bg.device) * 100.0
     if percentiles:
         out["pct"], out["zone"] = pct, zone
         out["bg_min"], out["bg_max"] = pct[0].clamp(50, 400), pct[1].clamp(50, 400)

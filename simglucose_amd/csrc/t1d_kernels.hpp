@@ -1834,9 +1834,11 @@ __global__ __launch_bounds__(kBlock) void restart_kernel(const KArgs<T> a, const
 }
 
 // ---- outcome statistics of a BG history on the device (analysis/report.py) ------------------------------
-// One lane = one env, rows are read coalesced.  The two percentiles are exact: the order statistics are found
-// by radix selection on the order-preserving integer image of the values (one pass over the env's column per
-// bit), then interpolated as numpy's default 'linear' method does.
+// One lane = one env, rows are read coalesced.  The two percentiles: the order statistics are found exactly, by
+// radix selection on the order-preserving integer image of the values (one pass over the env's column per bit),
+// then interpolated in fp64 as numpy's default 'linear' method does (the rounding bound is in include/t1d.h).
+// A column that holds a NaN has NaN percentiles, as np.percentile has: in the integer image a NaN would sort
+// beyond the infinities and the env would get a finite percentile and a zone.
 template <typename T> struct OKey;
 template <> struct OKey<double> {
     typedef uint64_t U; static constexpr int bits = 64;
@@ -1849,9 +1851,9 @@ template <> struct OKey<float> {
     static __device__ __forceinline__ float val(U k) { const U u = (k >> 31) ? (k & 0x7fffffffu) : ~k; return __uint_as_float(u); }
 };
 
-// k-th smallest (0-based) of column i, and the next order statistic after it
+// k-th smallest (0-based) of column i, and the next order statistic after it; -> the column holds a NaN
 template <typename T>
-__device__ void order_stat_pair(const T* __restrict__ tr, int64_t n, int64_t rows, int64_t i, int64_t k, T& vk, T& vk1)
+__device__ bool order_stat_pair(const T* __restrict__ tr, int64_t n, int64_t rows, int64_t i, int64_t k, T& vk, T& vk1)
 {
     typedef typename OKey<T>::U U;
     U prefix = 0;
@@ -1861,14 +1863,17 @@ __device__ void order_stat_pair(const T* __restrict__ tr, int64_t n, int64_t row
         for (int64_t r = 0; r < rows; ++r) c += OKey<T>::key(tr[r * n + i]) < test;
         if (c <= k) prefix = test;
     }
-    int64_t le = 0; U next = ~(U)0; bool have = false;
+    int64_t le = 0; U next = ~(U)0; bool have = false, nan = false;
     for (int64_t r = 0; r < rows; ++r) {
-        const U key = OKey<T>::key(tr[r * n + i]);
+        const T v = tr[r * n + i];
+        const U key = OKey<T>::key(v);
+        nan |= v != v;
         le += key <= prefix;
         if (key > prefix && (!have || key < next)) { next = key; have = true; }
     }
     vk = OKey<T>::val(prefix);
     vk1 = (le > k + 1 || !have) ? vk : OKey<T>::val(next);      // duplicates of the k-th value cover rank k + 1
+    return nan;
 }
 
 template <typename T>
@@ -1879,7 +1884,7 @@ __device__ __forceinline__ T percentile_linear(const T* tr, int64_t n, int64_t r
     lo = lo < 0 ? 0 : (lo > rows - 1 ? rows - 1 : lo);
     const double t = pos - (double)lo;
     T a, b;
-    order_stat_pair(tr, n, rows, i, lo, a, b);
+    if (order_stat_pair(tr, n, rows, i, lo, a, b)) return (T)__builtin_nan("");
     if (lo >= rows - 1) b = a;
     const double d = (double)b - (double)a;                       // numpy _lerp
     double r = (double)a + d * t;

@@ -6,6 +6,7 @@ import functools
 import math
 import os
 import re
+from fractions import Fraction
 
 import numpy as np
 
@@ -764,3 +765,317 @@ def meal_tables_cover_the_branches():
     assert c0["kept"][DAYS - 1].all(axis=0).any()                                # a full last day: all six meals of it
     assert c14["kept"][DAYS].any() and not c0["kept"][DAYS].any()                # ... and a cut one after a late start
     assert any(meal_reference("same_minute_%d" % g).cand["same_minute"].any() for g in SAME_MINUTE_GIDS)
+
+
+# ------------------------------------------------------------------------------------------------ outcome statistics
+# test_outcome_host.py, test_gpu_outcome.py: t1d_outcome_stats (outcome_kernel) against references that share no code with
+# it.  The inputs are built here so that the host file can show that they reach what they are meant to reach -- every
+# threshold, both sides of every zone bound, every kind of row the risk trace skips -- on exactly what the GPU file runs.
+OUT_NS = (1, 63, 64, 65, 257, 300)            # a lane, a wave short of / at / past its end, past a 256-thread block
+OUT_ROWS = (1, 2, 3, 40, 41, 481)
+OUT_QS = ((2.5, 97.5), (0.0, 100.0), (50.0, 50.0), (33.3, 99.9))
+OUT_U = Fraction(1, 2 ** 53)
+OUT_KINDS = ("distinct", "constant", "two_valued", "sign_mixed", "tie_at_rank", "adjacent_at_rank", "negative", "thresholds")
+OUT_THRESHOLDS = (50, 70, 180, 250)
+RISK_ROWS, RISK_N = 127, 70                   # 127 is prime: no chunk but 1 and 127 divides it
+RISK_CHUNKS = (1, 7, 60, RISK_ROWS, RISK_ROWS + 5)
+RISK_C_LIMIT = 64                             # an asserted C beyond this is an arithmetic error, not rounding
+
+
+def out_np(dtype):
+    return {"f64": np.float64, "f32": np.float32}[dtype]
+
+
+def out_ut(dtype):
+    """the unit roundoff of the final cast: none in fp64"""
+    return Fraction(0) if dtype == "f64" else Fraction(1, 2 ** 24)
+
+
+def _next(v, up):
+    v = np.asarray(v)
+    return np.nextafter(v, np.array(np.inf if up else -np.inf, v.dtype))
+
+
+def outcome_threshold_pool(ft):
+    """50, 70, 180 and 250 with the float of type ft on either side of each, and five values away from them"""
+    t = np.array(OUT_THRESHOLDS, ft)
+    return np.concatenate([_next(t, False), t, _next(t, True), np.array([30, 60, 100, 200, 300], ft)])
+
+
+def outcome_threshold_inputs(n, rows, dtype, seed=3):
+    """[rows, n]: every env draws its rows from the threshold pool with weights of its own, so that the counters differ"""
+    pool = outcome_threshold_pool(out_np(dtype))
+    out = np.empty((rows, n), pool.dtype)
+    for i in range(n):
+        rs = np.random.RandomState(seed * 100003 + i * 13 + rows)
+        out[:, i] = rs.choice(pool, rows, p=rs.dirichlet(np.ones(len(pool))))
+    return out
+
+
+def outcome_counts(bg):
+    """the five counters of percent_stats by numpy's comparisons in the inputs' own type -> int64 [5, n]; NaN is in no range"""
+    with np.errstate(invalid="ignore"):
+        return np.stack([(bg > 180).sum(0), (bg < 70).sum(0), ((bg >= 70) & (bg <= 180)).sum(0), (bg > 250).sum(0),
+                         (bg < 50).sum(0)]).astype(np.int64)
+
+
+def rank_of(rows, q):
+    """pos = (rows - 1) q / 100 exactly (q as the double the kernel gets) -> (pos, floor(pos))"""
+    pos = Fraction(rows - 1) * Fraction(float(q)) / 100
+    return pos, pos.numerator // pos.denominator
+
+
+def outcome_columns(n, rows, dtype, qs=OUT_QS[0], seed=1):
+    """[rows, n], a column per env and no two alike, the kinds of OUT_KINDS in turn: distinct values; one value; two values;
+    both signs with both zeros, subnormals and values near the top of the format; the order statistics k and k + 1 of either
+    percentile of qs equal, and adjacent floats; all negative; draws from the threshold pool"""
+    ft = out_np(dtype)
+    big, sub = (1e300, 5e-324) if dtype == "f64" else (1e38, 1.4e-45)
+    ranks = [rank_of(rows, q)[1] for q in qs]
+    out = np.empty((rows, n), ft)
+    for i in range(n):
+        rs = np.random.RandomState(seed * 100003 + i * 7 + rows)
+        kind = OUT_KINDS[i % len(OUT_KINDS)]
+        if kind == "distinct":
+            c = rs.uniform(40, 400, rows)
+        elif kind == "constant":
+            c = np.full(rows, 100 + 0.37 * i)
+        elif kind == "two_valued":
+            c = np.where(rs.rand(rows) < 0.4, 80 + 0.01 * i, 200 + 0.01 * i)
+        elif kind == "sign_mixed":
+            pool = np.array([0.0, -0.0, sub, -sub, 3 * sub, -7 * sub, big, -big, 0.5 * big, -0.25 * big, 1.5 + i, -2.5 - i,
+                             1e-3 * (i + 1), -1e-3 * (i + 1)])
+            c = rs.permutation(pool)[:rows]
+            c = np.concatenate([c, rs.uniform(-300, 300, rows - len(c))])
+        elif kind in ("tie_at_rank", "adjacent_at_rank"):
+            c = np.sort(rs.uniform(40, 400, rows).astype(ft))
+            for k in ranks:
+                if k + 1 < rows:
+                    c[k + 1] = c[k] if kind == "tie_at_rank" else _next(c[k], True)
+        elif kind == "negative":
+            c = -rs.uniform(1e-3, 500, rows)
+        else:
+            c = rs.choice(outcome_threshold_pool(ft), rows)
+        out[:, i] = np.asarray(c).astype(ft)[rs.permutation(rows)]
+    return out
+
+
+def percentile_reference(bg, q, dtype):
+    """The q-th percentile of every column of bg [rows, n] (the values the kernel sees) in exact rational arithmetic:
+    pos = (rows - 1) q / 100, lo = floor(pos), a + (b - a)(pos - lo) over the sorted column -> (ref, bound), a Fraction per
+    env, None for a column that holds a NaN.
+
+    bound = (2 pos + 3) u |b - a| + (2 u + u_T) |ref| + underflow, u = 2^-53: two roundings in pos, three in the lerp, two
+    of the result and the final cast (u_T = 2^-24 in fp32).  Those are relative errors, which a product that ends below the
+    normal range does not keep: the lerp's one product may then be off by half the smallest fp64 subnormal, 2^-1075, and a
+    cast that ends below fp32's normal range by 2^-150.  That is the underflow term; it is below every other term unless
+    |b - a| and |ref| are both subnormal.  The bound takes floor(pos) in floating point to be the exact one
+    (test_outcome_host.py checks that for every pair of OUT_ROWS and OUT_QS)."""
+    bg = np.asarray(bg)
+    rows, n = bg.shape
+    pos, lo = rank_of(rows, q)
+    hi, t = min(lo + 1, rows - 1), pos - lo
+    s = np.sort(bg.astype(np.float64), axis=0)                  # by value; NaN sorts last
+    under = Fraction(1, 2 ** 1075) + (Fraction(0) if dtype == "f64" else Fraction(1, 2 ** 150))
+    ref, bound = [], []
+    for i in range(n):
+        if np.isnan(s[-1, i]):
+            ref.append(None); bound.append(None)
+            continue
+        a, b = Fraction(float(s[lo, i])), Fraction(float(s[hi, i]))
+        r = a + (b - a) * t
+        ref.append(r)
+        bound.append((2 * pos + 3) * OUT_U * abs(b - a) + (2 * OUT_U + out_ut(dtype)) * abs(r) + under)
+    return ref, bound
+
+
+def percentile_error(got, ref, bound):
+    """|got - ref| / bound per env -> float [n]; by value, so -0.0 is +0.0; a NaN where the reference has one is 0, any
+    other non-finite result +Inf"""
+    out = np.zeros(len(ref))
+    for i, (r, b) in enumerate(zip(ref, bound)):
+        g = float(got[i])
+        if r is None or not math.isfinite(g):
+            out[i] = 0.0 if (r is None and math.isnan(g)) else math.inf
+        else:
+            out[i] = float(abs(Fraction(g) - r) / b)
+    return out
+
+
+def worst_by_kind(err):
+    """the largest entry of err [n] among the sign_mixed columns (where the underflow term of the bound can be the one that
+    counts) and among all others -> (others, sign_mixed)"""
+    mixed = np.arange(len(err)) % len(OUT_KINDS) == OUT_KINDS.index("sign_mixed")
+    return float(err[~mixed].max(initial=0.0)), float(err[mixed].max(initial=0.0))
+
+
+# the comparisons of CVGA_analysis (report.py:198-217), one row per zone: its code and its alternatives, each a conjunction
+CVGA_CLAUSES = (
+    (0, ((("mn", ">", 90), ("mn", "<=", 110), ("mx", ">=", 110), ("mx", "<", 180)),)),
+    (1, ((("mn", ">", 70), ("mn", "<=", 110), ("mx", ">=", 110), ("mx", "<", 300)),)),
+    (2, ((("mn", ">", 90), ("mn", "<=", 110), ("mx", ">=", 300)), (("mn", "<=", 70), ("mx", ">=", 110), ("mx", "<", 180)))),
+    (3, ((("mn", ">", 70), ("mn", "<=", 90), ("mx", ">=", 300)), (("mn", "<=", 70), ("mx", ">=", 180), ("mx", "<", 300)))),
+    (4, ((("mn", "<=", 70), ("mx", ">=", 300)),)),
+)
+_CVGA_OPS = {">": np.greater, ">=": np.greater_equal, "<": np.less, "<=": np.less_equal}
+_CVGA_FLIP = {">": ">=", ">=": ">", "<": "<=", "<=": "<"}
+CVGA_COMPARISONS = tuple((z, a, t) for z, alts in CVGA_CLAUSES for a, alt in enumerate(alts) for t in range(len(alt)))
+
+
+def cvga_alternatives(mn, mx, flip=None):
+    """{(zone, alternative): bool [n]} on the clipped percentiles; flip = (zone, alternative, term) moves the equality of
+    that one comparison to its other side (> for >=, < for <=, and back)"""
+    v = {"mn": np.clip(np.asarray(mn, np.float64), 50, 400), "mx": np.clip(np.asarray(mx, np.float64), 50, 400)}
+    out = {}
+    for z, alts in CVGA_CLAUSES:
+        for a, alt in enumerate(alts):
+            ok = np.ones(v["mn"].shape, bool)
+            for t, (name, op, b) in enumerate(alt):
+                ok &= _CVGA_OPS[_CVGA_FLIP[op] if flip == (z, a, t) else op](v[name], b)
+            out[z, a] = ok
+    return out
+
+
+def cvga_zone_codes(mn, mx, flip=None):
+    """the zone code of every env, first zone that holds in the order A..E, else 5: a restatement of the oracle's
+    report_cvga from the table above, held to it by test_outcome_host.py; flip as in cvga_alternatives"""
+    alt = cvga_alternatives(mn, mx, flip)
+    code = np.full(np.shape(mn), 5)
+    for z, alts in reversed(CVGA_CLAUSES):
+        hit = np.zeros(np.shape(mn), bool)
+        for a in range(len(alts)):
+            hit |= alt[z, a]
+        code = np.where(hit, z, code)
+    return code
+
+
+@functools.lru_cache(maxsize=None)
+def zone_grid(dtype):
+    """Two-row columns [2, n] whose min and max walk every zone bound and both clip bounds: the bound and the float of the
+    batch's type on either side of it, and values between and beyond the bounds, in every combination with min <= max.
+    With q = (0, 100) the percentiles are the min and the max themselves.  -> (bg, mn, mx); which row holds the min
+    alternates with the env.  Read-only."""
+    ft = out_np(dtype)
+
+    def around(bounds, other):
+        b = np.array(bounds, ft)
+        return np.concatenate([_next(b, False), b, _next(b, True), np.array(other, ft)])
+    mn_vals = around((50, 70, 90, 110, 400), (30, 60, 80, 100, 150, 450))
+    mx_vals = around((50, 110, 180, 300, 400), (40, 100, 150, 250, 350, 500))
+    pairs = np.array([(a, b) for a in mn_vals for b in mx_vals if a <= b], ft)
+    mn, mx = pairs[:, 0].copy(), pairs[:, 1].copy()
+    swap = np.arange(len(mn)) % 2 == 1
+    bg = np.stack([np.where(swap, mx, mn), np.where(swap, mn, mx)])
+    for a in (bg, mn, mx):
+        a.setflags(write=False)
+    return bg, mn, mx
+
+
+@functools.lru_cache(maxsize=None)
+def risk_inputs(dtype):
+    """[RISK_ROWS, RISK_N], read-only: BG-like columns, twelve that stay low (f < 0), twelve high (f > 0), eight around
+    112.5 mg/dL where f changes sign, and in the first eight envs the rows risk_index_trace skips: BG <= 0 with both zeros,
+    0 < BG < 1, BG = 1 (ln = 0, the lowest usable f), +Inf, a first week of rows and a last chunk of 60 with nothing usable,
+    and a column with no usable row at all"""
+    rs = np.random.RandomState(5)
+    bg = rs.uniform(40, 400, (RISK_ROWS, RISK_N))
+    bg[:, 8:20] = rs.uniform(45, 100, (RISK_ROWS, 12))
+    bg[:, 20:32] = rs.uniform(150, 400, (RISK_ROWS, 12))
+    bg[:, 32:40] = rs.uniform(105, 120, (RISK_ROWS, 8))
+    bg[3, 0], bg[5, 0], bg[3, 1], bg[3, 2], bg[64, 2], bg[3, 3], bg[10, 4] = 0.0, -0.0, -5.0, 0.5, 1e-30, 1.0, np.inf
+    bg[0:7, 5] = (0.0, -1.0, 0.5, -0.0, 0.25, -3.0, 0.999)
+    bg[:, 6] = 0.5
+    bg[120:, 7] = 0.0
+    bg = bg.astype(out_np(dtype))
+    bg.setflags(write=False)
+    return bg
+
+
+def risk_terms(bg):
+    """per sample, at 50 digits: ln(BG)^1.084 where 1.509 (ln(BG)^1.084 - 5.381) is a real number -- BG >= 1, +Inf
+    included -- and None elsewhere (BG <= 0, NaN, and 0 < BG < 1, the power of a negative logarithm) -> object [rows, n].
+    The constants are the doubles the code holds."""
+    import mpmath
+    out = np.empty(bg.shape, object)
+    with mpmath.workdps(50):
+        for idx, v in np.ndenumerate(np.asarray(bg, np.float64)):
+            out[idx] = mpmath.log(mpmath.mpf(float(v))) ** mpmath.mpf(1.084) if v >= 1 else None
+    return out
+
+
+def risk_reference(terms, chunk):
+    """risk_index_trace from risk_terms: per chunk and env (cnt, f, S) -> three arrays [n_chunks, n]; f = the mean of
+    1.509 (p - 5.381) over the cnt usable rows (None without one), S = 1.509 (mean p + 5.381) the scale of its rounding"""
+    import mpmath
+    rows, n = terms.shape
+    nch = (rows + chunk - 1) // chunk
+    cnt, f, S = np.zeros((nch, n), np.int64), np.empty((nch, n), object), np.empty((nch, n), object)
+    with mpmath.workdps(50):
+        a, b = mpmath.mpf(1.509), mpmath.mpf(5.381)
+        for c in range(nch):
+            for i in range(n):
+                p = [v for v in terms[c * chunk:(c + 1) * chunk, i] if v is not None]
+                cnt[c, i] = len(p)
+                mean = mpmath.fsum(p) / len(p) if p else None
+                f[c, i] = a * (mean - b) if p else None
+                S[c, i] = a * (mean + b) if p else None
+    return cnt, f, S
+
+
+def risk_compare(lbgi, hbgi, ref, dtype, C):
+    """LBGI and HBGI [n_chunks, n] of a run against risk_reference -> dict:
+    nan_equal: NaN exactly where the reference has no usable row; where f is +Inf (a +Inf sample) LBGI = 0 and HBGI = +Inf;
+    c_needed:  fp64 only -- the largest |f - f_ref| / (u S) - cnt, f recovered from the outputs as -sqrt(LBGI / 10) or
+               +sqrt(HBGI / 10) at 50 digits (an fp32 output carries f to 2^-25 only, so there the next figure is the check);
+    worst:     the largest error of LBGI or HBGI over 10 (2 |f_ref| D + D^2) + (3 u + u_T) |ref|, D = (cnt + C) u S."""
+    import mpmath
+    cnt, f, S = ref
+    u, ut = mpmath.mpf(2) ** -53, mpmath.mpf(float(out_ut(dtype)))
+    res = {"nan_equal": True, "c_needed": -math.inf, "worst": 0.0}
+    with mpmath.workdps(50):
+        for idx in np.ndindex(cnt.shape):
+            L, H = float(lbgi[idx]), float(hbgi[idx])
+            if f[idx] is None:
+                res["nan_equal"] &= math.isnan(L) and math.isnan(H)
+                continue
+            if math.isnan(L) or math.isnan(H):
+                res["nan_equal"] = False
+                continue
+            if mpmath.isinf(f[idx]):
+                res["nan_equal"] &= L == 0.0 and H == math.inf
+                continue
+            fr = f[idx]
+            if dtype == "f64":
+                fg = -mpmath.sqrt(mpmath.mpf(L) / 10) if L > 0 else mpmath.sqrt(mpmath.mpf(H) / 10)
+                res["c_needed"] = max(res["c_needed"], float(abs(fg - fr) / (u * S[idx]) - int(cnt[idx])))
+            D = (int(cnt[idx]) + C) * u * S[idx]
+            for got, want in ((L, 10 * fr * fr if fr < 0 else mpmath.mpf(0)), (H, 10 * fr * fr if fr > 0 else mpmath.mpf(0))):
+                bound = 10 * (2 * abs(fr) * D + D * D) + (3 * u + ut) * abs(want)
+                res["worst"] = max(res["worst"], float(abs(mpmath.mpf(got) - want) / bound))
+    return res
+
+
+NAN_N, NAN_ROWS = 300, 41
+# env -> (rows that hold a NaN, its sign bit): first row, last row, an inner row, the last env, and a whole column
+NAN_CASES = {5: ((0,), 0), 64: ((NAN_ROWS - 1,), 1), 130: ((7,), 0), 299: ((0,), 1), 257: (tuple(range(NAN_ROWS)), None)}
+
+
+def nan_inputs(dtype):
+    """-> (clean, poisoned): outcome_columns for NAN_N envs, and a copy with the NaNs of NAN_CASES (None: alternating signs)"""
+    clean = outcome_columns(NAN_N, NAN_ROWS, dtype)
+    bad = clean.copy()
+    for env, (rows, sign) in NAN_CASES.items():
+        for r in rows:
+            bad[r, env] = np.copysign(np.nan, -1.0 if (r % 2 if sign is None else sign) else 1.0)
+    return clean, bad
+
+
+@functools.lru_cache(maxsize=None)
+def risk_reference_of(dtype, chunk):
+    """risk_reference of risk_inputs(dtype); the 50-digit terms are computed once per dtype.  Read-only."""
+    return risk_reference(_risk_terms_of(dtype), chunk)
+
+
+@functools.lru_cache(maxsize=None)
+def _risk_terms_of(dtype):
+    return risk_terms(risk_inputs(dtype))

@@ -282,9 +282,11 @@ def test_split_integrator_other_substep_counts_and_table_rebuild(n_sub):
 
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
 def test_outcome_statistics_match_reference_report(golden, dtype):
-    """t1d_outcome_stats on fixture G11: the reference's percent_stats and CVGA_analysis outputs
-    exactly (percentiles by radix selection == np.percentile), zones, and the chunked risk trace against the
-    oracle's restatement of risk_index_trace."""
+    """t1d_outcome_stats on fixture G11: the reference's percent_stats counts exactly, its CVGA_analysis
+    percentiles to 1e-12 (order statistics by radix selection, interpolated as np.percentile does: within the rounding
+    bound of include/t1d.h of the exact percentile, not bit-equal to numpy; test_gpu_outcome.py holds the bound), zones,
+    and the chunked risk trace against the oracle's restatement of risk_index_trace.  NaN-free histories only: a column
+    that holds a NaN has NaN percentiles and no zone (test_gpu_outcome.py)."""
     import torch
     from simglucose_amd.analysis import report
     from oracle import t1d_oracle as O
