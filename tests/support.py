@@ -574,13 +574,14 @@ def status_oracle(sensor="Navigator", exact=False, poison=None, n=STATUS_N, feed
     return out
 
 
-def status_env(sensor="Navigator", n=STATUS_N, feed=3, options=(), dtype=None, exact=False, z=None, meal_step=1, make=None, **kw):
+def status_env(sensor="Navigator", n=STATUS_N, feed=3, options=(), dtype=None, exact=False, z=None, meal_step=1, make=None, inputs=None, **kw):
     """the device env of the status inputs: host normals (z: others), the meal table, `options` as (name, value) pairs
     set before reset(), reset.  make: what builds the env from BatchedT1DSimEnv's arguments (test_gpu_parity._env with its
-    variant bound, for the generic kernel's other schemes), None: BatchedT1DSimEnv itself"""
+    variant bound, for the generic kernel's other schemes), None: BatchedT1DSimEnv itself.  inputs: what builds the inputs
+    from (sensor, n, feed, meal_step), None: status_inputs (gut_inputs: the same with more meals)"""
     torch = gpu_torch()
     from simglucose_amd.batch_env import BatchedT1DSimEnv
-    inp = status_inputs(sensor, n, feed, meal_step)
+    inp = (inputs or status_inputs)(sensor, n, feed, meal_step)
     e = (make or BatchedT1DSimEnv)(patient=inp["pid"], sensor=sensor, noise="host", normals=inp["z"] if z is None else z, n_sub=4,
                                    dtype=dtype or torch.float64, integrator="dopri5" if exact else None, **kw)
     for name, value in options:
@@ -609,6 +610,7 @@ EDGE_CROSSING = {"cross_m1": 1, "cross_m2": 2}   # kind -> the minute after the 
 EDGE_HELD = {"held3": (3, -0.25), "neg4": (4, -1e-3), "neg12": (12, -2e-3)}     # kind -> the word the reference holds, its value
 EDGE_SNAP = -1e-10                               # where the fixed-step scheme leaves an x3 that a step took below 0 (o_knob[3])
 EDGE_OUT = GRID_OUT + ("last_cgm", "x")
+GUT_WORDS = ("planned", "last_qsto", "last_food")    # the meal bookkeeping beside the state (t1dpatient.py:82-107, 222-236)
 
 
 def edge_states(x, pid):
@@ -651,14 +653,17 @@ def edge_lanes(*kinds):
     return sorted({i for k in kinds for i in EDGE_LANES[k]})
 
 
-def edge_oracle_run(sensor="Navigator", integrator="split_adaptive", feed=3, meal_step=1, after_edit=None, minutes=False):
+def edge_oracle_run(sensor="Navigator", integrator="split_adaptive", feed=3, meal_step=1, after_edit=None, minutes=False,
+                    inputs=None, edit=None):
     """The oracle over the status inputs with edge_states written after STATUS_PRE steps (after_edit(x): a further edit of
     the state, in place).  minutes: the same patients' minutes under a one-minute sensor, minute by minute, as status_lanes
-    drives them -- the patient does not depend on the sensor.
-    -> dict: EDGE_OUT after every step (minute) as arrays [K, n] (x: [K, 13, n]), x_edit = the state as written, level2 =
-    lane-minutes at level 2 per step [K], final = the last x, lanes = EDGE_LANES.  A solver that gives up raises."""
+    drives them -- the patient does not depend on the sensor.  inputs, edit: gut_inputs and gut_states in place of
+    status_inputs and edge_states (edit(orc, pid) -> the lane table).
+    -> dict: EDGE_OUT and the meal words GUT_WORDS after every step (minute) as arrays [K, n] (x: [K, 13, n]), x_edit = the
+    state as written, level2 = lane-minutes at level 2 per step [K], final = the last x, lanes = the lane table.  A solver
+    that gives up raises."""
     from oracle import t1d_oracle as O
-    inp = status_inputs(sensor, STATUS_N, feed, meal_step)
+    inp = (inputs or status_inputs)(sensor, STATUS_N, feed, meal_step)
     st = inp["st"]
     if minutes:
         orc = O.OracleEnv(inp["pid"], sensor="Navigator", normals=inp["z"], integrator=integrator, n_sub=4)
@@ -667,11 +672,12 @@ def edge_oracle_run(sensor="Navigator", integrator="split_adaptive", feed=3, mea
         orc = status_oracle_env(inp, integrator)
     per = st if minutes else 1                                   # oracle steps per step of the inputs
     orc.reset()
-    rows = {k: [] for k in EDGE_OUT + ("level2",)}
-    x_edit = None
+    x_reset = orc.x.copy()
+    rows = {k: [] for k in EDGE_OUT + GUT_WORDS + ("level2",)}
+    x_edit, lanes = None, EDGE_LANES
     for k in range(inp["K"] * per):
         if k == STATUS_PRE * per:
-            edge_states(orc.x, inp["pid"])
+            lanes = edge_states(orc.x, inp["pid"]) if edit is None else edit(orc, inp["pid"])
             if after_edit is not None:
                 after_edit(orc.x)
             x_edit = orc.x.copy()
@@ -680,9 +686,11 @@ def edge_oracle_run(sensor="Navigator", integrator="split_adaptive", feed=3, mea
         for key in GRID_OUT:
             rows[key].append(r[key].copy())
         rows["last_cgm"].append(orc.last_cgm.copy()); rows["x"].append(orc.x.copy())
+        for key in GUT_WORDS:
+            rows[key].append(getattr(orc, key).copy())
         rows["level2"].append(int(orc.level_count[2]) - before)
     out = {k: np.stack(v) for k, v in rows.items()}
-    out.update(x_edit=x_edit, final=orc.x.copy(), lanes=EDGE_LANES)
+    out.update(x_reset=x_reset, x_edit=x_edit, final=orc.x.copy(), lanes=lanes)
     return out
 
 
@@ -690,6 +698,159 @@ def edge_oracle_run(sensor="Navigator", integrator="split_adaptive", feed=3, mea
 def edge_oracle(sensor="Navigator", integrator="split_adaptive", feed=3, meal_step=1):
     """edge_oracle_run, computed once per argument set; treat as read-only"""
     return edge_oracle_run(sensor, integrator, feed, meal_step)
+
+
+# ------------------------------------------------------------------------------------------------ gastric-emptying edge states
+# test_gut_states_host.py, test_gpu_gut_states.py: the status inputs with more meals, and after the STATUS_PRE steps an edit of
+# the gut words (x0, x1, last_qsto, last_food and, on the device, the dbar row beside them) that takes the tanh pair of
+# t1dpatient.py:135-142 to arguments no trajectory from an empty stomach reaches.  The edited lanes are unfed lanes of the
+# feed = 3 inputs (neither eating nor with a meal planned: the one-minute kernels read `dbar` in place of the two words
+# there), but for the two transition kinds: an argument moves by more than the step-size rule's kMove = 4 in a minute only
+# while the lane eats (emptying moves qsto by kgut x1 < 0.07 qsto a minute), so these sit in fed lanes, which are eating at
+# the edit: last_food = 1 g becomes 6 g in the next minute and qsto is b (d) times 6 g.  A 70 g meal is eaten for 14 minutes, longer than the minutes left after the edit, so a lane that the table feeds
+# is still eating when a further meal arrives and takes no new last_qsto (meal_while_eating); the second_meal lanes get their
+# full stomach by the edit instead -- 45 g in transit of a finished 70 g meal -- and then 30 g through the table.
+GUT_LANES = {                                    # kind -> lanes: each kind in chunk 0, in chunk 1 and in the partial chunk
+    "no_dbar": (1, 65, 130),                     # grams in the stomach, Dbar = 0: kgut = kmax (:142)
+    "overfull": (4, 32, 64, 128),                # qsto = 30 Dbar (4, 64: patient row 4, b = 0.988; 32: row 2, the smallest b)
+    "deep_negative": (34, 26, 94, 86, 146),      # qsto = 0 (34, 86) or 0.1 g (the others), Dbar = 70 g, b >= 0.952
+    "at_transition_b": (6, 69, 132),             # fed lanes: qsto = b Dbar exactly at the start of the first minute ...
+    "at_transition_d": (9, 72, 135),             # ... = d Dbar exactly, Dbar = 6 g and growing by 5 g a minute
+    "tiny_dbar": (10, 73, 134),                  # Dbar = 50 mg, 40 mg in the stomach
+    "huge_in_transit": (11, 74, 136),            # last_food = 400 g, 370 g in the stomach
+    "residue": (13, 76, 137),                    # x0 = 1e-300, x1 = 5e-324 (fp32: both round to 0), Dbar = 70 g
+    "second_meal": (14, 77, 139, 16, 79, 140),   # 45 g in transit by the edit, then 30 g: first minute / (16, 79, 140) second
+    "tiny_meal": (17, 80, 142),                  # 0.05 g on an empty stomach
+    "huge_meal": (19, 82, 143),                  # 400 g on an empty stomach
+    "back_to_back": (20, 83, 145),               # 4 g and 3 g in the last minute of a step and the first of the next
+    "meal_while_eating": (21, 84, 147),          # fed lanes of the feed = 3 inputs: 30 g more while the 70 g are being eaten
+}
+GUT_DEEP_ZERO = (34, 86)
+GUT_SECOND_LATE = (16, 79, 140)
+GUT_EDITED = ("no_dbar", "overfull", "deep_negative", "at_transition_b", "at_transition_d", "tiny_dbar", "huge_in_transit",
+              "residue", "second_meal")
+GUT_OVERFULL, GUT_DBAR_SMALL, GUT_DBAR_EATING, GUT_DBAR_MEAL, GUT_DBAR_HUGE = 30.0, 2.0, 1.0, 70.0, 400.0   # a ratio; grams
+
+
+def gut_meals(st):
+    """the meals after the edit: lane -> [(minute, grams)]; t0 = the first minute after the edit"""
+    t0, L, out = STATUS_PRE * st, GUT_LANES, {}
+    for i in L["second_meal"]:
+        out[i] = [(t0 + (i in GUT_SECOND_LATE), 30.0)]           # Dexcom: the first / the middle minute of the step
+    for i in L["tiny_meal"]:
+        out[i] = [(t0, 0.05)]
+    for i in L["huge_meal"]:
+        out[i] = [(t0, 400.0)]
+    for i in L["back_to_back"]:
+        out[i] = [(t0 + st - 1, 4.0), (t0 + st, 3.0)]
+    for i in L["meal_while_eating"]:
+        out[i] = [(t0 + 1, 30.0)]
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def gut_inputs(sensor="Navigator", n=STATUS_N, feed=3, meal_step=1):
+    """status_inputs with gut_meals added: mt / ma = the meal table [3, n], ascending per env, and cho = the same meals per
+    minute.  A meal in the minute of the 70 g meal (feed = 1: every env is fed in the first minute after the edit) is one
+    entry with it."""
+    from simglucose_amd import _lib
+    inp = dict(status_inputs(sensor, n, feed, meal_step))
+    meals = [[(int(inp["mt"][0, i]), float(inp["ma"][0, i]))] if inp["fed"][i] else [] for i in range(n)]
+    for i, extra in gut_meals(inp["st"]).items():
+        for t, g in extra:
+            same = [j for j, (tt, _) in enumerate(meals[i]) if tt == t]
+            if same:
+                meals[i][same[0]] = (t, meals[i][same[0]][1] + g)
+            else:
+                meals[i].append((t, g))
+        meals[i].sort()
+    rows = max(len(m) for m in meals)
+    mt, ma, cho = np.full((rows, n), _lib.MEAL_UNUSED, dtype=np.int64), np.zeros((rows, n)), np.zeros_like(inp["cho"])
+    for i, m in enumerate(meals):
+        for j, (t, g) in enumerate(m):
+            mt[j, i], ma[j, i], cho[t, i] = t, g, g
+    inp.update(mt=mt, ma=ma, cho=cho)
+    return inp
+
+
+def fma_word(a, b, c):
+    """a * b + c rounded once to fp64, as the device's fma forms it"""
+    v = Fraction(a) * Fraction(b) + Fraction(c)
+    return v.numerator / v.denominator           # int / int is correctly rounded
+
+
+def gut_states(target, pid):
+    """target: the oracle (numpy rows x [13, n], last_qsto, last_food) or a device env (torch rows, and dbar), n >= 150,
+    edited in place after the STATUS_PRE steps; pid: the patient row per env.  Every value is formed on the host in fp64
+    and written as a Python float, so the oracle and an fp64 env receive the same words.  dbar is formed from the two words
+    as the row holds them, 1000 last_food + last_qsto rounded once, which is what the kernels store there
+    (test_gut_states_host.py: in fp64 the plain expression gives the same word in every lane).  -> GUT_LANES."""
+    from simglucose_amd import params
+    _, tab = params.patient_table()
+    pid = np.asarray(pid)
+    b, d = tab[pid, params.P_COL["b"]], tab[pid, params.P_COL["d"]]
+
+    def put(i, x0, x1, lq, lf):
+        target.x[0][i] = float(x0); target.x[1][i] = float(x1)
+        target.last_qsto[i] = float(lq); target.last_food[i] = float(lf)
+        if hasattr(target, "dbar"):
+            target.dbar[i] = fma_word(float(target.last_food[i]), 1000.0, float(target.last_qsto[i]))
+
+    L = GUT_LANES
+    for i in L["no_dbar"]:
+        put(i, 3000.0, 5000.0, 0.0, 0.0)
+    for i in L["overfull"]:                                          # 20 g + 40 g on a 2 g meal
+        q = GUT_OVERFULL * 1000.0 * GUT_DBAR_SMALL
+        put(i, q / 3.0, q - q / 3.0, 0.0, GUT_DBAR_SMALL)
+    for i in L["deep_negative"]:
+        put(i, 0.0, 0.0 if i in GUT_DEEP_ZERO else 100.0, 0.0, GUT_DBAR_MEAL)
+    for kind, frac in (("at_transition_b", b), ("at_transition_d", d)):
+        for i in L[kind]:                                            # two equal halves: their sum is the product, exactly
+            q = float(frac[i]) * (1000.0 * (GUT_DBAR_EATING + 5.0))
+            put(i, 0.5 * q, 0.5 * q, 0.0, GUT_DBAR_EATING)
+    for i in L["tiny_dbar"]:                                         # both words in use: 20 mg + 1000 * 0.03 g
+        put(i, 15.0, 25.0, 20.0, 0.03)
+    for i in L["huge_in_transit"]:
+        put(i, 150000.0, 220000.0, 0.0, GUT_DBAR_HUGE)
+    for i in L["residue"]:
+        put(i, 1e-300, 5e-324, 0.0, GUT_DBAR_MEAL)
+    for i in L["second_meal"]:
+        put(i, 20000.0, 25000.0, 0.0, GUT_DBAR_MEAL)
+    return L
+
+
+def gut_lanes(*kinds):
+    """the lanes of the given kinds, sorted, each once"""
+    return sorted({i for k in kinds for i in GUT_LANES[k]})
+
+
+def gut_arguments(o, pid):
+    """from a gut_oracle run made minute by minute: the doubled arguments of the tanh pair -- what the kernels' exponentials
+    take, 2 aa (qsto - b Dbar) and 2 cc (qsto - d Dbar) of t1dpatient.py:136-140 -- at the start of every minute, with the
+    meal words as that minute uses them -> (A2, C2, Dbar, qsto), each [minutes, n]; A2 = C2 = 0 where Dbar = 0"""
+    from simglucose_amd import params
+    _, tab = params.patient_table()
+    b, d = tab[pid, params.P_COL["b"]], tab[pid, params.P_COL["d"]]
+    start = np.concatenate([o["x_reset"][None], o["x"][:-1]])
+    t0 = len(start) * STATUS_PRE // (STATUS_PRE + STATUS_POST)
+    start[t0] = o["x_edit"]
+    qsto = start[:, 0] + start[:, 1]
+    dbar = o["last_qsto"] + 1000.0 * o["last_food"]
+    safe = np.where(dbar > 0, dbar, 1.0)
+    a2 = np.where(dbar > 0, 5.0 / (1.0 - b) / safe * (qsto - b * safe), 0.0)
+    c2 = np.where(dbar > 0, 5.0 / d / safe * (qsto - d * safe), 0.0)
+    return a2, c2, dbar, qsto
+
+
+def gut_oracle_run(sensor="Navigator", integrator="split_adaptive", feed=3, meal_step=1, after_edit=None, minutes=False):
+    """edge_oracle_run over gut_inputs with gut_states as the edit"""
+    return edge_oracle_run(sensor, integrator, feed, meal_step, after_edit, minutes, inputs=gut_inputs, edit=gut_states)
+
+
+@functools.lru_cache(maxsize=None)
+def gut_oracle(sensor="Navigator", integrator="split_adaptive", feed=3, meal_step=1, minutes=False):
+    """gut_oracle_run, computed once per argument set; treat as read-only"""
+    return gut_oracle_run(sensor, integrator, feed, meal_step, minutes=minutes)
 
 
 # ------------------------------------------------------------------------------------------------ the random streams

@@ -63,23 +63,24 @@ def _scheme(path):
     return "split_adaptive" if variant is None else _integ(variant)
 
 
-def _device_run(path, dtype):
+def _device_run(path, dtype, inputs=support.status_inputs, write=lambda e, pid: support.edge_states(e.x, pid), keys=EDGE_OUT):
     """K steps of the status inputs' actions with the edge states written after STATUS_PRE of them -> EDGE_OUT after every
     step as fp64 arrays [K, n] (x: [K, 13, n]), raw_x / raw_edit = the states and the state as written in the env's own
-    precision"""
+    precision.  inputs, write(env, pid), keys: other inputs of the same shape, another edit, the attributes to record
+    (test_gpu_gut_states.py)"""
     torch = _torch()
     sensor, feed, meal_step, options, variant = PATHS.get(path) or ALL_FED
-    inp = support.status_inputs(sensor, STATUS_N, feed, meal_step)
+    inp = inputs(sensor, STATUS_N, feed, meal_step)
     make = None if variant is None else functools.partial(_variant_env, variant)
-    e = support.status_env(sensor, STATUS_N, feed, options, _dtype(dtype), meal_step=meal_step, make=make)
+    e = support.status_env(sensor, STATUS_N, feed, options, _dtype(dtype), meal_step=meal_step, make=make, inputs=inputs)
     d = _Step(e, inp)
-    rows = {k: [] for k in EDGE_OUT}
+    rows = {k: [] for k in keys}
     for k in range(K):
         if k == STATUS_PRE:
-            assert support.edge_states(e.x, inp["pid"]) is EDGE_LANES
+            assert write(e, inp["pid"]) is (EDGE_LANES if inputs is support.status_inputs else support.GUT_LANES)
             edit = e.x.clone()
         d.run(1)
-        for key in EDGE_OUT:
+        for key in keys:
             rows[key].append(getattr(e, key).clone())
     assert e.sync() == 0                                        # nothing non-finite, no normal missing, no stall
     assert int(e.t.min()) == int(e.t.max()) == K * inp["st"]
@@ -227,10 +228,11 @@ def test_rollouts_match_their_step_loops_through_the_branch_points(shared, ctrl,
     assert bool((e.x[3, L] == torch.as_tensor(EDGE_SNAP, dtype=e.dtype)).all())
 
 
-def _mlp_pair(collect, exact):
+def _mlp_pair(collect, exact, write=lambda e: support.edge_states(e.x, e.patient_idx)):
     """A: rollout_mlp (collect: collect_mlp with on_done="restart"; exact: their _dopri5 twins) in launches of STATUS_PRE and
-    STATUS_POST steps; B: support.loop_of_entry_points; the edge states written into both after the first launch; equal bit
-    for bit -> (A, B's episode counters before the second launch, A's state as edited)"""
+    STATUS_POST steps; B: support.loop_of_entry_points; the edge states written into both after the first launch (write(env):
+    another edit, test_gpu_gut_states.py); equal bit for bit -> (A, B's episode counters before the second launch, A's state
+    as edited)"""
     torch = _torch()
     pol = support.random_policy(widths=(8, 1), n_policies=2, seed=4)
     A, B = (support.gym_env(MLP_N, exact=exact) for _ in range(2))
@@ -244,7 +246,7 @@ def _mlp_pair(collect, exact):
     nfa, nfb = (torch.zeros(MLP_N, dtype=torch.int64, device=A.device) for _ in range(2))
     for steps in (STATUS_PRE, STATUS_POST):
         if steps == STATUS_POST:
-            support.edge_states(A.x, A.patient_idx); support.edge_states(B.x, B.patient_idx)
+            write(A); write(B)
             edit, before = A.x.clone(), B.episode.clone()
         sta = fn(steps, pol, policy_state=sta, stats=sa, trace=ta, **kw)
         nfa += A.nfev if exact else 0
