@@ -811,11 +811,50 @@ int t1d_rollout_mlp_dopri5_rel(t1d_ctx* ctx, const t1d_batch* b, const t1d_mlp* 
  * T1D_E_INVALID before anything is launched, nothing changed: whatever the matching existing call rejects; a NULL limit,
  *   max_minutes < 1 or reserved != 0; on_done != T1D_COLLECT_RESTART (a cut restarts); n_steps * minutes > max_minutes -- so an
  *   env is cut at most once per call and one cut_feat column per env is enough.
- * The other collectors (t1d_collect_mlp_dopri5, t1d_collect_pid, t1d_collect_bb and their exact forms) have no time limit. */
+ * The other collectors have the same limit: the five calls below.  What has none is the exact MLP collector under a meal bolus
+ *   or a relative output: there is no t1d_collect_mlp_dopri5_bolus or _rel to put a limit on, and t1d_collect_mlp_dopri5_limit
+ *   takes neither struct. */
 int t1d_collect_mlp_limit(t1d_ctx* ctx, const t1d_batch* batch, const t1d_mlp* mlp, const t1d_collect* collect,
                           const t1d_env_output* env_output /* NULL = t1d_mlp's out_scale / out_bias */,
                           const t1d_meal_bolus* meal_bolus /* NULL = no bolus */,
                           const t1d_time_limit* limit, int n_steps, int minutes, int n_sub, void* hip_stream);
+
+/* t1d_collect_pid, t1d_collect_bb, t1d_collect_mlp_dopri5, t1d_collect_pid_dopri5 and t1d_collect_bb_dopri5 with the time limit
+ * of t1d_collect_mlp_limit, in one launch as they are: the matching existing call is the one without _limit in its name, and
+ * everything the limit does not touch -- arguments, state, traces, draws, h_carry and nfev -- is that call's.
+ * When a step is cut: after a step closes, done is formed as ever; cut = !done && t >= max_minutes, t the env's clock after the
+ *   step (minutes since its reset).  Termination wins over truncation.
+ * What is recorded for a cut step: done_trace holds 0, cut_trace holds 1 and batch.done stays 0.  cut_feat[j][i] holds the F =
+ *   2 H + 3 features of the state after that step (H = feat.history for the controllers), formed by the collectors' own device
+ *   function from the shifted windows, prev_meal = the step's meal and the clock start_minute + t: what t1d_mlp_features would
+ *   return at that moment, bit for bit.  cut_feat is written for cut envs only.  Every trace row, cut_trace's too, is the row of
+ *   the call's other traces: the controller's trace_row in the four controller calls, mlp.trace_row in the MLP call.
+ * What happens to a cut env: what happens to a finished one, which is t1d_restart_done with its mask byte set -- the episode
+ *   accumulators move to last_*, terminal_cgm is written, the env gets a new start hour, a new meal column, a reset and
+ *   episode + 1 -- then the reset of the feature windows (every cgm_hist row the new first observation, ins_hist and prev_meal 0)
+ *   and of the controller state (pid.integ = pid.prev = 0; bb.prev_meal = 0), and in the exact mode h_carry = 0: the first
+ *   minute of the new episode probes the step size.
+ * Equivalence: after the call everything is what n_steps x (t1d_mlp_features for the trace row; the matching one-step call; for
+ *   the controllers the shift of the windows; cut = !done && t >= max_minutes; t1d_mlp_features for the cut envs;
+ *   t1d_restart_done(mask = done | cut); the reset of windows, prev_meal and controller state of the masked envs) leave, bit
+ *   for bit (in the exact mode: for envs whose solver does not give up), wherever the call is cut into launches -- each launch
+ *   takes the same t1d_time_limit.  With a max_minutes no env reaches the result is the matching existing call's, bit for bit.
+ * T1D_E_INVALID before anything is launched, nothing changed: whatever the matching existing call rejects, under this call's
+ *   name; a NULL limit, max_minutes < 1 or reserved != 0; on_done != T1D_COLLECT_RESTART (a cut restarts); n_steps * minutes >
+ *   max_minutes -- so an env is cut at most once per call and one cut_feat column per env is enough. */
+int t1d_collect_pid_limit(t1d_ctx* ctx, const t1d_batch* batch, const t1d_pid* pid, const t1d_mlp* feat, const t1d_collect* collect,
+                          const t1d_time_limit* limit, int n_steps, int minutes, int n_sub, void* hip_stream);
+int t1d_collect_bb_limit(t1d_ctx* ctx, const t1d_batch* batch, const t1d_bb* bb, const t1d_mlp* feat, const t1d_collect* collect,
+                         const t1d_time_limit* limit, int n_steps, int minutes, int n_sub, void* hip_stream);
+int t1d_collect_mlp_dopri5_limit(t1d_ctx* ctx, const t1d_batch* b, const t1d_mlp* mlp, const t1d_collect* collect,
+                                 const t1d_time_limit* limit, double* h_carry, int32_t* nfev, int n_steps, int minutes,
+                                 void* hip_stream);
+int t1d_collect_pid_dopri5_limit(t1d_ctx* ctx, const t1d_batch* b, const t1d_pid* pid, const t1d_mlp* feat,
+                                 const t1d_collect* collect, const t1d_time_limit* limit, double* h_carry, int32_t* nfev,
+                                 int n_steps, int minutes, void* hip_stream);
+int t1d_collect_bb_dopri5_limit(t1d_ctx* ctx, const t1d_batch* b, const t1d_bb* bb, const t1d_mlp* feat,
+                                const t1d_collect* collect, const t1d_time_limit* limit, double* h_carry, int32_t* nfev,
+                                int n_steps, int minutes, void* hip_stream);
 
 /* t1d_mlp_action under t1d_env_output: action[i] = the basal, before the pump, that the next step of a *_rel call would ask for
  * env i, by the kernels' own function.  It takes no meal_bolus: t1d_mlp_bolus is the bolus half of a step loop, with or without

@@ -39,7 +39,9 @@ EXPORTS = ("t1d_abi_version", "t1d_last_error", "t1d_ctx_create", "t1d_ctx_set_o
            "t1d_mlp_loss_tiles_workspace", "t1d_mlp_loss_tiles", "t1d_collect_pid", "t1d_collect_bb",
            "t1d_collect_pid_dopri5", "t1d_collect_bb_dopri5", "t1d_rollout_mlp_bolus", "t1d_collect_mlp_bolus",
            "t1d_rollout_mlp_dopri5_bolus", "t1d_mlp_bolus", "t1d_rollout_mlp_rel", "t1d_collect_mlp_rel",
-           "t1d_rollout_mlp_dopri5_rel", "t1d_mlp_action_rel", "t1d_collect_mlp_limit", "t1d_gae_limit")
+           "t1d_rollout_mlp_dopri5_rel", "t1d_mlp_action_rel", "t1d_collect_mlp_limit", "t1d_gae_limit",
+           "t1d_collect_pid_limit", "t1d_collect_bb_limit", "t1d_collect_mlp_dopri5_limit", "t1d_collect_pid_dopri5_limit",
+           "t1d_collect_bb_dopri5_limit")
 
 
 class T1DError(RuntimeError):
@@ -257,6 +259,16 @@ def lib():
     L.t1d_mlp_action_rel.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), eo, vp, vp]
     L.t1d_collect_mlp_limit.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), C.POINTER(Collect), eo, mb, C.POINTER(TimeLimit),
                                         C.c_int, C.c_int, C.c_int, vp]
+    tl = C.POINTER(TimeLimit)
+    L.t1d_collect_pid_limit.argtypes = [vp, C.POINTER(Batch), C.POINTER(Pid), C.POINTER(Mlp), C.POINTER(Collect), tl, C.c_int, C.c_int,
+                                        C.c_int, vp]
+    L.t1d_collect_bb_limit.argtypes = [vp, C.POINTER(Batch), C.POINTER(Bb), C.POINTER(Mlp), C.POINTER(Collect), tl, C.c_int, C.c_int,
+                                       C.c_int, vp]
+    L.t1d_collect_mlp_dopri5_limit.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), C.POINTER(Collect), tl, vp, vp, C.c_int, C.c_int, vp]
+    L.t1d_collect_pid_dopri5_limit.argtypes = [vp, C.POINTER(Batch), C.POINTER(Pid), C.POINTER(Mlp), C.POINTER(Collect), tl, vp, vp,
+                                               C.c_int, C.c_int, vp]
+    L.t1d_collect_bb_dopri5_limit.argtypes = [vp, C.POINTER(Batch), C.POINTER(Bb), C.POINTER(Mlp), C.POINTER(Collect), tl, vp, vp,
+                                              C.c_int, C.c_int, vp]
     L.t1d_mlp_grad_workspace.argtypes = [C.POINTER(Mlp), C.c_int, i64, i64]
     L.t1d_mlp_grad.argtypes = [C.c_int, C.c_int, i64, C.POINTER(Mlp), C.POINTER(MlpBatch), vp]
     L.t1d_mlp_loss_workspace.argtypes = [C.POINTER(Mlp), C.c_int, i64, i64]

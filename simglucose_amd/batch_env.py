@@ -433,7 +433,7 @@ class BatchedT1DSimEnv:
         with meal_bolus) the meal bolus of step r, before the pump.
         collect_mlp only: "reward", "done" (uint8) and "eps" of step r, and "features" [n_steps + 1, F, n], what the
         network was given in step r (F = 2 history + 3: pass the policy's history=); their row 0 is NaN (0 for "done").
-        "truncated" (uint8, collect_mlp_limit): 1 where step r was cut by the time limit; row 0 is 0.
+        "truncated" (uint8, collect_mlp_limit and the other *_limit collectors): 1 where step r was cut by the time limit; row 0 is 0.
         Call right after reset(); pass the dict as rollout_*(trace=...)."""
         tr = {"row": 1}
         for k in columns:
@@ -834,8 +834,11 @@ class BatchedT1DSimEnv:
             ...                                              # new_policy_state() for the masked envs
 
         With a limit no env reaches, the result is collect_mlp(on_done="restart")'s, bit for bit.  A method of its own and not
-        two keywords of collect_mlp, whose parameter list is that of collect_mlp_dopri5 and stays so; collect_mlp_dopri5,
-        collect_pid and collect_bb (both modes) have no time limit.  Measurements: profiles/collect/README.md."""
+        two keywords of collect_mlp, whose parameter list is that of collect_mlp_dopri5 and stays so.  The other collectors have
+        the same limit under the same rules: collect_pid_limit, collect_bb_limit, collect_mlp_dopri5_limit,
+        collect_pid_dopri5_limit and collect_bb_dopri5_limit; what has none is the exact MLP collector under a meal_bolus or
+        relative_to policy, which collect_mlp_dopri5_limit refuses as collect_mlp_dopri5 does.  Measurements:
+        profiles/collect/README.md."""
         self._no_dopri5_rollout()
         lim = self._time_limit_struct(n_steps, policy, trace, on_done, max_episode_steps, cut_features)
         policy_state, p, g, keep = self._collect_structs("collect_mlp_limit", n_steps, policy, policy_state, stats, trace, on_done, days,
@@ -846,26 +849,29 @@ class BatchedT1DSimEnv:
         self._keep = keep + (cut_features,)
         return policy_state
 
-    def _time_limit_struct(self, n_steps, policy, trace, on_done, max_episode_steps, cut_features):
-        """The t1d_time_limit of collect_mlp_limit, checked before anything is launched.  Call before _set_trace advances
+    def _time_limit_struct(self, n_steps, policy, trace, on_done, max_episode_steps, cut_features, who="collect_mlp_limit"):
+        """The t1d_time_limit of the six *_limit collectors, checked before anything is launched; `who` is the caller's name in
+        the messages, `policy` the network that acts or the controller's features=.  Call before _set_trace advances
         trace["row"]: "truncated" is written from the row the call starts at."""
         t = trace.get("truncated") if trace else None
         n_steps, L = self._n_steps(n_steps), int(max_episode_steps)
         if L < 1:
-            raise ValueError("collect_mlp_limit: max_episode_steps must be at least 1")
+            raise ValueError("%s: max_episode_steps must be at least 1" % who)
         if on_done != "restart":
-            raise ValueError("collect_mlp_limit: max_episode_steps needs on_done='restart' (a cut env starts its next episode)")
+            raise ValueError("%s: max_episode_steps needs on_done='restart' (a cut env starts its next episode)" % who)
         if n_steps > L:
-            raise ValueError("collect_mlp_limit: n_steps must not exceed max_episode_steps (an env is cut at most once per call); "
-                             "take the batch in several calls")
+            raise ValueError("%s: n_steps must not exceed max_episode_steps (an env is cut at most once per call); "
+                             "take the batch in several calls" % who)
         lim = _lib.TimeLimit()
         lim.max_minutes, lim.reserved = L * self.minutes_per_step, 0
         lim.cut_trace = lim.cut_feat = None
         if cut_features is not None:
+            if policy is None:
+                raise ValueError("%s: features= takes the MLPController whose history and scales form the features" % who)
             F = 2 * int(policy.history) + 3
             if not isinstance(cut_features, torch.Tensor) or cut_features.dtype != self.dtype or cut_features.device != self.device \
                     or tuple(cut_features.shape) != (F, self.n) or not cut_features.is_contiguous():
-                raise ValueError("collect_mlp_limit: cut_features must be a contiguous [%d, %d] tensor of %s on the env's device" % (F, self.n, self.dtype))
+                raise ValueError("%s: cut_features must be a contiguous [%d, %d] tensor of %s on the env's device" % (who, F, self.n, self.dtype))
             lim.cut_feat = cut_features.data_ptr()
         if t is not None:
             row = int(trace.get("row", 0))
@@ -926,12 +932,14 @@ class BatchedT1DSimEnv:
         return policy_state, p, g, (params, policy_state, sigma, r, terminal_obs, episode_stats, stats, trace)
 
     def _collect_ctrl(self, who, fn, ctl, ctl_state, n_steps, features, policy_state, stats, trace, on_done, days, terminal_obs,
-                      episode_stats, reset_outputs):
-        """collect_pid / collect_bb: fn (t1d_collect_pid, t1d_collect_bb) with the controller's struct ctl -> policy_state"""
+                      episode_stats, reset_outputs, lim=None, cut_features=None):
+        """collect_pid / collect_bb: fn (t1d_collect_pid, t1d_collect_bb) with the controller's struct ctl -> policy_state.
+        lim: the t1d_time_limit of the *_limit forms (_time_limit_struct, made before anything else of the call), whose fn
+        takes it behind the t1d_collect; cut_features is kept alive with the rest"""
         policy_state, f, g, keep = self._collect_structs(who, n_steps, features, policy_state, stats, trace, on_done, days,
                                                          terminal_obs, episode_stats, reset_outputs, draw=None)
-        self._rollout(fn, (ctl, f, g), n_steps, trace, restarts=on_done == "restart")
-        self._keep = keep + (ctl_state,)
+        self._rollout(fn, (ctl, f, g) if lim is None else (ctl, f, g, lim), n_steps, trace, restarts=on_done == "restart")
+        self._keep = keep + (ctl_state, cut_features)
         return policy_state
 
     def collect_pid(self, n_steps, P, I, D, target=140.0, features=None, pid_state=None, policy_state=None, stats=None, trace=None,
@@ -974,6 +982,53 @@ class BatchedT1DSimEnv:
                                           trace, on_done, days, terminal_obs, episode_stats, reset_outputs)
         return bb_state, policy_state
 
+    def collect_pid_limit(self, n_steps, P, I, D, max_episode_steps, cut_features=None, target=140.0, features=None, pid_state=None,
+                          policy_state=None, stats=None, trace=None, on_done="restart", days=2, terminal_obs=None,
+                          episode_stats=None, reset_outputs=False):
+        """collect_pid(on_done="restart") with collect_mlp_limit's time limit on every episode (t1d_collect_pid_limit,
+        include/t1d.h): the classical baseline under the rules a policy trained with collect_mlp_limit(L) is scored by.
+        max_episode_steps = L, cut_features (contiguous [F, n] of the env's dtype, F from features=, or None), the "truncated"
+        trace column, on_done="restart" only and n_steps <= L: as collect_mlp_limit, ValueError before anything is launched.
+        A cut env goes through what a finished one goes through: its integ and prev become 0.  The result is that of n_steps
+        times this loop, bit for bit, wherever the call is cut into launches:
+
+            f = env.policy_features(features, st); env.rollout_pid(1, P, I, D, pid_state=ps)   # rollout_launches = 0
+            ...                                              # the shift of the windows in st, prev_meal = env.meal
+            cut = ~env.done.bool() & (env.t >= L * env.minutes_per_step)
+            cut_features[:, cut] = env.policy_features(features, st)[:, cut]
+            env.restart_done(mask=env.done.bool() | cut, ...)
+            ...                                              # new_policy_state() and a zeroed pid_state for the masked envs
+
+        With a limit no env reaches, the result is collect_pid(on_done="restart")'s, bit for bit.  Every other argument, and
+        the return value, as collect_pid.  Measurements: profiles/collect/README.md.  -> (pid_state, policy_state)"""
+        self._no_dopri5_rollout()
+        lim = self._time_limit_struct(n_steps, features, trace, on_done, max_episode_steps, cut_features, "collect_pid_limit")
+        pid_state, p = self._pid_struct(P, I, D, target, pid_state, stats)
+        policy_state = self._collect_ctrl("collect_pid_limit", self._L.t1d_collect_pid_limit, p, pid_state, n_steps, features,
+                                          policy_state, stats, trace, on_done, days, terminal_obs, episode_stats, reset_outputs,
+                                          lim, cut_features)
+        return pid_state, policy_state
+
+    def collect_bb_limit(self, n_steps, max_episode_steps, cut_features=None, target=140.0, features=None, bb_state=None,
+                         policy_state=None, stats=None, trace=None, on_done="restart", days=2, terminal_obs=None, episode_stats=None,
+                         reset_outputs=False):
+        """collect_bb(on_done="restart") with the time limit (t1d_collect_bb_limit): everything as collect_pid_limit, the loop
+        with rollout_bb(1); a cut env's bb_state["prev_meal"] becomes 0.  The baseline beside a policy trained under L, and a
+        critic's warm start with states to bootstrap from:
+
+            cut = torch.zeros(F, env.n, dtype=env.dtype, device=env.device)
+            tr = env.new_trace(K, columns=("reward", "done", "truncated", "features"), history=pol.history)
+            env.collect_bb_limit(K, L, cut_features=cut, features=pol, trace=tr, episode_stats=es)     # K <= L
+
+        -> (bb_state, policy_state)"""
+        self._no_dopri5_rollout()
+        lim = self._time_limit_struct(n_steps, features, trace, on_done, max_episode_steps, cut_features, "collect_bb_limit")
+        bb_state, p = self._bb_struct(target, bb_state, stats)
+        policy_state = self._collect_ctrl("collect_bb_limit", self._L.t1d_collect_bb_limit, p, bb_state, n_steps, features,
+                                          policy_state, stats, trace, on_done, days, terminal_obs, episode_stats, reset_outputs,
+                                          lim, cut_features)
+        return bb_state, policy_state
+
     def collect_mlp_dopri5(self, n_steps, policy, sigma=None, explore_seed=None, policy_state=None, stats=None, trace=None,
                            on_done="continue", days=2, terminal_obs=None, episode_stats=None, reset_outputs=False,
                            max_minutes_per_launch=240):
@@ -986,32 +1041,68 @@ class BatchedT1DSimEnv:
         whose solver does not give up); with sigma=None and on_done="continue" it is rollout_mlp_dopri5's.  Measurements:
         profiles/collect (exact_collect_bench.json).  A policy with meal_bolus is refused: the exact mode's collector has no
         meal bolus (there is no t1d_collect_mlp_dopri5_bolus), and it does not drop it silently."""
-        self._need_dopri5("collect_mlp_dopri5")
+        return self._collect_mlp_dopri5("collect_mlp_dopri5", "t1d_collect_mlp_dopri5", n_steps, policy, sigma, explore_seed,
+                                        policy_state, stats, trace, on_done, days, terminal_obs, episode_stats, reset_outputs,
+                                        max_minutes_per_launch)
+
+    def _collect_mlp_dopri5(self, who, fn, n_steps, policy, sigma, explore_seed, policy_state, stats, trace, on_done, days, terminal_obs,
+                            episode_stats, reset_outputs, max_minutes_per_launch, limit=None):
+        """collect_mlp_dopri5 and, with limit = (max_episode_steps, cut_features), collect_mlp_dopri5_limit, whose entry point fn
+        (by name: an env of the other mode is turned away before anything of it is read) takes a t1d_time_limit behind the
+        t1d_collect -- the same one in every launch the call is cut into -> policy_state"""
+        self._need_dopri5(who)
         if getattr(policy, "meal_bolus", None) is not None:
-            raise _lib.T1DError("collect_mlp_dopri5: the exact-mode collector has no meal bolus (there is no t1d_collect_mlp_dopri5_bolus): "
-                                "a policy with meal_bolus takes rollout_mlp_dopri5, or collect_mlp on a fixed-step env")
+            raise _lib.T1DError("%s: the exact-mode collector has no meal bolus (there is no t1d_collect_mlp_dopri5_bolus): "
+                                "a policy with meal_bolus takes rollout_mlp_dopri5, or collect_mlp on a fixed-step env" % who)
         if getattr(policy, "relative_to", None) is not None:
-            raise _lib.T1DError("collect_mlp_dopri5: the exact-mode collector has no patient-relative output (relative_to=%r; there is no "
+            raise _lib.T1DError("%s: the exact-mode collector has no patient-relative output (relative_to=%r; there is no "
                                 "t1d_collect_mlp_dopri5_rel): such a policy takes rollout_mlp_dopri5, or collect_mlp on a fixed-step env"
-                                % (policy.relative_to,))
-        policy_state, p, g, keep = self._collect_structs("collect_mlp_dopri5", n_steps, policy, policy_state, stats, trace, on_done,
+                                % (who, policy.relative_to))
+        lim = None if limit is None else self._time_limit_struct(n_steps, policy, trace, on_done, limit[0], limit[1], who)
+        policy_state, p, g, keep = self._collect_structs(who, n_steps, policy, policy_state, stats, trace, on_done,
                                                          days, terminal_obs, episode_stats, reset_outputs, draw=(sigma, explore_seed),
                                                          keep_h_carry=True)
-        self._rollout_dopri5(self._L.t1d_collect_mlp_dopri5, p, n_steps, trace, max_minutes_per_launch, extra=(C.byref(g),),
-                             restarts=on_done == "restart")
-        self._keep = keep
+        self._rollout_dopri5(getattr(self._L, fn), p, n_steps, trace, max_minutes_per_launch,
+                             extra=(C.byref(g),) if lim is None else (C.byref(g), C.byref(lim)), restarts=on_done == "restart")
+        self._keep = keep + (limit,)
         return policy_state
 
+    def collect_mlp_dopri5_limit(self, n_steps, policy, max_episode_steps, cut_features=None, sigma=None, explore_seed=None,
+                                 policy_state=None, stats=None, trace=None, on_done="restart", days=2, terminal_obs=None,
+                                 episode_stats=None, reset_outputs=False, max_minutes_per_launch=240):
+        """collect_mlp_dopri5(on_done="restart") with collect_mlp_limit's time limit on every episode
+        (t1d_collect_mlp_dopri5_limit, include/t1d.h): a policy trained under a limit, scored or fine-tuned on the exact
+        integrator under the same limit.  max_episode_steps = L, cut_features, the "truncated" trace column, on_done="restart"
+        only and n_steps <= L: as collect_mlp_limit, ValueError before anything is launched.  A cut env goes through what a
+        finished one goes through; its h_carry becomes 0.  The call is cut into launches as collect_mlp_dopri5 is, each under
+        the same limit; an env is still cut at most once per call.  The result is that of n_steps times this loop, bit for bit
+        (for envs whose solver does not give up):
+
+            env.rollout_mlp_dopri5(1, pol, policy_state=st)  # or collect_mlp_dopri5(1, ..., on_done="continue") with sigma
+            cut = ~env.done.bool() & (env.t >= L * env.minutes_per_step)
+            cut_features[:, cut] = env.policy_features(pol, st)[:, cut]
+            env.restart_done(mask=env.done.bool() | cut, ...)
+            ...                                              # new_policy_state() for the masked envs
+
+        With a limit no env reaches, the result is collect_mlp_dopri5(on_done="restart")'s, bit for bit.  A policy with
+        meal_bolus or relative_to is refused as collect_mlp_dopri5 refuses it: that is what still has no time limit in the
+        exact mode.  Measurements: profiles/collect/README.md."""
+        return self._collect_mlp_dopri5("collect_mlp_dopri5_limit", "t1d_collect_mlp_dopri5_limit", n_steps, policy, sigma,
+                                        explore_seed, policy_state, stats, trace, on_done, days, terminal_obs, episode_stats,
+                                        reset_outputs, max_minutes_per_launch, limit=(max_episode_steps, cut_features))
+
     def _collect_ctrl_dopri5(self, who, fn, ctl, ctl_state, n_steps, features, policy_state, stats, trace, on_done, days,
-                             terminal_obs, episode_stats, reset_outputs, max_minutes_per_launch):
+                             terminal_obs, episode_stats, reset_outputs, max_minutes_per_launch, lim=None, cut_features=None):
         """collect_pid_dopri5 / collect_bb_dopri5: fn with the controller's struct ctl, whose trace_row -- the row of every
         trace of these calls -- _rollout_dopri5 advances from launch to launch; the feature struct holds pointers only and
-        needs nothing advanced -> policy_state"""
+        needs nothing advanced.  lim, cut_features: as in _collect_ctrl; every launch takes the same t1d_time_limit
+        -> policy_state"""
         policy_state, f, g, keep = self._collect_structs(who, n_steps, features, policy_state, stats, trace, on_done, days,
                                                          terminal_obs, episode_stats, reset_outputs, draw=None, keep_h_carry=True)
-        self._rollout_dopri5(fn, ctl, n_steps, trace, max_minutes_per_launch, extra=(C.byref(f), C.byref(g)),
+        self._rollout_dopri5(fn, ctl, n_steps, trace, max_minutes_per_launch,
+                             extra=(C.byref(f), C.byref(g)) if lim is None else (C.byref(f), C.byref(g), C.byref(lim)),
                              restarts=on_done == "restart")
-        self._keep = keep + (ctl_state,)
+        self._keep = keep + (ctl_state, cut_features)
         return policy_state
 
     def collect_pid_dopri5(self, n_steps, P, I, D, target=140.0, features=None, pid_state=None, policy_state=None, stats=None,
@@ -1054,6 +1145,35 @@ class BatchedT1DSimEnv:
                                                  reset_outputs, max_minutes_per_launch)
         return bb_state, policy_state
 
+    def collect_pid_dopri5_limit(self, n_steps, P, I, D, max_episode_steps, cut_features=None, target=140.0, features=None,
+                                 pid_state=None, policy_state=None, stats=None, trace=None, on_done="restart", days=2,
+                                 terminal_obs=None, episode_stats=None, reset_outputs=False, max_minutes_per_launch=240):
+        """collect_pid_dopri5(on_done="restart") with the time limit of collect_pid_limit (t1d_collect_pid_dopri5_limit,
+        include/t1d.h): max_episode_steps, cut_features, "truncated" and the refusals as there; a cut env's h_carry, integ and
+        prev become 0.  The call is cut into launches as collect_pid_dopri5 is, each under the same limit.  The result is that
+        of collect_pid_limit's loop with rollout_pid_dopri5(1), bit for bit (for envs whose solver does not give up); with a
+        limit no env reaches it is collect_pid_dopri5(on_done="restart")'s.  -> (pid_state, policy_state)"""
+        self._need_dopri5("collect_pid_dopri5_limit")
+        lim = self._time_limit_struct(n_steps, features, trace, on_done, max_episode_steps, cut_features, "collect_pid_dopri5_limit")
+        pid_state, p = self._pid_struct(P, I, D, target, pid_state, stats)
+        policy_state = self._collect_ctrl_dopri5("collect_pid_dopri5_limit", self._L.t1d_collect_pid_dopri5_limit, p, pid_state,
+                                                 n_steps, features, policy_state, stats, trace, on_done, days, terminal_obs,
+                                                 episode_stats, reset_outputs, max_minutes_per_launch, lim, cut_features)
+        return pid_state, policy_state
+
+    def collect_bb_dopri5_limit(self, n_steps, max_episode_steps, cut_features=None, target=140.0, features=None, bb_state=None,
+                                policy_state=None, stats=None, trace=None, on_done="restart", days=2, terminal_obs=None,
+                                episode_stats=None, reset_outputs=False, max_minutes_per_launch=240):
+        """collect_bb_dopri5(on_done="restart") with the time limit of collect_bb_limit (t1d_collect_bb_dopri5_limit):
+        everything as collect_pid_dopri5_limit; a cut env's bb_state["prev_meal"] becomes 0.  -> (bb_state, policy_state)"""
+        self._need_dopri5("collect_bb_dopri5_limit")
+        lim = self._time_limit_struct(n_steps, features, trace, on_done, max_episode_steps, cut_features, "collect_bb_dopri5_limit")
+        bb_state, p = self._bb_struct(target, bb_state, stats)
+        policy_state = self._collect_ctrl_dopri5("collect_bb_dopri5_limit", self._L.t1d_collect_bb_dopri5_limit, p, bb_state,
+                                                 n_steps, features, policy_state, stats, trace, on_done, days, terminal_obs,
+                                                 episode_stats, reset_outputs, max_minutes_per_launch, lim, cut_features)
+        return bb_state, policy_state
+
     def _rollout_dopri5(self, fn, p, n_steps, trace, max_minutes_per_launch, extra=(), restarts=False):
         """the launches of one exact-mode roll-out: whole steps, at most max_minutes_per_launch simulated minutes each.
         State, controller state and h_carry carry over, so the cut changes no result; nfev is summed over the launches.
@@ -1088,7 +1208,7 @@ class BatchedT1DSimEnv:
     def _need_dopri5(self, who):
         if self.integrator != "dopri5":
             raise _lib.T1DError("%s needs an env built with integrator='dopri5' (the fixed-step envs take %s)"
-                                % (who, who[:-len("_dopri5")]))
+                                % (who, who.replace("_dopri5", "")))
 
     def rollout_pid_dopri5(self, n_steps, P, I, D, target=140.0, pid_state=None, stats=None, trace=None,
                            max_minutes_per_launch=240):

@@ -1470,9 +1470,17 @@ static t1d_mlp features_only(const t1d_mlp* m)
     return f;
 }
 
+template <typename T> using CtrlCollectLimitFn = KernelFn<T, PidArgs<T>, MlpArgs<T>, CollectArgs<T>, RestartArgs<T>, LimitArgs<T>>;
+template <typename T>
+static CtrlCollectLimitFn<T> ctrl_collect_limit_fn(int variant)
+{
+    return by_variant<T>(variant, [](auto v) -> CtrlCollectLimitFn<T> { return ctrl_collect_limit_kernel<decltype(v)::value, T>; });
+}
+
+// lim == NULL: t1d_collect_pid / t1d_collect_bb; with lim the time limit's family (t1d_collect_pid_limit / t1d_collect_bb_limit)
 template <typename T>
 static int run_collect_ctrl(const char* who, t1d_ctx* c, const t1d_batch* b, const PidArgs<T>& pa, const t1d_mlp* feat, const t1d_collect* g,
-                            Plan p, int minutes, int n_sub, hipStream_t s)
+                            const t1d_time_limit* lim, Plan p, int minutes, int n_sub, hipStream_t s)
 {
     const t1d_mlp fm = features_only(feat);
     MlpArgs<T> fa = make_mlp<T>(&fm, pa.n_steps);
@@ -1480,13 +1488,15 @@ static int run_collect_ctrl(const char* who, t1d_ctx* c, const t1d_batch* b, con
     const int rc = shape_mlp<T>(who, c, b, 4 * fm.history + 3, p, fa);
     if (rc) return rc;
     const RestartArgs<T> ra = g->on_done == T1D_COLLECT_RESTART ? make_restart<T>(g->restart) : RestartArgs<T>{};
+    if (lim) return launch(c, b, p, minutes, n_sub, s, ctrl_collect_limit_fn<T>(p.variant), pa, fa, make_collect<T>(c, g), ra, make_limit<T>(lim));
     return launch(c, b, p, minutes, n_sub, s, ctrl_collect_fn<T>(p.variant), pa, fa, make_collect<T>(c, g), ra);
 }
 
 // a collector under the PID controller pid or the basal-bolus controller bb (the other one NULL).  What needs no device is
 // checked first, so that a bad call is refused on any machine.
 static int launch_collect_ctrl(const char* who, t1d_ctx* c, const t1d_batch* b, const t1d_pid* pid, const t1d_bb* bb, const t1d_mlp* feat,
-                               const t1d_collect* g, int n_steps, int minutes, int n_sub, void* stream)
+                               const t1d_collect* g, int n_steps, int minutes, int n_sub, void* stream, const t1d_time_limit* lim = nullptr,
+                               bool limited = false)
 {
     const std::string w = std::string(who) + ": ";
     if (!feat) return fail(T1D_E_INVALID, w + "feat is NULL");
@@ -1499,14 +1509,18 @@ static int launch_collect_ctrl(const char* who, t1d_ctx* c, const t1d_batch* b, 
     if (b && b->cho) return fail(T1D_E_INVALID, w + "dense cho is not supported, use the meal table");
     if (minutes < 1 || minutes > 100000) return fail(T1D_E_INVALID, w + "minutes out of range");
     if (n_sub < 1 || n_sub > 4096) return fail(T1D_E_INVALID, w + "n_sub out of range");
+    if (limited) {                              // the *_limit calls: the sibling's checks that need no device, then the limit's
+        rc = check_time_limit(who, g, lim, n_steps, minutes);
+        if (rc) return rc;
+    }
     rc = check_closed_loop(who, c, b, n_steps);
     if (rc) return rc;
     Plan p;
     rc = plan_and_tables(who, c, b, minutes, n_sub, true, &p, true);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (p.f64) rc = run_collect_ctrl<double>(who, c, b, pid ? make_pid<double>(pid, n_steps) : make_bb<double>(bb, n_steps), feat, g, p, minutes, n_sub, s);
-    else rc = run_collect_ctrl<float>(who, c, b, pid ? make_pid<float>(pid, n_steps) : make_bb<float>(bb, n_steps), feat, g, p, minutes, n_sub, s);
+    if (p.f64) rc = run_collect_ctrl<double>(who, c, b, pid ? make_pid<double>(pid, n_steps) : make_bb<double>(bb, n_steps), feat, g, lim, p, minutes, n_sub, s);
+    else rc = run_collect_ctrl<float>(who, c, b, pid ? make_pid<float>(pid, n_steps) : make_bb<float>(bb, n_steps), feat, g, lim, p, minutes, n_sub, s);
     if (rc) return rc;
     T1D_HIP(hipGetLastError());
     return T1D_OK;
@@ -1527,12 +1541,29 @@ extern "C" int t1d_collect_bb(t1d_ctx* c, const t1d_batch* b, const t1d_bb* bb, 
     return launch_collect_ctrl("t1d_collect_bb", c, b, nullptr, bb, feat, g, n_steps, minutes, n_sub, stream);
 }
 
+// the two calls above under a time limit (ctrl_collect_limit_kernel): their checks under this call's name, then the limit's
+extern "C" int t1d_collect_pid_limit(t1d_ctx* c, const t1d_batch* b, const t1d_pid* pid, const t1d_mlp* feat, const t1d_collect* g,
+                                     const t1d_time_limit* lim, int n_steps, int minutes, int n_sub, void* stream)
+{
+    if (!pid || !pid->integ || !pid->prev) return fail(T1D_E_INVALID, "t1d_collect_pid_limit: pid state is NULL");
+    return launch_collect_ctrl("t1d_collect_pid_limit", c, b, pid, nullptr, feat, g, n_steps, minutes, n_sub, stream, lim, true);
+}
+
+extern "C" int t1d_collect_bb_limit(t1d_ctx* c, const t1d_batch* b, const t1d_bb* bb, const t1d_mlp* feat, const t1d_collect* g,
+                                    const t1d_time_limit* lim, int n_steps, int minutes, int n_sub, void* stream)
+{
+    if (!bb || !bb->basal || !bb->cr || !bb->cf || !bb->prev_meal)
+        return fail(T1D_E_INVALID, "t1d_collect_bb_limit: basal / cr / cf / prev_meal must be set");
+    return launch_collect_ctrl("t1d_collect_bb_limit", c, b, nullptr, bb, feat, g, n_steps, minutes, n_sub, stream, lim, true);
+}
+
 // The exact mode's collector (dopri5_mlp_collect_kernel, t1d_dopri5.hpp): the checks of t1d_rollout_mlp_dopri5 and of
 // t1d_collect_mlp, then one launch in the shape of t1d_rollout_mlp_dopri5.
-extern "C" int t1d_collect_mlp_dopri5(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_collect* g, double* h_carry,
-                                      int32_t* nfev, int n_steps, int minutes, void* stream)
+// limited: t1d_collect_mlp_dopri5_limit (dopri5_mlp_collect_limit_kernel), the same checks under that name, then the limit's.
+static int collect_mlp_dopri5_entry(const char* who, t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_collect* g,
+                                    const t1d_time_limit* lim, bool limited, double* h_carry, int32_t* nfev, int n_steps, int minutes,
+                                    void* stream)
 {
-    const char* who = "t1d_collect_mlp_dopri5";
     int rc = check_dopri5(who, c, b, h_carry, n_steps, minutes);
     if (rc) return rc;
     rc = check_collect(who, b, mlp, g, h_carry);
@@ -1540,12 +1571,32 @@ extern "C" int t1d_collect_mlp_dopri5(t1d_ctx* c, const t1d_batch* b, const t1d_
     int cols = 0;
     rc = check_mlp(who, b, mlp, &cols);
     if (rc) return rc;
+    if (limited) {
+        rc = check_time_limit(who, g, lim, n_steps, minutes);
+        if (rc) return rc;
+    }
     MlpArgs<double> ma = make_mlp<double>(mlp, n_steps);
     ma.cols = cols;
     RestartArgs<double> ra = g->on_done == T1D_COLLECT_RESTART ? make_restart<double>(g->restart) : RestartArgs<double>{};
     if (g->on_done == T1D_COLLECT_RESTART) ra.h_carry = h_carry;      // the env's predicted step is part of what restarts
+    if (limited)
+        return launch_mlp_dopri5(who, c, b, cols, minutes, stream, dopri5_mlp_collect_limit_kernel, ma, make_collect<double>(c, g), ra,
+                                 make_limit<double>(lim), (const double*)c->d_raw64, h_carry, nfev);
     return launch_mlp_dopri5(who, c, b, cols, minutes, stream, dopri5_mlp_collect_kernel, ma, make_collect<double>(c, g), ra,
                              (const double*)c->d_raw64, h_carry, nfev);
+}
+
+extern "C" int t1d_collect_mlp_dopri5(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_collect* g, double* h_carry,
+                                      int32_t* nfev, int n_steps, int minutes, void* stream)
+{
+    return collect_mlp_dopri5_entry("t1d_collect_mlp_dopri5", c, b, mlp, g, nullptr, false, h_carry, nfev, n_steps, minutes, stream);
+}
+
+extern "C" int t1d_collect_mlp_dopri5_limit(t1d_ctx* c, const t1d_batch* b, const t1d_mlp* mlp, const t1d_collect* g,
+                                            const t1d_time_limit* lim, double* h_carry, int32_t* nfev, int n_steps, int minutes,
+                                            void* stream)
+{
+    return collect_mlp_dopri5_entry("t1d_collect_mlp_dopri5_limit", c, b, mlp, g, lim, true, h_carry, nfev, n_steps, minutes, stream);
 }
 
 // The exact mode's collectors under the PID controller pid or the basal-bolus controller bb, the other one NULL
@@ -1554,7 +1605,7 @@ extern "C" int t1d_collect_mlp_dopri5(t1d_ctx* c, const t1d_batch* b, const t1d_
 // then one launch in the shape of t1d_rollout_mlp_dopri5 with a wave's columns of ctrl_collect_kernel.
 static int launch_collect_ctrl_dopri5(const char* who, t1d_ctx* c, const t1d_batch* b, const t1d_pid* pid, const t1d_bb* bb,
                                       const t1d_mlp* feat, const t1d_collect* g, double* h_carry, int32_t* nfev, int n_steps,
-                                      int minutes, void* stream)
+                                      int minutes, void* stream, const t1d_time_limit* lim = nullptr, bool limited = false)
 {
     const std::string w = std::string(who) + ": ";
     if (!feat) return fail(T1D_E_INVALID, w + "feat is NULL");
@@ -1566,6 +1617,10 @@ static int launch_collect_ctrl_dopri5(const char* who, t1d_ctx* c, const t1d_bat
     if (g->sigma || g->eps_trace) return fail(T1D_E_INVALID, w + "sigma and eps_trace must be NULL (a controller has no exploration noise)");
     rc = check_dopri5(who, c, b, h_carry, n_steps, minutes);
     if (rc) return rc;
+    if (limited) {                              // the *_limit calls: the sibling's checks, then the limit's
+        rc = check_time_limit(who, g, lim, n_steps, minutes);
+        if (rc) return rc;
+    }
     const PidArgs<double> pa = pid ? make_pid<double>(pid, n_steps) : make_bb<double>(bb, n_steps);
     const t1d_mlp fm = features_only(feat);
     MlpArgs<double> fa = make_mlp<double>(&fm, n_steps);
@@ -1573,6 +1628,9 @@ static int launch_collect_ctrl_dopri5(const char* who, t1d_ctx* c, const t1d_bat
     fa.cols = cols;
     RestartArgs<double> ra = g->on_done == T1D_COLLECT_RESTART ? make_restart<double>(g->restart) : RestartArgs<double>{};
     if (g->on_done == T1D_COLLECT_RESTART) ra.h_carry = h_carry;      // the env's predicted step is part of what restarts
+    if (limited)
+        return launch_mlp_dopri5(who, c, b, cols, minutes, stream, dopri5_ctrl_collect_limit_kernel, pa, fa, make_collect<double>(c, g), ra,
+                                 make_limit<double>(lim), (const double*)c->d_raw64, h_carry, nfev);
     return launch_mlp_dopri5(who, c, b, cols, minutes, stream, dopri5_ctrl_collect_kernel, pa, fa, make_collect<double>(c, g), ra,
                              (const double*)c->d_raw64, h_carry, nfev);
 }
@@ -1590,6 +1648,26 @@ extern "C" int t1d_collect_bb_dopri5(t1d_ctx* c, const t1d_batch* b, const t1d_b
     if (!bb || !bb->basal || !bb->cr || !bb->cf || !bb->prev_meal)
         return fail(T1D_E_INVALID, "t1d_collect_bb_dopri5: bb is NULL, or basal / cr / cf / prev_meal is not set");
     return launch_collect_ctrl_dopri5("t1d_collect_bb_dopri5", c, b, nullptr, bb, feat, g, h_carry, nfev, n_steps, minutes, stream);
+}
+
+// the two calls above under a time limit (dopri5_ctrl_collect_limit_kernel)
+extern "C" int t1d_collect_pid_dopri5_limit(t1d_ctx* c, const t1d_batch* b, const t1d_pid* pid, const t1d_mlp* feat, const t1d_collect* g,
+                                            const t1d_time_limit* lim, double* h_carry, int32_t* nfev, int n_steps, int minutes,
+                                            void* stream)
+{
+    if (!pid || !pid->integ || !pid->prev) return fail(T1D_E_INVALID, "t1d_collect_pid_dopri5_limit: pid state is NULL");
+    return launch_collect_ctrl_dopri5("t1d_collect_pid_dopri5_limit", c, b, pid, nullptr, feat, g, h_carry, nfev, n_steps, minutes, stream,
+                                      lim, true);
+}
+
+extern "C" int t1d_collect_bb_dopri5_limit(t1d_ctx* c, const t1d_batch* b, const t1d_bb* bb, const t1d_mlp* feat, const t1d_collect* g,
+                                           const t1d_time_limit* lim, double* h_carry, int32_t* nfev, int n_steps, int minutes,
+                                           void* stream)
+{
+    if (!bb || !bb->basal || !bb->cr || !bb->cf || !bb->prev_meal)
+        return fail(T1D_E_INVALID, "t1d_collect_bb_dopri5_limit: bb is NULL, or basal / cr / cf / prev_meal is not set");
+    return launch_collect_ctrl_dopri5("t1d_collect_bb_dopri5_limit", c, b, nullptr, bb, feat, g, h_carry, nfev, n_steps, minutes, stream,
+                                      lim, true);
 }
 
 extern "C" int t1d_random_meals(int hip_device, uint64_t seed, int64_t env_offset, int64_t n, int dtype, int days,

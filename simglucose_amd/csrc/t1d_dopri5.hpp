@@ -1095,6 +1095,281 @@ __global__ __launch_bounds__(kBlock, 1) void dopri5_ctrl_collect_kernel(const KA
     dopri5_mlp_store_windows(a, f, i, col, s);
 }
 
+// ---- the two collectors above with episodes cut at a time limit (t1d_collect_mlp_dopri5_limit, t1d_collect_pid_dopri5_limit,
+// t1d_collect_bb_dopri5_limit; LimitArgs, t1d_policy.hpp) ------------------------------------------------------------------
+// dopri5_mlp_collect_kernel and dopri5_ctrl_collect_kernel, line for line, with a LimitArgs behind their arguments.  Written out
+// beside them and not shared with them through a template flag: the two kernels above keep their text, hence their registers
+// and their instruction streams (a change to one of them is a change to the matching lines here).  What differs sits in the
+// boundary block, where a step closes:
+//   cut             !fin and the env's clock e.t has reached max_minutes; to cut_trace's row of the step.  Termination wins.
+//   a cut env       in the restart branch, before anything of it goes to memory: its cut features -- mlp_features on the shifted
+//                   windows (the head the block has just computed), the step's meal (the word prev_meal has just been given) and
+//                   the clock start_minute + e.t, what t1d_mlp_features would return; buf is free between two steps -- to
+//                   cut_feat.  Then the restart of a finished env, with collect_restart_masked (its done byte is 0) where
+//                   collect_restart stands.
+// The restart stays inlined (the comment above dopri5_ctrl_collect_kernel).  Of the limit only max_minutes, a kernel argument, is
+// looked at outside the cut branch, and nothing of it is in a register across dopri5_attempt.
+__global__ __launch_bounds__(kBlock, 1) void dopri5_mlp_collect_limit_kernel(const KArgs<double> a, const MlpArgs<double> c,
+                                                                             const CollectArgs<double> g, const RestartArgs<double> ra,
+                                                                             const LimitArgs<double> lim, const double* __restrict__ raw,
+                                                                             double* h_carry, int32_t* nfev)
+{
+    typedef RollColdT<64> Cold;
+    typedef const __attribute__((address_space(4))) double* WPtr;
+    __shared__ double lds[kRawPars * kMaxPatients];
+    for (int j = threadIdx.x; j < kRawPars * kMaxPatients; j += blockDim.x) lds[j] = raw[j];
+    __syncthreads();
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    __builtin_assume(i < (1u << 28));          // host guarantees n <= 2^28: i * sizeof(T) fits a 32-bit voffset
+    if ((int64_t)i >= a.n) return;             // n is a multiple of 64: whole waves leave
+    const MlpLaneLds piece = dopri5_mlp_lane_lds(c);
+    const Cold cold = piece.cold;
+    double* const col = piece.col;
+    const int H = c.history, F = 2 * H + 3;
+    double* const buf = col + 2 * H * 64;
+    const uint32_t meta = at(a.meta, i);
+    const uint32_t pid = T1D_META_PID(meta);
+    Env<double> e;
+    load_env(a, i, meta, e);
+    const ParsRaw p{lds, (int)pid};
+    NoDerivedPars nop;
+    const double div = double(a.minutes);
+    dopri5_mlp_load_windows(a, c, i, col);
+    double hc = at(h_carry, i), noise = 0.0, insulin = 0.0, d_mg = 0.0;
+    StepOut<double> o{0.0, 0.0, 0.0, 0.0};
+    Dopri5Run r{};
+    int nf = 0, m = 0, s = 0;
+    bool due = false, failed = false, boundary = true, fresh = true;
+    bool stored = false;                        // the last step ended the episode: the state in memory is the new episode's
+    cold.save(e, o, noise, hc);
+    for (;;) {
+        if (boundary) {
+            cold.load(e, o, noise, hc);
+            if (!fresh) {
+                e.t += 1;
+                const double gsub = e.x[12] / p(T1D_P_VG);                                    // t1dpatient.py:217-218
+                const double cgm = measure_apply(a, e, gsub, noise, due);                     // env.py:62
+                o.bg += gsub / div; o.cgm += cgm / div;                                       // env.py:80-81
+                if (++m == a.minutes) {                  // the step is complete: what t1d_step_dopri5 leaves, then the collector's own
+                    const double rp = e.prev_risk;
+                    write_outputs<0>(a, i, e, o, rp);
+                    const double reward = rp - e.prev_risk;     // the word write_outputs stored in batch.reward
+                    const bool fin = o.bg < 70.0 || o.bg > 350.0;
+                    const bool cut = !fin && e.t >= lim.max_minutes;    // the time limit ends the episode here (never a finished one)
+                    const int64_t tr = (c.trace_row + s) * a.n + i;
+                    if (g.reward_trace) g.reward_trace[tr] = reward;
+                    if (g.done_trace) g.done_trace[tr] = fin ? 1 : 0;
+                    if (lim.cut_trace) lim.cut_trace[tr] = cut ? 1 : 0;
+                    dopri5_mlp_step_words(c, i, tr, o);
+                    m = 0; ++s;
+                    const int q = s % H, head = q ? H - q : 0;  // the oldest row becomes the newest
+                    col[head * 64] = o.cgm; col[(H + head) * 64] = o.ins;
+                    if (g.on_done) {
+                        if (fin || cut) {
+                            if (cut && lim.cut_feat) {          // the features of the state the cut episode ended in
+                                const int start = c.start_minute ? (int)at(c.start_minute, i) : 0;
+                                mlp_features(c, col, buf, head, o.meal, start + e.t);
+                                for (int j = 0; j < F; ++j) at(rowv(lim.cut_feat, a.n, j), i) = buf[j * 64];
+                            }
+                            // the finished step is in memory (write_outputs); the state follows, and the restart works on those words
+                            store_env(a, i, pid, e);
+                            if (failed) atomicOr(a.status, T1D_ST_SOLVER_FAILED);
+                            collect_restart_masked<double>(a, ra, g.slots, i);          // a cut env's done is 0
+                            load_env(a, i, at(a.meta, i), e);
+                            const double first = at(a.cgm, i);  // the new episode's first observation
+                            for (int k = 0; k < H; ++k) { col[k * 64] = first; col[(H + k) * 64] = 0.0; }
+                            at(c.prev_meal, i) = 0.0;
+                            hc = 0.0;                           // T1DPatient.reset builds the solver afresh: the first minute probes
+                            failed = false;
+                            stored = s == c.n_steps;
+                        } else if (ra.ep_return) {              // restart_front's accumulators for an env that goes on
+                            const double sum = at(ra.ep_return, i) + reward;
+                            const int len = at(ra.ep_length, i) + 1;
+                            at(ra.ep_return, i) = sum; at(ra.ep_length, i) = len;
+                        }
+                    }
+                }
+            }
+            if (s == c.n_steps) break;
+            if (m == 0) {                                // a step opens: features, layers, the draw, the output function, the pump
+                const int q = s % H, head = q ? H - q : 0;
+                const int start = c.start_minute ? (int)at(c.start_minute, i) : 0;
+                const double prev_meal = at(c.prev_meal, i);
+                const unsigned wave0 = __builtin_amdgcn_readfirstlane(i & ~63u);
+                const unsigned pol = wave0 / c.envs_per_policy;
+                const WPtr w = (WPtr)(c.params + (size_t)pol * (size_t)c.n_params);
+                mlp_features(c, col, buf, head, prev_meal, start + e.t);
+                if (g.feat_trace)
+                    for (int j = 0; j < F; ++j) g.feat_trace[((c.trace_row + s) * F + j) * a.n + i] = buf[j * 64];
+                double y = mlp_layers(c, w, buf, F);
+                double eps = 0.0;
+                if (g.sigma) {                           // wave-uniform
+                    const uint32_t ep = a.episode ? at(a.episode, i) : 0u;
+                    eps = (double)philox_pair(g.explore_seed, (uint64_t)(a.env_offset + i), ep, (uint32_t)e.t).x;
+                    y = fma((double)((WPtr)g.sigma)[pol], eps, y);
+                }
+                if (g.eps_trace) g.eps_trace[(c.trace_row + s) * a.n + i] = eps;
+                const double u = mlp_output(c, y);
+                if (c.act_trace) c.act_trace[(c.trace_row + s) * a.n + i] = u;
+                insulin = dopri5_mlp_pump(a, u);
+                o = StepOut<double>{0.0, 0.0, 0.0, 0.0};
+            }
+            const double meal = meal_lookup(a, i, e);                                         // env.py:50
+            noise = measure_noise<true>(a, i, e, due);
+            const MinuteIn<double> u = eat_minute<0, double>(nop, e.x, meal, insulin, e.planned, e.lq, e.lf, e.eating);
+            d_mg = u.d_mg;
+            o.meal += meal / div; o.ins += insulin / div;                                     // env.py:78-79
+            if (!failed) dopri5_enter(p, e.x, d_mg, insulin, e.lq, e.lf, hc, (double)e.t, r, nf);
+            cold.save(e, o, noise, hc);
+            fresh = false; boundary = false;
+        }
+        if (failed) { boundary = true; continue; }
+        const int rc = dopri5_attempt(p, e.x, d_mg, insulin, e.lq, e.lf, cold.f[Cold::HC * 64], (double)e.t + 1.0, r, nf);
+        failed = rc < 0;
+        boundary = rc != 0;
+    }
+    if (!stored) store_env(a, i, pid, e);
+    at(h_carry, i) = hc;
+    if (nfev) at(nfev, i) = nf;
+    if (failed) atomicOr(a.status, T1D_ST_SOLVER_FAILED);
+    dopri5_mlp_store_windows(a, c, i, col, s);
+}
+
+__global__ __launch_bounds__(kBlock, 1) void dopri5_ctrl_collect_limit_kernel(const KArgs<double> a, const PidArgs<double> c,
+                                                                              const MlpArgs<double> f, const CollectArgs<double> g,
+                                                                              const RestartArgs<double> ra, const LimitArgs<double> lim,
+                                                                              const double* __restrict__ raw, double* h_carry, int32_t* nfev)
+{
+    typedef RollColdT<64> Cold;
+    __shared__ double lds[kRawPars * kMaxPatients];
+    for (int j = threadIdx.x; j < kRawPars * kMaxPatients; j += blockDim.x) lds[j] = raw[j];
+    __syncthreads();
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    __builtin_assume(i < (1u << 28));          // host guarantees n <= 2^28: i * sizeof(T) fits a 32-bit voffset
+    if ((int64_t)i >= a.n) return;             // any n: the lanes past the end leave, the others never look at them
+    const MlpLaneLds piece = dopri5_mlp_lane_lds(f);
+    const Cold cold = piece.cold;
+    double* const col = piece.col;
+    const int H = f.history, F = 2 * H + 3;
+    double* const buf = col + 2 * H * 64;
+    const uint32_t meta = at(a.meta, i);
+    const uint32_t pid = T1D_META_PID(meta);
+    Env<double> e;
+    load_env(a, i, meta, e);
+    const ParsRaw p{lds, (int)pid};
+    NoDerivedPars nop;
+    const double div = double(a.minutes), st = double(a.sen.st);
+    dopri5_mlp_load_windows(a, f, i, col);
+    double hc = at(h_carry, i), noise = 0.0, insulin = 0.0, d_mg = 0.0;
+    StepOut<double> o{0.0, 0.0, 0.0, 0.0};
+    Dopri5Run r{};
+    int nf = 0, m = 0, s = 0;
+    bool due = false, failed = false, boundary = true, fresh = true;
+    bool stored = false;                        // the last step ended the episode: the state in memory is the new episode's
+    cold.save(e, o, noise, hc);
+    for (;;) {
+        if (boundary) {
+            cold.load(e, o, noise, hc);
+            if (!fresh) {
+                e.t += 1;
+                const double gsub = e.x[12] / p(T1D_P_VG);                                    // t1dpatient.py:217-218
+                const double cgm = measure_apply(a, e, gsub, noise, due);                     // env.py:62
+                o.bg += gsub / div; o.cgm += cgm / div;                                       // env.py:80-81
+                if (++m == a.minutes) {                  // the step is complete: what t1d_step_dopri5 leaves, then the collector's own
+                    const double rp = e.prev_risk;
+                    write_outputs<0>(a, i, e, o, rp);
+                    const double reward = rp - e.prev_risk;     // the word write_outputs stored in batch.reward
+                    const bool fin = o.bg < 70.0 || o.bg > 350.0;
+                    const bool cut = !fin && e.t >= lim.max_minutes;    // the time limit ends the episode here (never a finished one)
+                    const int64_t tr = (c.trace_row + s) * a.n + i;
+                    if (g.reward_trace) g.reward_trace[tr] = reward;
+                    if (g.done_trace) g.done_trace[tr] = fin ? 1 : 0;
+                    if (lim.cut_trace) lim.cut_trace[tr] = cut ? 1 : 0;
+                    if (c.bg_trace) c.bg_trace[tr] = o.bg;
+                    if (c.cgm_trace) c.cgm_trace[tr] = o.cgm;
+                    if (c.cho_trace) c.cho_trace[tr] = o.meal;
+                    if (c.ins_trace) c.ins_trace[tr] = o.ins;
+                    if (c.kind == 1) at(c.bb_prev_meal, i) = o.meal;
+                    at(f.prev_meal, i) = o.meal;
+                    if (c.sum_risk) { double l, h, rk; risk_index1<0>(o.bg, l, h, rk); at(c.sum_risk, i) = at(c.sum_risk, i) + rk; }
+                    if (c.min_bg) { const double v = at(c.min_bg, i); at(c.min_bg, i) = o.bg < v ? o.bg : v; }
+                    if (c.max_bg) { const double v = at(c.max_bg, i); at(c.max_bg, i) = o.bg > v ? o.bg : v; }
+                    if (c.n_low) at(c.n_low, i) = at(c.n_low, i) + (o.bg < 70.0);
+                    if (c.n_high) at(c.n_high, i) = at(c.n_high, i) + (o.bg > 180.0);
+                    m = 0; ++s;
+                    const int q = s % H, head = q ? H - q : 0;  // the oldest row becomes the newest
+                    col[head * 64] = o.cgm; col[(H + head) * 64] = o.ins;
+                    if (g.on_done) {
+                        if (fin || cut) {
+                            if (cut && lim.cut_feat) {          // the features of the state the cut episode ended in
+                                const int start = f.start_minute ? (int)at(f.start_minute, i) : 0;
+                                mlp_features(f, col, buf, head, o.meal, start + e.t);
+                                for (int j = 0; j < F; ++j) at(rowv(lim.cut_feat, a.n, j), i) = buf[j * 64];
+                            }
+                            // the finished step is in memory (write_outputs); the state follows, and the restart works on those words
+                            store_env(a, i, pid, e);
+                            if (failed) atomicOr(a.status, T1D_ST_SOLVER_FAILED);
+                            collect_restart_masked<double>(a, ra, g.slots, i);          // a cut env's done is 0
+                            load_env(a, i, at(a.meta, i), e);
+                            const double first = at(a.cgm, i);  // the new episode's first observation
+                            for (int k = 0; k < H; ++k) { col[k * 64] = first; col[(H + k) * 64] = 0.0; }
+                            at(f.prev_meal, i) = 0.0;
+                            if (c.kind == 1) at(c.bb_prev_meal, i) = 0.0;                     // BBController.reset
+                            else { at(c.integ, i) = 0.0; at(c.prev, i) = 0.0; }               // PIDController.reset
+                            hc = 0.0;                           // T1DPatient.reset builds the solver afresh: the first minute probes
+                            failed = false;
+                            stored = s == c.n_steps;
+                        } else if (ra.ep_return) {              // restart_front's accumulators for an env that goes on
+                            const double sum = at(ra.ep_return, i) + reward;
+                            const int len = at(ra.ep_length, i) + 1;
+                            at(ra.ep_return, i) = sum; at(ra.ep_length, i) = len;
+                        }
+                    }
+                }
+            }
+            if (s == c.n_steps) break;
+            if (m == 0) {                                // a step opens: features, the controller on the last observation, the pump
+                const int q = s % H, head = q ? H - q : 0;
+                const int start = f.start_minute ? (int)at(f.start_minute, i) : 0;
+                const double prev_meal = at(f.prev_meal, i);
+                mlp_features(f, col, buf, head, prev_meal, start + e.t);
+                if (g.feat_trace)
+                    for (int j = 0; j < F; ++j) g.feat_trace[((c.trace_row + s) * F + j) * a.n + i] = buf[j * 64];
+                double u, bolus;
+                dopri5_controller(c, i, at(a.cgm, i), st, u, bolus);
+                if (f.act_trace) {                       // what the controller asked for, before the pump: one addition
+#pragma clang fp contract(off)
+                    f.act_trace[(c.trace_row + s) * a.n + i] = u + bolus;
+                }
+                double q_basal = u, q_bolus = bolus;     // as step_body with a bolus given: env.py:51-52
+                if (!(a.flags & T1D_BATCH_NO_PUMP)) {
+                    q_basal = pump_quantise(u, a.pump.inc_basal, a.pump.min_basal, a.pump.max_basal);
+                    q_bolus = pump_quantise(bolus, a.pump.inc_bolus, a.pump.min_bolus, a.pump.max_bolus);
+                }
+                insulin = q_basal + q_bolus;
+                o = StepOut<double>{0.0, 0.0, 0.0, 0.0};
+            }
+            const double meal = meal_lookup(a, i, e);                                         // env.py:50
+            noise = measure_noise<true>(a, i, e, due);
+            const MinuteIn<double> u = eat_minute<0, double>(nop, e.x, meal, insulin, e.planned, e.lq, e.lf, e.eating);
+            d_mg = u.d_mg;
+            o.meal += meal / div; o.ins += insulin / div;                                     // env.py:78-79
+            if (!failed) dopri5_enter(p, e.x, d_mg, insulin, e.lq, e.lf, hc, (double)e.t, r, nf);
+            cold.save(e, o, noise, hc);
+            fresh = false; boundary = false;
+        }
+        if (failed) { boundary = true; continue; }
+        const int rc = dopri5_attempt(p, e.x, d_mg, insulin, e.lq, e.lf, cold.f[Cold::HC * 64], (double)e.t + 1.0, r, nf);
+        failed = rc < 0;
+        boundary = rc != 0;
+    }
+    if (!stored) store_env(a, i, pid, e);
+    at(h_carry, i) = hc;
+    if (nfev) at(nfev, i) = nf;
+    if (failed) atomicOr(a.status, T1D_ST_SOLVER_FAILED);
+    dopri5_mlp_store_windows(a, f, i, col, s);
+}
+
 // t1d_mlp_action: the policy alone, one lane per env -- the action the next step of a roll-out would ask for, from
 // batch.cgm (CGM[0]), rows 1 .. of cgm_hist, ins_hist, prev_meal, batch.t and start_minute.  Reads only; writes action [n].
 // Dynamic LDS: cols * 64 words for each wave, the lane's column in window order (head 0).

@@ -789,11 +789,15 @@ __device__ __forceinline__ void ctrl_policy(const PidArgs<T>& c, bool bb, T st, 
     }
 }
 
-template <int VARIANT, typename T, typename P, typename PR = NoProp>
+// LM: nothing (t1d_collect_pid / t1d_collect_bb) or one LimitArgs (t1d_collect_pid_limit / t1d_collect_bb_limit): an env whose
+// clock has reached max_minutes when a step closes is cut and restarts, as in mlp_collect_body.
+template <int VARIANT, typename T, typename P, typename PR = NoProp, typename... LM>
 __device__ __forceinline__ void ctrl_collect_body(const KArgs<T>& a, const PidArgs<T>& c, const MlpArgs<T>& f, const CollectArgs<T>& g,
-                                                  const RestartArgs<T>& r, P& p, unsigned i, uint32_t pid, Env<T>& e, T* col, PR pr = PR())
+                                                  const RestartArgs<T>& r, P& p, unsigned i, uint32_t pid, Env<T>& e, T* col, PR pr = PR(),
+                                                  const LM&... lm)
 {
     constexpr int MATH = VariantMath<VARIANT>::value;
+    constexpr bool LIMIT = sizeof...(LM) == 1;
     const int H = f.history, F = 2 * H + 3;
     T* const buf = col + 2 * H * 64;
     T obs = at(a.cgm, i);
@@ -847,12 +851,28 @@ __device__ __forceinline__ void ctrl_collect_body(const KArgs<T>& a, const PidAr
         max_bg = o.bg > max_bg ? o.bg : max_bg;
         n_low += o.bg < T(70); n_high += o.bg > T(180);
         fresh = false;
+        bool cut = false;                       // the time limit ends the episode here (never a finished one)
+        if constexpr (LIMIT) {
+            const LimitArgs<T>& lim = pack_first(lm...);
+            cut = !fin && e.t >= lim.max_minutes;
+            if (lim.cut_trace) lim.cut_trace[trow] = cut ? 1 : 0;
+        }
         if (g.on_done) {
-            if (fin) {
+            if (fin || cut) {
+                if constexpr (LIMIT) {
+                    // the features of the state the cut episode ended in: the windows are shifted, feat_meal is the step's meal
+                    // and e.t the clock after the step -- what t1d_mlp_features would read; buf is free between two steps
+                    const LimitArgs<T>& lim = pack_first(lm...);
+                    if (cut && lim.cut_feat) {
+                        mlp_features(f, col, buf, head, feat_meal, start + e.t);
+                        for (int j = 0; j < F; ++j) at(rowv(lim.cut_feat, a.n, j), i) = buf[j * 64];
+                    }
+                }
                 // the finished step goes to memory as the end of a launch leaves it; the restart works on those words
                 write_outputs<MATH>(a, i, e, o, rp);
                 store_env(a, i, pid, e);
-                collect_restart<T>(a, r, g.slots, i);
+                if constexpr (LIMIT) collect_restart_masked<T>(a, r, g.slots, i);      // a cut env's done is 0
+                else collect_restart<T>(a, r, g.slots, i);
                 load_env(a, i, at(a.meta, i), e);
                 obs = at(a.cgm, i);                             // the new episode's first observation
                 for (int k = 0; k < H; ++k) { col[k * 64] = obs; col[(H + k) * 64] = T(0); }
@@ -918,6 +938,44 @@ __global__ __launch_bounds__(T1D_POLICY_THREADS) void ctrl_collect_kernel(const 
     } else {
         ParsLds<T> p{lds, (int)pid};
         ctrl_collect_body<VARIANT>(a, c, f, g, r, p, i, pid, e, col);
+    }
+}
+
+// ctrl_collect_kernel with episodes cut at a time limit (t1d_collect_pid_limit, t1d_collect_bb_limit): the same body with a
+// LimitArgs in its trailing pack.  A kernel of its own name, as mlp_collect_limit_kernel is, so that ctrl_collect_kernel's
+// instances keep their symbols and their instruction streams.
+template <int VARIANT, typename T>
+__global__ __launch_bounds__(T1D_POLICY_THREADS) void ctrl_collect_limit_kernel(const KArgs<T> a, const PidArgs<T> c, const MlpArgs<T> f,
+                                                                                const CollectArgs<T> g, const RestartArgs<T> r,
+                                                                                const LimitArgs<T> lim)
+{
+    using VI = VariantInfo<VARIANT>;
+    constexpr int kParRows = VI::split ? DP_COUNT : DP_RK4_COUNT;
+    __shared__ T lds[VI::lds_pars ? kParRows * kMaxPatients : 1];
+    if (VI::lds_pars) stage_pars(a, lds, kParRows);
+    if (VI::split) stage_prop(a, (T*)t1d_dyn_lds);
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    __builtin_assume(i < (1u << 28));          // host guarantees n <= 2^28: i * sizeof(T) fits a 32-bit voffset
+    if ((int64_t)i >= a.n) return;
+    T* const col = (T*)(t1d_dyn_lds + f.lds_off) + (threadIdx.x >> 6) * (f.cols * 64) + (threadIdx.x & 63u);
+    const uint32_t meta = at(a.meta, i);
+    const uint32_t pid = T1D_META_PID(meta);
+    Env<T> e;
+    load_env(a, i, meta, e);
+    if constexpr (VARIANT == 4 || VARIANT == 6) {
+        ParsReg<T> p;
+        p.load(a.dpar, (int)pid);
+        ctrl_collect_body<VARIANT>(a, c, f, g, r, p, i, pid, e, col, PropLds<T>{(const T*)t1d_dyn_lds, a.np_pad, (int)pid}, lim);
+    } else if constexpr (VARIANT == 7) {
+        ParsLds<T> p{lds, (int)pid};
+        ctrl_collect_body<VARIANT>(a, c, f, g, r, p, i, pid, e, col, PropLds<T>{(const T*)t1d_dyn_lds, a.np_pad, (int)pid}, lim);
+    } else if constexpr (VARIANT == 3) {
+        ParsReg<T> p;
+        p.load(a.dpar, (int)pid);
+        ctrl_collect_body<VARIANT>(a, c, f, g, r, p, i, pid, e, col, NoProp(), lim);
+    } else {
+        ParsLds<T> p{lds, (int)pid};
+        ctrl_collect_body<VARIANT>(a, c, f, g, r, p, i, pid, e, col, NoProp(), lim);
     }
 }
 

@@ -36,6 +36,11 @@ same in each (`finish_rate_runs` shows it).
 `cut_rate` is the share of env-steps of the timed window that were cut.
 
     python tools/collect_bench.py --limit --policies net --out profiles/collect/limit_bench.json
+
+--limit --exact: the first four of those legs in the exact mode (collect_mlp_dopri5_limit, t1d_collect_mlp_dopri5_limit; the loop's
+one-step call is rollout_mlp_dopri5(1), with noise collect_mlp_dopri5(1)), between two events on the stream.
+
+    python tools/collect_bench.py --limit --exact --policies hypo --out profiles/collect/exact_limit_bench.json
 """
 import argparse
 
@@ -93,17 +98,19 @@ def run_leg(leg, n, pol, K, warm_steps, sigma, seed, exact):
 LIMIT_LEGS = ("collect", "limit_far", "limit", "loop_limit", "collect_sync", "limit_sync")
 
 
-def run_limit_leg(leg, n, pol, K, warm_steps, sigma, seed, limit_steps):
+def run_limit_leg(leg, n, pol, K, warm_steps, sigma, seed, limit_steps, exact=False):
     import torch
-    e = benchlib.mixed_env(n, seed)
+    e = benchlib.mixed_env(n, seed, integrator="dopri5" if exact else None)
+    plain, limited, rollout = (e.collect_mlp_dopri5, e.collect_mlp_dopri5_limit, e.rollout_mlp_dopri5) if exact else \
+        (e.collect_mlp, e.collect_mlp_limit, e.rollout_mlp)
     sync = leg.endswith("_sync")
     L = {"limit_far": 10 ** 6, "limit": limit_steps, "loop_limit": limit_steps, "limit_sync": K}.get(leg)
     cut_features = torch.zeros(2 * pol.history + 3, n, dtype=e.dtype, device=e.device)
 
     def collect(k, **kw):                       # today's call, or the one with the limit
         if L is None:
-            return e.collect_mlp(k, pol, policy_state=state, on_done="restart", days=DAYS, **kw)
-        return e.collect_mlp_limit(k, pol, L, cut_features, policy_state=state, days=DAYS, **kw)
+            return plain(k, pol, policy_state=state, on_done="restart", days=DAYS, **kw)
+        return limited(k, pol, L, cut_features, policy_state=state, days=DAYS, **kw)
     state = e.new_policy_state(pol)
     left = 0 if sync else warm_steps
     while left:                                 # a call with a limit takes at most max_episode_steps steps
@@ -125,9 +132,9 @@ def run_limit_leg(leg, n, pol, K, warm_steps, sigma, seed, limit_steps):
         rew, don, trn = [], [], []
         for _ in range(K):
             if sigma is not None:
-                e.collect_mlp(1, pol, sigma=sigma, policy_state=state, trace=tr)
+                plain(1, pol, sigma=sigma, policy_state=state, trace=tr)
             else:
-                e.rollout_mlp(1, pol, policy_state=state, trace=tr)
+                rollout(1, pol, policy_state=state, trace=tr)
             done = e.done.bool()
             cut = ~done & (e.t >= L * e.minutes_per_step)
             rew.append(e.reward.clone()); don.append(e.done.clone()); trn.append(cut)
@@ -139,10 +146,10 @@ def run_limit_leg(leg, n, pol, K, warm_steps, sigma, seed, limit_steps):
             state["prev_meal"].copy_(torch.where(mask, zero, state["prev_meal"]))
         tr["reward"], tr["done"], tr["truncated"] = torch.stack(rew), torch.stack(don), torch.stack(trn)
         finished, cuts = tr["done"].sum(), tr["truncated"].sum()
-    ms = benchlib.timed_leg(go, go, "host")
+    ms = benchlib.timed_leg(go, go, "events" if exact else "host")
     status = benchlib.close_leg(e)
     rates = float(finished) / (K * n), float(cuts) / (K * n)
-    del e
+    del e, plain, limited, rollout              # the bound methods hold the env too
     torch.cuda.empty_cache()
     return {"ms": ms, "status": status, "finish_rate": rates[0], "cut_rate": rates[1]}
 
@@ -154,11 +161,15 @@ def limit_main(args):
         pol = make_policy(kind, basal=args.hypo_basal)
         sigma = None if kind == "hypo" or args.sigma <= 0 else args.sigma
         for n in args.n:
-            runs = benchlib.alternate(LIMIT_LEGS, args.reps, lambda leg: run_limit_leg(leg, n, pol, args.steps, args.warm_steps, sigma,
-                                                                                     args.seed, args.limit_steps))
+            legs = LIMIT_LEGS[:4] if args.exact else LIMIT_LEGS
+            runs = benchlib.alternate(legs, args.reps, lambda leg: run_limit_leg(leg, n, pol, args.steps, args.warm_steps, sigma,
+                                                                               args.seed, args.limit_steps, args.exact))
             res = {"policy": kind, "hypo_basal": args.hypo_basal if kind == "hypo" else None, "n_envs": n, "dtype": "float64",
                    "steps": args.steps, "warm_steps": args.warm_steps, "limit_steps": args.limit_steps, "sigma": sigma,
-                   "sensor": "Dexcom", "label": args.label, "device": torch.cuda.get_device_name(0), "legs": {}}
+                   "sensor": "Dexcom"}
+            if args.exact:
+                res["integrator"] = "dopri5"
+            res.update({"label": args.label, "device": torch.cuda.get_device_name(0), "legs": {}})
             for leg, rr in runs.items():
                 res["legs"][leg] = {**benchlib.summarise([r["ms"] for r in rr], "ms", spread=True), "status": max(r["status"] for r in rr),
                                     "finish_rate": rr[-1]["finish_rate"], "cut_rate": rr[-1]["cut_rate"]}
@@ -166,7 +177,8 @@ def limit_main(args):
             res["limit_far_over_collect"] = med["limit_far"] / med["collect"]
             res["limit_over_collect"] = med["limit"] / med["collect"]
             res["loop_limit_over_limit"] = med["loop_limit"] / med["limit"]
-            res["limit_sync_over_collect_sync"] = med["limit_sync"] / med["collect_sync"]
+            if "limit_sync" in med:
+                res["limit_sync_over_collect_sync"] = med["limit_sync"] / med["collect_sync"]
             benchlib.emit(results, res)
     benchlib.write(results, args.out)
 
@@ -184,14 +196,14 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--label", default=None)
     ap.add_argument("--exact", action="store_true", help="the four legs in the exact mode (integrator='dopri5'), timed with events")
-    ap.add_argument("--limit", action="store_true", help="the legs of a time limit (collect_mlp_limit) instead")
+    ap.add_argument("--limit", action="store_true", help="the legs of a time limit (collect_mlp_limit; with --exact collect_mlp_dopri5_limit) instead")
     ap.add_argument("--limit-steps", type=int, default=48, help="max_episode_steps of the limit and loop_limit legs (>= --steps)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     benchlib.require_gpu("collect_bench.py")
     if args.limit:
-        if args.exact or args.limit_steps < args.steps:
-            raise SystemExit("--limit runs the fixed-step mode and needs --limit-steps >= --steps")
+        if args.limit_steps < args.steps:
+            raise SystemExit("--limit needs --limit-steps >= --steps")
         return limit_main(args)
     import torch
     results = []
