@@ -207,6 +207,15 @@ typedef struct t1d_pid {
     int64_t trace_row;
 } t1d_pid;
 
+/* The PID controller's four numbers per env (t1d_rollout_pid_gains, t1d_rollout_pid_dopri5_gains): device arrays of n words in
+ * the batch's dtype, read only.  All four must be set; a caller with one value for every env fills an array with it. */
+typedef struct t1d_pid_gains {
+    const void* P;            /* [n] */
+    const void* I;            /* [n] */
+    const void* D;            /* [n] */
+    const void* target;       /* [n] */
+} t1d_pid_gains;
+
 /* BBController (controller/basal_bolus_ctrller.py:15-80) for closed-loop roll-outs: per-env constants the
  * host takes from vpatient_params.csv / Quest.csv (unknown patients: CR 1/15, CF 1/50, basal 1.43*57/6000,
  * :61-64) and one word of state. */
@@ -539,6 +548,19 @@ int t1d_step_dopri5(t1d_ctx* ctx, const t1d_batch* b, double* h_carry, int32_t* 
 int t1d_rollout_pid(t1d_ctx* ctx, const t1d_batch* b, const t1d_pid* pid, int n_steps, int minutes,
                     int n_sub, void* hip_stream);
 
+/* t1d_rollout_pid with a controller of its own for every env: env i computes PIDController.policy (pid_ctrller.py:17-36) with
+ * gains.P[i], gains.I[i], gains.D[i] and gains.target[i] -- what batch_sim computes for a list of SimObj, each with its own
+ * PIDController(P, I, D, target).  The four scalars pid.P, pid.I, pid.D and pid.target are NOT read; everything else of pid
+ * (integ, prev, the accumulators, the trace columns, trace_row) means what it means in t1d_rollout_pid, as do the other
+ * arguments, the plan and the state left behind.  The expression, its arithmetic and its contraction are those of the scalar
+ * call: env i of a mixed batch is, bit for bit, env i of the same batch run by t1d_rollout_pid under
+ * (P[i], I[i], D[i], target[i]), whichever kernel the plan picks.  The launch-per-step form reads the four words once per
+ * env and step (and target once more when the step ends), the all-steps-in-one-launch form once per call.
+ * T1D_E_INVALID, before the batch is looked at and before anything is launched: pid or its state NULL, as t1d_rollout_pid;
+ * gains NULL, or any of its members NULL (the message names the member).  Then whatever t1d_rollout_pid rejects. */
+int t1d_rollout_pid_gains(t1d_ctx* ctx, const t1d_batch* b, const t1d_pid* pid, const t1d_pid_gains* gains, int n_steps,
+                          int minutes, int n_sub, void* hip_stream);
+
 /* SimObj.simulate (sim_engine.py:29-39) with BBController for n_steps env.steps in ONE launch: per step
  * basal = bb.basal; bolus = (prev_meal*sample_time/CR + (CGM > 150)*(CGM - target)/CF) / sample_time if
  * prev_meal > 0 else 0 (basal_bolus_ctrller.py:66-79), where CGM is the previous step's observation (batch.cgm on
@@ -640,6 +662,14 @@ int t1d_collect_bb(t1d_ctx* ctx, const t1d_batch* batch, const t1d_bb* bb, const
  * T1D_ST_SOLVER_FAILED; the other envs are unaffected. */
 int t1d_rollout_pid_dopri5(t1d_ctx* ctx, const t1d_batch* b, const t1d_pid* pid, double* h_carry, int32_t* nfev,
                            int n_steps, int minutes, void* hip_stream);
+
+/* t1d_rollout_pid_dopri5 with gains.P[i], gains.I[i], gains.D[i] and gains.target[i] for env i, as t1d_rollout_pid_gains
+ * has them: the four scalars of pid are NOT read, everything else is t1d_rollout_pid_dopri5's.  The controller is evaluated
+ * without FMA contraction, operation by operation, as there: env i is bit for bit env i of the scalar call under its gains.
+ * T1D_E_INVALID as t1d_rollout_pid_gains (NULL gains or member, ahead of the batch's checks), then whatever
+ * t1d_rollout_pid_dopri5 rejects. */
+int t1d_rollout_pid_dopri5_gains(t1d_ctx* ctx, const t1d_batch* b, const t1d_pid* pid, const t1d_pid_gains* gains,
+                                 double* h_carry, int32_t* nfev, int n_steps, int minutes, void* hip_stream);
 
 /* The same with BBController (basal_bolus_ctrller.py:34-80; sim_engine.py:29-39; t1dpatient.py:110-113,276): t1d_rollout_bb
  * in the exact mode -- the reference's own regression run (sim_results.csv).  bb.prev_meal is updated. */

@@ -10,7 +10,7 @@ LIB_PATH = os.environ.get("T1D_LIB_PATH") or os.path.join(_PKG, "libt1d_hip.so")
 SOURCES = [os.path.join(_PKG, "csrc", "t1d_abi.hip"), os.path.join(_PKG, "csrc", "t1d_kernels.hpp"),
            os.path.join(_PKG, "csrc", "t1d_device.hpp"), os.path.join(_PKG, "csrc", "t1d_dopri5.hpp"),
            os.path.join(_PKG, "csrc", "t1d_policy.hpp"), os.path.join(_PKG, "csrc", "t1d_policy_grad.hpp"),
-           os.path.join(_PKG, "csrc", "t1d_gae.hpp"),
+           os.path.join(_PKG, "csrc", "t1d_gae.hpp"), os.path.join(_PKG, "csrc", "t1d_stepn_body.inc"),
            os.path.join(_ROOT, "include", "t1d.h")]
 
 T1D_F64, T1D_F32 = 0, 1
@@ -41,7 +41,7 @@ EXPORTS = ("t1d_abi_version", "t1d_last_error", "t1d_ctx_create", "t1d_ctx_set_o
            "t1d_rollout_mlp_dopri5_bolus", "t1d_mlp_bolus", "t1d_rollout_mlp_rel", "t1d_collect_mlp_rel",
            "t1d_rollout_mlp_dopri5_rel", "t1d_mlp_action_rel", "t1d_collect_mlp_limit", "t1d_gae_limit",
            "t1d_collect_pid_limit", "t1d_collect_bb_limit", "t1d_collect_mlp_dopri5_limit", "t1d_collect_pid_dopri5_limit",
-           "t1d_collect_bb_dopri5_limit")
+           "t1d_collect_bb_dopri5_limit", "t1d_rollout_pid_gains", "t1d_rollout_pid_dopri5_gains")
 
 
 class T1DError(RuntimeError):
@@ -73,6 +73,11 @@ class Pid(C.Structure):
     """struct t1d_pid (include/t1d.h)"""
     _fields_ = [("P", C.c_double), ("I", C.c_double), ("D", C.c_double), ("target", C.c_double),
                 ("integ", C.c_void_p), ("prev", C.c_void_p)] + _STATS_FIELDS + _TRACE_FIELDS + [("trace_row", C.c_int64)]
+
+
+class PidGains(C.Structure):
+    """struct t1d_pid_gains (include/t1d.h)"""
+    _fields_ = [("P", C.c_void_p), ("I", C.c_void_p), ("D", C.c_void_p), ("target", C.c_void_p)]
 
 
 class Bb(C.Structure):
@@ -233,12 +238,14 @@ def lib():
     L.t1d_step.argtypes = [vp, C.POINTER(Batch), C.c_int, C.c_int, vp]
     L.t1d_step_dopri5.argtypes = [vp, C.POINTER(Batch), vp, vp, C.c_int, vp]
     L.t1d_rollout_pid.argtypes = [vp, C.POINTER(Batch), C.POINTER(Pid), C.c_int, C.c_int, C.c_int, vp]
+    L.t1d_rollout_pid_gains.argtypes = [vp, C.POINTER(Batch), C.POINTER(Pid), C.POINTER(PidGains), C.c_int, C.c_int, C.c_int, vp]
     L.t1d_rollout_bb.argtypes = [vp, C.POINTER(Batch), C.POINTER(Bb), C.c_int, C.c_int, C.c_int, vp]
     L.t1d_rollout_mlp.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), C.c_int, C.c_int, C.c_int, vp]
     L.t1d_collect_mlp.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), C.POINTER(Collect), C.c_int, C.c_int, C.c_int, vp]
     L.t1d_collect_pid.argtypes = [vp, C.POINTER(Batch), C.POINTER(Pid), C.POINTER(Mlp), C.POINTER(Collect), C.c_int, C.c_int, C.c_int, vp]
     L.t1d_collect_bb.argtypes = [vp, C.POINTER(Batch), C.POINTER(Bb), C.POINTER(Mlp), C.POINTER(Collect), C.c_int, C.c_int, C.c_int, vp]
     L.t1d_rollout_pid_dopri5.argtypes = [vp, C.POINTER(Batch), C.POINTER(Pid), vp, vp, C.c_int, C.c_int, vp]
+    L.t1d_rollout_pid_dopri5_gains.argtypes = [vp, C.POINTER(Batch), C.POINTER(Pid), C.POINTER(PidGains), vp, vp, C.c_int, C.c_int, vp]
     L.t1d_rollout_bb_dopri5.argtypes = [vp, C.POINTER(Batch), C.POINTER(Bb), vp, vp, C.c_int, C.c_int, vp]
     L.t1d_rollout_mlp_dopri5.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), vp, vp, C.c_int, C.c_int, vp]
     L.t1d_collect_mlp_dopri5.argtypes = [vp, C.POINTER(Batch), C.POINTER(Mlp), C.POINTER(Collect), vp, vp, C.c_int, C.c_int, vp]

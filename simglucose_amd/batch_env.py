@@ -459,14 +459,79 @@ class BatchedT1DSimEnv:
                                 "rollout_bb_dopri5 / rollout_mlp_dopri5 / collect_mlp_dopri5 (collect_pid and collect_bb have no "
                                 "exact-mode form in these kernels: collect_pid_dopri5 / collect_bb_dopri5)")
 
-    def rollout_pid(self, n_steps, P, I, D, target=140.0, pid_state=None, stats=None, trace=None):
+    def rollout_pid(self, n_steps, P, I=None, D=None, target=140.0, pid_state=None, stats=None, trace=None):
         """n_steps closed-loop PID steps in one launch (PIDController.policy + env.step per step).
         pid_state: dict(integ, prev) tensors [n] (created zeroed if None).  stats: optional dict
-        with any of sum_risk, min_bg, max_bg (float [n]) and n_low, n_high (int32 [n])."""
+        with any of sum_risk, min_bg, max_bg (float [n]) and n_low, n_high (int32 [n]).
+        P, I, D, target: four numbers, one controller for every env (t1d_rollout_pid) -- or, any of them a tensor or array of
+        n numbers, or P the dict pid_gains() returns (I and D then left out), a controller per env (t1d_rollout_pid_gains):
+        env i runs under P[i], I[i], D[i], target[i] and is, bit for bit, the env of a batch run entirely under those four
+        numbers, so a grid of gain sets x patients x scenarios is one batch and one roll-out."""
         self._no_dopri5_rollout()
-        pid_state, p = self._pid_struct(P, I, D, target, pid_state, stats)
-        self._rollout(self._L.t1d_rollout_pid, (p,), n_steps, trace)
+        gains = self._per_env_gains("rollout_pid", P, I, D, target)
+        if gains is None:
+            pid_state, p = self._pid_struct(P, I, D, target, pid_state, stats)
+            self._rollout(self._L.t1d_rollout_pid, (p,), n_steps, trace)
+        else:
+            pid_state, p = self._pid_struct(0.0, 0.0, 0.0, 0.0, pid_state, stats)
+            self._rollout(self._L.t1d_rollout_pid_gains, (p, self._gains_struct(gains)), n_steps, trace)
         return pid_state
+
+    _GAIN_NAMES = ("P", "I", "D", "target")
+
+    @staticmethod
+    def _is_per_env(v):
+        """a gain given per env: anything with a length or a shape, i.e. not a plain number"""
+        return isinstance(v, (torch.Tensor, np.ndarray, list, tuple))
+
+    def pid_gains(self, P, I, D, target=140.0):
+        """The four [n] arrays of a per-env PID controller, as rollout_pid / rollout_pid_dopri5 take them in place of four
+        numbers: dict(P, I, D, target) of contiguous tensors in the env's dtype on its device.  A number is broadcast; a
+        tensor or array of n numbers is taken in float64 and rounded once to the env's dtype (what the scalar call does
+        with its doubles); any other length is a ValueError.  A tensor that already is [n], contiguous, of the env's
+        dtype and on its device is used in place: the caller may edit it between roll-outs."""
+        out = {}
+        for name, v in zip(self._GAIN_NAMES, (P, I, D, target)):
+            if isinstance(v, torch.Tensor) and v.shape == (self.n,) and v.dtype == self.dtype and v.device == self.device and v.is_contiguous():
+                out[name] = v
+                continue
+            if self._is_per_env(v):
+                w = v.detach().to("cpu", torch.float64) if isinstance(v, torch.Tensor) else torch.as_tensor(np.asarray(v, dtype=np.float64))
+                if w.dim() == 0:
+                    w = w.reshape(1).expand(self.n)
+                elif tuple(w.shape) != (self.n,):
+                    raise ValueError("pid_gains: %s has shape %s, the env has %d envs (one number, or [%d])"
+                                     % (name, tuple(w.shape), self.n, self.n))
+            else:
+                w = torch.full((self.n,), float(v), dtype=torch.float64)
+            out[name] = w.to(self.dtype).to(self.device).contiguous()
+        return out
+
+    def _per_env_gains(self, who, P, I, D, target):
+        """None where the four are plain numbers (the scalar entry point); else the dict of pid_gains, checked"""
+        if isinstance(P, dict):
+            if I is not None or D is not None:
+                raise ValueError("%s: with the dict of pid_gains() as P, leave I and D out" % who)
+            missing = [k for k in self._GAIN_NAMES if k not in P]
+            if missing:
+                raise ValueError("%s: the gains dict has no %s (see pid_gains)" % (who, ", ".join(missing)))
+            return self.pid_gains(P["P"], P["I"], P["D"], P["target"])
+        if I is None or D is None:
+            raise TypeError("%s needs P, I and D (or the dict of pid_gains() as P)" % who)
+        if not any(self._is_per_env(v) for v in (P, I, D, target)):
+            return None
+        return self.pid_gains(P, I, D, target)
+
+    def _gains_struct(self, gains):
+        g = _lib.PidGains()
+        g.P, g.I, g.D, g.target = (gains[k].data_ptr() for k in self._GAIN_NAMES)
+        self._keep_gains = gains                       # the arrays outlive the launch
+        return g
+
+    def _no_per_env_gains(self, who, *gains):
+        if any(isinstance(v, dict) or self._is_per_env(v) for v in gains):
+            raise _lib.T1DError("%s takes one P, I, D and target for the whole batch: per-env gains are a roll-out feature "
+                                "(rollout_pid / rollout_pid_dopri5 take tensors or the dict of pid_gains())" % who)
 
     @staticmethod
     def _n_steps(n_steps):
@@ -960,6 +1025,7 @@ class BatchedT1DSimEnv:
         it wins by 20 % under the stock basal-bolus constants (0.27 % of the envs finish per step) and LOSES by 12 % where
         1 % finish per step, like collect_mlp.  -> (pid_state, policy_state)"""
         self._no_dopri5_rollout()
+        self._no_per_env_gains("collect_pid", P, I, D, target)
         pid_state, p = self._pid_struct(P, I, D, target, pid_state, stats)
         policy_state = self._collect_ctrl("collect_pid", self._L.t1d_collect_pid, p, pid_state, n_steps, features, policy_state, stats,
                                           trace, on_done, days, terminal_obs, episode_stats, reset_outputs)
@@ -1002,6 +1068,7 @@ class BatchedT1DSimEnv:
         With a limit no env reaches, the result is collect_pid(on_done="restart")'s, bit for bit.  Every other argument, and
         the return value, as collect_pid.  Measurements: profiles/collect/README.md.  -> (pid_state, policy_state)"""
         self._no_dopri5_rollout()
+        self._no_per_env_gains("collect_pid_limit", P, I, D, target)
         lim = self._time_limit_struct(n_steps, features, trace, on_done, max_episode_steps, cut_features, "collect_pid_limit")
         pid_state, p = self._pid_struct(P, I, D, target, pid_state, stats)
         policy_state = self._collect_ctrl("collect_pid_limit", self._L.t1d_collect_pid_limit, p, pid_state, n_steps, features,
@@ -1119,6 +1186,7 @@ class BatchedT1DSimEnv:
         are rollout_pid_dopri5's.  Measurements: profiles/collect (exact_ctrl_collect_bench.json).
         -> (pid_state, policy_state)"""
         self._need_dopri5("collect_pid_dopri5")
+        self._no_per_env_gains("collect_pid_dopri5", P, I, D, target)
         pid_state, p = self._pid_struct(P, I, D, target, pid_state, stats)
         policy_state = self._collect_ctrl_dopri5("collect_pid_dopri5", self._L.t1d_collect_pid_dopri5, p, pid_state, n_steps,
                                                  features, policy_state, stats, trace, on_done, days, terminal_obs, episode_stats,
@@ -1154,6 +1222,7 @@ class BatchedT1DSimEnv:
         of collect_pid_limit's loop with rollout_pid_dopri5(1), bit for bit (for envs whose solver does not give up); with a
         limit no env reaches it is collect_pid_dopri5(on_done="restart")'s.  -> (pid_state, policy_state)"""
         self._need_dopri5("collect_pid_dopri5_limit")
+        self._no_per_env_gains("collect_pid_dopri5_limit", P, I, D, target)
         lim = self._time_limit_struct(n_steps, features, trace, on_done, max_episode_steps, cut_features, "collect_pid_dopri5_limit")
         pid_state, p = self._pid_struct(P, I, D, target, pid_state, stats)
         policy_state = self._collect_ctrl_dopri5("collect_pid_dopri5_limit", self._L.t1d_collect_pid_dopri5_limit, p, pid_state,
@@ -1210,17 +1279,24 @@ class BatchedT1DSimEnv:
             raise _lib.T1DError("%s needs an env built with integrator='dopri5' (the fixed-step envs take %s)"
                                 % (who, who.replace("_dopri5", "")))
 
-    def rollout_pid_dopri5(self, n_steps, P, I, D, target=140.0, pid_state=None, stats=None, trace=None,
+    def rollout_pid_dopri5(self, n_steps, P, I=None, D=None, target=140.0, pid_state=None, stats=None, trace=None,
                            max_minutes_per_launch=240):
         """rollout_pid in the exact mode (t1d_rollout_pid_dopri5): n_steps closed-loop PID steps with scipy's dopri5, every
         env at its own pace inside a launch; results as a step() loop with the controller evaluated operation by operation
         in between, bit for bit.  Arguments and return value as rollout_pid; uses the env's h_carry and leaves the RHS
         evaluations of the whole call in nfev.  max_minutes_per_launch: the call is cut into launches of at most that many
         simulated minutes (whole steps) -- at 240 a wave costs 1.41 times its mean lane against 1.36 uncut, and a launch of
-        1 Mi envs stays in the range of a second; the cut changes no result."""
+        1 Mi envs stays in the range of a second; the cut changes no result.  Per-env gains as in rollout_pid
+        (t1d_rollout_pid_dopri5_gains)."""
         self._need_dopri5("rollout_pid_dopri5")
-        pid_state, p = self._pid_struct(P, I, D, target, pid_state, stats)
-        self._rollout_dopri5(self._L.t1d_rollout_pid_dopri5, p, n_steps, trace, max_minutes_per_launch)
+        gains = self._per_env_gains("rollout_pid_dopri5", P, I, D, target)
+        if gains is None:
+            pid_state, p = self._pid_struct(P, I, D, target, pid_state, stats)
+            self._rollout_dopri5(self._L.t1d_rollout_pid_dopri5, p, n_steps, trace, max_minutes_per_launch)
+        else:
+            pid_state, p = self._pid_struct(0.0, 0.0, 0.0, 0.0, pid_state, stats)
+            self._rollout_dopri5(self._L.t1d_rollout_pid_dopri5_gains, p, n_steps, trace, max_minutes_per_launch,
+                                 extra=(C.byref(self._gains_struct(gains)),))
         return pid_state
 
     def rollout_bb_dopri5(self, n_steps, target=140.0, bb_state=None, stats=None, trace=None, max_minutes_per_launch=240):

@@ -840,6 +840,75 @@ extern "C" int t1d_rollout_pid(t1d_ctx* c, const t1d_batch* b, const t1d_pid* pi
     return launch_rollout("t1d_rollout_pid", c, b, pid, nullptr, n_steps, minutes, n_sub, stream);
 }
 
+// ---- t1d_pid_gains: the PID controller's four numbers per env (t1d_rollout_pid_gains, t1d_rollout_pid_dopri5_gains) -------
+// needs no device: both calls check it ahead of the batch, so that a bad call is refused on any machine
+static int check_pid_gains(const char* who, const t1d_pid_gains* g)
+{
+    const std::string w = std::string(who) + ": ";
+    if (!g) return fail(T1D_E_INVALID, w + "gains is NULL");
+    if (!g->P) return fail(T1D_E_INVALID, w + "gains.P is NULL");
+    if (!g->I) return fail(T1D_E_INVALID, w + "gains.I is NULL");
+    if (!g->D) return fail(T1D_E_INVALID, w + "gains.D is NULL");
+    if (!g->target) return fail(T1D_E_INVALID, w + "gains.target is NULL");
+    return T1D_OK;
+}
+
+// make_pid with the arrays of g; the four scalars of p are not read
+template <typename T>
+static PidGainArgs<T> make_pid_gains(const t1d_pid* p, const t1d_pid_gains* g, int n_steps)
+{
+    t1d_pid q = *p;
+    q.P = q.I = q.D = q.target = 0.0;
+    PidGainArgs<T> c;
+    static_cast<PidArgs<T>&>(c) = make_pid<T>(&q, n_steps);
+    c.gP = (const T*)g->P; c.gI = (const T*)g->I; c.gD = (const T*)g->D; c.gtarget = (const T*)g->target;
+    return c;
+}
+
+template <typename T>
+static KernelFn<T, PidGainArgs<T>> rollout_gains_fn(int variant)
+{
+    return by_variant<T>(variant, [](auto v) -> KernelFn<T, PidGainArgs<T>> { return rollout_pid_gains_kernel<decltype(v)::value, T>; });
+}
+
+// run_rollout with the per-env form of the plan's kernel: rollout_pid_gains_kernel where the plan says rollout_pid_kernel,
+// one stepn_gains_kernel per step behind its refill where it says stepn_kernel<T, true, true>.  The plan is the scalar call's.
+template <typename T>
+static int run_rollout_gains(t1d_ctx* c, const t1d_batch* b, const Plan& p, const PidGainArgs<T>& pa, int n_steps, int minutes, int n_sub, hipStream_t s)
+{
+    if (p.kernel == Kern::rollout) return launch(c, b, p, minutes, n_sub, s, rollout_gains_fn<T>(p.variant), pa);
+    if (p.kernel != Kern::stepn || !p.ctrl) return fail(T1D_E_INVALID, "t1d_rollout_pid_gains: the plan names no roll-out kernel");
+    for (int k = 0; k < n_steps; ++k) {
+        PidGainArgs<T> one = pa;
+        one.n_steps = 1; one.trace_row += k;
+        if (p.refill_ahead)
+            hipLaunchKernelGGL(refill_kernel<T>, grid_for(b->n), dim3(kBlock), 0, s, make_args<T>(c, b, minutes, n_sub));
+        const int rc = launch(c, b, p, minutes, n_sub, s, stepn_gains_kernel<T>, one, p.nchunks, p.cap, p.mode);
+        if (rc) return rc;
+    }
+    return T1D_OK;
+}
+
+extern "C" int t1d_rollout_pid_gains(t1d_ctx* c, const t1d_batch* b, const t1d_pid* pid, const t1d_pid_gains* gains, int n_steps,
+                                     int minutes, int n_sub, void* stream)
+{
+    const char* who = "t1d_rollout_pid_gains";
+    if (!pid || !pid->integ || !pid->prev) return fail(T1D_E_INVALID, "t1d_rollout_pid_gains: pid state is NULL");
+    int rc = check_pid_gains(who, gains);
+    if (rc) return rc;
+    rc = check_closed_loop(who, c, b, n_steps);
+    if (rc) return rc;
+    Plan p;
+    rc = plan_and_tables(who, c, b, minutes, n_sub, true, &p);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (p.f64) rc = run_rollout_gains<double>(c, b, p, make_pid_gains<double>(pid, gains, n_steps), n_steps, minutes, n_sub, s);
+    else rc = run_rollout_gains<float>(c, b, p, make_pid_gains<float>(pid, gains, n_steps), n_steps, minutes, n_sub, s);
+    if (rc) return rc;
+    T1D_HIP(hipGetLastError());
+    return T1D_OK;
+}
+
 extern "C" int t1d_rollout_bb(t1d_ctx* c, const t1d_batch* b, const t1d_bb* bb, int n_steps, int minutes,
                               int n_sub, void* stream)
 {
@@ -1094,6 +1163,21 @@ extern "C" int t1d_rollout_pid_dopri5(t1d_ctx* c, const t1d_batch* b, const t1d_
 {
     if (!pid || !pid->integ || !pid->prev) return fail(T1D_E_INVALID, "t1d_rollout_pid_dopri5: pid state is NULL");
     return launch_rollout_dopri5("t1d_rollout_pid_dopri5", c, b, pid, nullptr, h_carry, nfev, n_steps, minutes, stream);
+}
+
+extern "C" int t1d_rollout_pid_dopri5_gains(t1d_ctx* c, const t1d_batch* b, const t1d_pid* pid, const t1d_pid_gains* gains,
+                                            double* h_carry, int32_t* nfev, int n_steps, int minutes, void* stream)
+{
+    const char* who = "t1d_rollout_pid_dopri5_gains";
+    if (!pid || !pid->integ || !pid->prev) return fail(T1D_E_INVALID, "t1d_rollout_pid_dopri5_gains: pid state is NULL");
+    int rc = check_pid_gains(who, gains);
+    if (rc) return rc;
+    rc = check_dopri5(who, c, b, h_carry, n_steps, minutes);
+    if (rc) return rc;
+    hipLaunchKernelGGL(dopri5_rollout_gains_kernel, grid_for(b->n), dim3(kBlock), 0, (hipStream_t)stream, make_args<double>(c, b, minutes, 1),
+                       make_pid_gains<double>(pid, gains, n_steps), (const double*)c->d_raw64, h_carry, nfev);
+    T1D_HIP(hipGetLastError());
+    return T1D_OK;
 }
 
 extern "C" int t1d_rollout_bb_dopri5(t1d_ctx* c, const t1d_batch* b, const t1d_bb* bb, double* h_carry, int32_t* nfev,

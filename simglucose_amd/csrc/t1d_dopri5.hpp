@@ -445,6 +445,103 @@ __global__ __launch_bounds__(kBlock, 1) void dopri5_rollout_kernel(const KArgs<d
     if (failed) atomicOr(a.status, T1D_ST_SOLVER_FAILED);
 }
 
+// dopri5_rollout_kernel under PIDController with env i's own P[i], I[i], D[i] and target[i] (t1d_rollout_pid_dopri5_gains):
+// the controller below where dopri5_controller stands, the rest line for line.  The four words are loaded inside the
+// boundary block where a step opens, next to the controller's state, and are dead before dopri5_attempt like everything
+// else of that block.  The expression is dopri5_controller's, contraction off: an env under gains g computes, operation by
+// operation, what the scalar call computes under g.
+__device__ __forceinline__ void dopri5_controller_gains(const PidGainArgs<double>& c, unsigned i, double obs, double st, double& u)
+{
+#pragma clang fp contract(off)
+    const double integ = at(c.integ, i), prev = at(c.prev, i);
+    const double kP = at(c.gP, i), kI = at(c.gI, i), kD = at(c.gD, i), target = at(c.gtarget, i);
+    u = kP * (obs - target) + kI * integ + kD * (obs - prev) / st;
+    at(c.prev, i) = obs;
+    at(c.integ, i) = integ + (obs - target) * st;
+}
+
+__global__ __launch_bounds__(kBlock, 1) void dopri5_rollout_gains_kernel(const KArgs<double> a, const PidGainArgs<double> c,
+                                                                         const double* __restrict__ raw, double* h_carry, int32_t* nfev)
+{
+    __shared__ double lds[kRawPars * kMaxPatients];
+    __shared__ double cold_f[RollCold::NF * kBlock];
+    __shared__ int cold_w[RollCold::NI * kBlock];
+    for (int j = threadIdx.x; j < kRawPars * kMaxPatients; j += blockDim.x) lds[j] = raw[j];
+    __syncthreads();
+    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
+    __builtin_assume(i < (1u << 28));          // host guarantees n <= 2^28: i * sizeof(T) fits a 32-bit voffset
+    if ((int64_t)i >= a.n) return;
+    const uint32_t meta = at(a.meta, i);
+    const uint32_t pid = T1D_META_PID(meta);
+    Env<double> e;
+    load_env(a, i, meta, e);
+    const ParsRaw p{lds, (int)pid};
+    NoDerivedPars nop;
+    const RollCold cold{cold_f + threadIdx.x, cold_w + threadIdx.x};
+    const double div = double(a.minutes), st = double(a.sen.st);
+    double hc = at(h_carry, i), noise = 0.0, insulin = 0.0, d_mg = 0.0;
+    StepOut<double> o{0.0, 0.0, 0.0, 0.0};
+    Dopri5Run r{};
+    int nf = 0, m = 0, s = 0;
+    bool due = false, failed = false, boundary = true, fresh = true;
+    cold.save(e, o, noise, hc);
+    for (;;) {
+        if (boundary) {
+            cold.load(e, o, noise, hc);
+            if (!fresh) {
+                e.t += 1;
+                const double gsub = e.x[12] / p(T1D_P_VG);                                    // t1dpatient.py:217-218
+                const double cgm = measure_apply(a, e, gsub, noise, due);                     // env.py:62
+                o.bg += gsub / div; o.cgm += cgm / div;                                       // env.py:80-81
+                if (++m == a.minutes) {                  // the step is complete: what t1d_step_dopri5 leaves, then the roll-out's own
+                    const double rp = e.prev_risk;
+                    write_outputs<0>(a, i, e, o, rp);
+                    const int64_t tr = (c.trace_row + s) * a.n + i;
+                    if (c.bg_trace) c.bg_trace[tr] = o.bg;
+                    if (c.cgm_trace) c.cgm_trace[tr] = o.cgm;
+                    if (c.cho_trace) c.cho_trace[tr] = o.meal;
+                    if (c.ins_trace) c.ins_trace[tr] = o.ins;
+                    if (c.sum_risk) { double l, h, rk; risk_index1<0>(o.bg, l, h, rk); at(c.sum_risk, i) = at(c.sum_risk, i) + rk; }
+                    if (c.min_bg) { const double v = at(c.min_bg, i); at(c.min_bg, i) = o.bg < v ? o.bg : v; }
+                    if (c.max_bg) { const double v = at(c.max_bg, i); at(c.max_bg, i) = o.bg > v ? o.bg : v; }
+                    if (c.n_low) at(c.n_low, i) = at(c.n_low, i) + (o.bg < 70.0);
+                    if (c.n_high) at(c.n_high, i) = at(c.n_high, i) + (o.bg > 180.0);
+                    m = 0; ++s;
+                }
+            }
+            if (s == c.n_steps) break;
+            if (m == 0) {                                // a step opens: the controller on the last observation, then the pump
+                double u, bolus;
+                dopri5_controller_gains(c, i, at(a.cgm, i), st, u);
+                bolus = 0.0;
+                double q_basal = u, q_bolus = bolus;     // as step_body with a bolus given: env.py:51-52
+                if (!(a.flags & T1D_BATCH_NO_PUMP)) {
+                    q_basal = pump_quantise(u, a.pump.inc_basal, a.pump.min_basal, a.pump.max_basal);
+                    q_bolus = pump_quantise(bolus, a.pump.inc_bolus, a.pump.min_bolus, a.pump.max_bolus);
+                }
+                insulin = q_basal + q_bolus;
+                o = StepOut<double>{0.0, 0.0, 0.0, 0.0};
+            }
+            const double meal = meal_lookup(a, i, e);                                         // env.py:50
+            noise = measure_noise<true>(a, i, e, due);
+            const MinuteIn<double> u = eat_minute<0, double>(nop, e.x, meal, insulin, e.planned, e.lq, e.lf, e.eating);
+            d_mg = u.d_mg;
+            o.meal += meal / div; o.ins += insulin / div;                                     // env.py:78-79
+            if (!failed) dopri5_enter(p, e.x, d_mg, insulin, e.lq, e.lf, hc, (double)e.t, r, nf);
+            cold.save(e, o, noise, hc);
+            fresh = false; boundary = false;
+        }
+        if (failed) { boundary = true; continue; }
+        const int rc = dopri5_attempt(p, e.x, d_mg, insulin, e.lq, e.lf, cold.f[RollCold::HC * kBlock], (double)e.t + 1.0, r, nf);
+        failed = rc < 0;
+        boundary = rc != 0;
+    }
+    store_env(a, i, pid, e);
+    at(h_carry, i) = hc;
+    if (nfev) at(nfev, i) = nf;
+    if (failed) atomicOr(a.status, T1D_ST_SOLVER_FAILED);
+}
+
 // ---- closed-loop roll-outs in the exact mode under the policy of t1d_mlp (t1d_rollout_mlp_dopri5) -----------------------
 // dopri5_rollout_kernel with the network of t1d_policy.hpp where dopri5_controller stands: solver, eat_minute, measure_*,
 // the pump and the outputs are that kernel's, line for line; the action is mlp_action, the function mlp_rollout_kernel
