@@ -11,7 +11,7 @@ SOURCES = [os.path.join(_PKG, "csrc", "t1d_abi.hip"), os.path.join(_PKG, "csrc",
            os.path.join(_PKG, "csrc", "t1d_device.hpp"), os.path.join(_PKG, "csrc", "t1d_dopri5.hpp"),
            os.path.join(_PKG, "csrc", "t1d_policy.hpp"), os.path.join(_PKG, "csrc", "t1d_policy_grad.hpp"),
            os.path.join(_PKG, "csrc", "t1d_gae.hpp"), os.path.join(_PKG, "csrc", "t1d_stepn_body.inc"),
-           os.path.join(_ROOT, "include", "t1d.h")]
+           os.path.join(_PKG, "csrc", "t1d_dopri5_loop.inc"), os.path.join(_ROOT, "include", "t1d.h")]
 
 T1D_F64, T1D_F32 = 0, 1
 T1D_ST_NORMALS_EXHAUSTED, T1D_ST_NONFINITE, T1D_ST_BAD_INDEX, T1D_ST_STALL = 1, 2, 4, 8

@@ -363,93 +363,25 @@ typedef RollColdT<kBlock> RollCold;
 // The loop ends: a lane either completes a minute or spends one of the driver's nmax step attempts of that minute.
 // A lane whose solver gives up keeps its last accepted state for the rest of the launch; its clock, meals and noise go on.
 // Grid, block, tables and arguments as dopri5_step_kernel; nfev: RHS evaluations of each env in this launch.
+// The loop is one text, t1d_dopri5_loop.inc, which this kernel and the eight below include between their braces; a kernel
+// defines ahead of the include what it is and the action it takes where a step opens (the list is at the top of that file).
 __global__ __launch_bounds__(kBlock, 1) void dopri5_rollout_kernel(const KArgs<double> a, const PidArgs<double> c,
                                                                    const double* __restrict__ raw, double* h_carry, int32_t* nfev)
 {
-    __shared__ double lds[kRawPars * kMaxPatients];
-    __shared__ double cold_f[RollCold::NF * kBlock];
-    __shared__ int cold_w[RollCold::NI * kBlock];
-    for (int j = threadIdx.x; j < kRawPars * kMaxPatients; j += blockDim.x) lds[j] = raw[j];
-    __syncthreads();
-    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
-    __builtin_assume(i < (1u << 28));          // host guarantees n <= 2^28: i * sizeof(T) fits a 32-bit voffset
-    if ((int64_t)i >= a.n) return;
-    const uint32_t meta = at(a.meta, i);
-    const uint32_t pid = T1D_META_PID(meta);
-    Env<double> e;
-    load_env(a, i, meta, e);
-    const ParsRaw p{lds, (int)pid};
-    NoDerivedPars nop;
-    const RollCold cold{cold_f + threadIdx.x, cold_w + threadIdx.x};
-    const double div = double(a.minutes), st = double(a.sen.st);
-    double hc = at(h_carry, i), noise = 0.0, insulin = 0.0, d_mg = 0.0;
-    StepOut<double> o{0.0, 0.0, 0.0, 0.0};
-    Dopri5Run r{};
-    int nf = 0, m = 0, s = 0;
-    bool due = false, failed = false, boundary = true, fresh = true;
-    cold.save(e, o, noise, hc);
-    for (;;) {
-        if (boundary) {
-            cold.load(e, o, noise, hc);
-            if (!fresh) {
-                e.t += 1;
-                const double gsub = e.x[12] / p(T1D_P_VG);                                    // t1dpatient.py:217-218
-                const double cgm = measure_apply(a, e, gsub, noise, due);                     // env.py:62
-                o.bg += gsub / div; o.cgm += cgm / div;                                       // env.py:80-81
-                if (++m == a.minutes) {                  // the step is complete: what t1d_step_dopri5 leaves, then the roll-out's own
-                    const double rp = e.prev_risk;
-                    write_outputs<0>(a, i, e, o, rp);
-                    const int64_t tr = (c.trace_row + s) * a.n + i;
-                    if (c.bg_trace) c.bg_trace[tr] = o.bg;
-                    if (c.cgm_trace) c.cgm_trace[tr] = o.cgm;
-                    if (c.cho_trace) c.cho_trace[tr] = o.meal;
-                    if (c.ins_trace) c.ins_trace[tr] = o.ins;
-                    if (c.kind == 1) at(c.bb_prev_meal, i) = o.meal;
-                    if (c.sum_risk) { double l, h, rk; risk_index1<0>(o.bg, l, h, rk); at(c.sum_risk, i) = at(c.sum_risk, i) + rk; }
-                    if (c.min_bg) { const double v = at(c.min_bg, i); at(c.min_bg, i) = o.bg < v ? o.bg : v; }
-                    if (c.max_bg) { const double v = at(c.max_bg, i); at(c.max_bg, i) = o.bg > v ? o.bg : v; }
-                    if (c.n_low) at(c.n_low, i) = at(c.n_low, i) + (o.bg < 70.0);
-                    if (c.n_high) at(c.n_high, i) = at(c.n_high, i) + (o.bg > 180.0);
-                    m = 0; ++s;
-                }
-            }
-            if (s == c.n_steps) break;
-            if (m == 0) {                                // a step opens: the controller on the last observation, then the pump
-                double u, bolus;
-                dopri5_controller(c, i, at(a.cgm, i), st, u, bolus);
-                double q_basal = u, q_bolus = bolus;     // as step_body with a bolus given: env.py:51-52
-                if (!(a.flags & T1D_BATCH_NO_PUMP)) {
-                    q_basal = pump_quantise(u, a.pump.inc_basal, a.pump.min_basal, a.pump.max_basal);
-                    q_bolus = pump_quantise(bolus, a.pump.inc_bolus, a.pump.min_bolus, a.pump.max_bolus);
-                }
-                insulin = q_basal + q_bolus;
-                o = StepOut<double>{0.0, 0.0, 0.0, 0.0};
-            }
-            const double meal = meal_lookup(a, i, e);                                         // env.py:50
-            noise = measure_noise<true>(a, i, e, due);
-            const MinuteIn<double> u = eat_minute<0, double>(nop, e.x, meal, insulin, e.planned, e.lq, e.lf, e.eating);
-            d_mg = u.d_mg;
-            o.meal += meal / div; o.ins += insulin / div;                                     // env.py:78-79
-            if (!failed) dopri5_enter(p, e.x, d_mg, insulin, e.lq, e.lf, hc, (double)e.t, r, nf);
-            cold.save(e, o, noise, hc);
-            fresh = false; boundary = false;
-        }
-        if (failed) { boundary = true; continue; }
-        const int rc = dopri5_attempt(p, e.x, d_mg, insulin, e.lq, e.lf, cold.f[RollCold::HC * kBlock], (double)e.t + 1.0, r, nf);
-        failed = rc < 0;
-        boundary = rc != 0;
-    }
-    store_env(a, i, pid, e);
-    at(h_carry, i) = hc;
-    if (nfev) at(nfev, i) = nf;
-    if (failed) atomicOr(a.status, T1D_ST_SOLVER_FAILED);
+    // its own: RollCold in static LDS; PidArgs' bb_prev_meal; where a step opens, the controller on the last observation
+#define DOPRI5_STATE
+#define DOPRI5_BB
+#define DOPRI5_ACTION                                                                                                          \
+    double u, bolus;                                                                                                           \
+    dopri5_controller(c, i, at(a.cgm, i), st, u, bolus);
+#include "t1d_dopri5_loop.inc"
 }
 
 // dopri5_rollout_kernel under PIDController with env i's own P[i], I[i], D[i] and target[i] (t1d_rollout_pid_dopri5_gains):
-// the controller below where dopri5_controller stands, the rest line for line.  The four words are loaded inside the
-// boundary block where a step opens, next to the controller's state, and are dead before dopri5_attempt like everything
-// else of that block.  The expression is dopri5_controller's, contraction off: an env under gains g computes, operation by
-// operation, what the scalar call computes under g.
+// the controller below where dopri5_controller stands.  The four words are loaded inside the boundary block where a step
+// opens, next to the controller's state, and are dead before dopri5_attempt like everything else of that block.  The
+// expression is dopri5_controller's, contraction off: an env under gains g computes, operation by operation, what the
+// scalar call computes under g.
 __device__ __forceinline__ void dopri5_controller_gains(const PidGainArgs<double>& c, unsigned i, double obs, double st, double& u)
 {
 #pragma clang fp contract(off)
@@ -463,91 +395,21 @@ __device__ __forceinline__ void dopri5_controller_gains(const PidGainArgs<double
 __global__ __launch_bounds__(kBlock, 1) void dopri5_rollout_gains_kernel(const KArgs<double> a, const PidGainArgs<double> c,
                                                                          const double* __restrict__ raw, double* h_carry, int32_t* nfev)
 {
-    __shared__ double lds[kRawPars * kMaxPatients];
-    __shared__ double cold_f[RollCold::NF * kBlock];
-    __shared__ int cold_w[RollCold::NI * kBlock];
-    for (int j = threadIdx.x; j < kRawPars * kMaxPatients; j += blockDim.x) lds[j] = raw[j];
-    __syncthreads();
-    const unsigned i = blockIdx.x * kBlock + threadIdx.x;
-    __builtin_assume(i < (1u << 28));          // host guarantees n <= 2^28: i * sizeof(T) fits a 32-bit voffset
-    if ((int64_t)i >= a.n) return;
-    const uint32_t meta = at(a.meta, i);
-    const uint32_t pid = T1D_META_PID(meta);
-    Env<double> e;
-    load_env(a, i, meta, e);
-    const ParsRaw p{lds, (int)pid};
-    NoDerivedPars nop;
-    const RollCold cold{cold_f + threadIdx.x, cold_w + threadIdx.x};
-    const double div = double(a.minutes), st = double(a.sen.st);
-    double hc = at(h_carry, i), noise = 0.0, insulin = 0.0, d_mg = 0.0;
-    StepOut<double> o{0.0, 0.0, 0.0, 0.0};
-    Dopri5Run r{};
-    int nf = 0, m = 0, s = 0;
-    bool due = false, failed = false, boundary = true, fresh = true;
-    cold.save(e, o, noise, hc);
-    for (;;) {
-        if (boundary) {
-            cold.load(e, o, noise, hc);
-            if (!fresh) {
-                e.t += 1;
-                const double gsub = e.x[12] / p(T1D_P_VG);                                    // t1dpatient.py:217-218
-                const double cgm = measure_apply(a, e, gsub, noise, due);                     // env.py:62
-                o.bg += gsub / div; o.cgm += cgm / div;                                       // env.py:80-81
-                if (++m == a.minutes) {                  // the step is complete: what t1d_step_dopri5 leaves, then the roll-out's own
-                    const double rp = e.prev_risk;
-                    write_outputs<0>(a, i, e, o, rp);
-                    const int64_t tr = (c.trace_row + s) * a.n + i;
-                    if (c.bg_trace) c.bg_trace[tr] = o.bg;
-                    if (c.cgm_trace) c.cgm_trace[tr] = o.cgm;
-                    if (c.cho_trace) c.cho_trace[tr] = o.meal;
-                    if (c.ins_trace) c.ins_trace[tr] = o.ins;
-                    if (c.sum_risk) { double l, h, rk; risk_index1<0>(o.bg, l, h, rk); at(c.sum_risk, i) = at(c.sum_risk, i) + rk; }
-                    if (c.min_bg) { const double v = at(c.min_bg, i); at(c.min_bg, i) = o.bg < v ? o.bg : v; }
-                    if (c.max_bg) { const double v = at(c.max_bg, i); at(c.max_bg, i) = o.bg > v ? o.bg : v; }
-                    if (c.n_low) at(c.n_low, i) = at(c.n_low, i) + (o.bg < 70.0);
-                    if (c.n_high) at(c.n_high, i) = at(c.n_high, i) + (o.bg > 180.0);
-                    m = 0; ++s;
-                }
-            }
-            if (s == c.n_steps) break;
-            if (m == 0) {                                // a step opens: the controller on the last observation, then the pump
-                double u, bolus;
-                dopri5_controller_gains(c, i, at(a.cgm, i), st, u);
-                bolus = 0.0;
-                double q_basal = u, q_bolus = bolus;     // as step_body with a bolus given: env.py:51-52
-                if (!(a.flags & T1D_BATCH_NO_PUMP)) {
-                    q_basal = pump_quantise(u, a.pump.inc_basal, a.pump.min_basal, a.pump.max_basal);
-                    q_bolus = pump_quantise(bolus, a.pump.inc_bolus, a.pump.min_bolus, a.pump.max_bolus);
-                }
-                insulin = q_basal + q_bolus;
-                o = StepOut<double>{0.0, 0.0, 0.0, 0.0};
-            }
-            const double meal = meal_lookup(a, i, e);                                         // env.py:50
-            noise = measure_noise<true>(a, i, e, due);
-            const MinuteIn<double> u = eat_minute<0, double>(nop, e.x, meal, insulin, e.planned, e.lq, e.lf, e.eating);
-            d_mg = u.d_mg;
-            o.meal += meal / div; o.ins += insulin / div;                                     // env.py:78-79
-            if (!failed) dopri5_enter(p, e.x, d_mg, insulin, e.lq, e.lf, hc, (double)e.t, r, nf);
-            cold.save(e, o, noise, hc);
-            fresh = false; boundary = false;
-        }
-        if (failed) { boundary = true; continue; }
-        const int rc = dopri5_attempt(p, e.x, d_mg, insulin, e.lq, e.lf, cold.f[RollCold::HC * kBlock], (double)e.t + 1.0, r, nf);
-        failed = rc < 0;
-        boundary = rc != 0;
-    }
-    store_env(a, i, pid, e);
-    at(h_carry, i) = hc;
-    if (nfev) at(nfev, i) = nf;
-    if (failed) atomicOr(a.status, T1D_ST_SOLVER_FAILED);
+    // its own: RollCold in static LDS; where a step opens, the controller under the env's gains, no bolus
+#define DOPRI5_STATE
+#define DOPRI5_ACTION                                                                                                          \
+    double u, bolus;                                                                                                           \
+    dopri5_controller_gains(c, i, at(a.cgm, i), st, u);                                                                        \
+    bolus = 0.0;
+#include "t1d_dopri5_loop.inc"
 }
 
 // ---- closed-loop roll-outs in the exact mode under the policy of t1d_mlp (t1d_rollout_mlp_dopri5) -----------------------
 // dopri5_rollout_kernel with the network of t1d_policy.hpp where dopri5_controller stands: solver, eat_minute, measure_*,
-// the pump and the outputs are that kernel's, line for line; the action is mlp_action, the function mlp_rollout_kernel
-// calls, so a step asks for the word t1d_rollout_mlp would ask for from the same windows, prev_meal, clock and weights
-// (the functions of t1d_policy.hpp carry no contract(off): the pragma of this file is set per function and stays in the
-// solver's).  Where the policy's words live:
+// the pump and the outputs are the shared loop's (t1d_dopri5_loop.inc); the action is mlp_action, the function
+// mlp_rollout_kernel calls, so a step asks for the word t1d_rollout_mlp would ask for from the same windows, prev_meal,
+// clock and weights (the functions of t1d_policy.hpp carry no contract(off): the pragma of this file is set per function
+// and stays in the solver's).  Where the policy's words live:
 //   windows      2 H rows of the lane's LDS column ([row][lane], no bank conflict), a ring as in mlp_rollout_body.  The
 //                lanes of a wave are in different steps, so the head is per lane: after s steps of this launch CGM[0] sits
 //                in row (H - s mod H) mod H, worked out from the lane's own step counter when a step ends.  In window
@@ -562,21 +424,11 @@ __global__ __launch_bounds__(kBlock, 1) void dopri5_rollout_gains_kernel(const K
 // whose layout does not depend on the workgroup's size.
 constexpr int kRollColdWaveBytes = (int)(RollColdT<64>::NF * sizeof(double) + RollColdT<64>::NI * sizeof(int)) * 64;
 
-// dopri5_mlp_rollout_kernel's pieces outside the solver loop as functions, for dopri5_mlp_collect_kernel (below): the same
-// lines, inlined there.  The roll-out kernel keeps them written out: calling these from it changed its register
-// allocation and cost it 0.5 - 0.7 % at 1 Mi envs when tried (profiles/policy/kernel_resources_collect_exact.txt).  A
-// change to one of them is a change to the matching lines of that kernel.
-// The lane's piece of dynamic LDS: Cold's doubles, Cold's ints, then the columns.
-struct MlpLaneLds { RollColdT<64> cold; double* col; };
-__device__ __forceinline__ MlpLaneLds dopri5_mlp_lane_lds(const MlpArgs<double>& c)
-{
-    typedef RollColdT<64> Cold;
-    unsigned char* const piece = t1d_dyn_lds + (threadIdx.x >> 6) * (kRollColdWaveBytes + c.cols * 64 * (int)sizeof(double));
-    const unsigned lane = threadIdx.x & 63u;
-    return MlpLaneLds{Cold{(double*)piece + lane, (int*)(piece + Cold::NF * 64 * sizeof(double)) + lane},
-                      (double*)(piece + kRollColdWaveBytes) + lane};
-}
-
+// Three pieces of the loop (t1d_dopri5_loop.inc) as functions, called by every kernel with windows except
+// dopri5_mlp_rollout_kernel, for which the loop has the same lines in place (DOPRI5_WRITTEN_OUT): calling these from that
+// kernel changed its register allocation and cost it 0.5 - 0.7 % at 1 Mi envs when tried
+// (profiles/policy/kernel_resources_collect_exact.txt), and writing the lines out for the others moves all six of them and
+// makes two spill more (the figures are in t1d_dopri5_loop.inc).  A change to one of them is a change to those lines.
 // the windows into the lane's column, in window order (head 0)
 __device__ __forceinline__ void dopri5_mlp_load_windows(const KArgs<double>& a, const MlpArgs<double>& c, unsigned i, double* col)
 {
@@ -597,7 +449,7 @@ __device__ __forceinline__ void dopri5_mlp_store_windows(const KArgs<double>& a,
     }
 }
 
-// a step closes: its four trace columns (row tr), prev_meal and the statistics
+// a step closes under the policy: its four trace columns (row tr), prev_meal and the statistics
 __device__ __forceinline__ void dopri5_mlp_step_words(const MlpArgs<double>& c, unsigned i, int64_t tr, const StepOut<double>& o)
 {
     if (c.bg_trace) c.bg_trace[tr] = o.bg;
@@ -612,442 +464,106 @@ __device__ __forceinline__ void dopri5_mlp_step_words(const MlpArgs<double>& c, 
     if (c.n_high) at(c.n_high, i) = at(c.n_high, i) + (o.bg > 180.0);
 }
 
-// a step opens with the action u: the pump, as step_body with a bolus of 0 given (env.py:51-52); the insulin of its minutes
-__device__ __forceinline__ double dopri5_mlp_pump(const KArgs<double>& a, double u)
-{
-    double q_basal = u, q_bolus = 0.0;
-    if (!(a.flags & T1D_BATCH_NO_PUMP)) {
-        q_basal = pump_quantise(u, a.pump.inc_basal, a.pump.min_basal, a.pump.max_basal);
-        q_bolus = pump_quantise(0.0, a.pump.inc_bolus, a.pump.min_bolus, a.pump.max_bolus);
-    }
-    return q_basal + q_bolus;
-}
-
 __global__ __launch_bounds__(kBlock, 1) void dopri5_mlp_rollout_kernel(const KArgs<double> a, const MlpArgs<double> c,
                                                                        const double* __restrict__ raw, double* h_carry, int32_t* nfev)
 {
-    typedef RollColdT<64> Cold;
-    __shared__ double lds[kRawPars * kMaxPatients];
-    for (int j = threadIdx.x; j < kRawPars * kMaxPatients; j += blockDim.x) lds[j] = raw[j];
-    __syncthreads();
-    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-    __builtin_assume(i < (1u << 28));          // host guarantees n <= 2^28: i * sizeof(T) fits a 32-bit voffset
-    if ((int64_t)i >= a.n) return;             // n is a multiple of 64: whole waves leave
-    // the wave's piece of dynamic LDS: Cold's doubles, Cold's ints, the columns
-    unsigned char* const piece = t1d_dyn_lds + (threadIdx.x >> 6) * (kRollColdWaveBytes + c.cols * 64 * (int)sizeof(double));
-    const unsigned lane = threadIdx.x & 63u;
-    const Cold cold{(double*)piece + lane, (int*)(piece + Cold::NF * 64 * sizeof(double)) + lane};
-    double* const col = (double*)(piece + kRollColdWaveBytes) + lane;
-    const int H = c.history;
-    double* const buf = col + 2 * H * 64;
-    const uint32_t meta = at(a.meta, i);
-    const uint32_t pid = T1D_META_PID(meta);
-    Env<double> e;
-    load_env(a, i, meta, e);
-    const ParsRaw p{lds, (int)pid};
-    NoDerivedPars nop;
-    const double div = double(a.minutes);
-    col[0] = at(a.cgm, i);                                      // CGM[0] is the observation the first step starts from
-    for (int k = 1; k < H; ++k) col[k * 64] = at(rowv(c.cgm_hist, a.n, k), i);
-    for (int k = 0; k < H; ++k) col[(H + k) * 64] = at(rowv(c.ins_hist, a.n, k), i);
-    double hc = at(h_carry, i), noise = 0.0, insulin = 0.0, d_mg = 0.0;
-    StepOut<double> o{0.0, 0.0, 0.0, 0.0};
-    Dopri5Run r{};
-    int nf = 0, m = 0, s = 0;
-    bool due = false, failed = false, boundary = true, fresh = true;
-    cold.save(e, o, noise, hc);
-    for (;;) {
-        if (boundary) {
-            cold.load(e, o, noise, hc);
-            if (!fresh) {
-                e.t += 1;
-                const double gsub = e.x[12] / p(T1D_P_VG);                                    // t1dpatient.py:217-218
-                const double cgm = measure_apply(a, e, gsub, noise, due);                     // env.py:62
-                o.bg += gsub / div; o.cgm += cgm / div;                                       // env.py:80-81
-                if (++m == a.minutes) {                  // the step is complete: what t1d_step_dopri5 leaves, then the roll-out's own
-                    const double rp = e.prev_risk;
-                    write_outputs<0>(a, i, e, o, rp);
-                    const int64_t tr = (c.trace_row + s) * a.n + i;
-                    if (c.bg_trace) c.bg_trace[tr] = o.bg;
-                    if (c.cgm_trace) c.cgm_trace[tr] = o.cgm;
-                    if (c.cho_trace) c.cho_trace[tr] = o.meal;
-                    if (c.ins_trace) c.ins_trace[tr] = o.ins;
-                    at(c.prev_meal, i) = o.meal;
-                    if (c.sum_risk) { double l, h, rk; risk_index1<0>(o.bg, l, h, rk); at(c.sum_risk, i) = at(c.sum_risk, i) + rk; }
-                    if (c.min_bg) { const double v = at(c.min_bg, i); at(c.min_bg, i) = o.bg < v ? o.bg : v; }
-                    if (c.max_bg) { const double v = at(c.max_bg, i); at(c.max_bg, i) = o.bg > v ? o.bg : v; }
-                    if (c.n_low) at(c.n_low, i) = at(c.n_low, i) + (o.bg < 70.0);
-                    if (c.n_high) at(c.n_high, i) = at(c.n_high, i) + (o.bg > 180.0);
-                    m = 0; ++s;
-                    const int q = s % H, head = q ? H - q : 0;  // the oldest row becomes the newest
-                    col[head * 64] = o.cgm; col[(H + head) * 64] = o.ins;
-                }
-            }
-            if (s == c.n_steps) break;
-            if (m == 0) {                                // a step opens: the network on the windows, then the pump
-                const int q = s % H, head = q ? H - q : 0;
-                const int start = c.start_minute ? (int)at(c.start_minute, i) : 0;
-                const double prev_meal = at(c.prev_meal, i);
-                const double u = mlp_action(c, mlp_wave_weights(c, i), col, buf, head, prev_meal, start + e.t);
-                if (c.act_trace) c.act_trace[(c.trace_row + s) * a.n + i] = u;
-                double q_basal = u, q_bolus = 0.0;       // as step_body with a bolus given: env.py:51-52
-                if (!(a.flags & T1D_BATCH_NO_PUMP)) {
-                    q_basal = pump_quantise(u, a.pump.inc_basal, a.pump.min_basal, a.pump.max_basal);
-                    q_bolus = pump_quantise(0.0, a.pump.inc_bolus, a.pump.min_bolus, a.pump.max_bolus);
-                }
-                insulin = q_basal + q_bolus;
-                o = StepOut<double>{0.0, 0.0, 0.0, 0.0};
-            }
-            const double meal = meal_lookup(a, i, e);                                         // env.py:50
-            noise = measure_noise<true>(a, i, e, due);
-            const MinuteIn<double> u = eat_minute<0, double>(nop, e.x, meal, insulin, e.planned, e.lq, e.lf, e.eating);
-            d_mg = u.d_mg;
-            o.meal += meal / div; o.ins += insulin / div;                                     // env.py:78-79
-            if (!failed) dopri5_enter(p, e.x, d_mg, insulin, e.lq, e.lf, hc, (double)e.t, r, nf);
-            cold.save(e, o, noise, hc);
-            fresh = false; boundary = false;
-        }
-        if (failed) { boundary = true; continue; }
-        const int rc = dopri5_attempt(p, e.x, d_mg, insulin, e.lq, e.lf, cold.f[Cold::HC * 64], (double)e.t + 1.0, r, nf);
-        failed = rc < 0;
-        boundary = rc != 0;
-    }
-    store_env(a, i, pid, e);
-    at(h_carry, i) = hc;
-    if (nfev) at(nfev, i) = nf;
-    if (failed) atomicOr(a.status, T1D_ST_SOLVER_FAILED);
-    const int q = s % H;
-    for (int k = 0, row = q ? H - q : 0; k < H; ++k) {         // the windows back in window order
-        at(rowv(c.cgm_hist, a.n, k), i) = col[row * 64];
-        at(rowv(c.ins_hist, a.n, k), i) = col[(H + row) * 64];
-        row = row + 1 == H ? 0 : row + 1;
-    }
+    // its own: c's windows, with their load, store and step words as lines of the loop (above: the three functions); where
+    // a step opens, the network on them, no bolus
+#define DOPRI5_WINDOWS c
+#define DOPRI5_WRITTEN_OUT
+#define DOPRI5_ACTION                                                                                                         \
+    const double u = mlp_action(c, mlp_wave_weights(c, i), col, buf, head, prev_meal, start + e.t);                            \
+    if (c.act_trace) c.act_trace[(c.trace_row + s) * a.n + i] = u;                                                             \
+    const double bolus = 0.0;
+#include "t1d_dopri5_loop.inc"
 }
 
 // ---- t1d_rollout_mlp_dopri5_bolus: the roll-out above with the meal bolus of t1d_meal_bolus (t1d_policy.hpp) -----------------
-// dopri5_mlp_rollout_kernel, solver loop and boundary block line for line, from the pieces dopri5_mlp_collect_kernel is made
-// of.  The bolus is formed where a step opens, next to mlp_action: meal_bolus -- the function of the fixed-step kernels -- on
-// the column's CGM[0] (the observation the step starts from) and the prev_meal read there, to bolus_trace, then into the q_bolus
+// The bolus is formed where a step opens, next to mlp_action: meal_bolus -- the function of the fixed-step kernels -- on the
+// column's CGM[0] (the observation the step starts from) and the prev_meal read there, to bolus_trace, then into the q_bolus
 // quantiser call that receives 0.0 above.  Like the network's words, nothing of it is in a register across dopri5_attempt.
-// A kernel of its own and not a compile-time switch inside dopri5_mlp_rollout_kernel: that kernel's text moved into a function
+// A kernel of its own and not a run-time switch inside dopri5_mlp_rollout_kernel: that kernel's text moved into a function
 // shared by two wrappers no longer compiled to the same instructions (13 987 and 14 070 against 13 879, by reference and by
 // value), and it is the one whose machine code has to stay (tools/isa_diff.py).
-__device__ __forceinline__ double dopri5_mlp_pump(const KArgs<double>& a, double u, double bolus)
-{
-    double q_basal = u, q_bolus = bolus;         // as step_body with a bolus given: env.py:51-52
-    if (!(a.flags & T1D_BATCH_NO_PUMP)) {
-        q_basal = pump_quantise(u, a.pump.inc_basal, a.pump.min_basal, a.pump.max_basal);
-        q_bolus = pump_quantise(bolus, a.pump.inc_bolus, a.pump.min_bolus, a.pump.max_bolus);
-    }
-    return q_basal + q_bolus;
-}
-
 __global__ __launch_bounds__(kBlock, 1) void dopri5_mlp_rollout_bolus_kernel(const KArgs<double> a, const MlpArgs<double> c,
                                                                              const BolusArgs<double> mb, const double* __restrict__ raw,
                                                                              double* h_carry, int32_t* nfev)
 {
-    typedef RollColdT<64> Cold;
-    __shared__ double lds[kRawPars * kMaxPatients];
-    for (int j = threadIdx.x; j < kRawPars * kMaxPatients; j += blockDim.x) lds[j] = raw[j];
-    __syncthreads();
-    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-    __builtin_assume(i < (1u << 28));          // host guarantees n <= 2^28: i * sizeof(T) fits a 32-bit voffset
-    if ((int64_t)i >= a.n) return;             // n is a multiple of 64: whole waves leave
-    const MlpLaneLds piece = dopri5_mlp_lane_lds(c);
-    const Cold cold = piece.cold;
-    double* const col = piece.col;
-    const int H = c.history;
-    double* const buf = col + 2 * H * 64;
-    const uint32_t meta = at(a.meta, i);
-    const uint32_t pid = T1D_META_PID(meta);
-    Env<double> e;
-    load_env(a, i, meta, e);
-    const ParsRaw p{lds, (int)pid};
-    NoDerivedPars nop;
-    const double div = double(a.minutes);
-    dopri5_mlp_load_windows(a, c, i, col);
-    double hc = at(h_carry, i), noise = 0.0, insulin = 0.0, d_mg = 0.0;
-    StepOut<double> o{0.0, 0.0, 0.0, 0.0};
-    Dopri5Run r{};
-    int nf = 0, m = 0, s = 0;
-    bool due = false, failed = false, boundary = true, fresh = true;
-    cold.save(e, o, noise, hc);
-    for (;;) {
-        if (boundary) {
-            cold.load(e, o, noise, hc);
-            if (!fresh) {
-                e.t += 1;
-                const double gsub = e.x[12] / p(T1D_P_VG);                                    // t1dpatient.py:217-218
-                const double cgm = measure_apply(a, e, gsub, noise, due);                     // env.py:62
-                o.bg += gsub / div; o.cgm += cgm / div;                                       // env.py:80-81
-                if (++m == a.minutes) {                  // the step is complete: what t1d_step_dopri5 leaves, then the roll-out's own
-                    const double rp = e.prev_risk;
-                    write_outputs<0>(a, i, e, o, rp);
-                    dopri5_mlp_step_words(c, i, (c.trace_row + s) * a.n + i, o);
-                    m = 0; ++s;
-                    const int q = s % H, head = q ? H - q : 0;  // the oldest row becomes the newest
-                    col[head * 64] = o.cgm; col[(H + head) * 64] = o.ins;
-                }
-            }
-            if (s == c.n_steps) break;
-            if (m == 0) {                                // a step opens: the network on the windows, the meal bolus, then the pump
-                const int q = s % H, head = q ? H - q : 0;
-                const int start = c.start_minute ? (int)at(c.start_minute, i) : 0;
-                const double prev_meal = at(c.prev_meal, i);
-                const double u = mlp_action(c, mlp_wave_weights(c, i), col, buf, head, prev_meal, start + e.t);
-                if (c.act_trace) c.act_trace[(c.trace_row + s) * a.n + i] = u;
-                const double bolus = step_bolus(mb, bolus_lane(mb, i), i, double(a.sen.st), col[head * 64], prev_meal,
-                                                (c.trace_row + s) * a.n + i);
-                insulin = dopri5_mlp_pump(a, u, bolus);
-                o = StepOut<double>{0.0, 0.0, 0.0, 0.0};
-            }
-            const double meal = meal_lookup(a, i, e);                                         // env.py:50
-            noise = measure_noise<true>(a, i, e, due);
-            const MinuteIn<double> u = eat_minute<0, double>(nop, e.x, meal, insulin, e.planned, e.lq, e.lf, e.eating);
-            d_mg = u.d_mg;
-            o.meal += meal / div; o.ins += insulin / div;                                     // env.py:78-79
-            if (!failed) dopri5_enter(p, e.x, d_mg, insulin, e.lq, e.lf, hc, (double)e.t, r, nf);
-            cold.save(e, o, noise, hc);
-            fresh = false; boundary = false;
-        }
-        if (failed) { boundary = true; continue; }
-        const int rc = dopri5_attempt(p, e.x, d_mg, insulin, e.lq, e.lf, cold.f[Cold::HC * 64], (double)e.t + 1.0, r, nf);
-        failed = rc < 0;
-        boundary = rc != 0;
-    }
-    store_env(a, i, pid, e);
-    at(h_carry, i) = hc;
-    if (nfev) at(nfev, i) = nf;
-    if (failed) atomicOr(a.status, T1D_ST_SOLVER_FAILED);
-    dopri5_mlp_store_windows(a, c, i, col, s);
+    // its own: c's windows; where a step opens, the network on them and the meal bolus
+#define DOPRI5_WINDOWS c
+#define DOPRI5_ACTION                                                                                                          \
+    const double u = mlp_action(c, mlp_wave_weights(c, i), col, buf, head, prev_meal, start + e.t);                            \
+    if (c.act_trace) c.act_trace[(c.trace_row + s) * a.n + i] = u;                                                             \
+    const double bolus = step_bolus(mb, bolus_lane(mb, i), i, double(a.sen.st), col[head * 64], prev_meal,                     \
+                                    (c.trace_row + s) * a.n + i);
+#include "t1d_dopri5_loop.inc"
 }
 
 // ---- t1d_rollout_mlp_dopri5_rel: the roll-out under a relative policy (t1d_env_output, t1d_policy.hpp) ----------------------
-// dopri5_mlp_rollout_bolus_kernel line for line, with the action formed under the lane's scale and bias and the meal bolus a
-// wave-uniform switch (mb.cr == NULL: none).  The pair is loaded in the boundary block where a step opens, next to the network:
-// like the network's words and the bolus, nothing of it is in a register across dopri5_attempt.  A kernel of its own for the
-// reason given above: the kernels that exist keep their machine code.
+// dopri5_mlp_rollout_bolus_kernel with the action formed under the lane's scale and bias and the meal bolus a wave-uniform
+// switch (mb.cr == NULL: none).  The pair is loaded in the boundary block where a step opens, next to the network: like the
+// network's words and the bolus, nothing of it is in a register across dopri5_attempt.  A kernel of its own for the reason
+// given above: the kernels that exist keep their machine code.
 __global__ __launch_bounds__(kBlock, 1) void dopri5_mlp_rollout_rel_kernel(const KArgs<double> a, const MlpArgs<double> c,
                                                                            const EnvOutArgs<double> eo, const BolusArgs<double> mb,
                                                                            const double* __restrict__ raw, double* h_carry, int32_t* nfev)
 {
-    typedef RollColdT<64> Cold;
-    __shared__ double lds[kRawPars * kMaxPatients];
-    for (int j = threadIdx.x; j < kRawPars * kMaxPatients; j += blockDim.x) lds[j] = raw[j];
-    __syncthreads();
-    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-    __builtin_assume(i < (1u << 28));          // host guarantees n <= 2^28: i * sizeof(T) fits a 32-bit voffset
-    if ((int64_t)i >= a.n) return;             // n is a multiple of 64: whole waves leave
-    const MlpLaneLds piece = dopri5_mlp_lane_lds(c);
-    const Cold cold = piece.cold;
-    double* const col = piece.col;
-    const int H = c.history;
-    double* const buf = col + 2 * H * 64;
-    const uint32_t meta = at(a.meta, i);
-    const uint32_t pid = T1D_META_PID(meta);
-    Env<double> e;
-    load_env(a, i, meta, e);
-    const ParsRaw p{lds, (int)pid};
-    NoDerivedPars nop;
-    const double div = double(a.minutes);
-    dopri5_mlp_load_windows(a, c, i, col);
-    double hc = at(h_carry, i), noise = 0.0, insulin = 0.0, d_mg = 0.0;
-    StepOut<double> o{0.0, 0.0, 0.0, 0.0};
-    Dopri5Run r{};
-    int nf = 0, m = 0, s = 0;
-    bool due = false, failed = false, boundary = true, fresh = true;
-    cold.save(e, o, noise, hc);
-    for (;;) {
-        if (boundary) {
-            cold.load(e, o, noise, hc);
-            if (!fresh) {
-                e.t += 1;
-                const double gsub = e.x[12] / p(T1D_P_VG);                                    // t1dpatient.py:217-218
-                const double cgm = measure_apply(a, e, gsub, noise, due);                     // env.py:62
-                o.bg += gsub / div; o.cgm += cgm / div;                                       // env.py:80-81
-                if (++m == a.minutes) {                  // the step is complete: what t1d_step_dopri5 leaves, then the roll-out's own
-                    const double rp = e.prev_risk;
-                    write_outputs<0>(a, i, e, o, rp);
-                    dopri5_mlp_step_words(c, i, (c.trace_row + s) * a.n + i, o);
-                    m = 0; ++s;
-                    const int q = s % H, head = q ? H - q : 0;  // the oldest row becomes the newest
-                    col[head * 64] = o.cgm; col[(H + head) * 64] = o.ins;
-                }
-            }
-            if (s == c.n_steps) break;
-            if (m == 0) {                                // a step opens: the network under the lane's pair, the meal bolus, the pump
-                const int q = s % H, head = q ? H - q : 0;
-                const int start = c.start_minute ? (int)at(c.start_minute, i) : 0;
-                const double prev_meal = at(c.prev_meal, i);
-                const double u = mlp_action(c, mlp_wave_weights(c, i), col, buf, head, prev_meal, start + e.t, env_out_lane(eo, i));
-                if (c.act_trace) c.act_trace[(c.trace_row + s) * a.n + i] = u;
-                double bolus = 0.0;
-                if (mb.cr)                               // wave-uniform
-                    bolus = step_bolus(mb, bolus_lane(mb, i), i, double(a.sen.st), col[head * 64], prev_meal, (c.trace_row + s) * a.n + i);
-                insulin = dopri5_mlp_pump(a, u, bolus);
-                o = StepOut<double>{0.0, 0.0, 0.0, 0.0};
-            }
-            const double meal = meal_lookup(a, i, e);                                         // env.py:50
-            noise = measure_noise<true>(a, i, e, due);
-            const MinuteIn<double> u = eat_minute<0, double>(nop, e.x, meal, insulin, e.planned, e.lq, e.lf, e.eating);
-            d_mg = u.d_mg;
-            o.meal += meal / div; o.ins += insulin / div;                                     // env.py:78-79
-            if (!failed) dopri5_enter(p, e.x, d_mg, insulin, e.lq, e.lf, hc, (double)e.t, r, nf);
-            cold.save(e, o, noise, hc);
-            fresh = false; boundary = false;
-        }
-        if (failed) { boundary = true; continue; }
-        const int rc = dopri5_attempt(p, e.x, d_mg, insulin, e.lq, e.lf, cold.f[Cold::HC * 64], (double)e.t + 1.0, r, nf);
-        failed = rc < 0;
-        boundary = rc != 0;
-    }
-    store_env(a, i, pid, e);
-    at(h_carry, i) = hc;
-    if (nfev) at(nfev, i) = nf;
-    if (failed) atomicOr(a.status, T1D_ST_SOLVER_FAILED);
-    dopri5_mlp_store_windows(a, c, i, col, s);
+    // its own: c's windows; where a step opens, the network under the lane's pair and, where there is one, the meal bolus
+#define DOPRI5_WINDOWS c
+#define DOPRI5_ACTION                                                                                                          \
+    const double u = mlp_action(c, mlp_wave_weights(c, i), col, buf, head, prev_meal, start + e.t, env_out_lane(eo, i));       \
+    if (c.act_trace) c.act_trace[(c.trace_row + s) * a.n + i] = u;                                                             \
+    double bolus = 0.0;                                                                                                        \
+    if (mb.cr) /* wave-uniform */                                                                                              \
+        bolus = step_bolus(mb, bolus_lane(mb, i), i, double(a.sen.st), col[head * 64], prev_meal, (c.trace_row + s) * a.n + i);
+#include "t1d_dopri5_loop.inc"
 }
 
 // ---- trajectories for a policy-gradient trainer in the exact mode (t1d_collect_mlp_dopri5) ------------------------------
-// dopri5_mlp_rollout_kernel with the collector's work (mlp_collect_body, t1d_policy.hpp) in the boundary block; solver
-// loop, Cold words, columns, per-lane ring head and weights are that kernel's, line for line.  A kernel of its own: the
-// roll-out keeps its registers and its arguments.
+// dopri5_mlp_rollout_kernel with the collector's work (mlp_collect_body, t1d_policy.hpp) in the boundary block.  A kernel of
+// its own: the roll-out keeps its registers and its arguments.
 //   a step opens    mlp_action in its three parts: the features (to feat_trace), the layers, then the draw -- keyed by the
 //                   env's global id, its episode counter and its clock, as in mlp_collect_body -- and sigma on the last
 //                   layer's output, the output function, the pump.  eps_trace is written here: the step that uses the
 //                   draw is the row it describes, and nothing of it has to wait for the step's end.
 //   a step closes   reward and done as write_outputs forms them, to their trace rows; ep_return / ep_length advance.
-//   done, restart   the lane writes its state as the end of the launch would, runs collect_restart -- t1d_restart_done for
-//                   this env alone, on the words in memory -- loads the new episode, fills its window rows with the new
-//                   first observation, and starts again with prev_meal = 0, a carried step of 0 (the first minute probes)
-//                   and a working solver.  The ring head stays where the lane's step counter puts it: every row holds the
-//                   same word.  start_minute, the episode counter and prev_meal are read from memory where a step opens, so
-//                   the new ones are picked up there; the Cold words are saved again at the end of the boundary block.
-//                   The other lanes of the wave are inactive meanwhile and go on with their step attempts afterwards.
+//   done, restart   the loop's DOPRI5_COLLECT part (t1d_dopri5_loop.inc).
 // Nothing of the policy, the draw or the restart is in a register across dopri5_attempt.
+// DOPRI5_MLP_COLLECT_ACTION: the action of this kernel and of dopri5_mlp_collect_limit_kernel.
+#define DOPRI5_MLP_COLLECT_ACTION                                                                                              \
+    typedef const __attribute__((address_space(4))) double* WPtr;                                                              \
+    const unsigned wave0 = __builtin_amdgcn_readfirstlane(i & ~63u);                                                           \
+    const unsigned pol = wave0 / c.envs_per_policy;                                                                            \
+    const WPtr w = (WPtr)(c.params + (size_t)pol * (size_t)c.n_params);                                                        \
+    mlp_features(c, col, buf, head, prev_meal, start + e.t);                                                                   \
+    if (g.feat_trace)                                                                                                          \
+        for (int j = 0; j < F; ++j) g.feat_trace[((c.trace_row + s) * F + j) * a.n + i] = buf[j * 64];                         \
+    double y = mlp_layers(c, w, buf, F);                                                                                       \
+    double eps = 0.0;                                                                                                          \
+    if (g.sigma) { /* wave-uniform */                                                                                          \
+        const uint32_t ep = a.episode ? at(a.episode, i) : 0u;                                                                 \
+        eps = (double)philox_pair(g.explore_seed, (uint64_t)(a.env_offset + i), ep, (uint32_t)e.t).x;                          \
+        y = fma((double)((WPtr)g.sigma)[pol], eps, y);                                                                         \
+    }                                                                                                                          \
+    if (g.eps_trace) g.eps_trace[(c.trace_row + s) * a.n + i] = eps;                                                           \
+    const double u = mlp_output(c, y);                                                                                         \
+    if (c.act_trace) c.act_trace[(c.trace_row + s) * a.n + i] = u;                                                             \
+    const double bolus = 0.0;
 __global__ __launch_bounds__(kBlock, 1) void dopri5_mlp_collect_kernel(const KArgs<double> a, const MlpArgs<double> c,
                                                                        const CollectArgs<double> g, const RestartArgs<double> ra,
                                                                        const double* __restrict__ raw, double* h_carry, int32_t* nfev)
 {
-    typedef RollColdT<64> Cold;
-    typedef const __attribute__((address_space(4))) double* WPtr;
-    __shared__ double lds[kRawPars * kMaxPatients];
-    for (int j = threadIdx.x; j < kRawPars * kMaxPatients; j += blockDim.x) lds[j] = raw[j];
-    __syncthreads();
-    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-    __builtin_assume(i < (1u << 28));          // host guarantees n <= 2^28: i * sizeof(T) fits a 32-bit voffset
-    if ((int64_t)i >= a.n) return;             // n is a multiple of 64: whole waves leave
-    const MlpLaneLds piece = dopri5_mlp_lane_lds(c);
-    const Cold cold = piece.cold;
-    double* const col = piece.col;
-    const int H = c.history, F = 2 * H + 3;
-    double* const buf = col + 2 * H * 64;
-    const uint32_t meta = at(a.meta, i);
-    const uint32_t pid = T1D_META_PID(meta);
-    Env<double> e;
-    load_env(a, i, meta, e);
-    const ParsRaw p{lds, (int)pid};
-    NoDerivedPars nop;
-    const double div = double(a.minutes);
-    dopri5_mlp_load_windows(a, c, i, col);
-    double hc = at(h_carry, i), noise = 0.0, insulin = 0.0, d_mg = 0.0;
-    StepOut<double> o{0.0, 0.0, 0.0, 0.0};
-    Dopri5Run r{};
-    int nf = 0, m = 0, s = 0;
-    bool due = false, failed = false, boundary = true, fresh = true;
-    bool stored = false;                        // the last step ended the episode: the state in memory is the new episode's
-    cold.save(e, o, noise, hc);
-    for (;;) {
-        if (boundary) {
-            cold.load(e, o, noise, hc);
-            if (!fresh) {
-                e.t += 1;
-                const double gsub = e.x[12] / p(T1D_P_VG);                                    // t1dpatient.py:217-218
-                const double cgm = measure_apply(a, e, gsub, noise, due);                     // env.py:62
-                o.bg += gsub / div; o.cgm += cgm / div;                                       // env.py:80-81
-                if (++m == a.minutes) {                  // the step is complete: what t1d_step_dopri5 leaves, then the collector's own
-                    const double rp = e.prev_risk;
-                    write_outputs<0>(a, i, e, o, rp);
-                    const double reward = rp - e.prev_risk;     // the word write_outputs stored in batch.reward
-                    const bool fin = o.bg < 70.0 || o.bg > 350.0;
-                    const int64_t tr = (c.trace_row + s) * a.n + i;
-                    if (g.reward_trace) g.reward_trace[tr] = reward;
-                    if (g.done_trace) g.done_trace[tr] = fin ? 1 : 0;
-                    dopri5_mlp_step_words(c, i, tr, o);
-                    m = 0; ++s;
-                    const int q = s % H, head = q ? H - q : 0;  // the oldest row becomes the newest
-                    col[head * 64] = o.cgm; col[(H + head) * 64] = o.ins;
-                    if (g.on_done) {
-                        if (fin) {
-                            // the finished step is in memory (write_outputs); the state follows, and the restart works on those words
-                            store_env(a, i, pid, e);
-                            if (failed) atomicOr(a.status, T1D_ST_SOLVER_FAILED);
-                            collect_restart<double>(a, ra, g.slots, i);
-                            load_env(a, i, at(a.meta, i), e);
-                            const double first = at(a.cgm, i);  // the new episode's first observation
-                            for (int k = 0; k < H; ++k) { col[k * 64] = first; col[(H + k) * 64] = 0.0; }
-                            at(c.prev_meal, i) = 0.0;
-                            hc = 0.0;                           // T1DPatient.reset builds the solver afresh: the first minute probes
-                            failed = false;
-                            stored = s == c.n_steps;
-                        } else if (ra.ep_return) {              // restart_front's accumulators for an env that goes on
-                            const double sum = at(ra.ep_return, i) + reward;
-                            const int len = at(ra.ep_length, i) + 1;
-                            at(ra.ep_return, i) = sum; at(ra.ep_length, i) = len;
-                        }
-                    }
-                }
-            }
-            if (s == c.n_steps) break;
-            if (m == 0) {                                // a step opens: features, layers, the draw, the output function, the pump
-                const int q = s % H, head = q ? H - q : 0;
-                const int start = c.start_minute ? (int)at(c.start_minute, i) : 0;
-                const double prev_meal = at(c.prev_meal, i);
-                const unsigned wave0 = __builtin_amdgcn_readfirstlane(i & ~63u);
-                const unsigned pol = wave0 / c.envs_per_policy;
-                const WPtr w = (WPtr)(c.params + (size_t)pol * (size_t)c.n_params);
-                mlp_features(c, col, buf, head, prev_meal, start + e.t);
-                if (g.feat_trace)
-                    for (int j = 0; j < F; ++j) g.feat_trace[((c.trace_row + s) * F + j) * a.n + i] = buf[j * 64];
-                double y = mlp_layers(c, w, buf, F);
-                double eps = 0.0;
-                if (g.sigma) {                           // wave-uniform
-                    const uint32_t ep = a.episode ? at(a.episode, i) : 0u;
-                    eps = (double)philox_pair(g.explore_seed, (uint64_t)(a.env_offset + i), ep, (uint32_t)e.t).x;
-                    y = fma((double)((WPtr)g.sigma)[pol], eps, y);
-                }
-                if (g.eps_trace) g.eps_trace[(c.trace_row + s) * a.n + i] = eps;
-                const double u = mlp_output(c, y);
-                if (c.act_trace) c.act_trace[(c.trace_row + s) * a.n + i] = u;
-                insulin = dopri5_mlp_pump(a, u);
-                o = StepOut<double>{0.0, 0.0, 0.0, 0.0};
-            }
-            const double meal = meal_lookup(a, i, e);                                         // env.py:50
-            noise = measure_noise<true>(a, i, e, due);
-            const MinuteIn<double> u = eat_minute<0, double>(nop, e.x, meal, insulin, e.planned, e.lq, e.lf, e.eating);
-            d_mg = u.d_mg;
-            o.meal += meal / div; o.ins += insulin / div;                                     // env.py:78-79
-            if (!failed) dopri5_enter(p, e.x, d_mg, insulin, e.lq, e.lf, hc, (double)e.t, r, nf);
-            cold.save(e, o, noise, hc);
-            fresh = false; boundary = false;
-        }
-        if (failed) { boundary = true; continue; }
-        const int rc = dopri5_attempt(p, e.x, d_mg, insulin, e.lq, e.lf, cold.f[Cold::HC * 64], (double)e.t + 1.0, r, nf);
-        failed = rc < 0;
-        boundary = rc != 0;
-    }
-    if (!stored) store_env(a, i, pid, e);
-    at(h_carry, i) = hc;
-    if (nfev) at(nfev, i) = nf;
-    if (failed) atomicOr(a.status, T1D_ST_SOLVER_FAILED);
-    dopri5_mlp_store_windows(a, c, i, col, s);
+    // its own: c's windows, the collector's frame; where a step opens, features, layers, the draw, the output function
+#define DOPRI5_WINDOWS c
+#define DOPRI5_COLLECT
+#define DOPRI5_ACTION DOPRI5_MLP_COLLECT_ACTION
+#include "t1d_dopri5_loop.inc"
 }
 
 // ---- trajectories under the two hand-written controllers in the exact mode (t1d_collect_pid_dopri5 / t1d_collect_bb_dopri5) ----
 // dopri5_mlp_collect_kernel with dopri5_controller where the network stands, and the feature bookkeeping of ctrl_collect_body
-// (t1d_policy.hpp): solver loop, Cold words and the boundary block that finishes a minute are dopri5_rollout_kernel's, line
-// for line; the wave's piece of dynamic LDS is Cold's words and cols = 4 H + 3 columns -- the two windows as a ring with a
-// per-lane head, then the F = 2 H + 3 features; there are no activation columns.
+// (t1d_policy.hpp).  The wave's piece of dynamic LDS is Cold's words and cols = 4 H + 3 columns -- the two windows as a ring
+// with a per-lane head, then the F = 2 H + 3 features; there are no activation columns.
 //   a step opens    the features a network would have been given (mlp_features, to feat_trace), then dopri5_controller on the
 //                   last observation with its state in memory -- the word t1d_rollout_pid_dopri5 / t1d_rollout_bb_dopri5
 //                   computes -- then basal + bolus to the policy's action trace, then the pump on each.
@@ -1064,146 +580,40 @@ __global__ __launch_bounds__(kBlock, 1) void dopri5_mlp_collect_kernel(const KAr
 // that did not restart came back with other state words and garbage in h_carry once another lane of their wave had made the
 // call (profiles/collect/README.md).  Do not move the restart out of line without the restart test of
 // tests/test_gpu_collect_ctrl_dopri5.py.
+// DOPRI5_CTRL_COLLECT_ACTION: the action of this kernel and of dopri5_ctrl_collect_limit_kernel.  What the controller asked
+// for goes to the action trace before the pump: one addition, contraction off.
+#define DOPRI5_CTRL_COLLECT_ACTION                                                                                             \
+    mlp_features(f, col, buf, head, prev_meal, start + e.t);                                                                   \
+    if (g.feat_trace)                                                                                                          \
+        for (int j = 0; j < F; ++j) g.feat_trace[((c.trace_row + s) * F + j) * a.n + i] = buf[j * 64];                         \
+    double u, bolus;                                                                                                           \
+    dopri5_controller(c, i, at(a.cgm, i), st, u, bolus);                                                                       \
+    if (f.act_trace) {                                                                                                         \
+        _Pragma("clang fp contract(off)")                                                                                      \
+        f.act_trace[(c.trace_row + s) * a.n + i] = u + bolus;                                                                  \
+    }
 __global__ __launch_bounds__(kBlock, 1) void dopri5_ctrl_collect_kernel(const KArgs<double> a, const PidArgs<double> c,
                                                                         const MlpArgs<double> f, const CollectArgs<double> g,
                                                                         const RestartArgs<double> ra, const double* __restrict__ raw,
                                                                         double* h_carry, int32_t* nfev)
 {
-    typedef RollColdT<64> Cold;
-    __shared__ double lds[kRawPars * kMaxPatients];
-    for (int j = threadIdx.x; j < kRawPars * kMaxPatients; j += blockDim.x) lds[j] = raw[j];
-    __syncthreads();
-    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-    __builtin_assume(i < (1u << 28));          // host guarantees n <= 2^28: i * sizeof(T) fits a 32-bit voffset
-    if ((int64_t)i >= a.n) return;             // any n: the lanes past the end leave, the others never look at them
-    const MlpLaneLds piece = dopri5_mlp_lane_lds(f);
-    const Cold cold = piece.cold;
-    double* const col = piece.col;
-    const int H = f.history, F = 2 * H + 3;
-    double* const buf = col + 2 * H * 64;
-    const uint32_t meta = at(a.meta, i);
-    const uint32_t pid = T1D_META_PID(meta);
-    Env<double> e;
-    load_env(a, i, meta, e);
-    const ParsRaw p{lds, (int)pid};
-    NoDerivedPars nop;
-    const double div = double(a.minutes), st = double(a.sen.st);
-    dopri5_mlp_load_windows(a, f, i, col);
-    double hc = at(h_carry, i), noise = 0.0, insulin = 0.0, d_mg = 0.0;
-    StepOut<double> o{0.0, 0.0, 0.0, 0.0};
-    Dopri5Run r{};
-    int nf = 0, m = 0, s = 0;
-    bool due = false, failed = false, boundary = true, fresh = true;
-    bool stored = false;                        // the last step ended the episode: the state in memory is the new episode's
-    cold.save(e, o, noise, hc);
-    for (;;) {
-        if (boundary) {
-            cold.load(e, o, noise, hc);
-            if (!fresh) {
-                e.t += 1;
-                const double gsub = e.x[12] / p(T1D_P_VG);                                    // t1dpatient.py:217-218
-                const double cgm = measure_apply(a, e, gsub, noise, due);                     // env.py:62
-                o.bg += gsub / div; o.cgm += cgm / div;                                       // env.py:80-81
-                if (++m == a.minutes) {                  // the step is complete: what t1d_step_dopri5 leaves, then the collector's own
-                    const double rp = e.prev_risk;
-                    write_outputs<0>(a, i, e, o, rp);
-                    const double reward = rp - e.prev_risk;     // the word write_outputs stored in batch.reward
-                    const bool fin = o.bg < 70.0 || o.bg > 350.0;
-                    const int64_t tr = (c.trace_row + s) * a.n + i;
-                    if (g.reward_trace) g.reward_trace[tr] = reward;
-                    if (g.done_trace) g.done_trace[tr] = fin ? 1 : 0;
-                    if (c.bg_trace) c.bg_trace[tr] = o.bg;
-                    if (c.cgm_trace) c.cgm_trace[tr] = o.cgm;
-                    if (c.cho_trace) c.cho_trace[tr] = o.meal;
-                    if (c.ins_trace) c.ins_trace[tr] = o.ins;
-                    if (c.kind == 1) at(c.bb_prev_meal, i) = o.meal;
-                    at(f.prev_meal, i) = o.meal;
-                    if (c.sum_risk) { double l, h, rk; risk_index1<0>(o.bg, l, h, rk); at(c.sum_risk, i) = at(c.sum_risk, i) + rk; }
-                    if (c.min_bg) { const double v = at(c.min_bg, i); at(c.min_bg, i) = o.bg < v ? o.bg : v; }
-                    if (c.max_bg) { const double v = at(c.max_bg, i); at(c.max_bg, i) = o.bg > v ? o.bg : v; }
-                    if (c.n_low) at(c.n_low, i) = at(c.n_low, i) + (o.bg < 70.0);
-                    if (c.n_high) at(c.n_high, i) = at(c.n_high, i) + (o.bg > 180.0);
-                    m = 0; ++s;
-                    const int q = s % H, head = q ? H - q : 0;  // the oldest row becomes the newest
-                    col[head * 64] = o.cgm; col[(H + head) * 64] = o.ins;
-                    if (g.on_done) {
-                        if (fin) {
-                            // the finished step is in memory (write_outputs); the state follows, and the restart works on those words
-                            store_env(a, i, pid, e);
-                            if (failed) atomicOr(a.status, T1D_ST_SOLVER_FAILED);
-                            collect_restart<double>(a, ra, g.slots, i);
-                            load_env(a, i, at(a.meta, i), e);
-                            const double first = at(a.cgm, i);  // the new episode's first observation
-                            for (int k = 0; k < H; ++k) { col[k * 64] = first; col[(H + k) * 64] = 0.0; }
-                            at(f.prev_meal, i) = 0.0;
-                            if (c.kind == 1) at(c.bb_prev_meal, i) = 0.0;                     // BBController.reset
-                            else { at(c.integ, i) = 0.0; at(c.prev, i) = 0.0; }               // PIDController.reset
-                            hc = 0.0;                           // T1DPatient.reset builds the solver afresh: the first minute probes
-                            failed = false;
-                            stored = s == c.n_steps;
-                        } else if (ra.ep_return) {              // restart_front's accumulators for an env that goes on
-                            const double sum = at(ra.ep_return, i) + reward;
-                            const int len = at(ra.ep_length, i) + 1;
-                            at(ra.ep_return, i) = sum; at(ra.ep_length, i) = len;
-                        }
-                    }
-                }
-            }
-            if (s == c.n_steps) break;
-            if (m == 0) {                                // a step opens: features, the controller on the last observation, the pump
-                const int q = s % H, head = q ? H - q : 0;
-                const int start = f.start_minute ? (int)at(f.start_minute, i) : 0;
-                const double prev_meal = at(f.prev_meal, i);
-                mlp_features(f, col, buf, head, prev_meal, start + e.t);
-                if (g.feat_trace)
-                    for (int j = 0; j < F; ++j) g.feat_trace[((c.trace_row + s) * F + j) * a.n + i] = buf[j * 64];
-                double u, bolus;
-                dopri5_controller(c, i, at(a.cgm, i), st, u, bolus);
-                if (f.act_trace) {                       // what the controller asked for, before the pump: one addition
-#pragma clang fp contract(off)
-                    f.act_trace[(c.trace_row + s) * a.n + i] = u + bolus;
-                }
-                double q_basal = u, q_bolus = bolus;     // as step_body with a bolus given: env.py:51-52
-                if (!(a.flags & T1D_BATCH_NO_PUMP)) {
-                    q_basal = pump_quantise(u, a.pump.inc_basal, a.pump.min_basal, a.pump.max_basal);
-                    q_bolus = pump_quantise(bolus, a.pump.inc_bolus, a.pump.min_bolus, a.pump.max_bolus);
-                }
-                insulin = q_basal + q_bolus;
-                o = StepOut<double>{0.0, 0.0, 0.0, 0.0};
-            }
-            const double meal = meal_lookup(a, i, e);                                         // env.py:50
-            noise = measure_noise<true>(a, i, e, due);
-            const MinuteIn<double> u = eat_minute<0, double>(nop, e.x, meal, insulin, e.planned, e.lq, e.lf, e.eating);
-            d_mg = u.d_mg;
-            o.meal += meal / div; o.ins += insulin / div;                                     // env.py:78-79
-            if (!failed) dopri5_enter(p, e.x, d_mg, insulin, e.lq, e.lf, hc, (double)e.t, r, nf);
-            cold.save(e, o, noise, hc);
-            fresh = false; boundary = false;
-        }
-        if (failed) { boundary = true; continue; }
-        const int rc = dopri5_attempt(p, e.x, d_mg, insulin, e.lq, e.lf, cold.f[Cold::HC * 64], (double)e.t + 1.0, r, nf);
-        failed = rc < 0;
-        boundary = rc != 0;
-    }
-    if (!stored) store_env(a, i, pid, e);
-    at(h_carry, i) = hc;
-    if (nfev) at(nfev, i) = nf;
-    if (failed) atomicOr(a.status, T1D_ST_SOLVER_FAILED);
-    dopri5_mlp_store_windows(a, f, i, col, s);
+    // its own: f's windows, PidArgs' words, the collector's frame; where a step opens, the features, then the controller
+#define DOPRI5_STATE
+#define DOPRI5_BB
+#define DOPRI5_WINDOWS f
+#define DOPRI5_COLLECT
+#define DOPRI5_ACTION DOPRI5_CTRL_COLLECT_ACTION
+#include "t1d_dopri5_loop.inc"
 }
 
 // ---- the two collectors above with episodes cut at a time limit (t1d_collect_mlp_dopri5_limit, t1d_collect_pid_dopri5_limit,
 // t1d_collect_bb_dopri5_limit; LimitArgs, t1d_policy.hpp) ------------------------------------------------------------------
-// dopri5_mlp_collect_kernel and dopri5_ctrl_collect_kernel, line for line, with a LimitArgs behind their arguments.  Written out
-// beside them and not shared with them through a template flag: the two kernels above keep their text, hence their registers
-// and their instruction streams (a change to one of them is a change to the matching lines here).  What differs sits in the
-// boundary block, where a step closes:
+// dopri5_mlp_collect_kernel and dopri5_ctrl_collect_kernel with a LimitArgs behind their arguments.  Kernels of their own and
+// not a run-time switch in those two: the two kernels above keep their registers and their instruction streams.  What differs
+// is the loop's DOPRI5_LIMIT part, in the boundary block, where a step closes:
 //   cut             !fin and the env's clock e.t has reached max_minutes; to cut_trace's row of the step.  Termination wins.
-//   a cut env       in the restart branch, before anything of it goes to memory: its cut features -- mlp_features on the shifted
-//                   windows (the head the block has just computed), the step's meal (the word prev_meal has just been given) and
-//                   the clock start_minute + e.t, what t1d_mlp_features would return; buf is free between two steps -- to
-//                   cut_feat.  Then the restart of a finished env, with collect_restart_masked (its done byte is 0) where
-//                   collect_restart stands.
+//   a cut env       in the restart branch, before anything of it goes to memory: its cut features to cut_feat.  Then the restart
+//                   of a finished env, with collect_restart_masked (its done byte is 0) where collect_restart stands.
 // The restart stays inlined (the comment above dopri5_ctrl_collect_kernel).  Of the limit only max_minutes, a kernel argument, is
 // looked at outside the cut branch, and nothing of it is in a register across dopri5_attempt.
 __global__ __launch_bounds__(kBlock, 1) void dopri5_mlp_collect_limit_kernel(const KArgs<double> a, const MlpArgs<double> c,
@@ -1211,125 +621,11 @@ __global__ __launch_bounds__(kBlock, 1) void dopri5_mlp_collect_limit_kernel(con
                                                                              const LimitArgs<double> lim, const double* __restrict__ raw,
                                                                              double* h_carry, int32_t* nfev)
 {
-    typedef RollColdT<64> Cold;
-    typedef const __attribute__((address_space(4))) double* WPtr;
-    __shared__ double lds[kRawPars * kMaxPatients];
-    for (int j = threadIdx.x; j < kRawPars * kMaxPatients; j += blockDim.x) lds[j] = raw[j];
-    __syncthreads();
-    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-    __builtin_assume(i < (1u << 28));          // host guarantees n <= 2^28: i * sizeof(T) fits a 32-bit voffset
-    if ((int64_t)i >= a.n) return;             // n is a multiple of 64: whole waves leave
-    const MlpLaneLds piece = dopri5_mlp_lane_lds(c);
-    const Cold cold = piece.cold;
-    double* const col = piece.col;
-    const int H = c.history, F = 2 * H + 3;
-    double* const buf = col + 2 * H * 64;
-    const uint32_t meta = at(a.meta, i);
-    const uint32_t pid = T1D_META_PID(meta);
-    Env<double> e;
-    load_env(a, i, meta, e);
-    const ParsRaw p{lds, (int)pid};
-    NoDerivedPars nop;
-    const double div = double(a.minutes);
-    dopri5_mlp_load_windows(a, c, i, col);
-    double hc = at(h_carry, i), noise = 0.0, insulin = 0.0, d_mg = 0.0;
-    StepOut<double> o{0.0, 0.0, 0.0, 0.0};
-    Dopri5Run r{};
-    int nf = 0, m = 0, s = 0;
-    bool due = false, failed = false, boundary = true, fresh = true;
-    bool stored = false;                        // the last step ended the episode: the state in memory is the new episode's
-    cold.save(e, o, noise, hc);
-    for (;;) {
-        if (boundary) {
-            cold.load(e, o, noise, hc);
-            if (!fresh) {
-                e.t += 1;
-                const double gsub = e.x[12] / p(T1D_P_VG);                                    // t1dpatient.py:217-218
-                const double cgm = measure_apply(a, e, gsub, noise, due);                     // env.py:62
-                o.bg += gsub / div; o.cgm += cgm / div;                                       // env.py:80-81
-                if (++m == a.minutes) {                  // the step is complete: what t1d_step_dopri5 leaves, then the collector's own
-                    const double rp = e.prev_risk;
-                    write_outputs<0>(a, i, e, o, rp);
-                    const double reward = rp - e.prev_risk;     // the word write_outputs stored in batch.reward
-                    const bool fin = o.bg < 70.0 || o.bg > 350.0;
-                    const bool cut = !fin && e.t >= lim.max_minutes;    // the time limit ends the episode here (never a finished one)
-                    const int64_t tr = (c.trace_row + s) * a.n + i;
-                    if (g.reward_trace) g.reward_trace[tr] = reward;
-                    if (g.done_trace) g.done_trace[tr] = fin ? 1 : 0;
-                    if (lim.cut_trace) lim.cut_trace[tr] = cut ? 1 : 0;
-                    dopri5_mlp_step_words(c, i, tr, o);
-                    m = 0; ++s;
-                    const int q = s % H, head = q ? H - q : 0;  // the oldest row becomes the newest
-                    col[head * 64] = o.cgm; col[(H + head) * 64] = o.ins;
-                    if (g.on_done) {
-                        if (fin || cut) {
-                            if (cut && lim.cut_feat) {          // the features of the state the cut episode ended in
-                                const int start = c.start_minute ? (int)at(c.start_minute, i) : 0;
-                                mlp_features(c, col, buf, head, o.meal, start + e.t);
-                                for (int j = 0; j < F; ++j) at(rowv(lim.cut_feat, a.n, j), i) = buf[j * 64];
-                            }
-                            // the finished step is in memory (write_outputs); the state follows, and the restart works on those words
-                            store_env(a, i, pid, e);
-                            if (failed) atomicOr(a.status, T1D_ST_SOLVER_FAILED);
-                            collect_restart_masked<double>(a, ra, g.slots, i);          // a cut env's done is 0
-                            load_env(a, i, at(a.meta, i), e);
-                            const double first = at(a.cgm, i);  // the new episode's first observation
-                            for (int k = 0; k < H; ++k) { col[k * 64] = first; col[(H + k) * 64] = 0.0; }
-                            at(c.prev_meal, i) = 0.0;
-                            hc = 0.0;                           // T1DPatient.reset builds the solver afresh: the first minute probes
-                            failed = false;
-                            stored = s == c.n_steps;
-                        } else if (ra.ep_return) {              // restart_front's accumulators for an env that goes on
-                            const double sum = at(ra.ep_return, i) + reward;
-                            const int len = at(ra.ep_length, i) + 1;
-                            at(ra.ep_return, i) = sum; at(ra.ep_length, i) = len;
-                        }
-                    }
-                }
-            }
-            if (s == c.n_steps) break;
-            if (m == 0) {                                // a step opens: features, layers, the draw, the output function, the pump
-                const int q = s % H, head = q ? H - q : 0;
-                const int start = c.start_minute ? (int)at(c.start_minute, i) : 0;
-                const double prev_meal = at(c.prev_meal, i);
-                const unsigned wave0 = __builtin_amdgcn_readfirstlane(i & ~63u);
-                const unsigned pol = wave0 / c.envs_per_policy;
-                const WPtr w = (WPtr)(c.params + (size_t)pol * (size_t)c.n_params);
-                mlp_features(c, col, buf, head, prev_meal, start + e.t);
-                if (g.feat_trace)
-                    for (int j = 0; j < F; ++j) g.feat_trace[((c.trace_row + s) * F + j) * a.n + i] = buf[j * 64];
-                double y = mlp_layers(c, w, buf, F);
-                double eps = 0.0;
-                if (g.sigma) {                           // wave-uniform
-                    const uint32_t ep = a.episode ? at(a.episode, i) : 0u;
-                    eps = (double)philox_pair(g.explore_seed, (uint64_t)(a.env_offset + i), ep, (uint32_t)e.t).x;
-                    y = fma((double)((WPtr)g.sigma)[pol], eps, y);
-                }
-                if (g.eps_trace) g.eps_trace[(c.trace_row + s) * a.n + i] = eps;
-                const double u = mlp_output(c, y);
-                if (c.act_trace) c.act_trace[(c.trace_row + s) * a.n + i] = u;
-                insulin = dopri5_mlp_pump(a, u);
-                o = StepOut<double>{0.0, 0.0, 0.0, 0.0};
-            }
-            const double meal = meal_lookup(a, i, e);                                         // env.py:50
-            noise = measure_noise<true>(a, i, e, due);
-            const MinuteIn<double> u = eat_minute<0, double>(nop, e.x, meal, insulin, e.planned, e.lq, e.lf, e.eating);
-            d_mg = u.d_mg;
-            o.meal += meal / div; o.ins += insulin / div;                                     // env.py:78-79
-            if (!failed) dopri5_enter(p, e.x, d_mg, insulin, e.lq, e.lf, hc, (double)e.t, r, nf);
-            cold.save(e, o, noise, hc);
-            fresh = false; boundary = false;
-        }
-        if (failed) { boundary = true; continue; }
-        const int rc = dopri5_attempt(p, e.x, d_mg, insulin, e.lq, e.lf, cold.f[Cold::HC * 64], (double)e.t + 1.0, r, nf);
-        failed = rc < 0;
-        boundary = rc != 0;
-    }
-    if (!stored) store_env(a, i, pid, e);
-    at(h_carry, i) = hc;
-    if (nfev) at(nfev, i) = nf;
-    if (failed) atomicOr(a.status, T1D_ST_SOLVER_FAILED);
-    dopri5_mlp_store_windows(a, c, i, col, s);
+#define DOPRI5_WINDOWS c
+#define DOPRI5_COLLECT
+#define DOPRI5_LIMIT
+#define DOPRI5_ACTION DOPRI5_MLP_COLLECT_ACTION
+#include "t1d_dopri5_loop.inc"
 }
 
 __global__ __launch_bounds__(kBlock, 1) void dopri5_ctrl_collect_limit_kernel(const KArgs<double> a, const PidArgs<double> c,
@@ -1337,135 +633,16 @@ __global__ __launch_bounds__(kBlock, 1) void dopri5_ctrl_collect_limit_kernel(co
                                                                               const RestartArgs<double> ra, const LimitArgs<double> lim,
                                                                               const double* __restrict__ raw, double* h_carry, int32_t* nfev)
 {
-    typedef RollColdT<64> Cold;
-    __shared__ double lds[kRawPars * kMaxPatients];
-    for (int j = threadIdx.x; j < kRawPars * kMaxPatients; j += blockDim.x) lds[j] = raw[j];
-    __syncthreads();
-    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-    __builtin_assume(i < (1u << 28));          // host guarantees n <= 2^28: i * sizeof(T) fits a 32-bit voffset
-    if ((int64_t)i >= a.n) return;             // any n: the lanes past the end leave, the others never look at them
-    const MlpLaneLds piece = dopri5_mlp_lane_lds(f);
-    const Cold cold = piece.cold;
-    double* const col = piece.col;
-    const int H = f.history, F = 2 * H + 3;
-    double* const buf = col + 2 * H * 64;
-    const uint32_t meta = at(a.meta, i);
-    const uint32_t pid = T1D_META_PID(meta);
-    Env<double> e;
-    load_env(a, i, meta, e);
-    const ParsRaw p{lds, (int)pid};
-    NoDerivedPars nop;
-    const double div = double(a.minutes), st = double(a.sen.st);
-    dopri5_mlp_load_windows(a, f, i, col);
-    double hc = at(h_carry, i), noise = 0.0, insulin = 0.0, d_mg = 0.0;
-    StepOut<double> o{0.0, 0.0, 0.0, 0.0};
-    Dopri5Run r{};
-    int nf = 0, m = 0, s = 0;
-    bool due = false, failed = false, boundary = true, fresh = true;
-    bool stored = false;                        // the last step ended the episode: the state in memory is the new episode's
-    cold.save(e, o, noise, hc);
-    for (;;) {
-        if (boundary) {
-            cold.load(e, o, noise, hc);
-            if (!fresh) {
-                e.t += 1;
-                const double gsub = e.x[12] / p(T1D_P_VG);                                    // t1dpatient.py:217-218
-                const double cgm = measure_apply(a, e, gsub, noise, due);                     // env.py:62
-                o.bg += gsub / div; o.cgm += cgm / div;                                       // env.py:80-81
-                if (++m == a.minutes) {                  // the step is complete: what t1d_step_dopri5 leaves, then the collector's own
-                    const double rp = e.prev_risk;
-                    write_outputs<0>(a, i, e, o, rp);
-                    const double reward = rp - e.prev_risk;     // the word write_outputs stored in batch.reward
-                    const bool fin = o.bg < 70.0 || o.bg > 350.0;
-                    const bool cut = !fin && e.t >= lim.max_minutes;    // the time limit ends the episode here (never a finished one)
-                    const int64_t tr = (c.trace_row + s) * a.n + i;
-                    if (g.reward_trace) g.reward_trace[tr] = reward;
-                    if (g.done_trace) g.done_trace[tr] = fin ? 1 : 0;
-                    if (lim.cut_trace) lim.cut_trace[tr] = cut ? 1 : 0;
-                    if (c.bg_trace) c.bg_trace[tr] = o.bg;
-                    if (c.cgm_trace) c.cgm_trace[tr] = o.cgm;
-                    if (c.cho_trace) c.cho_trace[tr] = o.meal;
-                    if (c.ins_trace) c.ins_trace[tr] = o.ins;
-                    if (c.kind == 1) at(c.bb_prev_meal, i) = o.meal;
-                    at(f.prev_meal, i) = o.meal;
-                    if (c.sum_risk) { double l, h, rk; risk_index1<0>(o.bg, l, h, rk); at(c.sum_risk, i) = at(c.sum_risk, i) + rk; }
-                    if (c.min_bg) { const double v = at(c.min_bg, i); at(c.min_bg, i) = o.bg < v ? o.bg : v; }
-                    if (c.max_bg) { const double v = at(c.max_bg, i); at(c.max_bg, i) = o.bg > v ? o.bg : v; }
-                    if (c.n_low) at(c.n_low, i) = at(c.n_low, i) + (o.bg < 70.0);
-                    if (c.n_high) at(c.n_high, i) = at(c.n_high, i) + (o.bg > 180.0);
-                    m = 0; ++s;
-                    const int q = s % H, head = q ? H - q : 0;  // the oldest row becomes the newest
-                    col[head * 64] = o.cgm; col[(H + head) * 64] = o.ins;
-                    if (g.on_done) {
-                        if (fin || cut) {
-                            if (cut && lim.cut_feat) {          // the features of the state the cut episode ended in
-                                const int start = f.start_minute ? (int)at(f.start_minute, i) : 0;
-                                mlp_features(f, col, buf, head, o.meal, start + e.t);
-                                for (int j = 0; j < F; ++j) at(rowv(lim.cut_feat, a.n, j), i) = buf[j * 64];
-                            }
-                            // the finished step is in memory (write_outputs); the state follows, and the restart works on those words
-                            store_env(a, i, pid, e);
-                            if (failed) atomicOr(a.status, T1D_ST_SOLVER_FAILED);
-                            collect_restart_masked<double>(a, ra, g.slots, i);          // a cut env's done is 0
-                            load_env(a, i, at(a.meta, i), e);
-                            const double first = at(a.cgm, i);  // the new episode's first observation
-                            for (int k = 0; k < H; ++k) { col[k * 64] = first; col[(H + k) * 64] = 0.0; }
-                            at(f.prev_meal, i) = 0.0;
-                            if (c.kind == 1) at(c.bb_prev_meal, i) = 0.0;                     // BBController.reset
-                            else { at(c.integ, i) = 0.0; at(c.prev, i) = 0.0; }               // PIDController.reset
-                            hc = 0.0;                           // T1DPatient.reset builds the solver afresh: the first minute probes
-                            failed = false;
-                            stored = s == c.n_steps;
-                        } else if (ra.ep_return) {              // restart_front's accumulators for an env that goes on
-                            const double sum = at(ra.ep_return, i) + reward;
-                            const int len = at(ra.ep_length, i) + 1;
-                            at(ra.ep_return, i) = sum; at(ra.ep_length, i) = len;
-                        }
-                    }
-                }
-            }
-            if (s == c.n_steps) break;
-            if (m == 0) {                                // a step opens: features, the controller on the last observation, the pump
-                const int q = s % H, head = q ? H - q : 0;
-                const int start = f.start_minute ? (int)at(f.start_minute, i) : 0;
-                const double prev_meal = at(f.prev_meal, i);
-                mlp_features(f, col, buf, head, prev_meal, start + e.t);
-                if (g.feat_trace)
-                    for (int j = 0; j < F; ++j) g.feat_trace[((c.trace_row + s) * F + j) * a.n + i] = buf[j * 64];
-                double u, bolus;
-                dopri5_controller(c, i, at(a.cgm, i), st, u, bolus);
-                if (f.act_trace) {                       // what the controller asked for, before the pump: one addition
-#pragma clang fp contract(off)
-                    f.act_trace[(c.trace_row + s) * a.n + i] = u + bolus;
-                }
-                double q_basal = u, q_bolus = bolus;     // as step_body with a bolus given: env.py:51-52
-                if (!(a.flags & T1D_BATCH_NO_PUMP)) {
-                    q_basal = pump_quantise(u, a.pump.inc_basal, a.pump.min_basal, a.pump.max_basal);
-                    q_bolus = pump_quantise(bolus, a.pump.inc_bolus, a.pump.min_bolus, a.pump.max_bolus);
-                }
-                insulin = q_basal + q_bolus;
-                o = StepOut<double>{0.0, 0.0, 0.0, 0.0};
-            }
-            const double meal = meal_lookup(a, i, e);                                         // env.py:50
-            noise = measure_noise<true>(a, i, e, due);
-            const MinuteIn<double> u = eat_minute<0, double>(nop, e.x, meal, insulin, e.planned, e.lq, e.lf, e.eating);
-            d_mg = u.d_mg;
-            o.meal += meal / div; o.ins += insulin / div;                                     // env.py:78-79
-            if (!failed) dopri5_enter(p, e.x, d_mg, insulin, e.lq, e.lf, hc, (double)e.t, r, nf);
-            cold.save(e, o, noise, hc);
-            fresh = false; boundary = false;
-        }
-        if (failed) { boundary = true; continue; }
-        const int rc = dopri5_attempt(p, e.x, d_mg, insulin, e.lq, e.lf, cold.f[Cold::HC * 64], (double)e.t + 1.0, r, nf);
-        failed = rc < 0;
-        boundary = rc != 0;
-    }
-    if (!stored) store_env(a, i, pid, e);
-    at(h_carry, i) = hc;
-    if (nfev) at(nfev, i) = nf;
-    if (failed) atomicOr(a.status, T1D_ST_SOLVER_FAILED);
-    dopri5_mlp_store_windows(a, f, i, col, s);
+#define DOPRI5_STATE
+#define DOPRI5_BB
+#define DOPRI5_WINDOWS f
+#define DOPRI5_COLLECT
+#define DOPRI5_LIMIT
+#define DOPRI5_ACTION DOPRI5_CTRL_COLLECT_ACTION
+#include "t1d_dopri5_loop.inc"
 }
+#undef DOPRI5_MLP_COLLECT_ACTION
+#undef DOPRI5_CTRL_COLLECT_ACTION
 
 // t1d_mlp_action: the policy alone, one lane per env -- the action the next step of a roll-out would ask for, from
 // batch.cgm (CGM[0]), rows 1 .. of cgm_hist, ins_hist, prev_meal, batch.t and start_minute.  Reads only; writes action [n].

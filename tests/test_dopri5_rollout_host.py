@@ -85,6 +85,21 @@ def test_wave_cost_model_on_a_hand_made_array():
     assert r["free_running_wave_cost"] == ((9 + 1) + (6 + 2)) / 2 / 4.0
 
 
+def test_the_free_running_solver_loop_is_written_once():
+    """Every closed-loop kernel of the exact mode includes one text for its loop (t1d_dopri5_loop.inc): over the device
+    sources, dopri5_attempt( stands at its definition, in dopri5_minute and in that text; dopri5_enter( at its definition, in
+    dopri5_minute and in that text.  Nine includes, one per kernel, and the text is a source of the library."""
+    from simglucose_amd import _lib
+    csrc = os.path.join(ROOT, "simglucose_amd", "csrc")
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".hpp", ".inc"))}
+    loop = "t1d_dopri5_loop.inc"
+    for call in ("dopri5_attempt(", "dopri5_enter("):
+        counts = {f: t.count(call) for f, t in text.items() if call in t}
+        assert counts == {"t1d_dopri5.hpp": 2, loop: 1}, (call, counts)
+    assert text["t1d_dopri5.hpp"].count('#include "%s"' % loop) == 9
+    assert os.path.join(csrc, loop) in _lib.SOURCES
+
+
 def test_rollout_kernel_needs_no_scratch_and_the_step_kernel_still_none():
     """Both exact-mode kernels keep the stage vectors in the unified VGPR + AGPR file: the roll-out's per-minute words wait
     in LDS between the minute boundaries instead of being spilled inside the step-attempt loop."""
